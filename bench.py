@@ -18,7 +18,11 @@ transformer block, 218.1 M parameters in 7 Linears, 128 x 2048-token calibration
 Inputs (weights, activations) are resident in HBM before the timed region starts; there is no model forward in
 this region (synthetic Linears).
 
-The same JSON line carries, measured AFTER the timed region:
+A plain run sets up, warms up, times the --steps steps and prints ONE JSON line: the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  `--dump-outputs DIR` also writes what the last timed step computed
+(dump_outputs).  Everything else below runs only with `--full`.
+
+With `--full` the line carries, measured AFTER the timed region:
   * `whole_model`: the drop-in pipeline end to end -- a random-init Llama-3-8B-shaped LlamaForCausalLM built on the
     GPU, 128 x 2048 synthetic ids, `Quantizer.quantize` (the region the reference times, quant.py:251-254: capture
     forward, forward #1 + H, solve + column loop, forward #2, RTN of embed/lm_head, data.pth saving) with its split;
@@ -34,17 +38,18 @@ The same JSON line carries, measured AFTER the timed region:
 Other workloads (`--workload`): tinyllama-block-q4k, llama3-8b-block-mixed (configs[2]), llama3-70b-block-q4k
 (configs[3] shapes), mixtral-block (configs[4] shapes), llama3-8b-model-q4k (a step = the whole model).
 
-`python bench.py --gpus N` with N > 1 and no launcher re-executes itself under torch.distributed.run (one rank per GPU,
-RCCL); under a launcher it reads RANK / LOCAL_RANK / WORLD_SIZE.  A rank count other than --gpus is fatal.
+`python bench.py --gpus N` with N > 1 and no launcher runs itself again under torch.distributed.run in a child process
+(one rank per GPU, RCCL); under a launcher it reads RANK / LOCAL_RANK / WORLD_SIZE.  A rank count other than --gpus is fatal.
 
-Rank 0 prints the full result dict on one line and then, LAST, the compact headline line (<= 2 KB: the driver contract's
-keys with `roofline` and `cpu_baseline` flattened to scalars).
+With `--full`, rank 0 prints the full result dict on one line and then, LAST, the compact headline line (<= 2 KB: the
+driver contract's keys with `roofline` and `cpu_baseline` flattened to scalars).
 """
 import argparse
 from pathlib import Path
 import json
 import os
 import shutil
+import subprocess
 import sys
 import tempfile
 import time
@@ -199,6 +204,32 @@ def syrk_flops(wl, X):
             seen.add(inp)
             f += float(sum(x.shape[-2] for x in X[inp])) * C * (C + 128)
     return f
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # the whole dump stays below 64 MB
+
+
+def dump_outputs(out_dir, wl, layers, keep):
+    """What the last timed step handed its caller, as float32 `<out_dir>/<Linear>.<field>.npy`: per Linear the written-back
+    weight, BlockSchedule.quantize's (qweight, d, s, dmin, m) and the GGUF block bytes.  Every field of a Linear is cut to
+    the same rows: a sorted sample drawn with a fixed seed, at most 64 rows per Linear and fewer when the block's Linears
+    would not fit DUMP_BUDGET_BYTES.  Integer and fp16 fields are exact in float32."""
+    out = keep["__out__"]
+    fields = {}
+    for name, lin in layers.items():
+        q, d, s, dmin, m = out[name]
+        # at N > 1 the GGUF bytes exist only on the rank that computed the Linear; pack is a pure function of the result
+        packed = keep[name][1] if name in keep else ops.pack(int(q_of(wl, name)), q, d, s, dmin, m)
+        fields[name] = {"weight": lin.weight.data, "qweight": q, "d": d, "s": s, "dmin": dmin, "m": m, "packed": packed}
+    row_bytes = sum(4 * t[0].numel() for f in fields.values() for t in f.values())
+    n_rows = max(1, min(64, DUMP_BUDGET_BYTES // row_bytes))
+    rng = np.random.default_rng(0)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, f in fields.items():
+        R = f["weight"].shape[0]
+        rows = torch.from_numpy(np.sort(rng.choice(R, size=min(n_rows, R), replace=False))).to(f["weight"].device)
+        for field, t in f.items():
+            np.save(os.path.join(out_dir, f"{name}.{field}.npy"), t[rows].float().cpu().numpy())
 
 
 # ----------------------------------------------------------------------------- side legs (after the timed region)
@@ -751,9 +782,10 @@ def whole_model_run(wl, dev, world, rank, save_root=None, nseq=None, L=None, lay
 
 # ----------------------------------------------------------------------------- main
 def self_launch(args):
-    """`python bench.py --gpus N` (N > 1) without a launcher: re-exec under torch.distributed.run with one rank per GPU,
-    the way the reference's run_quant.sh:15 starts its own ranks (torchrun --nnodes=1 --nproc-per-node=$NUM_GPUS) and
-    quant.py:149-155 joins them.  nccl (= RCCL) needs N visible GPUs; fewer is refused unless --backend gloo was asked for."""
+    """`python bench.py --gpus N` (N > 1) without a launcher: run torch.distributed.run with one rank per GPU as a child
+    process and exit with its status, the way the reference's run_quant.sh:15 starts its own ranks (torchrun --nnodes=1
+    --nproc-per-node=$NUM_GPUS) and quant.py:149-155 joins them.  nccl (= RCCL) needs N visible GPUs; fewer is refused
+    unless --backend gloo was asked for.  A child, not an exec: counting the devices has started the HIP runtime here."""
     import socket
     n_dev = torch.cuda.device_count()
     if args.backend != "gloo" and n_dev < args.gpus:
@@ -767,7 +799,8 @@ def self_launch(args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execvpe(sys.executable, argv, env)
+    rc = subprocess.call(argv, env=env)
+    sys.exit(rc if rc >= 0 else 128 - rc)  # killed by a signal: the shell's 128 + signal
 
 
 def _get(d, *path):
@@ -862,17 +895,26 @@ def main():
     ap.add_argument("--calib-batch", type=int, default=1, help="whole-model workload: calibration samples per block forward")
     ap.add_argument("--fused-forward", nargs="?", const="all", default="exact", choices=["off", "exact", "all"],
                     help="whole-model workload: forward kernels (exact = the Quantizer's default; bare flag = all)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-whole-model", action="store_true", help="skip the whole-model leg of the block workloads")
-    ap.add_argument("--no-side-legs", action="store_true", help="skip trailing_update / tolerance_parity legs")
-    ap.add_argument("--breakdown", action="store_true", help="one extra profiled step: per-kernel ms to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: roofline, step latency, side legs, CPU baseline, "
+                         "whole-model legs (block workloads); prints the full dict, then the compact line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="block workloads: write what the last timed step computed to DIR/*.npy (float32, < 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-whole-model", action="store_true", help="--full: skip the whole-model leg of the block workloads")
+    ap.add_argument("--no-side-legs", action="store_true", help="--full: skip trailing_update / tolerance_parity legs")
+    ap.add_argument("--breakdown", action="store_true", help="--full: one extra profiled step: per-kernel ms to stderr")
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"],
                     help="torch.distributed backend: nccl (= RCCL over xGMI, default); gloo only to exercise the "
                          "N>1 code path with several ranks sharing one GPU (must be asked for explicitly)")
     args = ap.parse_args()
+    if args.breakdown and not args.full:
+        ap.error("--breakdown is part of --full")
+    if args.dump_outputs and "model" in WORKLOADS[args.workload]:
+        ap.error("--dump-outputs: block workloads only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args)  # does not return: `python bench.py --gpus N` starts its N ranks itself (run_quant.sh:15)
+        self_launch(args)  # exits: `python bench.py --gpus N` starts its N ranks itself (run_quant.sh:15)
     args.backend = args.backend or "nccl"
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -913,14 +955,18 @@ def main():
         dt = sum(r["wall_s_quantizer_region"] for r in timed)
         if rank == 0:
             params = timed[-1]["params_quantized_M"] * 1e6
-            emit({
+            head = {
                 "metric": "Mparams/s GPTQ-quantized", "value": round(params * args.steps / dt / 1e6, 2),
                 "unit": "Mparams/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": round(dt / args.steps * 1e3, 1), "higher_is_better": True, "scaling": "strong",
                 "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                 "config": {"workload": f"{args.workload}: Quantizer.quantize of the whole model, {nseq}x{L}-token "
                                        f"calibration", "parallelism": f"calib-dp{world}+matrix-fanout"},
-                "ranks_seen": ranks_seen, "whole_model": timed[-1]}, args, world)
+                "ranks_seen": ranks_seen}
+            if args.full:
+                emit(dict(head, whole_model=timed[-1]), args, world)
+            else:
+                print(json.dumps(head), flush=True)
         if world > 1:
             dist.destroy_process_group()
         return
@@ -935,7 +981,7 @@ def main():
     for _ in range(args.warmup):
         block_step(wl, layers, W16, X)
     sync()
-    if world > 1:
+    if world > 1 and args.full:
         # all-reduce of the widest Hessian's payload, alone: bytes per rank and time (RCCL over xGMI)
         C = max(c for _, c, _ in shapes.values())
         H = torch.zeros(C, C, device=dev)
@@ -959,9 +1005,10 @@ def main():
             assert float(lo_) == float(hi_) and float(w.float().abs().sum()) > 0, f"{name}: ranks disagree"
         if rank == 0:
             print("verify: all ranks hold identical results", file=sys.stderr)
-    # the dominant kernel (fp16 MFMA SYRK) and the far trailing update are timed live with HIP events on their
-    # launch streams, inside the timed region
-    _cabi.prof_enable(["syrk", "trailing_far_gemm32"])
+    if args.full:
+        # the dominant kernel (fp16 MFMA SYRK) and the far trailing update are timed live with HIP events on their
+        # launch streams, inside the timed region
+        _cabi.prof_enable(["syrk", "trailing_far_gemm32"])
     keep = {}
     sched = None
     coll0, collb0 = dict(dist_utils.collective_calls), dict(dist_utils.collective_bytes)
@@ -970,8 +1017,9 @@ def main():
         sched = block_step(wl, layers, W16, X, keep=keep if i == args.steps - 1 else None)
     sync()
     dt = time.perf_counter() - t0
-    prof = _cabi.prof_collect(busy=True)
-    _cabi.prof_enable([])
+    if args.full:
+        prof = _cabi.prof_collect(busy=True)
+        _cabi.prof_enable([])
     # data-path collectives one step issued on this rank (N > 1: one all-reduce per distinct Hessian, ONE all-gather of
     # the block's results, no broadcast -- asserted by tests/test_gpu_round3.py)
     coll = {k: (v - coll0.get(k, 0)) / args.steps for k, v in dist_utils.collective_calls.items()}
@@ -981,6 +1029,26 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     BlockSchedule.verify()  # the device flags of every reused factorisation of the timed steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl, layers, keep)  # before any later step replaces the written-back weights
+    head = {
+        "metric": "Mparams/s GPTQ-quantized", "value": round(params * args.steps / dt / 1e6, 2),
+        "unit": "Mparams/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.workload}: {len(shapes)} Linears of one block ({params / 1e6:.1f} M params), "
+                               f"{nseq}x{L}-token calibration fed per sequence through the package's BlockSchedule, "
+                               f"block_size 128, rel_damp 0.01, nstep 20",
+                   "calib_seqs_per_rank": nseq_local, "parallelism": f"calib-dp{world}+matrix-fanout",
+                   "owners": sched.owners if world > 1 else "rank0"},
+        "ranks_seen": ranks_seen, "collective_backend": (f"{args.backend} (RCCL over xGMI)" if args.backend == "nccl"
+                                                         else args.backend) if world > 1 else None}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # latency of ONE step alone (host and device idle before and after): the scheduler never synchronises, so the
     # K timed steps above are enqueued back to back and the tail of a step's chains (latency-bound, few CUs) runs
     # under the next step's SYRK; inside a model the block's second forward takes that place
@@ -1045,18 +1113,8 @@ def main():
         # collectives, which only rank 0 would enter here (a hang under RCCL): never at N > 1
         side = not args.no_side_legs and world == 1
         line = {
-            "metric": "Mparams/s GPTQ-quantized", "value": round(params * args.steps / dt / 1e6, 2),
-            "unit": "Mparams/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            **head,
             "step_latency_ms": round(latency_ms, 2),
-            "config": {"workload": f"{args.workload}: {len(shapes)} Linears of one block ({params / 1e6:.1f} M params), "
-                                   f"{nseq}x{L}-token calibration fed per sequence through the package's BlockSchedule, "
-                                   f"block_size 128, rel_damp 0.01, nstep 20",
-                       "calib_seqs_per_rank": nseq_local, "parallelism": f"calib-dp{world}+matrix-fanout",
-                       "owners": sched.owners if world > 1 else "rank0"},
-            "ranks_seen": ranks_seen, "collective_backend": (f"{args.backend} (RCCL over xGMI)" if args.backend == "nccl"
-                                                             else args.backend) if world > 1 else None,
             "collectives_per_step": coll if world > 1 else None,
             "collective_bytes_per_step": coll_bytes if world > 1 else None,  # this rank's payloads
             "allreduce_probe": ar_probe, "schedule": sched.stats,

@@ -44,7 +44,7 @@ cp $OUT/r04_syrk_traffic.json $R/profiles/r04_syrk_traffic.json  # bench.py read
 for W in $WLS; do
   EXTRA=""
   [ "$W" != "llama3-8b-block-q4k" ] && EXTRA="--no-whole-model"
-  cd $R && timeout 900 python bench.py --workload $W --steps 5 --warmup 2 $EXTRA 2>$OUT/r04_bench_$W.err | tail -1 > $OUT/r04_bench_$W.json
+  cd $R && timeout 900 python bench.py --workload $W --steps 5 --warmup 2 --full $EXTRA 2>$OUT/r04_bench_$W.err | tail -1 > $OUT/r04_bench_$W.json
   (cd /tmp && export TMPDIR=/tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$W -o p -- \
      python $R/bench.py --workload $W --steps 5 --warmup 2 --no-cpu-baseline --no-whole-model --no-side-legs > $OUT/prof_$W.log 2>&1 || echo "rocprofv3 failed for $W")
   cp $(find $OUT/prof_$W -name "*kernel_stats.csv" | head -1) $OUT/r04_bench_${W}_kernel_stats.csv 2>/dev/null

@@ -56,7 +56,7 @@ cp $OUT/r06_syrk_traffic.json $R/profiles/r06_syrk_traffic.json  # bench.py read
 for W in $WLS; do
   EXTRA=""
   [ "$W" != "llama3-8b-block-q4k" ] && EXTRA="--no-whole-model"
-  cd $R && timeout 900 python bench.py --workload $W --steps 5 --warmup 2 $EXTRA 2>$OUT/r06_bench_$W.err > $OUT/r06_bench_$W.out
+  cd $R && timeout 900 python bench.py --workload $W --steps 5 --warmup 2 --full $EXTRA 2>$OUT/r06_bench_$W.err > $OUT/r06_bench_$W.out
   tail -2 $OUT/r06_bench_$W.out | head -1 > $OUT/r06_bench_$W.json          # the full dict
   tail -1 $OUT/r06_bench_$W.out > $OUT/r06_bench_${W}_compact.json            # the compact headline (the LAST stdout line)
   rm -f $OUT/r06_bench_$W.out

@@ -1,5 +1,5 @@
-"""Timeline of one bench step from a GQ_PROF_DUMP file (bench.py --breakdown).
-usage: GQ_PROF_DUMP=gpurun_out/tl.txt python bench.py --breakdown ... ; python profiles/timeline.py gpurun_out/tl.txt
+"""Timeline of one bench step from a GQ_PROF_DUMP file (bench.py --full --breakdown).
+usage: GQ_PROF_DUMP=<file> python bench.py --full --breakdown ... ; python profiles/timeline.py <file>
 Prints, per stream, the first/last instant of each phase and, per 5-ms bucket, the busy fraction of each tag."""
 import sys, collections
 recs, cur = [], []

@@ -273,6 +273,39 @@ def test_bench_compact_line_and_self_launch_refusal():
         assert p.returncode != 0 and "RCCL needs one GPU per rank" in p.stderr and "{" not in p.stdout
 
 
+def test_bench_dump_outputs_fits_64_mb_for_every_block_workload(tmp_path, oracle):
+    """bench.py --dump-outputs on host tensors of the real shapes (zero-stride: no memory): every block workload's dump is
+    float32, below 64 MB, and every field of a Linear is cut to the same seeded rows."""
+    import importlib.util
+    from types import SimpleNamespace
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    for wl_name, wl in bench.WORKLOADS.items():
+        if "model" in wl:
+            continue
+        layers, keep = {}, {"__out__": {}}
+        for name, (R, C, _) in wl["shapes"].items():
+            ti = oracle.type_info(int(bench.q_of(wl, name)))
+            # each row holds its index mod 256: exact in uint8 and fp16, so equal first columns mean the same rows
+            row = lambda n, dt: (torch.arange(R) % 256).to(dt)[:, None].expand(R, n)  # noqa: E731
+            res = (row(C, torch.uint8), row(C // 256, torch.float16), row(C // ti["group"], torch.uint8),
+                   row(C // 256, torch.float16), row(C // ti["group"], torch.uint8))
+            keep["__out__"][name] = res
+            keep[name] = (res, row(C // 256 * ti["type_size"], torch.uint8), None)
+            layers[name] = SimpleNamespace(weight=SimpleNamespace(data=row(C, torch.float16)))
+        d = tmp_path / wl_name
+        bench.dump_outputs(str(d), wl, layers, keep)
+        arrays = {f: np.load(d / f) for f in os.listdir(d)}
+        assert len(arrays) == 7 * len(wl["shapes"]) and all(a.dtype == np.float32 for a in arrays.values())
+        assert sum(os.path.getsize(d / f) for f in arrays) < 64e6, wl_name
+        for name in wl["shapes"]:
+            fields = [a for f, a in arrays.items() if f.startswith(name + ".")]
+            assert len(fields) == 7 and all(np.array_equal(a[:, 0], fields[0][:, 0]) for a in fields), (wl_name, name)
+            assert 1 <= fields[0].shape[0] <= 64
+
+
 def test_gq_options_errors_fail_every_entry_point_without_abort():
     """GQ_OPTIONS with an unknown name, a non-integer value or a value outside the option's range must not silently
     become 0 / the default and must not abort() the host process: every entry point fails with GQ_E_UNSUPPORTED and a

@@ -344,7 +344,7 @@ def _spawn_bench(n, backend, extra=()):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr",
            "127.0.0.1", "--master-port", str(23000 + os.getpid() % 4000), os.path.join(ROOT, "bench.py"), "--gpus",
            str(n), "--steps", "1", "--warmup", "1", "--workload", "tinyllama-block-q4k", "--backend", backend,
-           "--no-cpu-baseline", "--no-whole-model", "--no-side-legs", *extra]
+           "--full", "--no-cpu-baseline", "--no-whole-model", "--no-side-legs", *extra]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]

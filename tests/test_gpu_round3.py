@@ -221,7 +221,7 @@ def test_bench_eight_ranks_one_allgather_per_block(workload):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr",
            "127.0.0.1", "--master-port", str(27000 + os.getpid() % 2000), os.path.join(ROOT, "bench.py"), "--gpus",
            str(n), "--steps", "1", "--warmup", "1" if backend == "nccl" else "0", "--workload", workload, "--backend", backend,
-           "--no-cpu-baseline", "--no-whole-model", "--no-side-legs"]
+           "--full", "--no-cpu-baseline", "--no-whole-model", "--no-side-legs"]
     if workload != "tinyllama-block-q4k":
         cmd += ["--calib-seqs", "32"]  # the plumbing, not the speed: a quarter of the 128 sequences (4 per rank)
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=2400, cwd=ROOT)

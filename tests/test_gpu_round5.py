@@ -21,7 +21,7 @@ def test_bench_launches_its_own_ranks(n):
     backend = [] if torch.cuda.device_count() >= n else ["--backend", "gloo"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), *backend, "--steps", "1", "--warmup", "1",
-           "--workload", "tinyllama-block-q4k"]
+           "--workload", "tinyllama-block-q4k", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1800, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]

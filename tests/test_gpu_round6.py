@@ -106,7 +106,7 @@ def test_default_workload_at_eight_ranks_with_the_whole_model_leg():
     backend = [] if torch.cuda.device_count() >= n else ["--backend", "gloo"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), *backend, "--steps", "1", "--warmup", "1",
-           "--calib-seqs", "16", "--layers", "2"]
+           "--calib-seqs", "16", "--layers", "2", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]
