@@ -1,0 +1,129 @@
+"""GGUF -> HF tensors on the GPU: the inverse of pack_gptq_into_gguf.py for the dense Llama family.
+
+The reference reads a .gguf back through transformers' GGUF loader (mapper/gguf_splitter.py:469-474), which needs gguf-py;
+that package is not installable here, so the file is parsed by gguf_writer.parse_gguf (spec level) and the K-quant payloads
+are decoded by this package's own kernel: bytes are uploaded as they lie in the file and `ops.dequantize_blocks` writes the
+weights in one pass.  The q_proj / k_proj rotary row permutation the converter applied (reference
+pack_gptq_into_gguf.py:2177-2183) is undone inside that pass by a row gather (`row_src`), for architecture "llama" only.
+F32 / F16 / BF16 tensors pass through with a cast; Q8_0 (`--outtype q8_0` writes it for the tensors GPTQ did not quantize)
+is two torch ops (d * q, ggml-quants.c dequantize_row_q8_0) and not a hot path.  The file is mapped, never read whole.
+Merged 3-D expert tensors (`*_exps`) are refused: splitting them back into per-expert HF names belongs to the MoE path.
+"""
+from typing import Dict, Iterator, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .gguf_writer import GGMLType, parse_gguf
+from .pack_gptq_into_gguf import _BLOCK_TABLE
+
+K_QUANTS = (GGMLType.Q2_K, GGMLType.Q3_K, GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q6_K)
+_TOP = {"token_embd.weight": "model.embed_tokens.weight", "output_norm.weight": "model.norm.weight",
+        "output.weight": "lm_head.weight"}
+_BLOCK_INV = {v: k for k, v in _BLOCK_TABLE.items() if not v.endswith("_exps.weight")}
+
+
+def unpermute(weights: torch.Tensor, n_head: int, n_head_kv) -> torch.Tensor:
+    """Exact inverse of pack_gptq_into_gguf.permute: GGUF's rotary row layout back to HF's; any trailing shape."""
+    if n_head_kv is not None and n_head != n_head_kv:
+        n_head = n_head_kv
+    return (weights.reshape(n_head, weights.shape[0] // n_head // 2, 2, *weights.shape[1:])
+            .swapaxes(1, 2).reshape(weights.shape))
+
+
+def unpermute_rows(R: int, n_head: int, n_head_kv) -> torch.Tensor:
+    """int32 [R]: x[unpermute_rows(R, h, kv)] == unpermute(x, h, kv) -- the `row_src` of ops.dequantize_blocks."""
+    return unpermute(torch.arange(R, dtype=torch.int32), n_head, n_head_kv).contiguous()
+
+
+def hf_tensor_name(gguf_name: str) -> str:
+    """Inverse of pack_gptq_into_gguf.map_tensor_name for the dense Llama table (and Mixtral's router)."""
+    if gguf_name in _TOP:
+        return _TOP[gguf_name]
+    parts = gguf_name.split(".")
+    if len(parts) >= 4 and parts[0] == "blk" and parts[1].isdecimal():
+        rest = ".".join(parts[2:])
+        if rest in _BLOCK_INV:
+            return f"model.layers.{parts[1]}.{_BLOCK_INV[rest]}"
+    raise ValueError(f"Can not map GGUF tensor {gguf_name!r} to an HF name")
+
+
+def _kv_int(kv, key) -> Optional[int]:
+    if key not in kv:
+        return None
+    v = kv[key][0]
+    if isinstance(v, (list, tuple)):  # per-layer head counts: one value for all layers, or refuse
+        if len(set(v)) != 1:
+            raise NotImplementedError(f"{key} differs from layer to layer: {sorted(set(v))}")
+        v = v[0]
+    return int(v)
+
+
+def _host(buf, off: int, nbytes: int) -> torch.Tensor:
+    """One tensor's bytes out of the mapped file (the only copy made on the host)."""
+    return torch.from_numpy(np.array(buf[off:off + nbytes], dtype=np.uint8, copy=True))
+
+
+def iter_gguf_tensors(path: str, device="cuda:0", dtype: Optional[torch.dtype] = None,
+                      hf_layout: bool = True) -> Iterator[Tuple[str, torch.Tensor]]:
+    """Yield (name, tensor on `device`) for every tensor of the file, in file order.  hf_layout: HF names and HF row order
+    of attn_q / attn_k (`rope_freqs.weight`, which no HF module owns, is left out); otherwise GGUF names and rows as stored.
+    dtype None: fp32 for quantized tensors, the stored dtype for F32 / F16 / BF16."""
+    device = torch.device(device)
+    kv, tensors, buf = parse_gguf(str(path), mmap=True)
+    arch = kv["general.architecture"][0] if "general.architecture" in kv else None
+    n_head, n_kv = _kv_int(kv, f"{arch}.attention.head_count"), _kv_int(kv, f"{arch}.attention.head_count_kv")
+    for name, shape, gt, off, nbytes in tensors:
+        if name.endswith("_exps.weight") or len(shape) > 2:
+            raise NotImplementedError(f"tensor {name!r} (shape {tuple(shape)}): merged expert tensors are not split back into "
+                                      f"per-expert HF tensors")
+        if hf_layout and name == "rope_freqs.weight":
+            continue
+        rows = None
+        if hf_layout and arch == "llama" and n_head and name.endswith((".attn_q.weight", ".attn_k.weight")):
+            rows = unpermute_rows(shape[0], n_head, n_head if name.endswith(".attn_q.weight") else n_kv).to(device)
+        raw = _host(buf, off, nbytes).to(device)
+        if gt in K_QUANTS:
+            t = ops.dequantize_blocks(gt, raw.view(shape[0], -1), dtype or torch.float32, rows)
+        else:
+            if gt == GGMLType.F32:
+                t = raw.view(torch.float32)
+            elif gt == GGMLType.F16:
+                t = raw.view(torch.float16)
+            elif gt == GGMLType.BF16:
+                t = raw.view(torch.bfloat16)
+            elif gt == GGMLType.Q8_0:
+                b = raw.view(-1, 34)
+                t = b[:, :2].contiguous().view(torch.float16).float() * b[:, 2:].contiguous().view(torch.int8).float()
+            else:
+                raise ValueError(f"tensor {name!r}: ggml type {gt} is not supported")
+            t = t.reshape(shape)
+            if dtype is not None:
+                t = t.to(dtype)
+            if rows is not None:
+                t = t[rows.long()]
+        yield (hf_tensor_name(name) if hf_layout else name), t
+
+
+def load_state_dict(path: str, device="cuda:0", dtype: Optional[torch.dtype] = None) -> Dict[str, torch.Tensor]:
+    """{HF name: tensor} of the whole file (HF row layout)."""
+    return dict(iter_gguf_tensors(path, device, dtype, hf_layout=True))
+
+
+def load_into_model(model: torch.nn.Module, path: str) -> torch.nn.Module:
+    """Load the file's weights into `model` (parameters on a GPU), strict on names and shapes.  A tied lm_head (no
+    `output.weight` in the file) follows token_embd."""
+    ref = next(model.parameters())
+    sd = load_state_dict(path, ref.device, ref.dtype)
+    want = model.state_dict()
+    if "lm_head.weight" in want and "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:
+        sd["lm_head.weight"] = sd["model.embed_tokens.weight"]
+    missing, extra = sorted(set(want) - set(sd)), sorted(set(sd) - set(want))
+    if missing or extra:
+        raise KeyError(f"{path}: tensors missing from the file {missing}, tensors the model does not have {extra}")
+    for k, t in sd.items():
+        if tuple(t.shape) != tuple(want[k].shape):
+            raise ValueError(f"{path}: {k} has shape {tuple(t.shape)}, the model expects {tuple(want[k].shape)}")
+    model.load_state_dict(sd, strict=True)
+    return model

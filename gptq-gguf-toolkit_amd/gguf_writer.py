@@ -253,10 +253,11 @@ class _Lazy:
         self.producer, self.nbytes = producer, nbytes
 
 
-def parse_gguf(path: str):
+def parse_gguf(path: str, mmap: bool = False):
     """-> (kv {key: (value, [value type ids])}, [(name, logical shape (outermost first), ggml type, absolute data
-    offset, n_bytes)], file bytes).  Spec-level reader for this package's tests and the GGUF splitter."""
-    buf = open(path, "rb").read()
+    offset, n_bytes)], file bytes).  Spec-level reader for this package's tests, the GGUF splitter and the loader.
+    mmap: the third item is a read-only np.memmap (uint8) of the file instead of its bytes read into memory."""
+    buf = np.memmap(path, np.uint8, "r") if mmap else open(path, "rb").read()
     pos = 0
 
     def rd(fmt):
@@ -268,7 +269,7 @@ def parse_gguf(path: str):
     def rs():
         nonlocal pos
         n = rd("<Q")
-        s = buf[pos:pos + n].decode("utf-8")
+        s = bytes(buf[pos:pos + n]).decode("utf-8")
         pos += n
         return s
 
@@ -280,7 +281,7 @@ def parse_gguf(path: str):
             return [rv(sub)[0] for _ in range(n)], [t, sub]
         return rd(_SCALAR_FMT[t]), [t]
 
-    assert buf[:4] == GGUF_MAGIC
+    assert bytes(buf[:4]) == GGUF_MAGIC
     pos = 4
     ver, nt, nkv = rd("<I"), rd("<Q"), rd("<Q")
     assert ver == GGUF_VERSION
@@ -299,6 +300,8 @@ def parse_gguf(path: str):
     data0 = (pos + align - 1) // align * align
     tensors = []
     for name, shape, gt, off in infos:
+        if gt not in GGML_QUANT_SIZES:
+            raise ValueError(f"tensor {name!r}: ggml type {gt} is not supported (F32, F16, BF16, Q8_0 and the K-quants are)")
         bs, ts = GGML_QUANT_SIZES[gt]
         tensors.append((name, shape, gt, data0 + off, int(np.prod(shape)) // bs * ts))
     return kv, tensors, buf

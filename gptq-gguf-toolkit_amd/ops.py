@@ -392,6 +392,40 @@ def pack(q_type: int, q, d, s, dmin=None, m=None) -> torch.Tensor:
     return out
 
 
+def unpack(q_type: int, blocks: torch.Tensor):
+    """Inverse of pack: uint8 [R, C/256*type_size] -> (q [R, C], d f16 [R, C/256], s [R, C/G], dmin, m) with the dtypes of the
+    quantize entry points (int8 views of q / s / m for Q3_K / Q6_K, whose dmin / m come back as zeros)."""
+    _need_cuda(blocks)
+    ts = type_info(q_type)["type_size"]
+    assert blocks.dtype == torch.uint8 and blocks.dim() == 2 and blocks.shape[1] % ts == 0
+    blocks = blocks.contiguous()
+    R, C = blocks.shape[0], blocks.shape[1] // ts * 256
+    q, d, s, dmin, m = _alloc_outs(R, C, q_type, blocks.device)
+    check(lib().gq_unpack(int(q_type), _ptr(blocks), R, C, _ptr(q), _ptr(d), _ptr(s), _ptr(dmin), _ptr(m), _stream(blocks)),
+          "gq_unpack")
+    t = _idt(q_type)
+    return q.view(t), d, s.view(t), dmin, m.view(t)
+
+
+def dequantize_blocks(q_type: int, blocks: torch.Tensor, out_dtype=torch.float32,
+                      row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Packed blocks uint8 [R, C/256*type_size] -> weights [R, C] in one pass (gq_dequantize_blocks): bit for bit
+    dequantize(*unpack(blocks)).  row_src (int32 [R] on the device): out[r] = decode(blocks[row_src[r]]); every index
+    must lie in [0, R) -- the kernel does not check."""
+    _need_cuda(blocks, row_src)
+    ts = type_info(q_type)["type_size"]
+    assert blocks.dtype == torch.uint8 and blocks.dim() == 2 and blocks.shape[1] % ts == 0
+    blocks = blocks.contiguous()
+    R, C = blocks.shape[0], blocks.shape[1] // ts * 256
+    if row_src is not None:
+        assert row_src.dtype == torch.int32 and row_src.numel() == R and row_src.device == blocks.device
+        row_src = row_src.contiguous()
+    out = torch.empty(R, C, dtype=out_dtype, device=blocks.device)
+    check(lib().gq_dequantize_blocks(int(q_type), _ptr(blocks), R, C, _ptr(row_src), _ptr(out), _DT[out_dtype],
+                                     _stream(blocks)), "gq_dequantize_blocks")
+    return out
+
+
 def trailing_update(Cm: torch.Tensor, A: torch.Tensor, B: torch.Tensor):
     """Cm -= A @ B (fp32; k-ordered fma chain then one subtraction per element)."""
     _need_cuda(Cm, A, B)

@@ -298,6 +298,24 @@ int gq_dequantize(int q_type, const uint8_t* qweight, const uint16_t* d, const u
 int gq_pack(int q_type, const uint8_t* qweight, const uint16_t* d, const uint8_t* s,
             const uint16_t* dmin, const uint8_t* m, int64_t R, int64_t C, uint8_t* out, void* stream);
 
+/* inverse of gq_pack (nothing in the reference: it reads a .gguf back through transformers' GGUF loader and gguf-py;
+   layouts per llama.cpp ggml-quants.c dequantize_row_q{2..6}_K, get_scale_min_k4).
+   blocks [R, C/256*type_size] -> the five data.pth tensors: one byte per value; int8 in the byte for Q3_K / Q6_K
+   with the +4 / +32 / +32 offsets of the packed form removed; dmin / m are written as zeros for Q3_K / Q6_K and
+   may be NULL there.  gq_pack(gq_unpack(b)) == b for every byte string b (the block layouts use every bit).
+   C % 256 == 0; blocks aligned to 2 (Q3_K, Q6_K), 4 (Q2_K) or 16 (Q4_K, Q5_K) bytes, qweight to 16, s / m to 4. */
+int gq_unpack(int q_type, const uint8_t* blocks, int64_t R, int64_t C,
+              uint8_t* qweight, uint16_t* d, uint8_t* s, uint16_t* dmin, uint8_t* m, void* stream);
+
+/* gq_unpack + gq_dequantize in one pass over the packed bytes, 2 or 4 B/param written and nothing else:
+   out[r, :] = decode(blocks[row_src ? row_src[r] : r, :]), out_dtype GQ_F32 / GQ_F16 / GQ_BF16, out 16-byte aligned.
+   Per value ds = f32(d)*f32(sc), dm = f32(dmin)*f32(mn), w = ds*f32(code) - dm, each operation rounded on its own
+   (quant_utils.py:277-310 on the decoded fields), then one round-to-nearest-even cast.
+   row_src: device int32 [R], a row gather on the packed rows (the q / k rotary un-permute of a .gguf costs
+   nothing), or NULL.  It is trusted like every device pointer: indices are not range-checked. */
+int gq_dequantize_blocks(int q_type, const uint8_t* blocks, int64_t R, int64_t C, const int32_t* row_src,
+                         void* out, int out_dtype, void* stream);
+
 /* C[M,N] (ldc) -= A[M,K] (lda) @ B[K,N] (ldb), fp32, each output a k-ordered fma
    chain from 0 followed by one subtraction: the trailing update of gptq.py:270,
    exposed for tests and benchmarks. */
