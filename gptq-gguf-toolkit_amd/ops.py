@@ -528,3 +528,94 @@ def group_search(x: torch.Tensor, q_type: int, rmin=-1.0, rdelta=0.1, nstep=20, 
           "gq_group_search")
     t = _idt(q_type)
     return gs, gz, d, s.view(t), dmin, m.view(t)
+
+
+# ---- scoring (gq_eval_*): logits [..., V] -> one fp32 value per row ----
+def _collapse(t: torch.Tensor):
+    """(rows, ld) when the leading dimensions of t [..., V] are one run of rows with a single stride, else None."""
+    dims = [(n, s) for n, s in zip(t.shape[:-1], t.stride()[:-1]) if n != 1]
+    for (_, s0), (n1, s1) in zip(dims, dims[1:]):
+        if s0 != n1 * s1:
+            return None
+    rows = 1
+    for n, _ in dims:
+        rows *= n
+    return rows, (dims[-1][1] if dims else t.shape[-1])
+
+
+def _row_blocks(*ts):
+    """The tensors [..., V] of one leading shape, cut into the fewest pieces each of which is [rows, V] with one row
+    stride in every tensor; pieces come in row-major order of the leading shape."""
+    cs = [_collapse(t) for t in ts]
+    if all(c is not None for c in cs):
+        yield cs[0][0], [(t, c[1]) for t, c in zip(ts, cs)]
+        return
+    for subs in zip(*(t.unbind(0) for t in ts)):
+        yield from _row_blocks(*subs)
+
+
+def _logits_ok(*ts):
+    _need_cuda(*ts)
+    for t in ts:
+        if t.dtype not in _DT or t.dim() < 1 or t.stride(-1) != 1 or t.shape[-1] == 0:
+            raise _cabi.GQError(f"eval ops take fp32 / fp16 / bf16 tensors [..., V] with a unit stride over V; got "
+                                f"{t.dtype} {tuple(t.shape)} strides {t.stride()}")
+
+
+def eval_nll(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100, want_lse: bool = False):
+    """F.cross_entropy(logits, labels, reduction="none") in one read of the logits (gq_eval_nll): fp32, shape of labels;
+    0 where labels == ignore_index.  want_lse: also the rows' logsumexp.  Row strides are passed on, nothing is copied.
+    A label outside [0, V) raises GQError (this op waits for the stream to find out)."""
+    _logits_ok(logits)
+    _need_cuda(labels)
+    lead, V = logits.shape[:-1], logits.shape[-1]
+    if tuple(labels.shape) != tuple(lead) or labels.dtype != torch.int64:
+        raise _cabi.GQError(f"eval_nll: labels must be int64 of shape {tuple(lead)}, got {labels.dtype} {tuple(labels.shape)}")
+    lab = labels.contiguous().view(-1)
+    nll = torch.empty(lab.numel(), dtype=torch.float32, device=logits.device)
+    lse = torch.empty_like(nll) if want_lse else None
+    a = 0
+    for rows, ((x, ld),) in _row_blocks(logits):
+        if rows:
+            check(lib().gq_eval_nll(_ptr(x), _DT[x.dtype], rows, V, ld, _ptr(lab[a:a + rows]), int(ignore_index),
+                                    _ptr(nll[a:a + rows]), _ptr(lse[a:a + rows] if want_lse else None), _stream(x)),
+                  "gq_eval_nll")
+        a += rows
+    return (nll.view(lead), lse.view(lead)) if want_lse else nll.view(lead)
+
+
+def eval_kl(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """Per row KL(softmax(target) || softmax(logits)) = F.kl_div(log_softmax(logits), log_softmax(target), log_target=True)
+    summed over V, in one read of both (gq_eval_kl): fp32, the leading shape.  Views are read in place."""
+    _logits_ok(logits, target)
+    if logits.shape != target.shape:
+        raise _cabi.GQError(f"eval_kl: logits {tuple(logits.shape)} and target {tuple(target.shape)} differ in shape")
+    lead, V = logits.shape[:-1], logits.shape[-1]
+    kl = torch.empty(lead, dtype=torch.float32, device=logits.device).view(-1)
+    a = 0
+    for rows, ((x, ld), (t, ldt)) in _row_blocks(logits, target):
+        if rows:
+            check(lib().gq_eval_kl(_ptr(x), _DT[x.dtype], _ptr(t), _DT[t.dtype], rows, V, ld, ldt, _ptr(kl[a:a + rows]),
+                                   _stream(x)), "gq_eval_kl")
+        a += rows
+    return kl.view(lead)
+
+
+def eval_kl_sparse(logits: torch.Tensor, target_vals: torch.Tensor, target_ids: torch.Tensor) -> torch.Tensor:
+    """The same KL over K columns per row: logits.gather(-1, target_ids) against target_vals, both softmaxes over the K
+    entries (gq_eval_kl_sparse; K <= 4096, ids int64 in [0, V)).  fp32, the leading shape."""
+    _logits_ok(logits, target_vals)
+    _need_cuda(target_ids)
+    lead, V, K = logits.shape[:-1], logits.shape[-1], target_vals.shape[-1]
+    if tuple(target_vals.shape[:-1]) != tuple(lead) or target_ids.shape != target_vals.shape or target_ids.dtype != torch.int64:
+        raise _cabi.GQError(f"eval_kl_sparse: target_vals / target_ids must be {tuple(lead)} + (K,), ids int64; got "
+                            f"{tuple(target_vals.shape)} and {target_ids.dtype} {tuple(target_ids.shape)}")
+    tv, ti = target_vals.contiguous().view(-1, K), target_ids.contiguous().view(-1, K)
+    kl = torch.empty(tv.shape[0], dtype=torch.float32, device=logits.device)
+    a = 0
+    for rows, ((x, ld),) in _row_blocks(logits):
+        if rows:
+            check(lib().gq_eval_kl_sparse(_ptr(x), _DT[x.dtype], rows, V, ld, _ptr(tv[a:a + rows]), _DT[tv.dtype],
+                                          _ptr(ti[a:a + rows]), K, _ptr(kl[a:a + rows]), _stream(x)), "gq_eval_kl_sparse")
+        a += rows
+    return kl.view(lead)

@@ -1,0 +1,181 @@
+#!/usr/bin/env python3
+"""Perplexity of a model whose Linear weights come from a per-layer level database or from a `.gguf`: the reference's
+eval/ppleval.py (:25-120 flags, :124-152 load_compressed_weights, :207-229 the result JSON) on the gq_eval_* kernels.
+
+    python -m gptq_gguf_toolkit_amd.ppleval --model_name_or_path HF_DIR --eval_datasets ids.pt --output_file out.json \
+        [--quant_weights_path DB [--quant_config_path FILE] [--quant_default_level N] | --gguf FILE] \
+        [--kl_against none|model|gguf:FILE]
+
+Evaluation data are `.pt` files of [1, L] id tensors (no tokenizer, no download).  Left out: --memory_efficient, wandb,
+the sparse / drop-layer branches, the fast-tokenizer flag.  Beyond the reference: --gguf (weights decoded from the file by
+gguf_loader) and --kl_against (dense KL of the scored model against the unmodified HF model or another .gguf; the target
+is evaluated first and its logits stay on the device in the model dtype)."""
+import argparse
+import glob
+import json
+import os
+import sys
+
+import torch
+
+if __package__ in (None, ""):  # run as a script: make the package importable under its alias
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import gptq_gguf_toolkit_amd  # noqa: F401
+    from gptq_gguf_toolkit_amd import gguf_loader, metrics
+else:
+    from . import gguf_loader, metrics
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser()
+    # Model params
+    p.add_argument("--model_name_or_path", type=str, required=True, help="The name or path to the model being evaluated")
+    # Data params
+    p.add_argument("--sequence_length", default=None, type=int, help="Length of sequences.")
+    p.add_argument("--eval_datasets", nargs="+", type=str, required=True,
+                   help=".pt files of [1, L] token-id tensors used for evaluation")
+    p.add_argument("--eval_batch_size", type=int, default=1, help="Batch size on evaluation")
+    p.add_argument("--eval_tokens", default=524288, type=int, help="Number of tokens for evaluation.")
+    # Quantization params
+    p.add_argument("--quant_weights_path", type=str, default=None, help="Path to quantized weights")
+    p.add_argument("--quant_config_path", type=str, default=None, help="Path to quantization config")
+    p.add_argument("--quant_default_level", type=int, default=0, help="Default quantization level")
+    # Output params
+    p.add_argument("--output_file", type=str, required=True, help="Path to output JSON file for storing results")
+    # Misc params
+    p.add_argument("--dtype", type=str, default="float16", choices=["auto", "float16", "float32", "bfloat16"],
+                   help="dtype to load the model.")
+    p.add_argument("--seed", default=0, type=int, help="Random seed.")
+    p.add_argument("--attn_implementation", type=str, default=None, choices=["eager", "sdpa", "flash_attention_2"],
+                   help="Attention implementation: eager, sdpa, or flash_attention_2")
+    # beyond the reference
+    p.add_argument("--gguf", type=str, default=None, help="take ALL weights from this .gguf (decoded on the GPU)")
+    p.add_argument("--kl_against", type=str, default="none",
+                   help="none | model | gguf:FILE -- also report the dense KL of the scored model against the unmodified "
+                        "HF model or against another .gguf")
+    args = p.parse_args(argv)
+    if args.gguf and args.quant_weights_path:
+        p.error("--gguf and --quant_weights_path are mutually exclusive")
+    if args.kl_against not in ("none", "model") and not (args.kl_against.startswith("gguf:") and args.kl_against[5:]):
+        p.error("--kl_against must be none, model or gguf:FILE")
+    for name in args.eval_datasets:  # refused BEFORE any work
+        if not os.path.isfile(name):
+            p.error(f"eval_datasets must be a .pt file of token-id tensors (got {name!r}); "
+                    "dataset downloads are not part of this package")
+    return args
+
+
+def level_file(layer_dir: str, level) -> str:
+    """The weight file of `level` in one layer directory of the database.  `<level>.pth` as the reference writes and reads
+    it (ppleval.py:138), else the names gguf_splitter's HF side writes (GGUFSplitter.bitwidth_prefix): `<bpw>-<Qn_K>.pth`
+    with bpw an integer ("4-Q4_K") or, with --exact, a fraction ("4.5-Q4_K").  `level` may be the whole stem ("4-Q4_K") or
+    its number alone ("4", 4, "4.5"), which then has to pick exactly one file."""
+    stem = str(level).strip()
+    try:
+        num = float(stem)
+        stem = str(int(num)) if num == int(num) else str(num)
+    except ValueError:
+        pass
+    exact = os.path.join(layer_dir, f"{stem}.pth")
+    if os.path.isfile(exact):
+        return exact
+    typed = sorted(glob.glob(os.path.join(glob.escape(layer_dir), f"{glob.escape(stem)}-*.pth")))
+    if len(typed) == 1:
+        return typed[0]
+    raise FileNotFoundError(f"{layer_dir}: no weight file for level {level!r} (looked for {stem}.pth and {stem}-<type>.pth, "
+                            f"found {[os.path.basename(f) for f in typed]})")
+
+
+def load_compressed_weights(model, compressed_weights_path, compressed_config_path=None, default_level=0, load=None):
+    """ppleval.py:124-152: with a config (lines `layer_name: level`) exactly the listed layers get the weights of their
+    level, without one every layer directory of the database gets `default_level`.  load(path, device) -> tensor
+    (default torch.load onto the layer's device)."""
+    if load is None:
+        load = lambda path, device: torch.load(path, map_location=device)  # noqa: E731
+    if compressed_config_path:
+        with open(compressed_config_path) as f:
+            todo = [tuple(x.strip() for x in line.split(":")) for line in f if line.strip()]
+    else:
+        todo = [(n, default_level) for n in sorted(os.listdir(compressed_weights_path))
+                if os.path.isdir(os.path.join(compressed_weights_path, n))]
+    for layer_name, level in todo:
+        layer = model.get_submodule(layer_name)
+        w = load(level_file(os.path.join(compressed_weights_path, layer_name), level), layer.weight.device)
+        if tuple(w.shape) != tuple(layer.weight.shape):
+            raise ValueError(f"{layer_name}: level {level!r} has shape {tuple(w.shape)}, the model expects "
+                             f"{tuple(layer.weight.shape)}")
+        layer.weight.data = w.to(layer.weight.dtype)
+    return model
+
+
+def load_hf_model(args, device):
+    import transformers
+    from transformers import AutoModelForCausalLM
+    dtype = args.dtype if args.dtype == "auto" else getattr(torch, args.dtype)
+    dtype_kw = "dtype" if int(transformers.__version__.split(".")[0]) >= 5 else "torch_dtype"  # renamed in 5.x
+    model = AutoModelForCausalLM.from_pretrained(args.model_name_or_path, low_cpu_mem_usage=True,
+                                                 attn_implementation=args.attn_implementation, **{dtype_kw: dtype})
+    model.config.use_cache = False
+    return model.to(device).eval()
+
+
+def apply_weights(model, args):
+    """The scored model: --gguf, the level database, or the HF weights as loaded."""
+    if args.gguf:
+        gguf_loader.load_into_model(model, args.gguf)
+    elif args.quant_weights_path:
+        load_compressed_weights(model, args.quant_weights_path, args.quant_config_path, args.quant_default_level)
+    return model
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    assert torch.cuda.is_available(), "ppleval needs a GPU (there is no CPU path)"
+    device = torch.device("cuda")
+    metrics.fix_seed(args.seed)
+    model = load_hf_model(args, device)
+    args.sequence_length = args.sequence_length or model.config.max_position_embeddings
+    datasets = [metrics.load_eval_data(n, args.eval_tokens, args.sequence_length) for n in args.eval_datasets]
+
+    targets = None
+    if args.kl_against != "none":  # the target first: its logits stay on the device, then the scored weights are loaded
+        if args.kl_against.startswith("gguf:"):
+            gguf_loader.load_into_model(model, args.kl_against[5:])
+        targets = [metrics.collect_target_logits(model, d) for d in datasets]
+        if args.kl_against.startswith("gguf:"):  # back to the HF weights a level database is laid over
+            model = load_hf_model(args, device)
+    apply_weights(model, args)
+
+    results = {
+        "model_name_or_path": args.model_name_or_path,
+        "evaluation_config": {"sequence_length": args.sequence_length, "eval_datasets": args.eval_datasets,
+                              "eval_batch_size": args.eval_batch_size, "eval_tokens": args.eval_tokens, "seed": args.seed,
+                              "dtype": str(args.dtype if args.dtype == "auto" else getattr(torch, args.dtype)),
+                              "attn_implementation": args.attn_implementation},
+        "compression_config": {"quant_weights_path": args.quant_weights_path, "quant_config_path": args.quant_config_path,
+                               "quant_default_level": args.quant_default_level, "gguf": args.gguf},
+        "perplexity_results": {},
+    }
+    print("-" * 10)
+    print("Test perplexities")
+    for name, data in zip(args.eval_datasets, datasets):
+        ppl = metrics.compute_perplexity(model, data, batch_size=args.eval_batch_size)
+        print(f"{name}: {ppl:.2f}")
+        results["perplexity_results"][name] = float(ppl)
+    if targets is not None:
+        results["evaluation_config"]["kl_against"] = args.kl_against
+        results["kl_results"] = {}
+        print(f"KL divergence against {args.kl_against}")
+        for name, data, tl in zip(args.eval_datasets, datasets, targets):
+            kl = metrics.compute_kl_div(model, data, tl, batch_size=args.eval_batch_size)
+            print(f"{name}: {kl:.6f}")
+            results["kl_results"][name] = float(kl)
+    print("-" * 10)
+    with open(args.output_file, "w") as f:
+        json.dump(results, f, indent=2)
+    print(f"Results saved to {args.output_file}")
+    return results
+
+
+if __name__ == "__main__":
+    main()

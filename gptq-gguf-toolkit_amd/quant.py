@@ -20,11 +20,11 @@ import torch.distributed as dist
 if __package__ in (None, ""):  # run as a script: make the package importable under its alias
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import gptq_gguf_toolkit_amd  # noqa: F401
-    from gptq_gguf_toolkit_amd import dist_utils
+    from gptq_gguf_toolkit_amd import dist_utils, metrics
     from gptq_gguf_toolkit_amd.quant_utils import GGMLQuantizationType
     from gptq_gguf_toolkit_amd.quantizer import Quantizer
 else:
-    from . import dist_utils
+    from . import dist_utils, metrics
     from .quant_utils import GGMLQuantizationType
     from .quantizer import Quantizer
 
@@ -83,6 +83,9 @@ def parse_args(argv=None):
                         "eager modules): exact (default) = rotary embedding, SwiGLU and RMSNorm, bit-identical to HF eager "
                         "(RMSNorm checked at run time); all (or the bare flag) = also the free-order RMSNorm kernel, "
                         "<= 2 ulp, where the exact one is not verified; off = none")
+    p.add_argument("--eval_data", type=str, default=None,
+                   help="a .pt file of [1, L] token-id tensors: what --eval_perplexity scores the quantized model on (the "
+                        "reference downloads WikiText-2 there)")
     return p.parse_args(argv)
 
 
@@ -121,9 +124,12 @@ def load_calibration(path_or_name, num_tokens, seq_len, tokenizer):
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.eval_perplexity:  # refused BEFORE any work (the reference evaluates WikiText-2 here: a dataset download)
+    if args.eval_perplexity and not args.eval_data:  # refused BEFORE any work (the reference evaluates WikiText-2 here: a dataset download)
         raise SystemExit("--eval_perplexity is not available in this package (WikiText-2 needs a dataset download); "
                          "run the quantization without it and evaluate the saved model separately")
+    if args.eval_perplexity and not os.path.isfile(args.eval_data):  # also before any work
+        raise SystemExit(f"--eval_data must be a .pt file of token-id tensors (got {args.eval_data!r}); "
+                         "dataset downloads are not part of this package")
     if dist.is_available() and "RANK" in os.environ:
         dist.init_process_group(backend="nccl", init_method="env://")  # RCCL
     try:
@@ -147,7 +153,7 @@ def _run(args):
     if not args.cpu_offload_modules:
         model = model.to(device)
     tokenizer = None
-    if not os.path.isfile(args.calibration_data) or args.eval_perplexity:
+    if not os.path.isfile(args.calibration_data):
         tokenizer = AutoTokenizer.from_pretrained(args.tokenizer_name or args.model_name_or_path, use_fast=False)
     args.calibration_sequence_length = args.calibration_sequence_length or model.config.max_position_embeddings
     data = load_calibration(args.calibration_data, args.calibration_tokens, args.calibration_sequence_length, tokenizer)
@@ -178,6 +184,15 @@ def _run(args):
     t2 = time.perf_counter()
     dist_utils.print_on_main(f"Quantization took {(t2 - t1)} s.")
     dist_utils.barrier()
+
+    if args.eval_perplexity and dist_utils.is_main():  # reference quant.py:258-267, on --eval_data instead of WikiText-2
+        model = model.to(device)
+        metrics.fix_seed(args.seed)
+        name = os.path.basename(args.eval_data)
+        print(f"Evaluating perplexity on {name}...")
+        eval_data = metrics.load_eval_data(args.eval_data, None, args.eval_sequence_length, what="eval_data")[:100]
+        ppl = metrics.compute_perplexity(model, eval_data)
+        print(f"Perplexity on {name}: {ppl:.3f}")
 
 
 if __name__ == "__main__":

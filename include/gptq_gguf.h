@@ -316,6 +316,34 @@ int gq_unpack(int q_type, const uint8_t* blocks, int64_t R, int64_t C,
 int gq_dequantize_blocks(int q_type, const uint8_t* blocks, int64_t R, int64_t C, const int32_t* row_src,
                          void* out, int out_dtype, void* stream);
 
+/* ---- scoring a model (evopress/src/metrics.py, quant/gptq/src/metrics.py): the tail of every evaluated sequence is a
+   logits matrix [T, V], row t at logits + t * ld elements (ld >= V; rows need element alignment only), dtype GQ_F32 /
+   GQ_F16 / GQ_BF16.  Each entry point reads every operand ONCE (online softmax, fp32 sums, the last step of a row in fp64)
+   and writes one fp32 value per row; no atomics, a row's value does not depend on the launch.  Special values as in torch:
+   a NaN in a row gives NaN, -inf logits are legal, a row of -inf only gives NaN.
+
+   replaces metrics.py:25-28 per row (F.cross_entropy(logits, labels, reduction="none"), no shifted copy):
+     nll[t] = logsumexp(logits[t, :]) - logits[t, labels[t]];  0 where labels[t] == ignore_index;  +inf on a -inf logit.
+   labels: int64 [T].  lse (fp32 [T], may be NULL) receives the row's logsumexp, ignored rows included.  A label outside
+   [0, V) that is not ignore_index is never read: its nll is NaN and the call returns GQ_E_BAD_SHAPE.  To report that, this
+   entry point -- unlike every other one -- WAITS for `stream` before it returns. */
+int gq_eval_nll(const void* logits, int dtype, int64_t T, int64_t V, int64_t ld, const int64_t* labels, int64_t ignore_index,
+                float* nll, float* lse, void* stream);
+
+/* replaces evopress/src/metrics.py:70-75 per row (F.kl_div(log_softmax(logits), log_softmax(target), log_target=True)
+   before its "batchmean"):  kl[t] = sum_v p_v (log p_v - log q_v),  p = softmax(target[t, :]), q = softmax(logits[t, :]).
+   One pass over both rows with five running values (m_t, S_t, A = sum e^(t - m_t) (t - x), m_x, S_x):
+   KL = A / S_t - lse_t + lse_x.  Operands of one dtype whose rows sit at equal offsets from a 16-byte boundary are read
+   with 16-byte loads, anything else element by element. */
+int gq_eval_kl(const void* logits, int dtype, const void* target, int target_dtype, int64_t T, int64_t V, int64_t ld,
+               int64_t ld_target, float* kl, void* stream);
+
+/* replaces evopress/src/metrics.py:102-112 per row: the same KL between target_vals[t, :] and logits[t, target_ids[t, :]],
+   both softmaxes over the K gathered entries only (a repeated id counts as often as it appears).  target_vals [T, K] in
+   target_dtype and target_ids int64 [T, K] are contiguous; 1 <= K <= 4096.  An id outside [0, V) is not read: its row is NaN. */
+int gq_eval_kl_sparse(const void* logits, int dtype, int64_t T, int64_t V, int64_t ld, const void* target_vals, int target_dtype,
+                      const int64_t* target_ids, int64_t K, float* kl, void* stream);
+
 /* C[M,N] (ldc) -= A[M,K] (lda) @ B[K,N] (ldb), fp32, each output a k-ordered fma
    chain from 0 followed by one subtraction: the trailing update of gptq.py:270,
    exposed for tests and benchmarks. */
