@@ -42,14 +42,12 @@ extern thread_local char g_err[512];
 // and read per call with opt() (a relaxed atomic load).  X(name, default, smallest, largest accepted value).
 #define GQ_OPTION_LIST(X)                                                                                                         \
     /* K1 SYRK */                                                                                                                 \
-    X(syrk_128, 0, 0, 1)          /* 1: the 128x128-tile kernel for every shape */                                                \
     X(syrk_image, 0, 0, 1)        /* 1: re-laid-out operand image + syrk16_256e_kernel instead of reading X in place */           \
     X(syrk_nosplit, 0, 0, 1)      /* 1: no K-split of the last, partial round of tiles */                                         \
-    X(syrk_persist, 1, 0, 1)      /* 0: one tile per workgroup instead of the persistent launch with XCD rendezvous */            \
     X(syrk_wgs, 0, 0, 4096)          /* resident workgroups of the persistent launch (0: one per CU) */                           \
     X(syrk_ck, 256, 0, 65536)     /* half-stages between the soft XCD rendezvous inside a tile (a power of two >= 16; 0: none) */  \
     X(syrk_gw, 4, 1, 32)          /* width in tiles of the super-tile an XCD's 32 workgroups share (1, 2, 4, 8, 16, 32; 32 / gw rows) */ \
-    X(syrk_w4, 1, 0, 1)           /* 0: eight waves with 128x64 wave tiles (syrk16_256n_kernel) instead of four with 128x128 */   \
+    X(syrk_w4, 1, 1, 1)           /* always 1, kept because the benchmark reads it: four waves (the eight-wave form is gone) */   \
     /* K3 Cholesky chain */                                                                                                       \
     X(chol_3p_min, 1792, 0, 1048576)    /* smallest half of a recursion node that runs on the image GEMMs (0: never) */           \
     X(chol_planes, 2, 2, 3)       /* 2: row-scaled fp16 x 2 images, 3: exact bf16 x 3 */                                          \
@@ -62,15 +60,11 @@ extern thread_local char g_err[512];
     /* K5/K6 column loop */                                                                                                       \
     X(no_lookahead, 0, 0, 1)      /* 1: trailing update after every block, no chained far update */                               \
     X(la, 8, 2, 8)                /* blocks per look-ahead super-block (even, 2..8) */                                            \
-    X(seg_pair, 1, 0, 1)          /* 0: one column-loop launch per 128-column block instead of one per 256-column pair */          \
-    X(near_classic, 0, 0, 1)      /* 1: a near launch after every block instead of the pair form */                               \
-    X(near_quad, 0, 0, 1)         /* 1: near launches after every second pair */                                                  \
+    X(near_classic, 0, 0, 0)      /* always 0, kept because the benchmark reads it: the pair form (the switch is gone) */         \
     X(near64_maxn, 768, 0, 1048576)     /* widest near update that takes gemm32_near256_kernel */                                 \
     X(far_sync, 0, 0, 1)          /* 1: far updates on the caller's stream (no helper stream) */                                  \
     X(far_async_max_rows, 8192, 0, 1073741824) X(far_async_min_sb, 8, 0, 1048576) /* shape window of the helper-stream form */    \
     X(far_wgs, 192, 1, 4096)         /* resident workgroups of the helper's persistent far GEMM */                                \
-    X(far_bdma, 1, 0, 1)          /* 0: the far GEMM B operand through registers + ds_write instead of LDS-DMA */                 \
-    X(chain_generic, 0, 0, 1)     /* 1: the generic chained kernel instead of the dedicated far kernel */                         \
     X(gemm32_64_max, 256, 0, 1073741824)   /* problems with fewer 128-tiles than this take 64x64 tiles (0: never) */              \
     /* K4 */                                                                                                                      \
     X(ss_wide, -1, -1, 2)          /* scale-search mapping: -1 by size, 1 eight lanes, 0 one lane, 2 a lane pair per group */     \

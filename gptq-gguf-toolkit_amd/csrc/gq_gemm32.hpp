@@ -543,9 +543,9 @@ __global__ __launch_bounds__(512, 2) void gemm32_chain_full_persistent_kernel(fl
     }
 }
 
-// r04, default (option far_bdma): the B chunk by LDS-DMA, A through registers -- the hybrid of the two forms: far alone 0.752 ->
-// 0.761 of the fp32 peak, the 4096 x 14336 column loop 11.8 -> 11.5 ms, the far launches inside a step 0.416 -> 0.44 (sum of
-// durations), bit-identical (test_trailing_update_kernel_choices_are_bit_identical).
+// r04: the B chunk by LDS-DMA, A through registers -- the hybrid of the two forms: far alone 0.752 -> 0.761 of the fp32 peak,
+// the 4096 x 14336 column loop 11.8 -> 11.5 ms, the far launches inside a step 0.416 -> 0.44 (sum of durations), bit-identical.
+// B through registers + ds_write remains for a B whose rows are not 16-byte aligned.
 // (Measured and removed, r03/r04: two LDS-DMA forms of the far update -- a four-slot ring with one workgroup per CU,
 // 6 % slower than the register-staged chunks above although it issues a tenth of the staging instructions, and a
 // two-slot ring with two workgroups per CU, +1.6 % -- DESIGN.md K6; they live in the git history.)
@@ -563,8 +563,8 @@ inline int launch_gemm32_chain_full(float* Cmat, int64_t ldc, const float* A, in
     const int64_t ntx = N / 128, ntiles = ntx * (M / 128);
     // (measured and removed, r04: EVERY far GEMM as a persistent launch of 256 workgroups -- no workgroup dispatch between tiles --:
     // far alone 0.766-0.770 against 0.760-0.767, the step 91.2-91.8 against 90.0-90.8 ms, the Mixtral block 317 against 314 ms)
-    // option far_bdma: the B operand by LDS-DMA (16-byte aligned rows: ldb % 4 == 0 and a 16-byte aligned B)
-    const bool bdma = opt(OPT_far_bdma) != 0 && ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(B) % 16 == 0) && 31 * ldb * 4 < (int64_t)1 << 31;
+    // the B operand by LDS-DMA needs 16-byte aligned rows: ldb % 4 == 0 and a 16-byte aligned B
+    const bool bdma = ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(B) % 16 == 0) && 31 * ldb * 4 < (int64_t)1 << 31;
     if (bdma) {
         static std::atomic<bool> attr_b{false};
         if (!attr_b) {
@@ -759,8 +759,7 @@ inline int launch_gemm32_ts(float* Cmat, int64_t ldc, const float* A, int64_t ld
                             int64_t N, int64_t K, hipStream_t st) {
     // whole tiles only (every GPTQ / Cholesky shape of a 128-multiple Linear): the unpredicated kernel
     if constexpr (CHAIN == 128 && TS == 128 && !TRANS_B && MODE == 0 && !LOWER && KR == 0) {
-        const bool generic = opt(OPT_chain_generic) != 0;  // the generic chained kernel
-        if (!generic && M % TS == 0 && N % TS == 0) return launch_gemm32_chain_full<CHAIN>(Cmat, ldc, A, lda, B, ldb, M, N, K, st);
+        if (M % TS == 0 && N % TS == 0) return launch_gemm32_chain_full<CHAIN>(Cmat, ldc, A, lda, B, ldb, M, N, K, st);
     }
     if (M % TS == 0 && N % TS == 0 && K % TK == 0 && ldc % 4 == 0)
         return launch_gemm32_full<TRANS_B, MODE, LOWER, KR, CHAIN, TS, true>(Cmat, ldc, A, lda, B, ldb, M, N, K, st);

@@ -525,8 +525,9 @@ static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_typ
     // errors to its partner (the odd block of the group) in the column-loop kernel's epilogue; after the odd block ONE
     // chained launch (K = 256, chain 128) brings both blocks' errors to the rest of the super-block.  Per element the
     // same subtractions in the same order as after-every-block updates (bit-identical: the parity tests run both);
-    // 3 launches per super-block instead of 7.  Option near_classic: one launch after every block (r02).
-    const bool pair_look = lookahead && !opt(OPT_near_classic) && la % 2 == 0 &&
+    // 3 launches per super-block instead of 7.  One launch after every block (r02) remains for uniform groups that do not
+    // divide 256.
+    const bool pair_look = lookahead && la % 2 == 0 &&
                            (!uni || uni->group <= 0 || 256 % uni->group == 0);
     const int64_t ldE = lookahead ? (int64_t)LA * B : B;
     float* Err0 = reinterpret_cast<float*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
@@ -574,7 +575,6 @@ static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_typ
                                    hipFuncAttributeMaxDynamicSharedMemorySize, SEG_LDS_BYTES));
         seg_attr = true;
     }
-    const bool seg_pair = opt(OPT_seg_pair) != 0;
     bool walked_by_partner = false;  // this block's columns were walked by the previous (even) block's launch
     for (int64_t c1 = 0; c1 < C; c1 += B) {  // gptq.py:222
         const int64_t c2 = c1 + B < C ? c1 + B : C;
@@ -619,7 +619,7 @@ static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_typ
             const float* srcp = single ? (W + a) : (Wblk + (a - c1));
             const int64_t ld_src = single ? C : B;
             // the partner block in the same launch (it is a whole single segment too: B == SEG, c2 + B <= C)
-            const int npair = (unext && seg_pair && !uni && B == SEG) ? 2 : 1;
+            const int npair = (unext && !uni && B == SEG) ? 2 : 1;
             walked_by_partner = npair == 2;
             {
                 ProfScope ps(PT_GPTQ_SEGMENT, st);
@@ -660,11 +660,10 @@ static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_typ
             // (23.5 vs 17.3 us per launch).  A rank-128 update moves 16 B of operands L2 -> LDS per output element for
             // 256 flops at 64 x 64 tiles: it is L2-bandwidth-bound near 50 TFLOP/s whatever the schedule.)
             if (pair_look) {
-                // GQ_NEAR_QUAD=1 (measured, off): a third level -- pair -> the quad's other pair (K = 256, N = 256), quad -> the
-                // rest of the super-block (K = 512, N = 512): same flops, deeper K on fewer tiles: 1.24 vs 1.05 ms of near
-                // launches for 4096 x 14336
-                const bool quad = opt(OPT_near_quad) != 0;
-                if ((pos & 1) && !quad) {  // end of a 256-group: both blocks' errors, in order, to the rest of the super-block
+                // (measured, 1.24 vs 1.05 ms of near launches for 4096 x 14336, removed: a third level -- pair -> the
+                // quad's other pair (K = 256, N = 256), quad -> the rest of the super-block (K = 512, N = 512): same flops,
+                // deeper K on fewer tiles)
+                if (pos & 1) {  // end of a 256-group: both blocks' errors, in order, to the rest of the super-block
                     ProfScope ps(PT_TRAILING, st);
                     // up to GQ_NEAR64_MAXN columns: 64x64 tiles with the K = 256 panels whole in LDS (gemm32_near256_kernel)
                     const int64_t near64_maxn = opt(OPT_near64_maxn);
@@ -673,17 +672,6 @@ static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_typ
                             return rc;
                     } else if ((rc = launch_gemm32<false, 0, false, 0, LA_B>(W + c2, C, Err + (pos - 1) * B, ldE,
                                                                              U + (c1 - B) * C + c2, C, R, S1 - c2, 2 * B, st)))
-                        return rc;
-                } else if ((pos & 3) == 1) {  // first pair of a 512-column quad: its two blocks' errors to the quad's other pair
-                    const int64_t n = (c2 + 2 * B < S1) ? 2 * B : S1 - c2;
-                    ProfScope ps(PT_TRAILING, st);
-                    if ((rc = launch_gemm32<false, 0, false, 0, LA_B>(W + c2, C, Err + (pos - 1) * B, ldE, U + (c1 - B) * C + c2, C, R, n,
-                                                                      2 * B, st)))
-                        return rc;
-                } else if ((pos & 3) == 3) {  // end of a quad: its four blocks' errors, in order, to the rest of the super-block
-                    ProfScope ps(PT_TRAILING, st);
-                    if ((rc = launch_gemm32<false, 0, false, 0, LA_B>(W + c2, C, Err + (pos - 3) * B, ldE, U + (c1 - 3 * B) * C + c2, C, R,
-                                                                      S1 - c2, 4 * B, st)))
                         return rc;
                 }
                 continue;

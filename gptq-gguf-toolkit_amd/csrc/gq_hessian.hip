@@ -96,7 +96,7 @@ struct SyrkProblem {
     int64_t C, Tp;
     float beta, alpha;
     int tile_begin, nt;
-    // syrk16_256n_kernel only: X given as separate blocks of hs_per_seg * 32 tokens each (the per-sample activation
+    // syrk16_256w_kernel only: X given as separate blocks of hs_per_seg * 32 tokens each (the per-sample activation
     // tensors of the forward hooks, read where they lie); segs[k] = device address of block k.  0: Xt is contiguous.
     const uint64_t* segs;
     int hs_per_seg;
@@ -115,12 +115,12 @@ struct SyrkGroup {
     // row x holds the tiles workgroups with blockIdx % 8 == x (= XCD x) process, in order
     const uint32_t* table;
     int per_xcd;
-    // syrk16_256n_kernel only (nullptr: none): K-split of the tiles of the last, partial round.  aux[i] belongs to
+    // syrk16_256w_kernel only (nullptr: none): K-split of the tiles of the last, partial round.  aux[i] belongs to
     // table[i]: 0xffffffff = the whole token range, H updated in the epilogue; else slot << 12 | part << 6 | nparts
     // = tokens [part, part+1) * T / nparts (in units of 128), raw fp32 sums stored to partial[slot] (256 x 256)
     const uint32_t* aux;
     float* partial;
-    // syrk16_256n_kernel, persistent launch (one workgroup per CU walks its XCD's list): bar[x] counts the workgroups
+    // syrk16_256w_kernel, persistent launch (one workgroup per CU walks its XCD's list): bar[x] counts the workgroups
     // of XCD x that finished a round; a round starts when all of them have, so the 32 tiles an XCD works on at a
     // time stay in step and share their 12 operand panels through the XCD's L2.  nullptr: one tile per workgroup.
     unsigned* bar;
@@ -538,348 +538,22 @@ __global__ __launch_bounds__(512, 2) void syrk16_256e_kernel(const SyrkGroup grp
     }  // tile loop
 }
 
-// -------------- 16-bit SYRK, 256x256 tiles, NATURAL activation layout (no re-layout pass), gfx950 transpose reads
-// Same tile / wave shape, ring, hand-ordered stream and tile table as syrk16_256e_kernel, but the ring slots hold
-// X as it lies in memory -- [32 tokens][256 channels] per operand, 512-byte rows -- and the MFMA fragments are
-// assembled by ds_read_b64_tr_b16: per 16-lane group, lane j passes the address of 4 consecutive channels of token
-// row j>>2 and receives channel j of that 4x16 block, i.e. 4 consecutive tokens of one channel; two reads (token
-// rows +0..3 and +4..7) are the 8-deep k-slice of one lane of a 16x16x32 operand (profiles/micro/tr_read_probe.hip).
+// -------------- 16-bit SYRK, 256x256 tiles, NATURAL activation layout (no re-layout pass), FOUR waves, 128 x 128 wave tiles
+// Same ring size, tile table and v_mfma_f32_16x16x32 as syrk16_256e_kernel, but the four ring slots hold X as it lies in
+// memory -- [32 tokens][256 channels] per operand, 512-byte rows, filled by 1 KiB global_load_lds pieces -- and the MFMA
+// fragments are assembled by ds_read_b64_tr_b16: per 16-lane group, lane j passes the address of 4 consecutive channels of
+// token row j>>2 and receives channel j of that 4x16 block, i.e. 4 consecutive tokens of one channel; two reads (token rows
+// +0..3 and +4..7) are the 8-deep k-slice of one lane of a 16x16x32 operand (profiles/micro/tr_read_probe.hip).
 // Bank conflicts: the 8 rows one instruction touches are 512 bytes apart; the 32-byte fragment slot F of row r is
 // therefore stored at slot F ^ g(r), g(r) = (r & 3) | ((r >> 3) & 1) << 2 (conflict-free, tr_read_banks.hip) -- the
-// permutation is applied by the DMA source addresses, the fragment address is base ^ (i << 5).
-// Per k32 step: 32 MFMAs; fragments a0,b0..b3,a1,a2 of the NEXT half-stage are read behind MFMAs 12..25 into the
-// other register set, a3..a7 of the CURRENT one behind MFMAs 0..9 (single set) -- never more than 15 LDS reads in
-// flight (lgkmcnt is 4 bits).  Requires T % 128 == 0 (whole ring turns); other T take the re-layout path.
-// (Measured and removed, r04, profiles/r04_syrk_stagger_ab.txt: waves 4-7 issuing their DMA pieces behind the step's last
-// MFMAs instead of its middle -- 1.21 vs 1.24 PFLOP/s, matrix pipe 76.5 vs 80.2 % busy; s_setprio 1 for waves 4-7: no change.)
-template <bool BF16>
-__global__ __launch_bounds__(512, 2) void syrk16_256n_kernel(const SyrkGroup grp) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wid >> 2, wn = wid & 3;
-    int round = 0;
-    for (int slot = (int)(blockIdx.x >> 3); slot < grp.per_xcd; slot += (int)(gridDim.x >> 3), ++round) {
-    if (grp.bar && round > 0) {  // XCD-wide rendezvous between rounds (persistent launch)
-        if (tid == 0) {
-            unsigned* b = grp.bar + (blockIdx.x & 7);
-            __hip_atomic_fetch_add(b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned want = (unsigned)round * (gridDim.x >> 3);
-            // a SOFT rendezvous (performance only, results do not depend on it): give up after ~30 us, so that a
-            // workgroup whose peers are not resident (another process on the same GPU) can never wait for ever
-            for (int spin = 0; spin < 64 && __hip_atomic_load(b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want; ++spin)
-                __builtin_amdgcn_s_sleep(16);
-        }
-    }
-    const uint32_t ent = (uint32_t)__builtin_amdgcn_readfirstlane((int)grp.table[(blockIdx.x & 7) * grp.per_xcd + slot]);
-    if (ent == 0xffffffffu) {
-        if (grp.bar) continue;  // keeps taking part in the rendezvous
-        break;
-    }
-    const uint32_t aux = grp.aux ? (uint32_t)__builtin_amdgcn_readfirstlane((int)grp.aux[(blockIdx.x & 7) * grp.per_xcd + slot])
-                                 : 0xffffffffu;
-    __syncthreads();
-    const SyrkProblem& P = grp.p[ent >> 24];
-    const int64_t ti = (ent >> 12) & 0xfff, tj = ent & 0xfff;
-    const int64_t C = P.C;
-    // token range of this unit, in units of 128 tokens (one turn of the ring): all of them, or part k of n
-    int64_t u0 = 0, u1 = P.Tp / (4 * SK);      // Tp = T here
-    if (aux != 0xffffffffu) {
-        const int64_t np = aux & 63, kp = (aux >> 6) & 63;
-        u0 = kp * u1 / np;
-        u1 = (kp + 1) * (P.Tp / (4 * SK)) / np;
-    }
-    const int nhs = (int)((u1 - u0) * 4);
-    const unsigned lds0 = (unsigned)(uintptr_t)smem;
-    // ---- DMA: waves 0-3 bring the A image (channels 256 ti ..), waves 4-7 the B image; wave w & 3 owns token rows
-    // 8 (w & 3) .. +7 of every half-stage as four 1 KiB pieces of two rows each
-    const int op = wid >> 2, rb = 8 * (wid & 3);
-    const int64_t hstride = 32 * C * 2;        // bytes per half-stage
-    const int64_t colofs = (op ? tj : ti) * 512;
-    const char* gsrc = reinterpret_cast<const char*>(P.Xt) + colofs + u0 * 4 * hstride;
-    // segmented X: half-stage (u0 * 4 + h) lies in block (..) / hs_per_seg at row 32 * ((..) % hs_per_seg)
-    int hsps = P.hs_per_seg, seg_within = 0;
-    const uint64_t* segp = P.segs;
-    const char* segbase = nullptr;
-    if (hsps) {
-        const int h0 = (int)(u0 * 4);
-        segp += h0 / hsps;
-        seg_within = h0 % hsps;
-        segbase = reinterpret_cast<const char*>(sload64_now(segp)) + colofs;
-        gsrc = segbase + (int64_t)seg_within * hstride;
-    }
-    asm volatile("" : "+s"(hsps), "+s"(segp));  // opaque SGPR values: never re-loaded from the kernel arguments
-    unsigned voff0, voff1, voff2, voff3;
-    {
-        const int hrow = lane >> 5, s16 = lane & 31;
-#define GQ_NVOFF(u)                                                                                   \
-        ([&] {                                                                                        \
-            const int r_ = rb + 2 * (u) + hrow;                                                       \
-            const int g_ = (r_ & 3) | (((r_ >> 3) & 1) << 2);                                         \
-            return (unsigned)(r_ * C * 2) + (unsigned)((((s16 >> 1) ^ g_) << 5) + ((s16 & 1) << 4));  \
-        }())
-        voff0 = GQ_NVOFF(0); voff1 = GQ_NVOFF(1); voff2 = GQ_NVOFF(2); voff3 = GQ_NVOFF(3);
-#undef GQ_NVOFF
-    }
-    const unsigned ldsw = lds0 + (unsigned)(op * 16384 + rb * 512);
-    int hnext = 0;
-    const char* gbase = gsrc;
-#define GQ_NDL(vo, slot_, u) GQ_NDL_(vo, slot_, u)
-#define GQ_NDL_(vo, slot_, u)                                                                         \
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"                      \
-                 :: "v"(vo), "s"(gbase), "s"(ldsw + (unsigned)((slot_) * S_BUF_BYTES + (u) * 1024)) : "memory")
-#define GQ_NADV()                                                                                     \
-    do {                                                                                              \
-        if (hnext + 1 < nhs) {                                                                        \
-            ++hnext;                                                                                  \
-            if (hsps) {                                                                               \
-                if (++seg_within == hsps) {                                                           \
-                    seg_within = 0;                                                                   \
-                    ++segp;                                                                           \
-                    segbase = reinterpret_cast<const char*>(sload64_now(segp)) + colofs;              \
-                }                                                                                     \
-                gbase = segbase + (int64_t)seg_within * hstride;                                      \
-            } else {                                                                                  \
-                gbase = gsrc + (int64_t)hnext * hstride;                                              \
-            }                                                                                         \
-        }                                                                                             \
-    } while (0)
-    // ---- fragment addresses (see header): lane = (k-group kc, row-in-group q, 8-byte chunk ch)
-    unsigned bAlo, bAhi, bBlo, bBhi;
-    {
-        const int kc = lane >> 4, q = (lane & 15) >> 2, ch = lane & 3;
-        const int r = 8 * kc + q, g = q | ((kc & 1) << 2);
-        bAlo = lds0 + (unsigned)(r * 512 + (((wm * 8) | g) << 5) + ch * 8);
-        bBlo = lds0 + 16384u + (unsigned)(r * 512 + ((((wn << 2)) ^ g) << 5) + ch * 8);
-        bAhi = bAlo + 65536u;
-        bBhi = bBlo + 65536u;
-    }
-    f32x4 c00, c01, c02, c03, c10, c11, c12, c13, c20, c21, c22, c23, c30, c31, c32, c33, c40, c41, c42, c43, c50, c51, c52, c53, c60, c61, c62, c63, c70, c71, c72, c73;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        c00[e] = 0.f;
-        c01[e] = 0.f;
-        c02[e] = 0.f;
-        c03[e] = 0.f;
-        c10[e] = 0.f;
-        c11[e] = 0.f;
-        c12[e] = 0.f;
-        c13[e] = 0.f;
-        c20[e] = 0.f;
-        c21[e] = 0.f;
-        c22[e] = 0.f;
-        c23[e] = 0.f;
-        c30[e] = 0.f;
-        c31[e] = 0.f;
-        c32[e] = 0.f;
-        c33[e] = 0.f;
-        c40[e] = 0.f;
-        c41[e] = 0.f;
-        c42[e] = 0.f;
-        c43[e] = 0.f;
-        c50[e] = 0.f;
-        c51[e] = 0.f;
-        c52[e] = 0.f;
-        c53[e] = 0.f;
-        c60[e] = 0.f;
-        c61[e] = 0.f;
-        c62[e] = 0.f;
-        c63[e] = 0.f;
-        c70[e] = 0.f;
-        c71[e] = 0.f;
-        c72[e] = 0.f;
-        c73[e] = 0.f;
-    }
-    u32x2 pa0l, pa0h, pb0l, pb0h, pb1l, pb1h, pb2l, pb2h, pb3l, pb3h, pa1l, pa1h, pa2l, pa2h;
-    u32x2 qa0l, qa0h, qb0l, qb0h, qb1l, qb1h, qb2l, qb2h, qb3l, qb3h, qa1l, qa1h, qa2l, qa2h;
-    u32x2 la3l, la3h, la4l, la4h, la5l, la5h, la6l, la6h, la7l, la7h;
-#define GQ_NRD(dst, base, idx, off)                                                                   \
-    do {                                                                                              \
-        const unsigned t_ = (base) ^ ((unsigned)(idx) << 5);                                          \
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(t_), "n"(off) : "memory"); \
-    } while (0)
-#define GQ_NWAIT(N, x, y) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(x), "+v"(y)::"memory")
-#define GQ_NMF(c, al, ah, bl, bh)                                                                     \
-    do {                                                                                              \
-        const u32x4 A_ = __builtin_shufflevector(al, ah, 0, 1, 2, 3), B_ = __builtin_shufflevector(bl, bh, 0, 1, 2, 3); \
-        if constexpr (BF16) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(A_), "v"(B_)); \
-        else asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(A_), "v"(B_));     \
-    } while (0)
-#define GQ_NBAR() asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory")
-#define GQ_NSTEP(X, Y, AC, OFFC, AN, BN, OFFN, L0, L1, L2, L3)                                        \
-    do {                                                                                              \
-        GQ_NWAIT(12, X##a0l, X##a0h);                                                                 \
-        GQ_NWAIT(10, X##b0l, X##b0h);                                                                 \
-        GQ_NMF(c00, X##a0l, X##a0h, X##b0l, X##b0h);                                                  \
-        GQ_NRD(la3l, AC, 3, (OFFC) + 0);                                                              \
-        GQ_NWAIT(9, X##b1l, X##b1h);                                                                  \
-        GQ_NMF(c01, X##a0l, X##a0h, X##b1l, X##b1h);                                                  \
-        GQ_NRD(la3h, AC, 3, (OFFC) + 2048);                                                           \
-        GQ_NWAIT(8, X##b2l, X##b2h);                                                                  \
-        GQ_NMF(c02, X##a0l, X##a0h, X##b2l, X##b2h);                                                  \
-        GQ_NRD(la4l, AC, 4, (OFFC) + 0);                                                              \
-        GQ_NWAIT(7, X##b3l, X##b3h);                                                                  \
-        GQ_NMF(c03, X##a0l, X##a0h, X##b3l, X##b3h);                                                  \
-        GQ_NRD(la4h, AC, 4, (OFFC) + 2048);                                                           \
-        GQ_NWAIT(6, X##a1l, X##a1h);                                                                  \
-        GQ_NMF(c10, X##a1l, X##a1h, X##b0l, X##b0h);                                                  \
-        GQ_NRD(la5l, AC, 5, (OFFC) + 0);                                                              \
-        GQ_NMF(c11, X##a1l, X##a1h, X##b1l, X##b1h);                                                  \
-        GQ_NRD(la5h, AC, 5, (OFFC) + 2048);                                                           \
-        GQ_NMF(c12, X##a1l, X##a1h, X##b2l, X##b2h);                                                  \
-        GQ_NRD(la6l, AC, 6, (OFFC) + 0);                                                              \
-        GQ_NMF(c13, X##a1l, X##a1h, X##b3l, X##b3h);                                                  \
-        GQ_NRD(la6h, AC, 6, (OFFC) + 2048);                                                           \
-        GQ_NWAIT(8, X##a2l, X##a2h);                                                                  \
-        GQ_NMF(c20, X##a2l, X##a2h, X##b0l, X##b0h);                                                  \
-        GQ_NRD(la7l, AC, 7, (OFFC) + 0);                                                              \
-        GQ_NMF(c21, X##a2l, X##a2h, X##b1l, X##b1h);                                                  \
-        GQ_NRD(la7h, AC, 7, (OFFC) + 2048);                                                           \
-        GQ_NMF(c22, X##a2l, X##a2h, X##b2l, X##b2h);                                                  \
-        GQ_NBAR();                                                                                    \
-        GQ_NMF(c23, X##a2l, X##a2h, X##b3l, X##b3h);                                                  \
-        L0;                                                                                           \
-        GQ_NWAIT(8, la3l, la3h);                                                                      \
-        GQ_NMF(c30, la3l, la3h, X##b0l, X##b0h);                                                      \
-        GQ_NRD(Y##a0l, AN, 0, (OFFN) + 0);                                                            \
-        GQ_NMF(c31, la3l, la3h, X##b1l, X##b1h);                                                      \
-        L1;                                                                                           \
-        GQ_NRD(Y##a0h, AN, 0, (OFFN) + 2048);                                                         \
-        GQ_NMF(c32, la3l, la3h, X##b2l, X##b2h);                                                      \
-        GQ_NRD(Y##b0l, BN, 0, (OFFN) + 0);                                                            \
-        GQ_NMF(c33, la3l, la3h, X##b3l, X##b3h);                                                      \
-        L2;                                                                                           \
-        GQ_NRD(Y##b0h, BN, 0, (OFFN) + 2048);                                                         \
-        GQ_NWAIT(10, la4l, la4h);                                                                     \
-        GQ_NMF(c40, la4l, la4h, X##b0l, X##b0h);                                                      \
-        GQ_NRD(Y##b1l, BN, 1, (OFFN) + 0);                                                            \
-        GQ_NMF(c41, la4l, la4h, X##b1l, X##b1h);                                                      \
-        L3;                                                                                           \
-        GQ_NRD(Y##b1h, BN, 1, (OFFN) + 2048);                                                         \
-        GQ_NMF(c42, la4l, la4h, X##b2l, X##b2h);                                                      \
-        GQ_NRD(Y##b2l, BN, 2, (OFFN) + 0);                                                            \
-        GQ_NMF(c43, la4l, la4h, X##b3l, X##b3h);                                                      \
-        GQ_NRD(Y##b2h, BN, 2, (OFFN) + 2048);                                                         \
-        GQ_NWAIT(12, la5l, la5h);                                                                     \
-        GQ_NMF(c50, la5l, la5h, X##b0l, X##b0h);                                                      \
-        GQ_NRD(Y##b3l, BN, 3, (OFFN) + 0);                                                            \
-        GQ_NMF(c51, la5l, la5h, X##b1l, X##b1h);                                                      \
-        GQ_NRD(Y##b3h, BN, 3, (OFFN) + 2048);                                                         \
-        GQ_NMF(c52, la5l, la5h, X##b2l, X##b2h);                                                      \
-        GQ_NRD(Y##a1l, AN, 1, (OFFN) + 0);                                                            \
-        GQ_NMF(c53, la5l, la5h, X##b3l, X##b3h);                                                      \
-        GQ_NWAIT(13, la6l, la6h);                                                                     \
-        GQ_NRD(Y##a1h, AN, 1, (OFFN) + 2048);                                                         \
-        GQ_NMF(c60, la6l, la6h, X##b0l, X##b0h);                                                      \
-        GQ_NRD(Y##a2l, AN, 2, (OFFN) + 0);                                                            \
-        GQ_NMF(c61, la6l, la6h, X##b1l, X##b1h);                                                      \
-        GQ_NWAIT(13, la7l, la7h);                                                                     \
-        GQ_NRD(Y##a2h, AN, 2, (OFFN) + 2048);                                                         \
-        GQ_NMF(c62, la6l, la6h, X##b2l, X##b2h);                                                      \
-        GQ_NMF(c63, la6l, la6h, X##b3l, X##b3h);                                                      \
-        GQ_NMF(c70, la7l, la7h, X##b0l, X##b0h);                                                      \
-        GQ_NMF(c71, la7l, la7h, X##b1l, X##b1h);                                                      \
-        GQ_NMF(c72, la7l, la7h, X##b2l, X##b2h);                                                      \
-        GQ_NMF(c73, la7l, la7h, X##b3l, X##b3h);                                                      \
-    } while (0)
-#define GQ_NINTERVAL(X, Y, AC, OFFC, AN, BN, OFFN, SLOT3)                                             \
-    GQ_NSTEP(X, Y, AC, OFFC, AN, BN, OFFN, GQ_NDL(voff0, SLOT3, 0), GQ_NDL(voff1, SLOT3, 1),          \
-             GQ_NDL(voff2, SLOT3, 2), GQ_NDL(voff3, SLOT3, 3));                                       \
-    GQ_NADV();
-
-    for (int h = 0; h < 3; ++h) {
-        GQ_NDL_(voff0, h, 0); GQ_NDL_(voff1, h, 1); GQ_NDL_(voff2, h, 2); GQ_NDL_(voff3, h, 3);
-        GQ_NADV();
-    }
-    asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-    GQ_NRD(pa0l, bAlo, 0, 0); GQ_NRD(pa0h, bAlo, 0, 2048);
-    GQ_NRD(pb0l, bBlo, 0, 0); GQ_NRD(pb0h, bBlo, 0, 2048);
-    GQ_NRD(pb1l, bBlo, 1, 0); GQ_NRD(pb1h, bBlo, 1, 2048);
-    GQ_NRD(pb2l, bBlo, 2, 0); GQ_NRD(pb2h, bBlo, 2, 2048);
-    GQ_NRD(pb3l, bBlo, 3, 0); GQ_NRD(pb3h, bBlo, 3, 2048);
-    GQ_NRD(pa1l, bAlo, 1, 0); GQ_NRD(pa1h, bAlo, 1, 2048);
-    GQ_NRD(pa2l, bAlo, 2, 0); GQ_NRD(pa2h, bAlo, 2, 2048);
-    for (int n = 0; n < nhs; n += 4) {  // nhs % 4 == 0; interval n multiplies slot n & 3
-        GQ_NINTERVAL(p, q, bAlo, 0, bAlo, bBlo, 32768, 3)
-        GQ_NINTERVAL(q, p, bAlo, 32768, bAhi, bBhi, 0, 0)
-        GQ_NINTERVAL(p, q, bAhi, 0, bAhi, bBhi, 32768, 1)
-        GQ_NINTERVAL(q, p, bAhi, 32768, bAlo, bBlo, 0, 2)
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
-#undef GQ_NDL
-#undef GQ_NDL_
-#undef GQ_NADV
-#undef GQ_NRD
-#undef GQ_NWAIT
-#undef GQ_NMF
-#undef GQ_NBAR
-#undef GQ_NSTEP
-#undef GQ_NINTERVAL
-    float* __restrict__ H = P.H;
-    const float beta = P.beta, alpha = P.alpha;
-    const int lr = lane & 15, lk = lane >> 4;
-    const int64_t i0 = ti * BT + wm * 128 + 4 * lk, j0 = tj * BT + wn * 64 + lr;
-    float* __restrict__ Pp = (aux != 0xffffffffu) ? grp.partial + (size_t)(aux >> 12) * (BT * BT) : nullptr;
-    const int rl0 = wm * 128 + 4 * lk, cl0 = wn * 64 + lr;  // position inside the tile
-#define GQ_NSTORE(c, i, j)                                                                            \
-    do {                                                                                              \
-        if (Pp) { /* K-split unit: raw sums, combined in fixed order by syrk_reduce_kernel */          \
-            float* q_ = Pp + (rl0 + (i) * 16) * BT + cl0 + (j) * 16;                                  \
-            q_[0] = c[0]; q_[BT] = c[1]; q_[2 * BT] = c[2]; q_[3 * BT] = c[3];                        \
-            break;                                                                                    \
-        }                                                                                             \
-        const int64_t col = j0 + (j) * 16, row = i0 + (i) * 16;                                       \
-        float4 h;                                                                                     \
-        h.x = beta * H[(row + 0) * C + col] + alpha * c[0];                                           \
-        h.y = beta * H[(row + 1) * C + col] + alpha * c[1];                                           \
-        h.z = beta * H[(row + 2) * C + col] + alpha * c[2];                                           \
-        h.w = beta * H[(row + 3) * C + col] + alpha * c[3];                                           \
-        H[(row + 0) * C + col] = h.x; H[(row + 1) * C + col] = h.y;                                   \
-        H[(row + 2) * C + col] = h.z; H[(row + 3) * C + col] = h.w;                                   \
-        if (ti != tj) *reinterpret_cast<float4*>(H + col * C + row) = h;                              \
-    } while (0)
-    GQ_NSTORE(c00, 0, 0);
-    GQ_NSTORE(c01, 0, 1);
-    GQ_NSTORE(c02, 0, 2);
-    GQ_NSTORE(c03, 0, 3);
-    GQ_NSTORE(c10, 1, 0);
-    GQ_NSTORE(c11, 1, 1);
-    GQ_NSTORE(c12, 1, 2);
-    GQ_NSTORE(c13, 1, 3);
-    GQ_NSTORE(c20, 2, 0);
-    GQ_NSTORE(c21, 2, 1);
-    GQ_NSTORE(c22, 2, 2);
-    GQ_NSTORE(c23, 2, 3);
-    GQ_NSTORE(c30, 3, 0);
-    GQ_NSTORE(c31, 3, 1);
-    GQ_NSTORE(c32, 3, 2);
-    GQ_NSTORE(c33, 3, 3);
-    GQ_NSTORE(c40, 4, 0);
-    GQ_NSTORE(c41, 4, 1);
-    GQ_NSTORE(c42, 4, 2);
-    GQ_NSTORE(c43, 4, 3);
-    GQ_NSTORE(c50, 5, 0);
-    GQ_NSTORE(c51, 5, 1);
-    GQ_NSTORE(c52, 5, 2);
-    GQ_NSTORE(c53, 5, 3);
-    GQ_NSTORE(c60, 6, 0);
-    GQ_NSTORE(c61, 6, 1);
-    GQ_NSTORE(c62, 6, 2);
-    GQ_NSTORE(c63, 6, 3);
-    GQ_NSTORE(c70, 7, 0);
-    GQ_NSTORE(c71, 7, 1);
-    GQ_NSTORE(c72, 7, 2);
-    GQ_NSTORE(c73, 7, 3);
-#undef GQ_NSTORE
-    }  // tile loop
-}
-
-// -------------- 16-bit SYRK, 256x256 tiles, FOUR waves with 128 x 128 wave tiles (option syrk_w4 = 1)
-// The vendor library's shape for this product (hipBLASLt MT256x256x32, MIWT8_8: DESIGN.md K1) on this kernel's ring:
-// same 4-slot LDS ring in the natural activation layout, same DMA pieces, same tile table / K-split / rendezvous and the
-// same k order per accumulator as syrk16_256n_kernel -- results are bit-identical -- but 2 x 2 waves, one per SIMD, each
-// with 8 x 8 accumulators of 16x16 in 256 AGPRs: 16 fragments per 64 MFMAs instead of 12 per 32, i.e. a third fewer LDS
-// read bytes per flop.  Every wave brings token rows 8 w .. 8 w + 7 of BOTH operands (8 DMA pieces per k32 step).
+// permutation is applied by the DMA source addresses, the address of fragment i is base ^ (i << 5).
+// Requires T % 128 == 0 (whole ring turns); other T take the re-layout path.
+// Waves: the vendor library's shape for this product (hipBLASLt MT256x256x32, MIWT8_8: DESIGN.md K1) -- 2 x 2 waves, one per
+// SIMD, each with 8 x 8 accumulators of 16x16 in 256 AGPRs, 16 fragments per 64 MFMAs.  Every wave brings token rows
+// 8 w .. 8 w + 7 of BOTH operands (8 DMA pieces per k32 step).
+// (Measured in r04, profiles/r04_syrk_w4_ab.txt: this form 1.306 / 1.329 against 1.247 / 1.270 PFLOP/s at C = 14336 for the
+// same ring under eight waves with 128 x 64 wave tiles, 12 fragments per 32 MFMAs, bit-identical; the eight-wave kernel
+// removed.)
 // Stream of one k32 step (64 MFMAs, row-major over the A fragments; B fragments double-buffered, A fragments single-
 // buffered: a_i of the next step is read right after row i of this step has issued):
 //   MFMA 0,1: reads of a7 (this step's, ring slot n)      MFMA 2: s_waitcnt vmcnt(8) + s_barrier (half-stage n+1 landed,
@@ -892,8 +566,7 @@ __global__ __launch_bounds__(512, 2) void syrk16_256n_kernel(const SyrkGroup grp
 // quarter of those tiles' MFMA energy, ~1 % of a launch -- as a second, MFMA-free loop for that wave: the extra path pushed the
 // register allocation over the edge, scratch reloads inside the hand-counted loop, half the speed.)
 // (Measured on this table and removed, profiles/r04_syrk_w4_ab.txt: the whole B set read in rows 0-3, a step without its
-// barrier, a step that never waits for its DMA -- all within 1 % of this order: no wait left that matters, as in the
-// eight-wave kernel.)
+// barrier, a step that never waits for its DMA -- all within 1 % of this order: no wait left that matters.)
 struct W4Sched {
     signed char rd[64][4];  // reads issued behind MFMA m (-1: none)
     signed char dma[64];    // DMA piece issued behind MFMA m: 0-3 A pieces, 4-7 B pieces (-1: none)
@@ -1052,11 +725,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int wm = wid >> 1, wn = wid & 1;
     int round = 0;
     for (int slot = (int)(blockIdx.x >> 3); slot < grp.per_xcd; slot += (int)(gridDim.x >> 3), ++round) {
-    if (grp.bar && round > 0) {  // XCD-wide soft rendezvous between rounds, as in syrk16_256n_kernel
+    if (grp.bar && round > 0) {  // XCD-wide rendezvous between rounds (persistent launch)
         if (tid == 0) {
             unsigned* b = grp.bar + (blockIdx.x & 7);
             __hip_atomic_fetch_add(b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned want = (unsigned)round * (gridDim.x >> 3);
+            // a SOFT rendezvous (performance only, results do not depend on it): give up after ~30 us, so that a
+            // workgroup whose peers are not resident (another process on the same GPU) can never wait for ever
             for (int spin = 0; spin < 64 && __hip_atomic_load(b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want; ++spin)
                 __builtin_amdgcn_s_sleep(16);
         }
@@ -1327,14 +1002,14 @@ __global__ __launch_bounds__(256) void syrk32_kernel(float* __restrict__ H, int6
         }
 }
 
-// 16-bit inputs with C % 256 == 0 and T % 128 == 0 are read in place (syrk16_256n_kernel): only the tile table
+// 16-bit inputs with C % 256 == 0 and T % 128 == 0 are read in place (syrk16_256w_kernel): only the tile table
 // needs scratch.  Everything else goes through the re-laid-out operand image.
 static inline bool syrk_in_place(int64_t T, int64_t C) {
-    return (C % BT == 0) && (T % (2 * HK) == 0) && !opt(OPT_syrk_image) && !opt(OPT_syrk_128);
+    return (C % BT == 0) && (T % (2 * HK) == 0) && !opt(OPT_syrk_image);
 }
 
-// K-split of the last (partial) round of tiles (syrk16_256n_kernel): partial-sum slots a problem may need.
-// Only long token ranges are split (every part is at least 8 turns of the ring); GQ_SYRK_NOSPLIT disables it.
+// K-split of the last (partial) round of tiles (syrk16_256w_kernel): partial-sum slots a problem may need.
+// Only long token ranges are split (every part is at least 8 turns of the ring); option syrk_nosplit disables it.
 static inline size_t syrk_partial_slots(int64_t T, size_t ntile) {
     if (T < 8192 || opt(OPT_syrk_nosplit)) return 0;
     return 4 * ntile < 512 ? 4 * ntile : 512;
@@ -1466,16 +1141,16 @@ static int syrk16_launch(int kind, const int* idx, int m, float* const* H, const
         wp = reinterpret_cast<unsigned char*>(((uintptr_t)wp + 255) & ~(uintptr_t)255);
         // rendezvous counters of the persistent launch (zeroed by this upload), then the block address lists of the
         // problems whose X arrives in separate blocks, behind the tile table
-        // default on: L2-miss reads of a 14336-wide launch 49.6 -> 37.5 GB (rocprofv3 FETCH_SIZE), +0.8 % speed
-        const bool persist = opt(OPT_syrk_persist) != 0;
+        // (more than one round per XCD; measured in r02, L2-miss reads of a 14336-wide launch 37.5 against 49.6 GB with one tile
+        // per workgroup, rocprofv3 FETCH_SIZE, +0.8 % speed: the switch to the one-tile form for every shape removed)
         size_t bar_at = 0;
-        if (kind == 2 && persist && per_xcd > 32) {
+        if (kind == 2 && per_xcd > 32) {
             bar_at = table.size();
             for (int x = 0; x < 16; ++x) table.push_back(0u);  // [0..7] rounds, [8..15] checkpoints inside a tile
             // checkpoints: only when every problem of the launch walks the same number of half-stages (a dense block's inputs do;
             // MoE experts with their own token counts do not)
             int64_t ck = opt(OPT_syrk_ck);
-            bool same = (ck & (ck - 1)) == 0 && ck >= 16 && opt(OPT_syrk_w4) != 0;
+            bool same = (ck & (ck - 1)) == 0 && ck >= 16;
             for (int k = 1; k < m && same; ++k) same = grp.p[k].Tp == grp.p[0].Tp;
             if (same && grp.p[0].Tp / 32 > ck) {
                 grp.ck = (int)ck;
@@ -1518,12 +1193,9 @@ static int syrk16_launch(int kind, const int* idx, int m, float* const* H, const
         // the block schedule's postponed folds -- so that the chain's kernels always find free CUs)
         int wgs = 256;
         if (const int64_t e = opt(OPT_syrk_wgs)) wgs = (e >= 8 && e <= 256) ? (int)(e & ~7) : 256;
-        const dim3 grid((unsigned)(grp.bar ? wgs : 8 * grp.per_xcd)), blk(512);
-        if (opt(OPT_syrk_w4)) {  // four waves, 128 x 128 wave tiles (default; bit-identical to the eight-wave form)
-            if (bf) hipLaunchKernelGGL(syrk16_256w_kernel<true>, grid, dim3(256), S_LDS_BYTES, st, grp);
-            else hipLaunchKernelGGL(syrk16_256w_kernel<false>, grid, dim3(256), S_LDS_BYTES, st, grp);
-        } else if (bf) hipLaunchKernelGGL(syrk16_256n_kernel<true>, grid, blk, S_LDS_BYTES, st, grp);
-        else hipLaunchKernelGGL(syrk16_256n_kernel<false>, grid, blk, S_LDS_BYTES, st, grp);
+        const dim3 grid((unsigned)(grp.bar ? wgs : 8 * grp.per_xcd));
+        if (bf) hipLaunchKernelGGL(syrk16_256w_kernel<true>, grid, block, S_LDS_BYTES, st, grp);
+        else hipLaunchKernelGGL(syrk16_256w_kernel<false>, grid, block, S_LDS_BYTES, st, grp);
         if (n_reduce > 0) {
             GQ_LAUNCH_CHECK();
             hipLaunchKernelGGL(syrk_reduce_kernel, dim3((unsigned)n_reduce, 16), dim3(256), 0, st, grp, reduce_list);
@@ -1714,7 +1386,7 @@ int h_accumulate_grouped(int n, float* const* H, const void* const* X, const int
         need += h_accumulate_workspace_bytes(T[i], C[i]);
         if (segs && segs[i] && nseg[i] > 1) {
             // separate blocks are only read in place: whole ring turns per block, 16-byte aligned rows
-            if (T[i] % nseg[i] || (T[i] / nseg[i]) % (2 * HK) || !syrk_in_place(T[i], C[i]) || opt(OPT_syrk_128))
+            if (T[i] % nseg[i] || (T[i] / nseg[i]) % (2 * HK) || !syrk_in_place(T[i], C[i]))
                 GQ_FAIL(GQ_E_UNSUPPORTED, "gq_h_accumulate_segments: %ld blocks of %ld tokens, C=%ld: blocks must hold a "
                         "multiple of 128 tokens and C %% 256 == 0 (stage the rows into one buffer instead)",
                         (long)nseg[i], (long)(T[i] / nseg[i]), (long)C[i]);
@@ -1729,8 +1401,6 @@ int h_accumulate_grouped(int n, float* const* H, const void* const* X, const int
         GQ_HIP(hipFuncSetAttribute((const void*)syrk16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * H_STAGE_BYTES));
         GQ_HIP(hipFuncSetAttribute((const void*)syrk16_256e_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES));
         GQ_HIP(hipFuncSetAttribute((const void*)syrk16_256e_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES));
-        GQ_HIP(hipFuncSetAttribute((const void*)syrk16_256n_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES));
-        GQ_HIP(hipFuncSetAttribute((const void*)syrk16_256n_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES));
         GQ_HIP(hipFuncSetAttribute((const void*)syrk16_256w_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES));
         GQ_HIP(hipFuncSetAttribute((const void*)syrk16_256w_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES));
         attr_set = true;
@@ -1738,9 +1408,8 @@ int h_accumulate_grouped(int n, float* const* H, const void* const* X, const int
     // Problems are sorted into at most three launches by the kernel they can take (usually all take the first):
     // in place (kind 2), 256x256 on the image (kind 1: T not a multiple of 128), 128x128 (kind 0: C % 256 != 0).
     int idx[3][H_MAX_GROUP], cnt[3] = {0, 0, 0};
-    const bool force128 = opt(OPT_syrk_128) != 0;
     for (int i = 0; i < n; ++i) {
-        const int kind = (force128 || C[i] % BT) ? 0 : (syrk_in_place(T[i], C[i]) ? 2 : 1);
+        const int kind = (C[i] % BT) ? 0 : (syrk_in_place(T[i], C[i]) ? 2 : 1);
         idx[kind][cnt[kind]++] = i;
     }
     unsigned char* wp = reinterpret_cast<unsigned char*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);

@@ -101,20 +101,19 @@ const char* gq_last_error(void);
 
    Options (gq_option_set / gq_option_get; defaults in brackets) are tuning and test switches: no option changes a result
    except where noted -- the tests flip them to prove exactly that.
-     syrk_128 [0] 128x128-tile SYRK everywhere | syrk_image [0] re-laid-out operand image instead of reading X in place |
-     syrk_nosplit [0] no K-split of the last round | syrk_persist [1] persistent launch with XCD rendezvous |
-     syrk_wgs [0 = one per CU] resident workgroups of that launch | syrk_ck [256] half-stages (32 tokens) between the soft XCD
-     rendezvous inside a tile of that launch (power of two >= 16, 0: none; results do not depend on it) | syrk_w4 [1] four waves with 128x128 wave tiles, 0 = eight
-     waves with 128x64 (bit-identical) | syrk_gw [4] width in 256-tiles of the super-tile an XCD's 32 workgroups work on at a time
-     (a power of two <= 32; 32 / gw rows; moves the K-split round: H within the tolerance class)
+     syrk_image [0] re-laid-out operand image instead of reading X in place | syrk_nosplit [0] no K-split of the last round |
+     syrk_wgs [0 = one per CU] resident workgroups of the persistent launch | syrk_ck [256] half-stages (32 tokens) between the
+     soft XCD rendezvous inside a tile of that launch (power of two >= 16, 0: none; results do not depend on it) |
+     syrk_gw [4] width in 256-tiles of the super-tile an XCD's 32 workgroups work on at a time (a power of two <= 32; 32 / gw
+     rows; moves the K-split round: H within the tolerance class) | syrk_w4 [1] accepts 1 only: the four-wave kernel is the
+     only in-place form, the name stays because the benchmark reads it
      chol_3p_min [1792] smallest half-node on the image GEMMs (0: never; changes U within the tolerance class) |
      chol_planes [2] 2 = row-scaled fp16 x 2, 3 = bf16 x 3 (tolerance class) | chol_3b_min [1024] | chol_fp32 [0] fp32 MFMA only
      (tolerance class) | chol_no_pair [0] | chol_no_equil [0] | chol_poison [0] NaN-fill scratch that must not be read |
      diag_ref [0] column-by-column leaf kernel (tolerance class)
-     no_lookahead [0] | la [8] blocks per super-block | seg_pair [1] one column-loop launch per 256-column pair of blocks (0: per
-     block) | near_classic [0] | near_quad [0] | near64_maxn [768] | far_sync [0] |
-     far_async_max_rows [8192] | far_async_min_sb [8] | far_wgs [192] | far_bdma [1] far GEMM B operand by LDS-DMA (0: registers + ds_write) |
-     chain_generic [0] | gemm32_64_max [256]
+     no_lookahead [0] | la [8] blocks per super-block | near64_maxn [768] | far_sync [0] | far_async_max_rows [8192] |
+     far_async_min_sb [8] | far_wgs [192] | gemm32_64_max [256] | near_classic [0] accepts 0 only: near updates go pair by
+     pair, the name stays because the benchmark reads it
      ss_wide [-1] scale-search mapping: -1 by size, 1 eight lanes, 0 one lane, 2 a lane pair per group
      stage_host_wgs [0] workgroups of gq_stage_to_host */
 int gq_option_count(void);

@@ -337,4 +337,11 @@ def test_gq_options_errors_fail_every_entry_point_without_abort():
              "except _cabi.GQError as e:\n    print('ERR', e)\n") % ROOT
     p = subprocess.run([sys.executable, "-c", code2], env=dict(os.environ, GQ_OPTIONS="la=abc"), capture_output=True, text=True)
     assert p.returncode == 0 and "ERR" in p.stdout and "not an integer" in p.stdout, (p.stdout, p.stderr[-500:])
-    assert _cabi.option_default("syrk_ck") == 256 and _cabi.option_default("seg_pair") == 1
+    assert _cabi.option_default("syrk_ck") == 256
+    # the two names the benchmark reads outlive the kernels they once selected: each reads its only value and refuses the other
+    assert _cabi.option_get("syrk_w4") == 1 and _cabi.option_get("near_classic") == 0
+    with pytest.raises(_cabi.GQError, match="outside"):
+        _cabi.option_set("syrk_w4", 0)
+    with pytest.raises(_cabi.GQError, match="outside"):
+        _cabi.option_set("near_classic", 1)
+    assert len(_cabi.option_names()) == 25

@@ -281,18 +281,15 @@ print("HASH", h.hexdigest())
 
 
 def test_trailing_update_kernel_choices_are_bit_identical():
-    """The column loop's trailing updates have several kernels: the 64-tile near kernel with whole K = 256 panels in LDS
-    (default) vs the 128-tile chained kernel (option near64_maxn = 0), the pair form of the near updates vs a launch after
-    every block (near_classic), the dedicated far kernel vs the generic chained one (chain_generic), set through the
-    process's GQ_OPTIONS variable.  Every output element is the same k-ordered chain in all of them: W and the quantized
-    tensors hash identically."""
+    """The near updates of the column loop have two kernels: the 64-tile near kernel with whole K = 256 panels in LDS
+    (default) and the 128-tile chained kernel (option near64_maxn = 0, set through the process's GQ_OPTIONS variable).
+    Every output element is the same k-ordered chain in both: W and the quantized tensors hash identically.  (The default
+    loop's other references: no_lookahead and far_sync in test_gpu_parity.py, the G6 goldens, the full-shape oracle rows.)"""
     import subprocess
     import sys
     from conftest import ROOT
     hashes = {}
-    for tag, opts in (("default", ""), ("near128", "near64_maxn=0"), ("classic", "near_classic"), ("generic_far", "chain_generic=1"),
-                      ("quad", "near_quad=1"), ("far_b_by_dma", "far_bdma=1"), ("far_b_by_registers", "far_bdma=0"),
-                      ("one_launch_per_block", "seg_pair=0")):  # r05: default = one column-loop launch per 256-column pair
+    for tag, opts in (("default", ""), ("near128", "near64_maxn=0")):
         env = dict(os.environ, GQ_OPTIONS=opts)
         p = subprocess.run([sys.executable, "-c", _LOOP_HASH.format(root=ROOT)], env=env, capture_output=True, text=True,
                            timeout=600)

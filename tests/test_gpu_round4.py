@@ -166,10 +166,16 @@ def test_down_proj_ints_rate_on_a_correlated_hessian(ops, oracle, massive, mean,
 @pytest.mark.gpu
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
 def test_h_accumulate_four_wave_form_is_bit_identical(ops, dt):
-    """Option syrk_w4: 2 x 2 waves with 128 x 128 wave tiles (syrk16_256w_kernel) on the same ring, tile table, K-split
-    and k order as the default 2 x 4 waves with 128 x 64 (syrk16_256n_kernel): every Hessian equal BIT FOR BIT -- two
-    problems in one grid, contiguous and per-sample blocks, T >= 8192 (K-split units), a single turn of the ring,
-    beta != 0 -- and close to fp64."""
+    """The in-place SYRK (syrk16_256w_kernel: 2 x 2 waves, 128 x 128 wave tiles, X read where it lies) against the other
+    independent form in the tree, the operand-image kernel (option syrk_image: re-layout pass + syrk16_256e_kernel, 2 x 4
+    waves): same k order per accumulator, so every Hessian is equal BIT FOR BIT wherever both add the same token ranges.
+      * a single turn of the ring (T = 128, beta != 0): default == image, bit for bit;
+      * two problems in one grid, T = 10240 >= 8192, beta != 0: the default cuts the last round of tiles into K-split
+        units, which the image form does not have -- syrk_nosplit == image bit for bit, and the default within 5e-6 of
+        fp64 (both problems);
+      * per-sample blocks are refused on the image path: the blocked fold == the contiguous fold bit for bit, with the
+        K-split (default) and without it (syrk_nosplit: hence == image as well).
+    Every result is symmetric."""
     torch.manual_seed(41)
     shapes = [(2048, 5, 2048), (1280, 40, 256)]  # (C, blocks, tokens per block)
     Xl = [[(torch.randn(L, C, device="cuda") * torch.exp(torch.randn(C, device="cuda") * 0.5)).to(dt) for _ in range(nb)]
@@ -177,21 +183,32 @@ def test_h_accumulate_four_wave_form_is_bit_identical(ops, dt):
     Xc = [torch.cat(b) for b in Xl]
     H0 = [torch.randn(C, C, device="cuda") for C, _, _ in shapes]
     H0 = [h + h.T for h in H0]
-    outs = []
-    for w4 in (0, 1):
-        with ops.options(syrk_w4=w4):
+    betas, alphas = [0.25, 0.5], [0.01, 0.02]
+
+    def fold(blocked=True, **opts):
+        with ops.options(**opts):
             Ha = [h.clone() for h in H0]
-            ops.h_accumulate_grouped(Ha, Xc, [0.25, 0.5], [0.01, 0.02])
+            ops.h_accumulate_grouped(Ha, Xc, betas, alphas)
             Hb = [h.clone() for h in H0]
-            ops.h_accumulate_grouped(Hb, Xl, [0.25, 0.5], [0.01, 0.02])
+            if blocked:
+                ops.h_accumulate_grouped(Hb, Xl, betas, alphas)
             Hc = H0[1].clone()
             ops.h_accumulate(Hc, Xc[1][:128], 0.5, 0.125)   # one turn of the ring
-            outs.append(Ha + Hb + [Hc])
-    for a, b in zip(outs[0], outs[1]):
-        assert torch.equal(a, b)
-        assert torch.equal(b, b.T)
-    ref = 0.25 * H0[0].double() + 0.01 * (Xc[0].double().T @ Xc[0].double())
-    assert (outs[1][0].double() - ref).abs().max().item() <= 5e-6 * ref.abs().max().item()
+        return Ha, Hb if blocked else None, Hc
+
+    dflt, nosplit, image = fold(), fold(syrk_nosplit=1), fold(blocked=False, syrk_image=1)
+    assert torch.equal(dflt[2], image[2])
+    for k in range(2):
+        assert torch.equal(nosplit[0][k], image[0][k]), k
+        assert torch.equal(dflt[1][k], dflt[0][k]), k
+        assert torch.equal(nosplit[1][k], nosplit[0][k]), k
+        ref = betas[k] * H0[k].double() + alphas[k] * (Xc[k].double().T @ Xc[k].double())
+        err = (dflt[0][k].double() - ref).abs().max().item() / ref.abs().max().item()
+        print(f"\n[K1 four-wave] {dt} problem {k}: default vs fp64 {err:.2e}, default == image bit for bit: "
+              f"{torch.equal(dflt[0][k], image[0][k])}")
+        assert err <= 5e-6
+    for h in dflt[0] + dflt[1] + [dflt[2]] + nosplit[0] + nosplit[1] + [nosplit[2]] + image[0] + [image[2]]:
+        assert torch.equal(h, h.T)
 
 
 # ----------------------------------------------------------------- stacked column loops (gq_gptq_quantize_stacked)
