@@ -11,19 +11,28 @@ schedules kernels:
                inputs into their Hessians with grouped SYRK launches once they hold `flush_tokens` tokens:
                the narrow inputs in one grid, then the widest input alone on the chip.  `pre_hook(name)` is the
                same feed from a forward PRE-hook; it ends forward #1 at the last hooked Linear (r04).
-  quantize()   phase 0  the remaining tokens are folded in;
-                        [N>1] ONE collective per distinct Hessian, widest first (gptq.py:131-132 does one all-reduce
-                        per handle): a reduce to the owner when all its Linears belong to one rank, else an all-reduce;
-               phase 1  every input group is an independent chain (h_prepare -> per Linear: working copy,
-                        column loop, dequantize) and runs on its own HIP stream, widest chain first: the
-                        single-workgroup leaves of one factorisation and the 64-CU column-loop kernels overlap
-                        with the GEMMs of the other chains.  A follower reuses its leader's U when both weights
-                        have the same all-zero columns (U depends on H, the dead channels and that set only,
-                        gptq.py:307-313); the sets are compared on the device when the block's first sample has
-                        shown who shares what, and the answer reaches the host long before quantize();
-               phase 2  [N>1] ONE all-gather per block: every rank contributes what it computed (the matrices it
-                        owns, its row slices of the row-split ones) as one packed byte buffer; the dequantized
-                        weight is written back (quantizer.py:257-264).
+  quantize()   reads as its phases, one method each:
+               _assign_ranks     [N>1] the row-split matrices, the owners of the others (LPT on `_owner_cost`), where every
+                                 Hessian is needed; MoE blocks agree on who shares what first (the one collective in front
+                                 of the Hessians');
+               _reduce_hessians  phase 0: the remaining tokens are folded in;
+                                 [N>1] ONE collective per distinct Hessian, widest first (gptq.py:131-132 does one all-reduce
+                                 per handle): a reduce to the owner when all its Linears belong to one rank, else an all-reduce;
+               _chains           phase 1: every input group is an independent chain (h_prepare -> per Linear: working copy,
+                                 column loop, dequantize), costliest first (`_chain_order_key`);
+               _plan_lanes       a pure function: which chain goes to which lane -- HIP stream -- and in which order they
+                                 are enqueued (LPT on `_lane_load`, the costliest chain on the caller's stream): the
+                                 single-workgroup leaves of one factorisation and the 64-CU column-loop kernels overlap
+                                 with the GEMMs of the other chains.  How many lanes there are is quantize()'s business:
+                                 one is lent to the library's far helper when a dense block's widest chain brings it along;
+               _run_chain        enqueues one chain on its lane.  A follower reuses its leader's U when both weights
+                                 have the same all-zero columns (U depends on H, the dead channels and that set only,
+                                 gptq.py:307-313); the sets are compared on the device when the block's first sample has
+                                 shown who shares what, and the answer reaches the host long before quantize();
+               _settle_late_followers   MoE blocks only: followers whose sharing became known too late -- one host read;
+               _exchange_and_write_back phase 2: [N>1] ONE all-gather per block: every rank contributes what it computed
+                                 (the matrices it owns, its row slices of the row-split ones) as one packed byte buffer; the
+                                 dequantized weight is written back (quantizer.py:257-264).
 quantize() never synchronises the host with the device (dense Linears): everything is ordered by streams and
 events, so the caller's next launches (the block's second forward, or the next block of a benchmark) queue up
 behind the chains.  The device-side flags of the reused factorisations are kept in `BlockSchedule.unverified`,
@@ -93,6 +102,66 @@ def _zero_columns(w: torch.Tensor) -> torch.Tensor:
     return (w.detach().reshape(w.shape[0], -1) == 0).all(dim=0)
 
 
+# ---- the three costs of a Linear of R rows and C columns.  They differ on purpose: each orders something else.
+def _owner_cost(h: GPTQ) -> float:
+    """R*C*(C+128), DESIGN.md 5b's LPT key: orders the Linears when they are dealt to the ranks (and picks the row-split ones)."""
+    return float(h.d_row) * h.d_col * (h.d_col + 128)
+
+
+def _chain_order_key(hs: List[GPTQ]):
+    """(not row-split, -sum R*C^2): orders a rank's chains -- the row-split ones first, then by the work of their column loops."""
+    return (not any(h._row_split_active() for h in hs), -sum(float(h.d_row) * h.d_col ** 2 for h in hs))
+
+
+def _lane_load(hs: List[GPTQ]) -> float:
+    """sum R*C^2 + C^3/3, column loop + factorisation: what a chain adds to the load of the lane it lands on."""
+    return sum(float(h.d_row) * h.d_col ** 2 + float(h.d_col) ** 3 / 3 for h in hs)
+
+
+def _plan_lanes(cost: List[float], lanes: int) -> Tuple[List[int], List[int]]:
+    """-> (lane_of, enq): the lane of every chain and the order in which the chains are enqueued.  `cost` is the lane load
+    of the chains in chain order (costliest first).  Longest-processing-time-first over all lanes, ties to the lowest lane:
+    the costliest chain lands on lane 0 = the caller's stream (a dense block: four chains over three lanes + the library's
+    helper; a Mixtral block: 20 chains over 4 lanes).  Zero or one lane: everything on lane 0, in chain order."""
+    n = len(cost)
+    lane_of, load = [0] * n, [0.0] * max(lanes, 1)
+    for k in range(n):
+        lane_of[k] = min(range(lanes), key=lambda i: (load[i], i)) if lanes else 0
+        load[lane_of[k]] += cost[k]
+    enq = list(range(n))
+    if lanes >= 4 and n > 2 * lanes:
+        # many chains per lane (a Mixtral block: eight 14336-wide w2 chains -- long strings of small dependent
+        # launches -- and eight stacked w1 / w3 chains -- short and GEMM-heavy): the upper half of the lanes walk
+        # their chains cheapest first, so that at any time half the lanes are in latency-bound chains and half in
+        # GEMM-bound ones instead of all in the same kind (measured, same box: 306.7 against 311.3 ms per block; a lane of its own
+        # for the GEMM-heavy chains and three for the others: 318.7)
+        per = [[k for k in range(n) if lane_of[k] == i] for i in range(lanes)]
+        for i in range(lanes // 2, lanes):
+            per[i].reverse()
+        enq = [per[i][j] for j in range(max(len(x) for x in per)) for i in range(lanes) if j < len(per[i])]
+    return lane_of, enq
+
+
+@contextlib.contextmanager
+def _far_helper_lease(on: bool):
+    """The library's far-update helper stream is allowed / forbidden for the column loops enqueued inside, then set back."""
+    was = _ops.far_helper_enable(on)
+    try:
+        yield
+    finally:
+        _ops.far_helper_enable(was)
+
+
+class _Call:
+    """What the phases of ONE quantize() call share: its arguments, who needs a factorisation of its own, and what the
+    chains have computed so far."""
+
+    def __init__(self, qtypes, writeback, extra, own: Dict[str, bool], world: int, rank: int):
+        self.qtypes, self.writeback, self.extra, self.own, self.world, self.rank = qtypes, writeback, extra, own, world, rank
+        self.results: Dict[str, tuple] = {}      # name -> the five result tensors
+        self.deq: Dict[str, torch.Tensor] = {}   # name -> the dequantized weight, where a chain already made it
+
+
 class BlockSchedule:
     unverified: List[torch.Tensor] = []  # device flags of speculative U reuses, see verify()
     # (Measured and removed, r04: starting the other chains only when the costliest chain's factorisation is through -- it
@@ -140,11 +209,14 @@ class BlockSchedule:
             self.feed(name, inp[0])
             self._fired.append(name)
             self._other_after = False
-            if interrupt and name == self._last_fired and len(self._fired) == len(self.handles) \
-                    and len(set(self._fired)) == len(self._fired):
+            if interrupt and name == self._last_fired and self._all_fired_once():
                 self.stats["forward1_interrupts"] = self.stats.get("forward1_interrupts", 0) + 1
                 raise ForwardInterrupt
         return _hook
+
+    def _all_fired_once(self) -> bool:
+        """Every handle was fed exactly once in the current sample."""
+        return len(self._fired) == len(self.handles) and len(set(self._fired)) == len(self._fired)
 
     def other_pre_hook(self):
         """Forward pre-hook for the block's Linears that are NOT quantized (not matched by --quantizable_modules): the first
@@ -174,8 +246,7 @@ class BlockSchedule:
     def sample_done(self) -> None:
         """Called after every calibration sample (one forward of the block)."""
         self._seen.clear()
-        if self._n_samples == 0 and len(self._fired) == len(self.handles) and len(set(self._fired)) == len(self._fired) \
-                and not self._other_after:
+        if self._n_samples == 0 and self._all_fired_once() and not self._other_after:
             self._last_fired = self._fired[-1]  # every Linear fired once: later samples may stop there (pre_hook)
         self._n_samples += 1
         self._fired = []
@@ -347,59 +418,15 @@ class BlockSchedule:
             if qtypes[n] == GGMLQuantizationType.Q3_K:
                 h.act_order = False  # reference gptq.py:204-206
         if world > 1:
-            costs = {n: float(h.d_row) * h.d_col * (h.d_col + 128) for n, h in handles.items()}
-            # a matrix that outweighs a fair share is quantized by every rank on its own rows (U replicated);
-            # the rest are handed out whole
-            split = {n for n in dist_utils.row_split_names(costs, world) if not handles[n].act_order}
-            for n in split:
-                handles[n].row_split = True
-            for n, r in dist_utils.assign_owners({n: c for n, c in costs.items() if n not in split}, world).items():
-                handles[n].owner_rank = r
-            if any(h.allow_no_samples for h in handles.values()):
-                self._agree_on_sharing()
-            self.owners = {n: (f"rows/{world}" if h._row_split_active() else h.owner_rank) for n, h in handles.items()}
-            # reduce-to-owner (SURVEY section 5 iii): a Hessian whose Linears -- the leader and its followers -- all belong to
-            # ONE rank is needed there only; row-split matrices are factorised by every rank: all-reduce
-            need: Dict[int, set] = {}
-            for n, h in handles.items():
-                lead = h.shared_H_with or h
-                need.setdefault(id(lead), set()).update(range(world) if h._row_split_active() else (h.owner_rank,))
-            for h in self.leaders():
-                ranks = need.get(id(h), set())
-                h.reduce_to = next(iter(ranks)) if len(ranks) == 1 else None
+            self._assign_ranks(world)
         dev = next(iter(handles.values())).W_device
         on_gpu = torch.device(dev).type == "cuda"
         main = torch.cuda.current_stream(dev) if on_gpu else None
-
-        # ---- phase 0: the rest of the tokens, then one all-reduce per distinct Hessian, widest first
-        ready: Dict[int, Any] = {}
-        self.flush()
-        for h in sorted(self.leaders(), key=lambda h: -h.d_col):
-            h.sync_hessian()
-            if world > 1:
-                self.stats["allreduce_bytes"] += dist_utils.hessian_payload_bytes(h.d_col)
-                if on_gpu:
-                    ready[id(h)] = torch.cuda.Event()
-                    ready[id(h)].record(main)
-        for h in handles.values():
-            h.sync_hessian()  # followers adopt their leader's H (no collective)
-        start = None
-        if on_gpu and world == 1:
-            start = torch.cuda.Event()
-            start.record(main)
+        ready, start = self._reduce_hessians(world, main)
 
         # ---- phase 1: one chain per distinct Hessian, each on its own stream, the costliest first
-        chains: Dict[int, List[str]] = {}
-        for n, h in handles.items():
-            if h.owner_rank == rank or h._row_split_active():
-                chains.setdefault(id(h.shared_H_with or h), []).append(n)
-
-        def chain_cost(ns):
-            return (not any(handles[n]._row_split_active() for n in ns),
-                    -sum(float(handles[n].d_row) * handles[n].d_col ** 2 for n in ns))
-
-        own = self._needs_own_factorisation()
-        order = sorted(chains.values(), key=chain_cost)
+        order = self._chains(rank)
+        call = _Call(qtypes, writeback, extra, self._needs_own_factorisation(), world, rank)
         # the costliest chain stays on the caller's stream (it ends last anyway), the others get side streams
         on_main = 1
         # a chain whose column loop keeps its far updates on the library's helper stream brings a hardware queue
@@ -409,94 +436,134 @@ class BlockSchedule:
         lent = 1 if on_gpu and 2 < self.n_streams and len(order) <= self.n_streams and any(
             _ops.uses_helper_stream(h.d_row, h.d_col, h.block_size) for h in handles.values()
             if h.owner_rank == rank and not h._row_split_active()) else 0
-        helper_was = _ops.far_helper_enable(bool(lent)) if on_gpu else None
-        try:
-            streams = [None] * on_main + _chain_streams(dev, min(self.n_streams - lent, len(order)) - on_main)
-            results: Dict[str, tuple] = {}
-            deq: Dict[str, torch.Tensor] = {}
+        streams = [None] * on_main + _chain_streams(dev, min(self.n_streams - lent, len(order)) - on_main)
+        trace = "sched" in os.environ.get("GQ_TRACE", "")
+        t_host = time.perf_counter()
+        lane_of, enq = _plan_lanes([_lane_load([handles[n] for n in names]) for names in order], len(streams))
+        with _far_helper_lease(bool(lent)) if on_gpu else contextlib.nullcontext():
             lanes = []
-            trace = "sched" in os.environ.get("GQ_TRACE", "")
-            t_host = time.perf_counter()
-            # lanes: longest-processing-time-first over all lanes; the costliest chain comes first and lands on lane 0 = the
-            # caller's stream (a dense block: four chains over three lanes + the library's helper; a Mixtral block: 20 chains over 4 lanes)
-            cost = [sum(float(handles[n].d_row) * handles[n].d_col ** 2 + float(handles[n].d_col) ** 3 / 3 for n in names)
-                    for names in order]
-            lane_of, load = [0] * len(order), [0.0] * max(len(streams), 1)
-            for k in range(len(order)):
-                lane_of[k] = min(range(len(streams)), key=lambda i: (load[i], i)) if streams else 0
-                load[lane_of[k]] += cost[k]
-            enq = list(range(len(order)))
-            if len(streams) >= 4 and len(order) > 2 * len(streams):
-                # many chains per lane (a Mixtral block: eight 14336-wide w2 chains -- long strings of small dependent
-                # launches -- and eight stacked w1 / w3 chains -- short and GEMM-heavy): the upper half of the lanes walk
-                # their chains cheapest first, so that at any time half the lanes are in latency-bound chains and half in
-                # GEMM-bound ones instead of all in the same kind (measured, same box: 306.7 against 311.3 ms per block; a lane of its own
-                # for the GEMM-heavy chains and three for the others: 318.7)
-                per = [[k for k in range(len(order)) if lane_of[k] == i] for i in range(len(streams))]
-                for i in range(len(streams) // 2, len(streams)):
-                    per[i].reverse()
-                enq = [per[i][j] for j in range(max(len(x) for x in per)) for i in range(len(streams)) if j < len(per[i])]
             for k in enq:
-                names = order[k]
                 if trace:
-                    print(f"  [sched] +{1e3 * (time.perf_counter() - t_host):7.2f} ms: enqueue chain {k} {names} on lane {lane_of[k]}",
+                    print(f"  [sched] +{1e3 * (time.perf_counter() - t_host):7.2f} ms: enqueue chain {k} {order[k]} on lane {lane_of[k]}",
                           file=sys.stderr)
-                lane = _Lane(streams[lane_of[k]] if streams else None, main)
-                lead = handles[names[0]].shared_H_with or handles[names[0]]
+                lane = _Lane(streams[lane_of[k]], main)
+                lead = handles[order[k][0]].shared_H_with or handles[order[k][0]]
                 lane.wait(ready.get(id(lead), start))
-                born = []
-
-                def computed(n, h, res):
-                    if n in own and h._pending_mismatch is not None:
-                        BlockSchedule.unverified.append(h._pending_mismatch)
-                        h._pending_mismatch = None
-                        self.stats["reused_U"] += 1
-                    elif own.get(n, False):
-                        self.stats["refactorised"] += 1
-                    results[n] = res
-                    born.extend(res)
-                    # what the row-split fallback (recompute_whole, on the caller's stream after the exchange) reads was born
-                    # on this lane too: U, the column flags, the re-search counter and the working copy
-                    born.extend(t for t in (h._last_U, h._last_cf, getattr(h, "_researches", None), h.W) if torch.is_tensor(t))
-                    if world == 1 and writeback:
-                        deq[n] = dequantize_linear_weight(qtypes[n], *res, out_dtype=h.layer.weight.data.dtype)
-                        born.append(deq[n])
-                    if extra is not None:
-                        out = extra(n, h, res)
-                        born.extend(t for t in (out if isinstance(out, (tuple, list)) else (out,)) if torch.is_tensor(t))
-
-                with lane.run():
-                    # the leader first: it factorises, the followers reuse its U.  Linears that are KNOWN to share the
-                    # factorisation (same input, same dead / zero-column sets) and the same grid walk the columns
-                    # together, stacked by rows (GPTQ.compute_stacked): q / k / v and gate / up cost one walk each
-                    for grp in self._stack_groups(sorted(names, key=lambda n: handles[n].shared_H_with is not None), qtypes, own):
-                        if self.verbose:
-                            for n in grp:
-                                print(f"[rank {rank}] Quantizing {n} with {qtypes[n].name}.")
-                        if len(grp) > 1:
-                            hs = [handles[n] for n in grp]
-                            self.stats["stacked"] = self.stats.get("stacked", 0) + len(grp)
-                            for n, h, res in zip(grp, hs, GPTQ.compute_stacked(hs, qtypes[grp[0]])):
-                                computed(n, h, res)
-                            continue
-                        n = grp[0]
-                        h = handles[n]
-                        h.make_working_copy()
-                        # follower with the same zero columns as its leader: reuse (flag kept for verify());
-                        # different: own factorisation; unknown (first fed after the first sample): checked below
-                        computed(n, h, h.compute(qtypes[n], defer_check=True, own_U=own.get(n, False)))
-                lanes.append((lane, born))
+                lanes.append((lane, self._run_chain(call, order[k], lane)))
             for lane, born in lanes:
                 lane.join(born)
-        finally:
-            if helper_was is not None:
-                _ops.far_helper_enable(helper_was)
         if trace:
             print(f"  [sched] +{1e3 * (time.perf_counter() - t_host):7.2f} ms: all chains enqueued", file=sys.stderr)
+        self._settle_late_followers(call)
+        self.stats["own_U"] = len(call.results) - self.stats["reused_U"]
+        return self._exchange_and_write_back(call)
 
-        # followers whose sharing was not known after the block's first sample (an expert that got its first token
-        # later): the device flag is read now -- the one host sync, MoE blocks only
-        pending = [(n, handles[n]._pending_mismatch) for n in results if handles[n]._pending_mismatch is not None]
+    def _assign_ranks(self, world: int) -> None:
+        """[N>1] Who computes what: the row-split matrices, the owners of the others, `self.owners`, and where every
+        Hessian is needed (`reduce_to`).  Holds a collective (_agree_on_sharing): runs before the Hessians' on every rank."""
+        handles = self.handles
+        costs = {n: _owner_cost(h) for n, h in handles.items()}
+        # a matrix that outweighs a fair share is quantized by every rank on its own rows (U replicated);
+        # the rest are handed out whole
+        split = {n for n in dist_utils.row_split_names(costs, world) if not handles[n].act_order}
+        for n in split:
+            handles[n].row_split = True
+        for n, r in dist_utils.assign_owners({n: c for n, c in costs.items() if n not in split}, world).items():
+            handles[n].owner_rank = r
+        if any(h.allow_no_samples for h in handles.values()):
+            self._agree_on_sharing()
+        self.owners = {n: (f"rows/{world}" if h._row_split_active() else h.owner_rank) for n, h in handles.items()}
+        # reduce-to-owner (SURVEY section 5 iii): a Hessian whose Linears -- the leader and its followers -- all belong to
+        # ONE rank is needed there only; row-split matrices are factorised by every rank: all-reduce
+        need: Dict[int, set] = {}
+        for n, h in handles.items():
+            lead = h.shared_H_with or h
+            need.setdefault(id(lead), set()).update(range(world) if h._row_split_active() else (h.owner_rank,))
+        for h in self.leaders():
+            ranks = need.get(id(h), set())
+            h.reduce_to = next(iter(ranks)) if len(ranks) == 1 else None
+
+    def _reduce_hessians(self, world: int, main):
+        """Phase 0: the rest of the tokens, then one all-reduce per distinct Hessian, widest first.
+        -> (ready, start): what a chain's lane waits for before it touches its Hessian -- [N>1] the event behind its
+        leader's collective, {id(leader): event}; [N=1] the one event behind the fold (None on the CPU)."""
+        ready: Dict[int, Any] = {}
+        self.flush()
+        for h in sorted(self.leaders(), key=lambda h: -h.d_col):
+            h.sync_hessian()
+            if world > 1:
+                self.stats["allreduce_bytes"] += dist_utils.hessian_payload_bytes(h.d_col)
+                if main is not None:
+                    ready[id(h)] = torch.cuda.Event()
+                    ready[id(h)].record(main)
+        for h in self.handles.values():
+            h.sync_hessian()  # followers adopt their leader's H (no collective)
+        start = None
+        if main is not None and world == 1:
+            start = torch.cuda.Event()
+            start.record(main)
+        return ready, start
+
+    def _chains(self, rank: int) -> List[List[str]]:
+        """The chains of this rank, costliest first: the Linears it computes (the ones it owns, its rows of the row-split
+        ones), grouped by the Hessian they share."""
+        chains: Dict[int, List[str]] = {}
+        for n, h in self.handles.items():
+            if h.owner_rank == rank or h._row_split_active():
+                chains.setdefault(id(h.shared_H_with or h), []).append(n)
+        return sorted(chains.values(), key=lambda ns: _chain_order_key([self.handles[n] for n in ns]))
+
+    def _run_chain(self, call: _Call, names: List[str], lane: _Lane) -> List[torch.Tensor]:
+        """Enqueue one chain on its lane -> the tensors born there (the join keeps them valid for the caller's stream)."""
+        handles, qtypes = self.handles, call.qtypes
+        born: List[torch.Tensor] = []
+        with lane.run():
+            # the leader first: it factorises, the followers reuse its U.  Linears that are KNOWN to share the
+            # factorisation (same input, same dead / zero-column sets) and the same grid walk the columns
+            # together, stacked by rows (GPTQ.compute_stacked): q / k / v and gate / up cost one walk each
+            for grp in self._stack_groups(sorted(names, key=lambda n: handles[n].shared_H_with is not None), qtypes, call.own):
+                if self.verbose:
+                    for n in grp:
+                        print(f"[rank {call.rank}] Quantizing {n} with {qtypes[n].name}.")
+                if len(grp) > 1:
+                    hs = [handles[n] for n in grp]
+                    self.stats["stacked"] = self.stats.get("stacked", 0) + len(grp)
+                    for n, h, res in zip(grp, hs, GPTQ.compute_stacked(hs, qtypes[grp[0]])):
+                        self._computed(call, born, n, h, res)
+                    continue
+                n = grp[0]
+                h = handles[n]
+                h.make_working_copy()
+                # follower with the same zero columns as its leader: reuse (flag kept for verify());
+                # different: own factorisation; unknown (first fed after the first sample): checked below
+                self._computed(call, born, n, h, h.compute(qtypes[n], defer_check=True, own_U=call.own.get(n, False)))
+        return born
+
+    def _computed(self, call: _Call, born: List[torch.Tensor], n: str, h: GPTQ, res: tuple) -> None:
+        """A Linear's column loop is enqueued: book it, and dequantize / run `extra` behind it on the same lane."""
+        if n in call.own and h._pending_mismatch is not None:
+            BlockSchedule.unverified.append(h._pending_mismatch)
+            h._pending_mismatch = None
+            self.stats["reused_U"] += 1
+        elif call.own.get(n, False):
+            self.stats["refactorised"] += 1
+        call.results[n] = res
+        born.extend(res)
+        # what the row-split fallback (recompute_whole, on the caller's stream after the exchange) reads was born
+        # on this lane too (ADVICE r05): U, the column flags, the re-search counter and the working copy
+        born.extend(t for t in (h._last_U, h._last_cf, getattr(h, "_researches", None), h.W) if torch.is_tensor(t))
+        if call.world == 1 and call.writeback:
+            call.deq[n] = dequantize_linear_weight(call.qtypes[n], *res, out_dtype=h.layer.weight.data.dtype)
+            born.append(call.deq[n])
+        if call.extra is not None:
+            out = call.extra(n, h, res)
+            born.extend(t for t in (out if isinstance(out, (tuple, list)) else (out,)) if torch.is_tensor(t))
+
+    def _settle_late_followers(self, call: _Call) -> None:
+        """Followers whose sharing was not known after the block's first sample (an expert that got its first token
+        later): the device flag is read now -- the one host sync, MoE blocks only."""
+        handles = self.handles
+        pending = [(n, handles[n]._pending_mismatch) for n in call.results if handles[n]._pending_mismatch is not None]
         if pending:
             flags = torch.cat([f.reshape(1) for _, f in pending]).tolist()
             for (n, _), bad in zip(pending, flags):
@@ -505,23 +572,24 @@ class BlockSchedule:
                 if bad:
                     self.stats["refactorised"] += 1
                     h.make_working_copy()
-                    results[n] = h.compute(qtypes[n], own_U=True)
-                    deq.pop(n, None)
+                    call.results[n] = h.compute(call.qtypes[n], own_U=True)
+                    call.deq.pop(n, None)
                 else:
                     self.stats["reused_U"] += 1
-        self.stats["own_U"] = len(results) - self.stats["reused_U"]
 
-        # ---- phase 2: exchange, write-back.  ONE all-gather per block: every rank packs what it computed (whole
-        # matrices it owns, its row slices of the row-split ones) into one byte buffer whose layout every rank can
-        # derive from the owner map alone (the reference broadcasts five tensors per Linear from rank 0,
-        # gptq.py:287-293: 35 collectives per Llama block, 140 for a Mixtral block).
-        if world > 1:
-            out = self._exchange_block(handles, qtypes, results, world, rank)
+    def _exchange_and_write_back(self, call: _Call) -> Dict[str, Tuple[torch.Tensor, ...]]:
+        """Phase 2: exchange, write-back.  ONE all-gather per block: every rank packs what it computed (whole
+        matrices it owns, its row slices of the row-split ones) into one byte buffer whose layout every rank can
+        derive from the owner map alone (the reference broadcasts five tensors per Linear from rank 0,
+        gptq.py:287-293: 35 collectives per Llama block, 140 for a Mixtral block)."""
+        handles, qtypes = self.handles, call.qtypes
+        if call.world > 1:
+            out = self._exchange_block(handles, qtypes, call.results, call.world, call.rank)
         else:
-            out = {n: results[n] for n in handles}
+            out = {n: call.results[n] for n in handles}
         for n, h in handles.items():
-            if writeback:
-                w = deq.get(n)
+            if call.writeback:
+                w = call.deq.get(n)
                 if w is None:
                     w = dequantize_linear_weight(qtypes[n], *out[n], out_dtype=h.layer.weight.data.dtype)
                 h.layer.weight.data = w
@@ -554,15 +622,15 @@ class BlockSchedule:
 
     @staticmethod
     def _piece_layout(q_type, rows: int, cols: int):
-        """[(dtype, shape, byte offset)] of the five result tensors of `rows` rows, each padded to 256 bytes; total."""
+        """[(dtype, shape, byte offset, bytes)] of the five result tensors of `rows` rows, each padded to 256 bytes; total."""
         bits, clamp, scale_maxq, group_size, supergroup_size, sz_dtype, q_dtype = GGML_QUANT_SIZES[q_type]
         shapes = ((q_dtype, (rows, cols)), (torch.float16, (rows, cols // supergroup_size)),
                   (sz_dtype, (rows, cols // group_size)), (torch.float16, (rows, cols // supergroup_size)),
                   (sz_dtype, (rows, cols // group_size)))
         lay, off = [], 0
         for dt, shp in shapes:
-            lay.append((dt, shp, off))
             n = shp[0] * shp[1] * torch.empty(0, dtype=dt).element_size()
+            lay.append((dt, shp, off, n))
             off += (n + 255) & ~255
         return lay, off
 
@@ -589,8 +657,7 @@ class BlockSchedule:
         buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         off = 0
         for n, r0, r1, lay, tot in layouts[rank]:
-            for t, (dt, shp, o) in zip(results[n], lay):
-                k = shp[0] * shp[1] * t.element_size()
+            for t, (dt, shp, o, k) in zip(results[n], lay):
                 buf[off + o:off + o + k].view(dt).view(shp).copy_(t)
             off += tot
         if split:
@@ -606,11 +673,7 @@ class BlockSchedule:
         for r in range(world):
             off = 0
             for n, r0, r1, lay, tot in layouts[r]:
-                views = []
-                for dt, shp, o in lay:
-                    k = shp[0] * shp[1] * torch.empty(0, dtype=dt).element_size()
-                    views.append(gathered[r, off + o:off + o + k].view(dt).view(shp))
-                parts[n].append(views)
+                parts[n].append([gathered[r, off + o:off + o + k].view(dt).view(shp) for dt, shp, o, k in lay])
                 off += tot
         out: Dict[str, tuple] = {}
         for n in handles:

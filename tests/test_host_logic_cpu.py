@@ -1329,6 +1329,115 @@ def test_stack_groups():
     assert [len(x) for x in g] == [8, 3] and g[0][0] == "x0"
 
 
+# --------------------------------------------------------------------------- the lane plan
+def _llama3_8b_block():
+    """name -> (R, C, input group), module order (bench.py's default workload)."""
+    return {"q_proj": (4096, 4096, "attn_in"), "k_proj": (1024, 4096, "attn_in"), "v_proj": (1024, 4096, "attn_in"),
+            "o_proj": (4096, 4096, "o_in"), "gate_proj": (14336, 4096, "mlp_in"), "up_proj": (14336, 4096, "mlp_in"),
+            "down_proj": (4096, 14336, "down_in")}
+
+
+def _mixtral_block():
+    """bench.py's `mixtral-block` shapes."""
+    s = {n: v for n, v in _llama3_8b_block().items() if n in ("q_proj", "k_proj", "v_proj", "o_proj")}
+    for e in range(8):
+        s[f"experts.{e}.w1"] = (14336, 4096, f"e{e}_in")
+        s[f"experts.{e}.w3"] = (14336, 4096, f"e{e}_in")
+        s[f"experts.{e}.w2"] = (4096, 14336, f"e{e}_mid")
+    return s
+
+
+def _plan_of(shapes, lanes):
+    """[(chain, its Linears, lane)] in enqueue order -- the fields of the `GQ_TRACE=sched` enqueue lines -- from the
+    module's own cost functions and `_plan_lanes`."""
+    from types import SimpleNamespace
+    from gptq_gguf_toolkit_amd import block_schedule as bs
+    chains = {}
+    for n, (r, c, g) in shapes.items():
+        chains.setdefault(g, []).append(SimpleNamespace(name=n, d_row=r, d_col=c, _row_split_active=lambda: False))
+    order = sorted(chains.values(), key=bs._chain_order_key)
+    lane_of, enq = bs._plan_lanes([bs._lane_load(hs) for hs in order], lanes)
+    return [(k, [h.name for h in order[k]], lane_of[k]) for k in enq]
+
+
+# Recorded at the commit BEFORE `_plan_lanes` existed, where the plan was computed inline in BlockSchedule.quantize: the
+# `enqueue chain k [...] on lane i` lines of GQ_TRACE=sched, quantize() run on the CPU through tests/fake_ops.py with
+# `_chain_streams` replaced by `lambda dev, n: [None] * n` (a lane without a stream runs in line) and n_streams = the lane
+# count.  The fake ops run the oracle, so every dimension -- rows AND columns -- was divided by 8 (4096 -> 512, 14336 ->
+# 1792, 1024 -> 128): all three costs are homogeneous of degree 3 in (R, C), so every one of them shrinks by exactly 2^9 --
+# exact in binary floating point -- and no comparison the plan makes can come out differently.  The same tables came out
+# of a second recording at full size with stand-in handles that compute nothing.
+_RECORDED_DENSE_3 = [(0, ["down_proj"], 0), (1, ["gate_proj", "up_proj"], 1), (2, ["q_proj", "k_proj", "v_proj"], 2),
+                     (3, ["o_proj"], 2)]
+_RECORDED_DENSE_4 = [(0, ["down_proj"], 0), (1, ["gate_proj", "up_proj"], 1), (2, ["q_proj", "k_proj", "v_proj"], 2),
+                     (3, ["o_proj"], 3)]
+_RECORDED_MIXTRAL_4 = [
+    (0, ["experts.0.w2"], 0), (1, ["experts.1.w2"], 1), (14, ["experts.6.w1", "experts.6.w3"], 2),
+    (15, ["experts.7.w1", "experts.7.w3"], 3), (4, ["experts.4.w2"], 0), (5, ["experts.5.w2"], 1),
+    (10, ["experts.2.w1", "experts.2.w3"], 2), (11, ["experts.3.w1", "experts.3.w3"], 3),
+    (8, ["experts.0.w1", "experts.0.w3"], 0), (9, ["experts.1.w1", "experts.1.w3"], 1), (6, ["experts.6.w2"], 2),
+    (7, ["experts.7.w2"], 3), (12, ["experts.4.w1", "experts.4.w3"], 0), (13, ["experts.5.w1", "experts.5.w3"], 1),
+    (2, ["experts.2.w2"], 2), (3, ["experts.3.w2"], 3), (16, ["q_proj", "k_proj", "v_proj"], 0), (17, ["o_proj"], 1)]
+# (3 lanes: 18 chains are more than 2 * 3, but the reversal needs four lanes -- enqueued in chain order)
+_RECORDED_MIXTRAL_3 = [
+    (0, ["experts.0.w2"], 0), (1, ["experts.1.w2"], 1), (2, ["experts.2.w2"], 2), (3, ["experts.3.w2"], 0),
+    (4, ["experts.4.w2"], 1), (5, ["experts.5.w2"], 2), (6, ["experts.6.w2"], 0), (7, ["experts.7.w2"], 1),
+    (8, ["experts.0.w1", "experts.0.w3"], 2), (9, ["experts.1.w1", "experts.1.w3"], 2),
+    (10, ["experts.2.w1", "experts.2.w3"], 2), (11, ["experts.3.w1", "experts.3.w3"], 2),
+    (12, ["experts.4.w1", "experts.4.w3"], 0), (13, ["experts.5.w1", "experts.5.w3"], 1),
+    (14, ["experts.6.w1", "experts.6.w3"], 2), (15, ["experts.7.w1", "experts.7.w3"], 0),
+    (16, ["q_proj", "k_proj", "v_proj"], 1), (17, ["o_proj"], 1)]
+
+
+def test_lane_plan_equals_the_plan_recorded_before_it_was_a_function():
+    """(a) a dense Llama-3-8B block's four chains on 3 lanes, (b) on 4 lanes, (c) bench.py's mixtral-block on 4 lanes --
+    18 chains > 2 * 4: the upper two lanes walk their chains cheapest first -- and (d) on 3 lanes, where nothing is
+    reversed.  Chain order, lanes and enqueue order against the tables recorded above."""
+    assert _plan_of(_llama3_8b_block(), 3) == _RECORDED_DENSE_3
+    assert _plan_of(_llama3_8b_block(), 4) == _RECORDED_DENSE_4
+    assert _plan_of(_mixtral_block(), 4) == _RECORDED_MIXTRAL_4
+    assert _plan_of(_mixtral_block(), 3) == _RECORDED_MIXTRAL_3
+
+
+def test_lane_plan_by_hand_and_edge_cases():
+    from gptq_gguf_toolkit_amd.block_schedule import _plan_lanes
+    # (a) by hand: lane load = sum R C^2 + C^3 / 3 per chain, costliest first
+    down = 4096 * 14336 ** 2 + 14336 ** 3 / 3                                    # 1.82e12
+    gate_up = 28672 * 4096 ** 2 + 2 * 4096 ** 3 / 3                              # 5.3e11
+    qkv = 6144 * 4096 ** 2 + 3 * 4096 ** 3 / 3                                   # 1.7e11
+    o = 4096 * 4096 ** 2 + 4096 ** 3 / 3                                         # 9.2e10
+    assert down > gate_up > qkv > o
+    # down -> lane 0, gate/up -> 1, q/k/v -> 2; then lane 2 holds the least (1.7e11 < 5.3e11 < 1.82e12): o_proj joins it
+    assert _plan_lanes([down, gate_up, qkv, o], 3) == ([0, 1, 2, 2], [0, 1, 2, 3])
+    assert _plan_lanes([down, gate_up, qkv, o], 4) == ([0, 1, 2, 3], [0, 1, 2, 3])
+    # no chains; no lane and one lane: everything on lane 0, in chain order
+    assert _plan_lanes([], 4) == ([], []) and _plan_lanes([], 0) == ([], [])
+    assert _plan_lanes([3.0, 2.0, 1.0], 0) == ([0, 0, 0], [0, 1, 2])
+    assert _plan_lanes([3.0, 2.0, 1.0], 1) == ([0, 0, 0], [0, 1, 2])
+    # equal costs: ties go to the lowest lane -- round robin
+    assert _plan_lanes([1.0] * 7, 3) == ([0, 1, 2, 0, 1, 2, 0], list(range(7)))
+    assert _plan_lanes([1.0] * 3, 4) == ([0, 1, 2], [0, 1, 2])
+    # exactly 2 * lanes chains: no reversal, enqueued in chain order; one more: lanes 2 and 3 cheapest first
+    assert _plan_lanes([1.0] * 8, 4) == ([0, 1, 2, 3, 0, 1, 2, 3], list(range(8)))
+    assert _plan_lanes([1.0] * 9, 4) == ([0, 1, 2, 3, 0, 1, 2, 3, 0], [0, 1, 6, 7, 4, 5, 2, 3, 8])
+    # the reversal needs four lanes: three lanes, seven chains -> chain order (loads 7 6 5 -> 7 6 9 -> 7 9 9 -> 9 9 9 -> tie: lane 0)
+    assert _plan_lanes([7.0, 6.0, 5.0, 4.0, 3.0, 2.0, 1.0], 3) == ([0, 1, 2, 2, 1, 0, 0], list(range(7)))
+
+
+def test_the_three_costs():
+    """Owner LPT key R C (C + 128) (test_row_split_plan feeds the same expression to row_split_names), chain
+    order key (not row-split, -sum R C^2), lane load sum R C^2 + C^3 / 3: floats, each with its own value."""
+    from types import SimpleNamespace
+    from gptq_gguf_toolkit_amd import block_schedule as bs
+    h = SimpleNamespace(d_row=4096, d_col=14336, _row_split_active=lambda: False)
+    s = SimpleNamespace(d_row=28672, d_col=4096, _row_split_active=lambda: True)
+    assert bs._owner_cost(h) == 4096.0 * 14336 * (14336 + 128) and isinstance(bs._owner_cost(h), float)
+    assert bs._chain_order_key([h]) == (True, -(4096.0 * 14336 ** 2))
+    assert bs._chain_order_key([h, s]) == (False, -(4096.0 * 14336 ** 2 + 28672.0 * 4096 ** 2))
+    assert bs._lane_load([h, s]) == 4096.0 * 14336 ** 2 + 14336.0 ** 3 / 3 + 28672.0 * 4096 ** 2 + 4096.0 ** 3 / 3
+    assert sorted([[h], [s]], key=bs._chain_order_key) == [[s], [h]]  # a row-split chain comes first whatever it costs
+
+
 # --------------------------------------------------------------------------- row split: the panel-wide `continue` (VERDICT r04 next #2)
 def _worker_rowsplit_corner(rank, world, port, ret, mode, tiny_slice, via_schedule, device="cpu"):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), GQ_ROW_SPLIT=mode)
