@@ -21,6 +21,8 @@ EXPORTS = (
     "gq_eval_nll", "gq_eval_kl", "gq_eval_kl_sparse",
     "gq_prof_enable", "gq_prof_ntags", "gq_prof_name", "gq_prof_collect", "gq_prof_collect2",
 )
+# include/gptq_gguf_errest.h: the additive extension of the ABI (same library, same version)
+EXPORTS_ERREST = ("gq_quad_form_workspace_bytes", "gq_quad_form")
 
 
 class GQError(RuntimeError):
@@ -111,6 +113,9 @@ def lib():
     L.gq_eval_nll.argtypes = [vp, ci, i64, i64, i64, vp, i64, vp, vp, vp]
     L.gq_eval_kl.argtypes = [vp, ci, vp, ci, i64, i64, i64, i64, vp, vp]
     L.gq_eval_kl_sparse.argtypes = [vp, ci, i64, i64, i64, vp, ci, vp, i64, vp, vp]
+    L.gq_quad_form_workspace_bytes.argtypes = [i64, i64]
+    L.gq_quad_form_workspace_bytes.restype = sz
+    L.gq_quad_form.argtypes = [vp, ci, i64, vp, ci, i64, vp, i64, i64, vp, vp, sz, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -118,7 +123,7 @@ def lib():
     L.gq_prof_collect.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
-    for name in EXPORTS:
+    for name in EXPORTS + EXPORTS_ERREST:
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

@@ -1,0 +1,398 @@
+#!/usr/bin/env python3
+"""Which Linear was hurt, and by how much, at each level of a per-layer level database: the reference's
+evopress/src/error_estimator.py on gq_h_accumulate (the Hessian) and gq_quad_form (both sums of its estimate()).
+
+    err(W_c) = sum((W - W_c) @ H * (W - W_c)) / sum(W @ H * W),    H = (2/n) sum x^T x
+
+    python -m gptq_gguf_toolkit_amd.error_estimator --model_name_or_path HF_DIR --calibration_data ids.pt \
+        --quant_weights_path DB --output_file errors.json [--calibration_tokens N] [--sequence_length L] [--verbose]
+
+`LayerErrorEstimator` has the reference's methods (update, reset, pre_step, estimate); estimate returns a 0-dim fp64
+DEVICE tensor.  Weights are never copied to fp32 (the kernel converts on load), activations are read in their own dtype,
+and H is not modified: the dead-channel fix of pre_step (:88-89) happens where the kernel reads the diagonal.
+`ErrorEstimator` takes the reference's constructor arguments and returns the same dict from estimate(group_by_numel).
+
+The one deliberate difference: the levels of a Linear are ordered by the file name's numeric prefix parsed as a FLOAT
+("4.5-Q4_K.pth" after "4-Q4_K.pth"; the reference's int(name.split(".")[0]) cannot tell them apart), and the file names
+are kept next to the values (`ErrorEstimator.levels`).  Left out: convolutions (nn.Linear only), more than one rank."""
+import argparse
+import json
+import os
+import re
+import sys
+from collections import defaultdict
+from typing import Dict, Iterable, List, Optional
+
+import torch
+import torch.nn as nn
+
+if __package__ in (None, ""):  # run as a script: make the package importable under its alias
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import gptq_gguf_toolkit_amd  # noqa: F401
+    from gptq_gguf_toolkit_amd import dist_utils, metrics, ops as _ops
+    from gptq_gguf_toolkit_amd.model_utils import LINEAR_LAYERS, ForwardInterrupt, InputCollector, _to, select_layers
+else:
+    from . import dist_utils, metrics, ops as _ops
+    from .model_utils import LINEAR_LAYERS, ForwardInterrupt, InputCollector, _to, select_layers
+
+
+def _single_rank():
+    if dist_utils.is_dist_available_and_initialized() and dist_utils.get_world_size() > 1:
+        raise NotImplementedError("error_estimator runs on one rank (torch.distributed is initialised with "
+                                  f"{dist_utils.get_world_size()} ranks)")
+
+
+class LayerErrorEstimator:
+
+    def __init__(self, layer: nn.Module):
+        self._validate_layer(layer)
+        self.layer = layer
+        self.W = layer.weight
+        self.d_row, self.d_col = layer.weight.shape
+        self.W_device, self.W_dtype, self.W_shape = self.W.device, self.W.dtype, self.W.shape
+        self.H = None
+        self.num_samples = 0
+        self.shared_H_with = None  # another handle fed by the SAME input tensor (q/k/v, gate/up): its H is this one's
+        self.pre_step_completed = False
+        self._norm = None
+
+    @staticmethod
+    def _validate_layer(layer):
+        if not isinstance(layer, nn.Linear):
+            raise TypeError(f"LayerErrorEstimator supports nn.Linear only, got {type(layer).__name__}")
+
+    @torch.no_grad()
+    def update(self, input: torch.Tensor) -> None:
+        """H <- n/(n+b) H + 2/(n+b) X^T X with b = input.shape[0] samples at once (the telescoped form of b single
+        updates, as GPTQ.update); X is read where it lies, in its own dtype."""
+        batch_size = input.shape[0]
+        if self.shared_H_with is None:
+            x = input.reshape(-1, input.shape[-1])
+            if x.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                x = x.float()
+            if not x.is_contiguous():
+                x = x.contiguous()
+            if self.H is None:
+                self.H = torch.zeros((self.d_col, self.d_col), device=x.device, dtype=torch.float32)
+            n = self.num_samples
+            _ops.h_accumulate(self.H, x, n / (n + batch_size), 2.0 / (n + batch_size))
+        self.num_samples += batch_size
+
+    def reset(self) -> None:
+        self.W = self.layer.weight
+        self.H = None
+        self.num_samples = 0
+        self.shared_H_with = None
+        self.pre_step_completed = False
+        self._norm = None
+
+    def hessian(self) -> Optional[torch.Tensor]:
+        return self.H if self.shared_H_with is None else self.shared_H_with.hessian()
+
+    @torch.no_grad()
+    def pre_step(self) -> None:
+        assert self.hessian() is not None, "One has to process at least one sample of calibration data to estimate errors"
+        _single_rank()
+        self.pre_step_completed = True
+
+    @torch.no_grad()
+    def norm(self) -> torch.Tensor:
+        """sum(W @ H * W), computed once per Linear."""
+        assert self.pre_step_completed
+        if self._norm is None:
+            self._norm = _ops.quad_form(self.W.detach(), self.hessian())
+        return self._norm
+
+    @torch.no_grad()
+    def estimate(self, W_c: torch.Tensor) -> torch.Tensor:
+        """sum((W - W_c) @ H * (W - W_c)) / sum(W @ H * W) as a 0-dim fp64 tensor on the device (no host read)."""
+        assert self.pre_step_completed
+        if tuple(W_c.shape) != tuple(self.W_shape):
+            raise ValueError(f"the compressed weight has shape {tuple(W_c.shape)}, the layer {tuple(self.W_shape)}")
+        return _ops.quad_form(self.W.detach(), self.hessian(), W_c) / self.norm()
+
+
+# ---- the level database (ppleval.load_compressed_weights reads the same layout) ----
+_NUM = re.compile(r"^[0-9]+(?:\.[0-9]+)?")
+
+
+def level_key(filename: str) -> float:
+    """The numeric prefix of a level's file name as a float: "4-Q4_K.pth" -> 4.0, "4.5-Q4_K.pth" -> 4.5, "3.pth" -> 3.0."""
+    m = _NUM.match(filename[:-4] if filename.endswith(".pth") else filename)
+    if not m:
+        raise ValueError(f"level file {filename!r} does not start with a number")
+    return float(m.group(0))
+
+
+def level_files(layer_dir: str) -> List[str]:
+    """The `.pth` files of one layer directory, ordered by numeric prefix (ties by name)."""
+    return sorted((f for f in os.listdir(layer_dir) if f.endswith(".pth")), key=lambda f: (level_key(f), f))
+
+
+def layer_dir(db: str, layer_name: str) -> str:
+    """<db>/<HF module name> (gguf_splitter --hf-layers), else <db>/<GGUF tensor name> (--gguf-layers)."""
+    d = os.path.join(db, layer_name)
+    if os.path.isdir(d):
+        return d
+    try:
+        from .pack_gptq_into_gguf import map_tensor_name
+    except ImportError:
+        from gptq_gguf_toolkit_amd.pack_gptq_into_gguf import map_tensor_name
+    try:
+        g = os.path.join(db, map_tensor_name(layer_name + ".weight"))
+    except ValueError:
+        g = d
+    if not os.path.isdir(g):
+        raise FileNotFoundError(f"{db}: no directory for {layer_name}")
+    return g
+
+
+def _rotary_rows(db: str, gguf_name: str, R: int, device):
+    """row_src undoing the converter's q / k rotary row permutation (gguf_loader.unpermute_rows), from the manifest."""
+    if not gguf_name.endswith((".attn_q.weight", ".attn_k.weight")):
+        return None
+    try:
+        with open(os.path.join(db, "manifest.json")) as f:
+            md = json.load(f).get("metadata", {})
+    except OSError:
+        return None
+    val = lambda k: md[k]["value"] if k in md else None  # noqa: E731
+    arch = val("general.architecture")
+    n_head = val(f"{arch}.attention.head_count")
+    if arch != "llama" or not n_head:
+        return None
+    n_kv = val(f"{arch}.attention.head_count_kv")
+    try:
+        from .gguf_loader import unpermute_rows
+    except ImportError:
+        from gptq_gguf_toolkit_amd.gguf_loader import unpermute_rows
+    return unpermute_rows(R, int(n_head), int(n_head) if gguf_name.endswith(".attn_q.weight") else n_kv).to(device)
+
+
+def load_level(path: str, device, db: Optional[str] = None) -> torch.Tensor:
+    """One level's weight on `device`.  A torch-saved tensor (the --hf-layers side) is loaded as it is; raw GGUF bytes
+    (the --gguf-layers side, described by `<stem>-metadata.json`) are decoded to fp16 by ops.dequantize_blocks."""
+    meta_path = path[:-4] + "-metadata.json"
+    info = None
+    if os.path.isfile(meta_path):
+        with open(meta_path) as f:
+            info = json.load(f).get("tensor_info", {})
+    if not info or "np_dtype" not in info:
+        return torch.load(path, map_location=device)
+    import numpy as np
+    # np_shape is the row-major shape of the stored bytes: [R, C] for plain types, [R, C / 256 * type_size] for K-quants
+    # ("shape" is ggml's ne order, columns first)
+    gt, np_shape = int(info["type"]), [int(n) for n in info["np_shape"]]
+    raw = torch.from_numpy(np.fromfile(path, dtype=np.uint8)).to(device)
+    plain = {0: torch.float32, 1: torch.float16, 30: torch.bfloat16}
+    rows = _rotary_rows(db, info.get("name", ""), np_shape[0], device) if db else None
+    if gt in plain:
+        w = raw.view(plain[gt]).reshape(np_shape)
+        return w[rows.long()] if rows is not None else w
+    return _ops.dequantize_blocks(gt, raw.view(np_shape[0], -1), torch.float16, rows)
+
+
+class ErrorEstimator:
+
+    def __init__(
+        self,
+        model: nn.Module,
+        data_loader: Iterable,
+        target_modules: str,
+        pre_block_modules: List[str],
+        block_modules: str,
+        compressed_weights_path: str,
+        device: Optional[torch.device] = None,
+        cpu_offload_modules: bool = False,
+        cpu_offload_activations: bool = False,
+        verbose: bool = False,
+    ) -> None:
+        self.model = model
+        self.data_loader = data_loader
+        self.target_modules = target_modules
+        self.pre_block_modules = pre_block_modules
+        self.block_modules = block_modules
+        self.device = device
+        self.cpu_offload_modules = cpu_offload_modules
+        self.cpu_offload_activations = cpu_offload_activations
+        self.verbose = verbose
+        self.compressed_weights_path = compressed_weights_path
+        self.levels: Dict[str, List[str]] = {}  # layer name -> level file names, in the order of its error list
+        self.hessians_built = 0                 # Hessians accumulated (not shared) over the whole walk
+
+    @torch.no_grad()
+    def estimate(self, group_by_numel: bool = False) -> Dict[int, Dict[str, List[float]]]:
+        """{-1: {layer: [error per level]}} or, with group_by_numel, {weight.numel(): {layer: [...]}} (reference :133-220)."""
+        _single_rank()
+        device = self.device or next(self.model.parameters()).device
+        blocks = self.model.get_submodule(self.block_modules)
+        pre_blocks = [self.model.get_submodule(name) for name in self.pre_block_modules]
+        blocks[0] = blocks[0].to(device)
+        for module in pre_blocks:
+            module.to(device)
+        has_cache = hasattr(self.model.config, "use_cache")
+        if has_cache:
+            use_cache = self.model.config.use_cache
+            self.model.config.use_cache = False
+        blocks[0] = InputCollector(blocks[0], cpu_offload=self.cpu_offload_activations)
+        for inp_args, inp_kwargs in self.data_loader:
+            try:
+                self.model(*_to(inp_args, device=device), **_to(inp_kwargs, device=device))
+            except ForwardInterrupt:
+                pass
+        input_args, input_kwargs = blocks[0].input_args, blocks[0].input_kwargs
+        blocks[0] = blocks[0].module
+        if self.cpu_offload_modules:
+            for module in pre_blocks:
+                module.cpu()
+
+        all_errors = defaultdict(dict)
+        for block_id, block in enumerate(blocks):
+            if self.verbose:
+                dist_utils.print_on_main(f"Processing {self.block_modules} {block_id}/{len(blocks)}.")
+            block = block.to(device)
+            layer_prefix = f"{self.block_modules}.{block_id}."
+            layers = select_layers(self.model, layer_prefix, self.target_modules, LINEAR_LAYERS)  # a conv raises below
+            handles, hooks, seen = self._prepare_hooks_and_handles(layers)
+            for i, (inp_args, inp_kwargs) in enumerate(zip(input_args, input_kwargs)):
+                inp_args, inp_kwargs = _to(inp_args, device=device), _to(inp_kwargs, device=device)
+                out = block(*inp_args, **inp_kwargs)
+                seen.clear()
+                out = out[0] if isinstance(out, (list, tuple)) else out
+                if self.cpu_offload_activations:
+                    out = out.cpu()
+                # only the first input argument changes from block to block
+                if len(inp_args) > 0:
+                    input_args[i] = (out, *inp_args[1:])
+                elif "hidden_states" in inp_kwargs:
+                    input_kwargs[i] = {**input_kwargs[i], "hidden_states": out}
+                else:
+                    raise ValueError("Unsupported block input format.")
+            for h in hooks.values():
+                h.remove()
+            self.hessians_built += sum(h.shared_H_with is None for h in handles.values())
+            block_errors = self._estimate_errors_group(handles)
+            if group_by_numel:
+                for k, v in block_errors.items():
+                    all_errors[handles[k].W.numel()][k] = v
+            else:
+                all_errors[-1].update(block_errors)
+            for h in handles.values():
+                h.reset()
+            if self.cpu_offload_modules:
+                block = block.cpu()
+            del handles, hooks
+        if has_cache:
+            self.model.config.use_cache = use_cache
+        return all_errors
+
+    def _prepare_hooks_and_handles(self, layers: Dict[str, nn.Module]):
+        handles, hooks = {}, {}
+        seen = {}  # inputs of the current forward: key -> (the handle that folds them, the tensor); cleared after every sample
+
+        def update_handle_hook(name):
+            def _hook(_, inp, out):
+                h, x = handles[name], inp[0]
+                # Linears fed the very same tensor (q/k/v, gate/up) share one Hessian, as BlockSchedule.feed
+                key = (x.data_ptr(), tuple(x.shape), tuple(x.stride()), x.dtype, x._version)
+                leader = seen.get(key, (None, None))[0]
+                if leader is not None and leader is not h and leader.d_col == h.d_col:
+                    assert h.shared_H_with in (None, leader) and h.H is None, "input sharing pattern changed between samples"
+                    h.shared_H_with = leader
+                else:
+                    assert h.shared_H_with is None, "input sharing pattern changed between samples"
+                    seen[key] = (h, x)  # x is kept so that its address is not reused within the sample
+                h.update(x)
+            return _hook
+
+        for layer_name, layer in layers.items():
+            handles[layer_name] = self._create_handle(layer)
+            hooks[layer_name] = layer.register_forward_hook(update_handle_hook(layer_name))
+        return handles, hooks, seen
+
+    def _create_handle(self, layer):
+        return LayerErrorEstimator(layer)
+
+    def _estimate_errors_group(self, handles: Dict[str, LayerErrorEstimator]) -> Dict[str, List[float]]:
+        errors = {}
+        for name, handle in handles.items():
+            handle.pre_step()
+            ldir = layer_dir(self.compressed_weights_path, name)
+            files = level_files(ldir)
+            vals = [handle.estimate(load_level(os.path.join(ldir, f), handle.W_device, self.compressed_weights_path))
+                    for f in files]
+            # numerators and the denominator were divided on the device in fp64: ONE host read per Linear
+            errors[name] = torch.stack(vals).tolist() if vals else []
+            self.levels[name] = files
+            if self.verbose:
+                dist_utils.print_on_main(f"{name}: " + "  ".join(f"{f[:-4]} {e:.4e}" for f, e in zip(files, errors[name])))
+        return errors
+
+
+def report(errors: Dict[int, Dict[str, List[float]]], levels: Dict[str, List[str]]) -> Dict[str, List[dict]]:
+    """{layer: [{"level": file stem, "error": value}, ...]} in level order: what the CLI writes."""
+    out = {}
+    for group in errors.values():
+        for name, vals in group.items():
+            out[name] = [{"level": f[:-4], "error": float(e)} for f, e in zip(levels[name], vals)]
+    return out
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--model_name_or_path", type=str, required=True, help="The name or path to the model")
+    p.add_argument("--calibration_data", type=str, required=True, help=".pt file of [1, L] token-id tensors")
+    p.add_argument("--calibration_tokens", default=None, type=int, help="Number of tokens for calibration (default: all).")
+    p.add_argument("--sequence_length", default=None, type=int, help="Length of sequences.")
+    p.add_argument("--quant_weights_path", type=str, required=True, help="Path to the per-layer level database")
+    p.add_argument("--output_file", type=str, required=True, help="Path to output JSON file for storing results")
+    p.add_argument("--dtype", type=str, default="float16", choices=["auto", "float16", "float32", "bfloat16"],
+                   help="dtype to load the model.")
+    p.add_argument("--seed", default=0, type=int, help="Random seed.")
+    p.add_argument("--attn_implementation", type=str, default=None, choices=["eager", "sdpa", "flash_attention_2"])
+    p.add_argument("--target_modules", type=str, default=r".*layers.*((q|k|v|o|gate|up|down)_proj)$",
+                   help="regex of the Linears to score")
+    p.add_argument("--pre_block_modules", nargs="+", type=str, default=["model.embed_tokens", "model.rotary_emb"])
+    p.add_argument("--block_modules", type=str, default="model.layers")
+    p.add_argument("--verbose", action="store_true", help="one line per Linear")
+    args = p.parse_args(argv)
+    if not os.path.isfile(args.calibration_data):  # refused BEFORE any work
+        p.error(f"calibration_data must be a .pt file of token-id tensors (got {args.calibration_data!r}); "
+                "dataset downloads are not part of this package")
+    if not os.path.isdir(args.quant_weights_path):
+        p.error(f"quant_weights_path {args.quant_weights_path!r} is not a directory")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    assert torch.cuda.is_available(), "error_estimator needs a GPU (there is no CPU path)"
+    try:
+        from .ppleval import load_hf_model
+    except ImportError:
+        from gptq_gguf_toolkit_amd.ppleval import load_hf_model
+    device = torch.device("cuda")
+    metrics.fix_seed(args.seed)
+    model = load_hf_model(args, device)
+    seq_len = args.sequence_length or model.config.max_position_embeddings
+    data = metrics.load_eval_data(args.calibration_data, args.calibration_tokens, seq_len, what="calibration_data")
+    pre = [m for m in args.pre_block_modules if _has_submodule(model, m)]
+    est = ErrorEstimator(model, [([], {"input_ids": ids}) for ids in data], args.target_modules, pre, args.block_modules,
+                         args.quant_weights_path, device=device, verbose=args.verbose)
+    out = report(est.estimate(), est.levels)
+    with open(args.output_file, "w") as f:
+        json.dump(out, f, indent=2)
+    print(f"Results saved to {args.output_file}")
+    return out
+
+
+def _has_submodule(model, name) -> bool:
+    try:
+        model.get_submodule(name)
+        return True
+    except AttributeError:
+        return False
+
+
+if __name__ == "__main__":
+    main()

@@ -619,3 +619,43 @@ def eval_kl_sparse(logits: torch.Tensor, target_vals: torch.Tensor, target_ids: 
                                           _ptr(ti[a:a + rows]), K, _ptr(kl[a:a + rows]), _stream(x)), "gq_eval_kl_sparse")
         a += rows
     return kl.view(lead)
+
+
+# ---- layer error estimate (gq_quad_form): sum_r d_r H~ d_r^T, d = A - B ----
+def _qf_rows(t: torch.Tensor) -> torch.Tensor:
+    """t [R, C] as the kernel can read it: unit column stride and 16-byte aligned rows; a copy only when that fails."""
+    es = t.element_size()
+    if t.stride(1) == 1 and t.data_ptr() % 16 == 0 and (t.shape[0] == 1 or (t.stride(0) >= t.shape[1] and t.stride(0) * es % 16 == 0)):
+        return t
+    return t.contiguous()
+
+
+def quad_form(A: torch.Tensor, H: torch.Tensor, B: Optional[torch.Tensor] = None,
+              ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """((D @ H~) * D).sum() with D = A - B (D = A when B is None), as a 0-dim fp64 device tensor (gq_quad_form): the two
+    sums of evopress/src/error_estimator.py:101-102.  A, B [R, C] fp32 / fp16 / bf16, read in their own dtype and with
+    their own row stride (a view is copied only when its rows are not 16-byte aligned); H [C, C] fp32 symmetric, a zero
+    on its diagonal counts as 1 and H is not written.  No host read."""
+    _need_cuda(A, H, B, ws)
+    if A.dim() != 2 or A.dtype not in _DT or (B is not None and (B.shape != A.shape or B.dtype not in _DT)):
+        raise _cabi.GQError(f"quad_form: A and B must be [R, C] fp32 / fp16 / bf16 tensors of one shape; got "
+                            f"{A.dtype} {tuple(A.shape)} and {None if B is None else (B.dtype, tuple(B.shape))}")
+    R, C = A.shape
+    for t in (H, B, ws):
+        if t is not None and t.device != A.device:
+            raise _cabi.GQError(f"quad_form: every tensor must be on A's device {A.device}; got one on {t.device}")
+    if ws is not None and (not ws.is_contiguous() or ws.data_ptr() % 8):
+        raise _cabi.GQError("quad_form: ws must be contiguous and 8-byte aligned")
+    if H.dtype != torch.float32 or tuple(H.shape) != (C, C) or not H.is_contiguous():
+        raise _cabi.GQError(f"quad_form: H must be a contiguous fp32 [{C}, {C}] tensor; got {H.dtype} {tuple(H.shape)}")
+    A = _qf_rows(A)
+    B = _qf_rows(B) if B is not None else None
+    need = int(lib().gq_quad_form_workspace_bytes(R, C))
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = _ws(need, A.device)
+    out = torch.empty((), dtype=torch.float64, device=A.device)
+    lda = A.stride(0) if R > 1 else max(A.stride(0), C)
+    ldb = 0 if B is None else (B.stride(0) if R > 1 else max(B.stride(0), C))
+    check(lib().gq_quad_form(_ptr(A), _DT[A.dtype], lda, _ptr(B), _DT[B.dtype] if B is not None else 0, ldb, _ptr(H), R, C,
+                             _ptr(out), _ptr(ws), ws.numel() * ws.element_size(), _stream(A)), "gq_quad_form")
+    return out
