@@ -23,6 +23,9 @@ EXPORTS = (
 )
 # include/gptq_gguf_errest.h: the additive extension of the ABI (same library, same version)
 EXPORTS_ERREST = ("gq_quad_form_workspace_bytes", "gq_quad_form")
+# include/gptq_gguf_search.h: the level switch of the bit-width search (additive in the same way)
+EXPORTS_SEARCH = ("gq_level_switch",)
+SWITCH_MAX_JOBS = 64  # GQ_SWITCH_MAX_JOBS: jobs of one launch (a longer list is cut by the library)
 
 
 class GQError(RuntimeError):
@@ -37,6 +40,12 @@ class TypeInfo(ctypes.Structure):
 class Search(ctypes.Structure):
     _fields_ = [("rmin", ctypes.c_double), ("rdelta", ctypes.c_double), ("nstep", ctypes.c_int),
                 ("quant_scale", ctypes.c_int), ("grid", ctypes.c_int), ("maxshrink", ctypes.c_double)]
+
+
+class SwitchJob(ctypes.Structure):
+    """gq_switch_job_t"""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("row_src", ctypes.c_void_p),
+                ("R", ctypes.c_int64), ("C", ctypes.c_int64), ("kind", ctypes.c_int32), ("out_dtype", ctypes.c_int32)]
 
 
 def build(force: bool = False) -> str:
@@ -116,6 +125,7 @@ def lib():
     L.gq_quad_form_workspace_bytes.argtypes = [i64, i64]
     L.gq_quad_form_workspace_bytes.restype = sz
     L.gq_quad_form.argtypes = [vp, ci, i64, vp, ci, i64, vp, i64, i64, vp, vp, sz, vp]
+    L.gq_level_switch.argtypes = [ctypes.POINTER(SwitchJob), ci, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -123,7 +133,7 @@ def lib():
     L.gq_prof_collect.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
-    for name in EXPORTS + EXPORTS_ERREST:
+    for name in EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH:
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

@@ -1,0 +1,204 @@
+// gq_switch.hip -- K18: one candidate of the bit-width search made current.  gq_level_switch takes a HOST table of jobs
+// (stored level -> live weight, packed K-quant blocks or a dense matrix as the source) and applies up to
+// GQ_SWITCH_MAX_JOBS of them per launch; the reference's load_layers (evopress/evo_quant_search.py:110-138) reads a dense
+// file from disk per changed Linear instead.
+//
+// The table travels in the kernel arguments (SwitchTable, 3080 bytes of the 4 KB segment): no staging buffer, no copy on
+// the stream, nothing to keep alive after the call returns.  Entry j carries the prefix sum `unit_end` of work units of
+// jobs 0 .. j; workgroup u (one unit each) finds its job by a binary search over that column -- all of it on block-uniform
+// values, i.e. scalar loads from the argument segment and scalar compares -- and then runs ONE turn of the job's kind:
+//   packed: blockdec::decode_turn<QT, OutT>, the very function gq_dequantize_blocks' kernel loops over (16 blocks of 256
+//           values staged in LDS with the type's natural load width, 16 values per thread, 16-byte stores).  Same text,
+//           same flags, so the same bits; reads and writes stay inside the job's own [src, ..) and [dst, ..) as there.
+//   dense : 512 chunks of 16 output bytes, two per thread, chunk k = (row k / cpr, 16 / elsize columns): one 8- / 16- /
+//           32-byte load of the (gathered) source row, exact widening to fp32, one RNE cast (f2h / f2bf: torch's
+//           .to(dtype)), one 16-byte store.
+// The kind / out_dtype dispatch is a switch on block-uniform values: a workgroup executes one arm.  HBM-bound like K15:
+// 0.33-0.82 B/param in, 2 or 4 B/param out; the unit is K15's turn so that the per-byte rate is K15's.
+#include "../../../include/gptq_gguf_search.h"
+#include "gq_block_decode.hpp"
+
+namespace gq {
+namespace {
+
+using namespace blockdec;
+
+constexpr int DENSE_CHUNKS = 512;  // 16-byte output chunks per dense unit (two per thread)
+
+struct SwitchEntry {
+    const uint8_t* src;
+    uint8_t* dst;
+    const int32_t* row_src;
+    int64_t n;          // packed: blocks of the job (R * C / 256); dense: 16-byte output chunks (R * cpr)
+    int32_t per_row;    // packed: blocks per row; dense: chunks per row (cpr)
+    uint32_t unit_end;  // work units of entries 0 .. this one
+    int32_t kind, out_dtype;
+};
+struct SwitchTable {
+    int32_t n;
+    int32_t pad;
+    SwitchEntry e[GQ_SWITCH_MAX_JOBS];
+};
+static_assert(sizeof(SwitchTable) <= 4096 - 64, "the job table must fit the kernel-argument segment");
+
+template <int QT>
+__device__ __forceinline__ void packed_unit(const SwitchEntry& J, int64_t b0, uint8_t* sb, int64_t* ssrc) {
+    const int nb = (int)((J.n - b0) < DB ? (J.n - b0) : DB);
+    switch (J.out_dtype) {
+    case GQ_F32: decode_turn<QT, float>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<float*>(J.dst), sb, ssrc); break;
+    case GQ_F16: decode_turn<QT, half_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<half_bits*>(J.dst), sb, ssrc); break;
+    default: decode_turn<QT, bf16_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<bf16_bits*>(J.dst), sb, ssrc); break;
+    }
+}
+
+template <int DT> __device__ __forceinline__ float widen(uint32_t bits);
+template <> __device__ __forceinline__ float widen<GQ_F32>(uint32_t bits) { return __builtin_bit_cast(float, bits); }
+template <> __device__ __forceinline__ float widen<GQ_F16>(uint32_t bits) { return h2f((uint16_t)bits); }
+template <> __device__ __forceinline__ float widen<GQ_BF16>(uint32_t bits) { return bf2f((uint16_t)bits); }
+
+// chunk k of a dense job: CH = 16 / sizeof(dst element) consecutive elements of one row
+template <int SD, int OD>
+__device__ __forceinline__ void dense_unit(const SwitchEntry& J, int64_t k0) {
+    constexpr int SES = SD == GQ_F32 ? 4 : 2, DES = OD == GQ_F32 ? 4 : 2, CH = 16 / DES, NW = CH * SES / 4;
+#pragma unroll
+    for (int i = 0; i < DENSE_CHUNKS / 256; ++i) {
+        const int64_t k = k0 + i * 256 + threadIdx.x;
+        if (k < J.n) {
+            const int64_t r = k / J.per_row, cc = k - r * J.per_row;
+            const int64_t sr = J.row_src ? (int64_t)J.row_src[r] : r;
+            const uint8_t* sp = J.src + (sr * J.per_row + cc) * (CH * SES);
+            uint32_t w[NW];
+            if constexpr (NW == 2) {
+                const uint2 v = *reinterpret_cast<const uint2*>(sp);
+                w[0] = v.x, w[1] = v.y;
+            } else {
+#pragma unroll
+                for (int q = 0; q < NW / 4; ++q) {
+                    const uint4 v = reinterpret_cast<const uint4*>(sp)[q];
+                    w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+                }
+            }
+            uint32_t o[4];
+#pragma unroll
+            for (int e = 0; e < CH; ++e) {
+                const float f = SES == 4 ? widen<SD>(w[e]) : widen<SD>((w[e >> 1] >> (16 * (e & 1))) & 0xffffu);
+                if constexpr (OD == GQ_F32) o[e] = __builtin_bit_cast(uint32_t, f);
+                else {
+                    const uint32_t h = OD == GQ_F16 ? f2h(f) : f2bf(f);
+                    o[e >> 1] = (e & 1) ? (o[e >> 1] | (h << 16)) : h;
+                }
+            }
+            *reinterpret_cast<uint4*>(J.dst + k * 16) = make_uint4(o[0], o[1], o[2], o[3]);
+        }
+    }
+}
+
+template <int SD>
+__device__ __forceinline__ void dense_unit_from(const SwitchEntry& J, int64_t k0) {
+    switch (J.out_dtype) {
+    case GQ_F32: dense_unit<SD, GQ_F32>(J, k0); break;
+    case GQ_F16: dense_unit<SD, GQ_F16>(J, k0); break;
+    default: dense_unit<SD, GQ_BF16>(J, k0); break;
+    }
+}
+
+__global__ __launch_bounds__(256) void level_switch_kernel(const SwitchTable t) {
+    __shared__ __attribute__((aligned(16))) uint8_t sb[DB * TSP_MAX];
+    __shared__ int64_t ssrc[DB];
+    const uint32_t u = blockIdx.x;
+    int lo = 0, hi = t.n - 1;  // the first entry whose unit_end exceeds u (the grid is e[n - 1].unit_end: it exists)
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (u < t.e[mid].unit_end) hi = mid;
+        else lo = mid + 1;
+    }
+    const SwitchEntry& J = t.e[lo];
+    const int64_t ul = (int64_t)(u - (lo ? t.e[lo - 1].unit_end : 0u));  // the unit within the job
+    switch (J.kind) {
+    case GQ_Q2_K: packed_unit<GQ_Q2_K>(J, ul * DB, sb, ssrc); break;
+    case GQ_Q3_K: packed_unit<GQ_Q3_K>(J, ul * DB, sb, ssrc); break;
+    case GQ_Q4_K: packed_unit<GQ_Q4_K>(J, ul * DB, sb, ssrc); break;
+    case GQ_Q5_K: packed_unit<GQ_Q5_K>(J, ul * DB, sb, ssrc); break;
+    case GQ_Q6_K: packed_unit<GQ_Q6_K>(J, ul * DB, sb, ssrc); break;
+    case GQ_F32: dense_unit_from<GQ_F32>(J, ul * DENSE_CHUNKS); break;
+    case GQ_F16: dense_unit_from<GQ_F16>(J, ul * DENSE_CHUNKS); break;
+    default: dense_unit_from<GQ_BF16>(J, ul * DENSE_CHUNKS); break;
+    }
+}
+
+bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+bool is_dtype(int d) { return d == GQ_F32 || d == GQ_F16 || d == GQ_BF16; }
+int elsize(int d) { return d == GQ_F32 ? 4 : 2; }
+int block_align(int q) { return q == GQ_Q2_K ? 4 : (q == GQ_Q4_K || q == GQ_Q5_K) ? 16 : 2; }
+
+constexpr int64_t MAX_UNITS = 0x7fffffff;  // of one launch (the grid's x extent) and so of one job
+
+// every check of job i; fills the job's table entry except unit_end, and its unit count
+int check_job(const gq_switch_job_t& j, int i, SwitchEntry& e, int64_t& units) {
+    const bool packed = j.kind >= GQ_Q2_K && j.kind <= GQ_Q6_K;
+    if (!packed && !is_dtype(j.kind)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_level_switch: job %d: unknown kind %d", i, j.kind);
+    if (!is_dtype(j.out_dtype)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_level_switch: job %d: unknown out_dtype %d", i, j.out_dtype);
+    if (!j.src) GQ_FAIL(GQ_E_NULL, "gq_level_switch: job %d: src is NULL", i);
+    if (!j.dst) GQ_FAIL(GQ_E_NULL, "gq_level_switch: job %d: dst is NULL", i);
+    if (j.R < 1) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: R=%ld (R < 1)", i, (long)j.R);
+    if (j.C < 1 || j.C > 0x7fffffff) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: C=%ld (not in [1, 2^31))", i, (long)j.C);
+    if (!aligned(j.dst, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: dst not 16-byte aligned", i);
+    if (!aligned(j.row_src, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: row_src not 4-byte aligned", i);
+    const int des = elsize(j.out_dtype);
+    int64_t per_unit;
+    if (packed) {
+        if (j.C % 256) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: C=%ld (C %% 256 != 0)", i, (long)j.C);
+        if (!aligned(j.src, block_align(j.kind)))
+            GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: src not %d-byte aligned", i, block_align(j.kind));
+        e.per_row = (int32_t)(j.C / 256), per_unit = DB;
+    } else {
+        const int ses = elsize(j.kind);
+        if (j.C * ses % 16 || j.C * des % 16)
+            GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: C=%ld (rows of src and dst must be multiples of 16 bytes)", i, (long)j.C);
+        if (!aligned(j.src, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: src not 16-byte aligned", i);
+        e.per_row = (int32_t)(j.C * des / 16), per_unit = DENSE_CHUNKS;
+    }
+    if (j.R > (MAX_UNITS * per_unit) / e.per_row)
+        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: R=%ld C=%ld is more than one launch takes", i, (long)j.R, (long)j.C);
+    e.src = static_cast<const uint8_t*>(j.src), e.dst = static_cast<uint8_t*>(j.dst), e.row_src = j.row_src;
+    e.n = j.R * e.per_row, e.kind = j.kind, e.out_dtype = j.out_dtype;
+    units = (e.n + per_unit - 1) / per_unit;
+    return GQ_OK;
+}
+
+}  // namespace
+}  // namespace gq
+
+using namespace gq;
+
+extern "C" {
+
+int gq_level_switch(const gq_switch_job_t* jobs_host, int n_jobs, void* stream) {
+    if (int rc = options_ok()) return rc;
+    if (n_jobs < 0) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: n_jobs=%d (n_jobs < 0)", n_jobs);
+    if (n_jobs == 0) return GQ_OK;
+    if (!jobs_host) GQ_FAIL(GQ_E_NULL, "gq_level_switch: jobs_host is NULL");
+    SwitchEntry e;
+    int64_t units;
+    for (int i = 0; i < n_jobs; ++i)  // all refusals first: a refused call has launched nothing
+        if (int rc = check_job(jobs_host[i], i, e, units)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    SwitchTable t;
+    for (int i = 0; i < n_jobs;) {
+        int64_t total = 0;
+        t.n = 0, t.pad = 0;
+        while (i < n_jobs && t.n < GQ_SWITCH_MAX_JOBS) {
+            check_job(jobs_host[i], i, t.e[t.n], units);
+            if (total + units > MAX_UNITS) break;  // (a single job never exceeds it: checked above)
+            total += units;
+            t.e[t.n++].unit_end = (uint32_t)total;
+            ++i;
+        }
+        for (int k = t.n; k < GQ_SWITCH_MAX_JOBS; ++k) t.e[k] = SwitchEntry{};
+        hipLaunchKernelGGL(level_switch_kernel, dim3((unsigned)total), dim3(256), 0, st, t);
+        GQ_LAUNCH_CHECK();
+    }
+    return GQ_OK;
+}
+
+}  // extern "C"

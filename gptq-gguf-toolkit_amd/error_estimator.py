@@ -206,7 +206,11 @@ class ErrorEstimator:
         cpu_offload_modules: bool = False,
         cpu_offload_activations: bool = False,
         verbose: bool = False,
+        level_store=None,
     ) -> None:
+        """level_store: an optional level_store.LevelStore holding the database on the device; the levels are then read
+        from it instead of from the files (the values are the same)."""
+        self.level_store = level_store
         self.model = model
         self.data_loader = data_loader
         self.target_modules = target_modules
@@ -319,8 +323,11 @@ class ErrorEstimator:
             handle.pre_step()
             ldir = layer_dir(self.compressed_weights_path, name)
             files = level_files(ldir)
-            vals = [handle.estimate(load_level(os.path.join(ldir, f), handle.W_device, self.compressed_weights_path))
-                    for f in files]
+            if self.level_store is not None:
+                vals = [handle.estimate(self.level_store.level_tensor(name, f)) for f in files]
+            else:
+                vals = [handle.estimate(load_level(os.path.join(ldir, f), handle.W_device, self.compressed_weights_path))
+                        for f in files]
             # numerators and the denominator were divided on the device in fp64: ONE host read per Linear
             errors[name] = torch.stack(vals).tolist() if vals else []
             self.levels[name] = files

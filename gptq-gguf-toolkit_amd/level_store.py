@@ -1,0 +1,208 @@
+"""Every level of every Linear of a per-layer level database, resident on the device in the form it is stored in, and the
+switch of the model from one level assignment to another in ONE kernel call (ops.level_switch / gq_level_switch).
+
+    store = LevelStore(model, db, device)          # uploads each level once; packed GGUF bytes stay packed
+    store.switch({"model.layers.0.mlp.up_proj": 4.0, ...})   # or the search's nested lists; decodes into weight.data
+
+The reference's load_layers (evopress/evo_quant_search.py:110-138) reads a dense [R, C] file per changed Linear and per
+candidate.  Here a switch reads the stored level where it lies on the device and writes the Linear's existing weight
+storage: no file, no host copy, no [R, C] temporary, no reallocation (weight.data_ptr() does not change).
+
+Both database layouts of gguf_splitter are read, through error_estimator.layer_dir / level_files / level_key:
+  --hf-layers   <db>/<HF module name>/<bpw>-<Qn_K>.pth   torch-saved dense tensors: kept dense in their own dtype; a switch
+                is a cast copy with .to(dtype) rounding, so the weight equals torch.load(file).to(dtype) bit for bit;
+  --gguf-layers <db>/<GGUF tensor name>/<bpw>.pth + -metadata.json   raw block bytes: kept packed; a switch decodes them
+                (with the q / k rotary row gather of the manifest) straight to the weight dtype.  For fp16 weights that is
+                error_estimator.load_level(file).to(dtype) bit for bit; for bf16 / fp32 weights the value is rounded ONCE
+                from the fp32 decode, where load_level's fp16 tensor followed by .to(dtype) rounds twice.
+One rank, nn.Linear only."""
+import json
+import os
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import ops
+from .error_estimator import _rotary_rows, layer_dir, level_files, level_key
+
+_PLAIN = {0: torch.float32, 1: torch.float16, 30: torch.bfloat16}  # ggml types stored as plain matrices
+_KQUANT = (10, 11, 12, 13, 14)
+_DENSE = (torch.float32, torch.float16, torch.bfloat16)
+
+State = Union[Dict[str, float], Sequence[Sequence[float]]]
+
+
+class _Level:
+    """One stored level: where it is on disk and, after upload, on the device."""
+    __slots__ = ("key", "file", "path", "kind", "nbytes", "np_shape", "dtype", "gguf_name", "data", "rows")
+
+
+def _describe(path: str) -> Tuple[Optional[int], Optional[list], Optional[str], str]:
+    """(ggml type or None for a torch-saved tensor, np_shape, np dtype name, gguf tensor name) of a level file."""
+    meta_path = path[:-4] + "-metadata.json"
+    info = None
+    if os.path.isfile(meta_path):
+        with open(meta_path) as f:
+            info = json.load(f).get("tensor_info", {})
+    if not info or "np_dtype" not in info:
+        return None, None, None, ""
+    return int(info["type"]), [int(n) for n in info["np_shape"]], info["np_dtype"], info.get("name", "")
+
+
+class LevelStore:
+
+    def __init__(self, model: nn.Module, db: str, device, layer_names: Optional[Sequence[str]] = None,
+                 capacity_bytes: Optional[int] = None):
+        """layer_names: the Linears to hold (default: every nn.Linear of the model that has a directory in `db`).
+        capacity_bytes: the device memory the levels may take (default: what torch reports free on `device`)."""
+        self.model, self.db, self.device = model, db, torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:  # "cuda" -> the current device, as tensors report it
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if layer_names is None:
+            layer_names = [n for n, m in model.named_modules() if isinstance(m, nn.Linear) and self._has_dir(n)]
+        self.layers: Dict[str, nn.Linear] = {}
+        self.levels: Dict[str, List[_Level]] = {}
+        need = 0
+        for name in layer_names:  # pass 1: the files only -- every refusal comes before the first upload
+            layer = model.get_submodule(name)
+            if not isinstance(layer, nn.Linear):
+                raise TypeError(f"LevelStore supports nn.Linear only, {name} is a {type(layer).__name__}")
+            if layer.weight.dtype not in _DENSE:
+                raise TypeError(f"{name}: weight dtype {layer.weight.dtype} is not fp32 / fp16 / bf16")
+            ldir = layer_dir(db, name)
+            self.layers[name], self.levels[name] = layer, []
+            for f in level_files(ldir):
+                lv = self._inspect(os.path.join(ldir, f), name, layer)
+                self.levels[name].append(lv)
+                need += lv.nbytes
+            if not self.levels[name]:
+                raise FileNotFoundError(f"{ldir}: no level file for {name}")
+        if capacity_bytes is None:
+            capacity_bytes = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else None
+        if capacity_bytes is not None and need > capacity_bytes:
+            raise MemoryError(f"the levels of {db} need {need} bytes on {self.device}, {capacity_bytes} are available "
+                              f"({sum(len(v) for v in self.levels.values())} levels of {len(self.levels)} Linears)")
+        self._rows: Dict[Tuple[str, int], Optional[torch.Tensor]] = {}
+        for name, lvs in self.levels.items():  # pass 2: upload, each level once
+            for lv in lvs:
+                self._upload(name, lv)
+        self.state: Dict[str, Optional[float]] = {name: None for name in self.layers}
+        self.jobs_issued = 0  # jobs of all switches so far (the diff is observable)
+
+    # ---- construction ----
+    def _has_dir(self, name: str) -> bool:
+        try:
+            layer_dir(self.db, name)
+            return True
+        except FileNotFoundError:
+            return False
+
+    def _inspect(self, path: str, name: str, layer: nn.Linear) -> _Level:
+        lv = _Level()
+        lv.path, lv.file, lv.key = path, os.path.basename(path), level_key(os.path.basename(path))
+        lv.data = lv.rows = None
+        gt, lv.np_shape, np_dtype, lv.gguf_name = _describe(path)
+        want = tuple(layer.weight.shape)
+        if gt is None:  # torch-saved: the shape is only known after loading; the file size bounds the bytes
+            lv.kind, lv.dtype, lv.nbytes = None, None, os.path.getsize(path)
+            return lv
+        R = lv.np_shape[0]
+        if gt in _PLAIN:
+            lv.kind, lv.dtype, shape = None, _PLAIN[gt], tuple(lv.np_shape)
+        elif gt in _KQUANT:
+            ts = ops.type_info(gt)["type_size"]
+            lv.kind, lv.dtype, shape = gt, torch.uint8, (R, lv.np_shape[1] // ts * 256)
+        else:
+            raise ValueError(f"{path}: ggml type {gt} is not a K-quant or a plain fp32 / fp16 / bf16 matrix")
+        if shape != want:
+            raise ValueError(f"{name}: level {lv.file!r} has shape {shape}, the Linear {want}")
+        lv.nbytes = int(np.prod(lv.np_shape)) * (1 if gt in _KQUANT else torch.empty(0, dtype=lv.dtype).element_size())
+        if os.path.getsize(path) != lv.nbytes:
+            raise ValueError(f"{path}: {os.path.getsize(path)} bytes on disk, its metadata describes {lv.nbytes}")
+        return lv
+
+    def _upload(self, name: str, lv: _Level) -> None:
+        want = tuple(self.layers[name].weight.shape)
+        if lv.np_shape is None:  # a torch-saved dense tensor (--hf-layers): kept as saved
+            t = torch.load(lv.path, map_location="cpu")
+            if tuple(t.shape) != want:
+                raise ValueError(f"{name}: level {lv.file!r} has shape {tuple(t.shape)}, the Linear {want}")
+            if t.dtype not in _DENSE:
+                t = t.float()
+            lv.dtype, lv.data = t.dtype, t.contiguous().to(self.device)
+        else:
+            raw = torch.from_numpy(np.fromfile(lv.path, dtype=np.uint8)).to(self.device)
+            lv.data = raw if lv.kind is not None else raw.view(lv.dtype).reshape(lv.np_shape)
+            key = (lv.gguf_name.rsplit(".", 2)[-2] if lv.gguf_name.count(".") >= 2 else "", want[0])
+            if key not in self._rows:  # the q / k row gather, built once per (tensor kind, R)
+                self._rows[key] = _rotary_rows(self.db, lv.gguf_name, want[0], self.device)
+            lv.rows = self._rows[key]
+        lv.nbytes = lv.data.numel() * lv.data.element_size()
+
+    # ---- use ----
+    def bytes(self) -> int:
+        """Device memory held: every level as stored, plus the row-gather index vectors."""
+        held = sum(lv.nbytes for lvs in self.levels.values() for lv in lvs)
+        return held + sum(r.numel() * 4 for r in self._rows.values() if r is not None)
+
+    def level_keys(self, name: str) -> List[float]:
+        return [lv.key for lv in self.levels[name]]
+
+    def find(self, name: str, key) -> _Level:
+        """The level of `name` whose numeric prefix is `key` (|difference| < 1e-6, as the reference matches bitwidths) or
+        whose file name / stem is `key`."""
+        for lv in self.levels[name]:
+            if isinstance(key, str):
+                if key in (lv.file, lv.file[:-4]):
+                    return lv
+            elif abs(lv.key - float(key)) < 1e-6:
+                return lv
+        raise KeyError(f"{name}: no level {key!r} (have {[lv.file for lv in self.levels[name]]})")
+
+    def flatten(self, state: State, grouped_layer_names=None) -> Dict[str, float]:
+        if isinstance(state, dict):
+            return state
+        if grouped_layer_names is None:
+            grouped_layer_names = self.grouped_layer_names
+        return {n: k for names, keys in zip(grouped_layer_names, state) for n, k in zip(names, keys)}
+
+    grouped_layer_names: Optional[Sequence[Sequence[str]]] = None  # set by the search: the meaning of nested-list states
+
+    @torch.no_grad()
+    def switch(self, state: State) -> int:
+        """Make `state` ({layer_name: level key} or the search's nested lists) current: the Linears whose level differs
+        from the recorded one are rewritten, in place, by ONE ops.level_switch call.  Layers the state does not name keep
+        their level.  Returns the number of Linears rewritten; no host read."""
+        flat = self.flatten(state)
+        jobs, new = [], {}
+        for name, key in flat.items():
+            lv = self.find(name, key)
+            if self.state[name] is not None and self.state[name] == lv.key:
+                continue
+            w = self.layers[name].weight.data
+            if w.device != self.device or not w.is_contiguous():
+                raise RuntimeError(f"{name}: the weight must be contiguous and on {self.device} (it is on {w.device})")
+            jobs.append((lv.data, w, lv.kind, lv.rows))
+            new[name] = lv.key
+        ops.level_switch(jobs)
+        self.state.update(new)
+        self.jobs_issued += len(jobs)
+        return len(jobs)
+
+    def weight_of(self, name: str, key, dtype=None) -> torch.Tensor:
+        """A fresh tensor holding level `key` of `name` in `dtype` (default: the Linear's), decoded by the same call
+        as a switch; the model is not touched."""
+        lv, w = self.find(name, key), self.layers[name].weight
+        out = torch.empty(tuple(w.shape), dtype=dtype or w.dtype, device=self.device)
+        ops.level_switch([(lv.data, out, lv.kind, lv.rows)])
+        return out
+
+    def level_tensor(self, name: str, key) -> torch.Tensor:
+        """Level `key` of `name` as error_estimator.load_level returns it: the stored dense tensor itself (no copy), or
+        the packed blocks decoded to fp16."""
+        lv = self.find(name, key)
+        if lv.kind is None and lv.rows is None:
+            return lv.data
+        return self.weight_of(name, key, dtype=torch.float16 if lv.kind is not None else lv.dtype)

@@ -659,3 +659,45 @@ def quad_form(A: torch.Tensor, H: torch.Tensor, B: Optional[torch.Tensor] = None
     check(lib().gq_quad_form(_ptr(A), _DT[A.dtype], lda, _ptr(B), _DT[B.dtype] if B is not None else 0, ldb, _ptr(H), R, C,
                              _ptr(out), _ptr(ws), ws.numel() * ws.element_size(), _stream(A)), "gq_quad_form")
     return out
+
+
+# ---- level switch of the bit-width search (gq_level_switch): stored levels -> live weights, one call ----
+def level_switch(jobs) -> None:
+    """Apply a list of jobs (src, dst, kind, row_src) in ONE gq_level_switch call on the current stream of their device.
+    dst: contiguous [R, C] fp32 / fp16 / bf16, written in place.  kind a K-quant q_type (10..14): src uint8, R rows of
+    C / 256 packed blocks (any 1-D / 2-D contiguous view of R * C / 256 * type_size bytes); kind None: src a dense
+    contiguous [R, C] tensor, cast as .to(dst.dtype).  row_src: None or int32 [R], dst[r] = f(src[row_src[r]]); every index
+    must lie in [0, R) -- the kernel does not check.  Returns None; no host read, no allocation on the device."""
+    jobs = list(jobs)
+    if not jobs:
+        return None
+    dev = jobs[0][1].device
+    table = (_cabi.SwitchJob * len(jobs))()
+    for i, (src, dst, kind, row_src) in enumerate(jobs):
+        _need_cuda(src, dst, row_src)
+        for t in (src, dst, row_src):
+            if t is not None and t.device != dev:
+                raise _cabi.GQError(f"level_switch: job {i}: every tensor must be on one device ({dev}); got one on {t.device}")
+        if dst.dim() != 2 or not dst.is_contiguous() or dst.dtype not in _DT:
+            raise _cabi.GQError(f"level_switch: job {i}: dst must be a contiguous [R, C] fp32 / fp16 / bf16 tensor; got "
+                                f"{dst.dtype} {tuple(dst.shape)} strides {tuple(dst.stride())}")
+        R, C = dst.shape
+        if not src.is_contiguous():
+            raise _cabi.GQError(f"level_switch: job {i}: src must be contiguous")
+        if kind is None:
+            if src.dtype not in _DT or tuple(src.shape) != (R, C):
+                raise _cabi.GQError(f"level_switch: job {i}: a dense src must be fp32 / fp16 / bf16 {(R, C)}; got {src.dtype} "
+                                    f"{tuple(src.shape)}")
+            k = _DT[src.dtype]
+        else:
+            k = int(kind)
+            need = R * (C // 256) * type_info(k)["type_size"]
+            if src.dtype != torch.uint8 or C % 256 or src.numel() != need:
+                raise _cabi.GQError(f"level_switch: job {i}: packed src of q_type {k} for {(R, C)} must be {need} uint8; got "
+                                    f"{src.dtype} {tuple(src.shape)}")
+        if row_src is not None and (row_src.dtype != torch.int32 or row_src.numel() != R or not row_src.is_contiguous()):
+            raise _cabi.GQError(f"level_switch: job {i}: row_src must be a contiguous int32 [{R}] tensor")
+        table[i] = _cabi.SwitchJob(src.data_ptr(), dst.data_ptr(), row_src.data_ptr() if row_src is not None else None,
+                                   R, C, k, _DT[dst.dtype])
+    check(lib().gq_level_switch(table, len(jobs), _stream(jobs[0][1])), "gq_level_switch")
+    return None

@@ -14,6 +14,7 @@ import argparse
 import glob
 import json
 import os
+import re
 import sys
 
 import torch
@@ -86,9 +87,13 @@ def level_file(layer_dir: str, level) -> str:
                             f"found {[os.path.basename(f) for f in typed]})")
 
 
+_CONFIG_FILE = re.compile(r"\(([^()]+\.pth)\)\s*$")  # evo_quant_search's `<bitwidth> (<file name>)`
+
+
 def load_compressed_weights(model, compressed_weights_path, compressed_config_path=None, default_level=0, load=None):
-    """ppleval.py:124-152: with a config (lines `layer_name: level`) exactly the listed layers get the weights of their
-    level, without one every layer directory of the database gets `default_level`.  load(path, device) -> tensor
+    """ppleval.py:124-152: with a config (lines `layer_name: level`, or `layer_name: bitwidth (file name)` as
+    evo_quant_search writes them) exactly the listed layers get the weights of their level, without one every layer
+    directory of the database gets `default_level`.  load(path, device) -> tensor
     (default torch.load onto the layer's device)."""
     if load is None:
         load = lambda path, device: torch.load(path, map_location=device)  # noqa: E731
@@ -100,7 +105,14 @@ def load_compressed_weights(model, compressed_weights_path, compressed_config_pa
                 if os.path.isdir(os.path.join(compressed_weights_path, n))]
     for layer_name, level in todo:
         layer = model.get_submodule(layer_name)
-        w = load(level_file(os.path.join(compressed_weights_path, layer_name), level), layer.weight.device)
+        named = _CONFIG_FILE.search(str(level))  # the search's own lines: `name: 4.5 (4.5-Q4_K.pth)` names the file
+        if named:
+            path = os.path.join(compressed_weights_path, layer_name, named.group(1))
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"{path}: the weight file named by the configuration line of {layer_name}")
+        else:
+            path = level_file(os.path.join(compressed_weights_path, layer_name), level)
+        w = load(path, layer.weight.device)
         if tuple(w.shape) != tuple(layer.weight.shape):
             raise ValueError(f"{layer_name}: level {level!r} has shape {tuple(w.shape)}, the model expects "
                              f"{tuple(layer.weight.shape)}")
