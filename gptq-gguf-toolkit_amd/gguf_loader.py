@@ -66,10 +66,10 @@ def _host(buf, off: int, nbytes: int) -> torch.Tensor:
 
 
 def iter_gguf_tensors(path: str, device="cuda:0", dtype: Optional[torch.dtype] = None,
-                      hf_layout: bool = True) -> Iterator[Tuple[str, torch.Tensor]]:
+                      hf_layout: bool = True, quant_dtype: Optional[torch.dtype] = None) -> Iterator[Tuple[str, torch.Tensor]]:
     """Yield (name, tensor on `device`) for every tensor of the file, in file order.  hf_layout: HF names and HF row order
     of attn_q / attn_k (`rope_freqs.weight`, which no HF module owns, is left out); otherwise GGUF names and rows as stored.
-    dtype None: fp32 for quantized tensors, the stored dtype for F32 / F16 / BF16."""
+    dtype None: fp32 for quantized tensors (`quant_dtype` for the K-quants when given), the stored dtype for F32 / F16 / BF16."""
     device = torch.device(device)
     kv, tensors, buf = parse_gguf(str(path), mmap=True)
     arch = kv["general.architecture"][0] if "general.architecture" in kv else None
@@ -85,7 +85,7 @@ def iter_gguf_tensors(path: str, device="cuda:0", dtype: Optional[torch.dtype] =
             rows = unpermute_rows(shape[0], n_head, n_head if name.endswith(".attn_q.weight") else n_kv).to(device)
         raw = _host(buf, off, nbytes).to(device)
         if gt in K_QUANTS:
-            t = ops.dequantize_blocks(gt, raw.view(shape[0], -1), dtype or torch.float32, rows)
+            t = ops.dequantize_blocks(gt, raw.view(shape[0], -1), dtype or quant_dtype or torch.float32, rows)
         else:
             if gt == GGMLType.F32:
                 t = raw.view(torch.float32)
