@@ -18,7 +18,6 @@ are kept next to the values (`ErrorEstimator.levels`).  Left out: convolutions (
 import argparse
 import json
 import os
-import re
 import sys
 from collections import defaultdict
 from typing import Dict, Iterable, List, Optional
@@ -29,11 +28,10 @@ import torch.nn as nn
 if __package__ in (None, ""):  # run as a script: make the package importable under its alias
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import gptq_gguf_toolkit_amd  # noqa: F401
-    from gptq_gguf_toolkit_amd import dist_utils, metrics, ops as _ops
-    from gptq_gguf_toolkit_amd.model_utils import LINEAR_LAYERS, ForwardInterrupt, InputCollector, _to, select_layers
-else:
-    from . import dist_utils, metrics, ops as _ops
-    from .model_utils import LINEAR_LAYERS, ForwardInterrupt, InputCollector, _to, select_layers
+    __package__ = "gptq_gguf_toolkit_amd"
+
+from . import dist_utils, level_db, metrics, ops as _ops  # noqa: E402
+from .model_utils import LINEAR_LAYERS, ForwardInterrupt, InputCollector, _to, select_layers  # noqa: E402
 
 
 def _single_rank():
@@ -110,86 +108,6 @@ class LayerErrorEstimator:
         if tuple(W_c.shape) != tuple(self.W_shape):
             raise ValueError(f"the compressed weight has shape {tuple(W_c.shape)}, the layer {tuple(self.W_shape)}")
         return _ops.quad_form(self.W.detach(), self.hessian(), W_c) / self.norm()
-
-
-# ---- the level database (ppleval.load_compressed_weights reads the same layout) ----
-_NUM = re.compile(r"^[0-9]+(?:\.[0-9]+)?")
-
-
-def level_key(filename: str) -> float:
-    """The numeric prefix of a level's file name as a float: "4-Q4_K.pth" -> 4.0, "4.5-Q4_K.pth" -> 4.5, "3.pth" -> 3.0."""
-    m = _NUM.match(filename[:-4] if filename.endswith(".pth") else filename)
-    if not m:
-        raise ValueError(f"level file {filename!r} does not start with a number")
-    return float(m.group(0))
-
-
-def level_files(layer_dir: str) -> List[str]:
-    """The `.pth` files of one layer directory, ordered by numeric prefix (ties by name)."""
-    return sorted((f for f in os.listdir(layer_dir) if f.endswith(".pth")), key=lambda f: (level_key(f), f))
-
-
-def layer_dir(db: str, layer_name: str) -> str:
-    """<db>/<HF module name> (gguf_splitter --hf-layers), else <db>/<GGUF tensor name> (--gguf-layers)."""
-    d = os.path.join(db, layer_name)
-    if os.path.isdir(d):
-        return d
-    try:
-        from .pack_gptq_into_gguf import map_tensor_name
-    except ImportError:
-        from gptq_gguf_toolkit_amd.pack_gptq_into_gguf import map_tensor_name
-    try:
-        g = os.path.join(db, map_tensor_name(layer_name + ".weight"))
-    except ValueError:
-        g = d
-    if not os.path.isdir(g):
-        raise FileNotFoundError(f"{db}: no directory for {layer_name}")
-    return g
-
-
-def _rotary_rows(db: str, gguf_name: str, R: int, device):
-    """row_src undoing the converter's q / k rotary row permutation (gguf_loader.unpermute_rows), from the manifest."""
-    if not gguf_name.endswith((".attn_q.weight", ".attn_k.weight")):
-        return None
-    try:
-        with open(os.path.join(db, "manifest.json")) as f:
-            md = json.load(f).get("metadata", {})
-    except OSError:
-        return None
-    val = lambda k: md[k]["value"] if k in md else None  # noqa: E731
-    arch = val("general.architecture")
-    n_head = val(f"{arch}.attention.head_count")
-    if arch != "llama" or not n_head:
-        return None
-    n_kv = val(f"{arch}.attention.head_count_kv")
-    try:
-        from .gguf_loader import unpermute_rows
-    except ImportError:
-        from gptq_gguf_toolkit_amd.gguf_loader import unpermute_rows
-    return unpermute_rows(R, int(n_head), int(n_head) if gguf_name.endswith(".attn_q.weight") else n_kv).to(device)
-
-
-def load_level(path: str, device, db: Optional[str] = None) -> torch.Tensor:
-    """One level's weight on `device`.  A torch-saved tensor (the --hf-layers side) is loaded as it is; raw GGUF bytes
-    (the --gguf-layers side, described by `<stem>-metadata.json`) are decoded to fp16 by ops.dequantize_blocks."""
-    meta_path = path[:-4] + "-metadata.json"
-    info = None
-    if os.path.isfile(meta_path):
-        with open(meta_path) as f:
-            info = json.load(f).get("tensor_info", {})
-    if not info or "np_dtype" not in info:
-        return torch.load(path, map_location=device)
-    import numpy as np
-    # np_shape is the row-major shape of the stored bytes: [R, C] for plain types, [R, C / 256 * type_size] for K-quants
-    # ("shape" is ggml's ne order, columns first)
-    gt, np_shape = int(info["type"]), [int(n) for n in info["np_shape"]]
-    raw = torch.from_numpy(np.fromfile(path, dtype=np.uint8)).to(device)
-    plain = {0: torch.float32, 1: torch.float16, 30: torch.bfloat16}
-    rows = _rotary_rows(db, info.get("name", ""), np_shape[0], device) if db else None
-    if gt in plain:
-        w = raw.view(plain[gt]).reshape(np_shape)
-        return w[rows.long()] if rows is not None else w
-    return _ops.dequantize_blocks(gt, raw.view(np_shape[0], -1), torch.float16, rows)
 
 
 class ErrorEstimator:
@@ -321,12 +239,13 @@ class ErrorEstimator:
         errors = {}
         for name, handle in handles.items():
             handle.pre_step()
-            ldir = layer_dir(self.compressed_weights_path, name)
-            files = level_files(ldir)
+            ldir = level_db.layer_dir(self.compressed_weights_path, name)
+            files = level_db.level_files(ldir)
             if self.level_store is not None:
                 vals = [handle.estimate(self.level_store.level_tensor(name, f)) for f in files]
             else:
-                vals = [handle.estimate(load_level(os.path.join(ldir, f), handle.W_device, self.compressed_weights_path))
+                vals = [handle.estimate(level_db.load_level(os.path.join(ldir, f), handle.W_device,
+                                                           self.compressed_weights_path))
                         for f in files]
             # numerators and the denominator were divided on the device in fp64: ONE host read per Linear
             errors[name] = torch.stack(vals).tolist() if vals else []
@@ -374,10 +293,7 @@ def parse_args(argv=None):
 def main(argv=None):
     args = parse_args(argv)
     assert torch.cuda.is_available(), "error_estimator needs a GPU (there is no CPU path)"
-    try:
-        from .ppleval import load_hf_model
-    except ImportError:
-        from gptq_gguf_toolkit_amd.ppleval import load_hf_model
+    from .ppleval import load_hf_model
     device = torch.device("cuda")
     metrics.fix_seed(args.seed)
     model = load_hf_model(args, device)

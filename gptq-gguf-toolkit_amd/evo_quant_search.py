@@ -6,7 +6,7 @@
         --survivors_per_selection 4 1 --tokens_per_selection 2048 16384 [--group_rule size|name|none] \
         [--fitness_fn kl|ppl|sparse_kl] [--targets_on device|cpu]
 
-The loop of the reference's main() (:401-779) is restated as functions of their arguments -- scan_available_bitwidths,
+The loop of the reference's main() (:401-779) is restated as functions of their arguments -- scan_available_bitwidths (level_db's),
 calculate_total_bits, get_next_bitwidth, initial_parent / initial_candidates, mutate, make_offspring, minibatch, selection,
 search -- that draw from ONE random.Random in the reference's call order: random.Random(seed) yields what the reference's
 module-level `random` yields after fix_seed(seed), so a seed fixes the same trajectory.  A candidate is evaluated as
@@ -18,7 +18,7 @@ What differs from the reference, on purpose:
   * --log_wandb is accepted and refused with a message when wandb is not installed;
   * --targets_on device (default): the KL targets stay on the device in the model dtype when they fit next to the level
     store, else (or with `cpu`) they go to the host as in the reference;
-  * level files are recognised by error_estimator.level_key ("4.pth" and "4-Q4_K.pth" both count; the reference's
+  * level files are recognised by level_db.level_key ("4.pth" and "4-Q4_K.pth" both count; the reference's
     filename.split('-')[0] drops the former with a warning), and the --gguf-layers layout is read too;
   * the reference's progress prints inside the mutation ("Can't decrease bits, continue ...") are not made.
 One rank, nn.Linear only."""
@@ -36,32 +36,14 @@ import numpy as np
 if __package__ in (None, ""):  # run as a script: make the package importable under its alias
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import gptq_gguf_toolkit_amd  # noqa: F401
-    from gptq_gguf_toolkit_amd.error_estimator import layer_dir, level_files, level_key
-else:
-    from .error_estimator import layer_dir, level_files, level_key
+    __package__ = "gptq_gguf_toolkit_amd"
 
-Levels = Dict[str, List[Tuple[float, str]]]
+from .level_db import Levels, filename_of, has_layer, scan_available_bitwidths  # noqa: E402
+
 State = List[List[float]]
 
 
-# ------------------------------------------------------------------------------------------------ the database
-def scan_available_bitwidths(quant_weights_path: str, layer_names: Optional[Sequence[str]] = None) -> Levels:
-    """{layer name: [(bitwidth, file name), ...] sorted by bitwidth} (:26-52).  Without layer_names every directory of the
-    database is a layer, named as the directory; with them (HF module names) the directory is error_estimator.layer_dir's,
-    which also finds the --gguf-layers layout."""
-    available = {}
-    if layer_names is None:
-        for layer_name in os.listdir(quant_weights_path):
-            layer_path = os.path.join(quant_weights_path, layer_name)
-            if os.path.isdir(layer_path):
-                available[layer_name] = sorted(((level_key(f), f) for f in level_files(layer_path)), key=lambda x: x[0])
-    else:
-        for layer_name in layer_names:
-            available[layer_name] = sorted(((level_key(f), f) for f in level_files(layer_dir(quant_weights_path, layer_name))),
-                                           key=lambda x: x[0])
-    return available
-
-
+# ------------------------------------------------------------------------------------------------ the layers
 def layer_order_fn(layer_name: str):
     """evopress/src/model_utils.py:365-369: (block index, the rest of the name)."""
     split_key = layer_name.split(".")
@@ -81,13 +63,6 @@ def group_layers(model, layer_names: Sequence[str], group_rule: str) -> Tuple[Li
     for n in layer_names:
         groups[key(n)].append(n)
     return tuple(groups.values())
-
-
-def filename_of(available_bitwidths: Levels, layer_name: str, bitwidth: float) -> Optional[str]:
-    for bw, fn in available_bitwidths[layer_name]:
-        if abs(bw - bitwidth) < 1e-6:
-            return fn
-    return None
 
 
 # ------------------------------------------------------------------------------------------------ the budget
@@ -407,10 +382,7 @@ def parse_args(argv=None):
 
 def compute_fitness(model, data, fitness_fn: str, target_logits=None) -> float:
     """:141-147"""
-    try:
-        from . import metrics
-    except ImportError:
-        from gptq_gguf_toolkit_amd import metrics
+    from . import metrics
     if fitness_fn == "ppl":
         return metrics.compute_perplexity(model, data)
     if fitness_fn == "kl":
@@ -423,10 +395,7 @@ def collect_targets(model, calibration_data, fitness_fn: str, kl_topk: int, targ
     only when all of them fit in the memory that is free now, less reserve_bytes; otherwise each one is moved to the
     host as it is produced."""
     import torch
-    try:
-        from . import metrics
-    except ImportError:
-        from gptq_gguf_toolkit_amd import metrics
+    from . import metrics
     if fitness_fn == "ppl":
         return [], targets_on
     device = next(model.parameters()).device
@@ -447,14 +416,9 @@ def collect_targets(model, calibration_data, fitness_fn: str, kl_topk: int, targ
 def main(argv=None):
     args = parse_args(argv)
     import torch
-    try:
-        from . import metrics
-        from .level_store import LevelStore
-        from .ppleval import load_hf_model
-    except ImportError:
-        from gptq_gguf_toolkit_amd import metrics
-        from gptq_gguf_toolkit_amd.level_store import LevelStore
-        from gptq_gguf_toolkit_amd.ppleval import load_hf_model
+    from . import metrics
+    from .level_store import LevelStore
+    from .ppleval import load_hf_model
     assert torch.cuda.is_available(), "evo_quant_search needs a GPU (there is no CPU path)"
     device = torch.device("cuda")
     metrics.fix_seed(args.seed)
@@ -473,7 +437,8 @@ def main(argv=None):
     # the levels: HF-named directories as the reference scans them, else the model's Linears through layer_dir
     available = scan_available_bitwidths(args.quant_weights_path)
     if not available or not all(_is_module(model, n) for n in available):
-        names = [n for n, m in model.named_modules() if isinstance(m, torch.nn.Linear) and _has_dir(args.quant_weights_path, n)]
+        names = [n for n, m in model.named_modules()
+                 if isinstance(m, torch.nn.Linear) and has_layer(args.quant_weights_path, n)]
         available = scan_available_bitwidths(args.quant_weights_path, names)
     print("Available bitwidths:")
     for layer_name, bitwidths in available.items():
@@ -543,14 +508,6 @@ def _is_module(model, name) -> bool:
     try:
         return hasattr(model.get_submodule(name), "weight")
     except AttributeError:
-        return False
-
-
-def _has_dir(db, name) -> bool:
-    try:
-        layer_dir(db, name)
-        return True
-    except FileNotFoundError:
         return False
 
 

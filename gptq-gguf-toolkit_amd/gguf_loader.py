@@ -15,10 +15,10 @@ import numpy as np
 import torch
 
 from . import ops
-from .gguf_writer import GGMLType, parse_gguf
+from .gguf_writer import K_QUANTS, PLAIN_TYPES, GGMLType, parse_gguf
 from .pack_gptq_into_gguf import _BLOCK_TABLE
 
-K_QUANTS = (GGMLType.Q2_K, GGMLType.Q3_K, GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q6_K)
+ROTARY_TENSORS = (".attn_q.weight", ".attn_k.weight")  # the tensors whose rows the converter permutes
 _TOP = {"token_embd.weight": "model.embed_tokens.weight", "output_norm.weight": "model.norm.weight",
         "output.weight": "lm_head.weight"}
 _BLOCK_INV = {v: k for k, v in _BLOCK_TABLE.items() if not v.endswith("_exps.weight")}
@@ -37,6 +37,15 @@ def unpermute_rows(R: int, n_head: int, n_head_kv) -> torch.Tensor:
     return unpermute(torch.arange(R, dtype=torch.int32), n_head, n_head_kv).contiguous()
 
 
+def rotary_row_src(name: str, R: int, arch, n_head, n_head_kv, device) -> Optional[torch.Tensor]:
+    """The `row_src` on `device` that undoes the converter's rotary row permutation of GGUF tensor `name` with R rows, or
+    None: attn_q / attn_k of architecture "llama" with a head count only.  The one statement of the rule; the values come
+    from a parsed file (iter_gguf_tensors) or from a level database's manifest (level_db.rotary_rows)."""
+    if arch != "llama" or not n_head or not name.endswith(ROTARY_TENSORS):
+        return None
+    return unpermute_rows(R, n_head, n_head if name.endswith(".attn_q.weight") else n_head_kv).to(device)
+
+
 def hf_tensor_name(gguf_name: str) -> str:
     """Inverse of pack_gptq_into_gguf.map_tensor_name for the dense Llama table (and Mixtral's router)."""
     if gguf_name in _TOP:
@@ -49,10 +58,10 @@ def hf_tensor_name(gguf_name: str) -> str:
     raise ValueError(f"Can not map GGUF tensor {gguf_name!r} to an HF name")
 
 
-def _kv_int(kv, key) -> Optional[int]:
-    if key not in kv:
+def kv_int(v, key) -> Optional[int]:
+    """A key/value entry (None: not there) that has to be one integer; `key` names it in the refusal."""
+    if v is None:
         return None
-    v = kv[key][0]
     if isinstance(v, (list, tuple)):  # per-layer head counts: one value for all layers, or refuse
         if len(set(v)) != 1:
             raise NotImplementedError(f"{key} differs from layer to layer: {sorted(set(v))}")
@@ -73,26 +82,21 @@ def iter_gguf_tensors(path: str, device="cuda:0", dtype: Optional[torch.dtype] =
     device = torch.device(device)
     kv, tensors, buf = parse_gguf(str(path), mmap=True)
     arch = kv["general.architecture"][0] if "general.architecture" in kv else None
-    n_head, n_kv = _kv_int(kv, f"{arch}.attention.head_count"), _kv_int(kv, f"{arch}.attention.head_count_kv")
+    n_head, n_kv = (kv_int(kv[k][0] if k in kv else None, k)
+                    for k in (f"{arch}.attention.head_count", f"{arch}.attention.head_count_kv"))
     for name, shape, gt, off, nbytes in tensors:
         if name.endswith("_exps.weight") or len(shape) > 2:
             raise NotImplementedError(f"tensor {name!r} (shape {tuple(shape)}): merged expert tensors are not split back into "
                                       f"per-expert HF tensors")
         if hf_layout and name == "rope_freqs.weight":
             continue
-        rows = None
-        if hf_layout and arch == "llama" and n_head and name.endswith((".attn_q.weight", ".attn_k.weight")):
-            rows = unpermute_rows(shape[0], n_head, n_head if name.endswith(".attn_q.weight") else n_kv).to(device)
+        rows = rotary_row_src(name, shape[0], arch, n_head, n_kv, device) if hf_layout else None
         raw = _host(buf, off, nbytes).to(device)
         if gt in K_QUANTS:
             t = ops.dequantize_blocks(gt, raw.view(shape[0], -1), dtype or quant_dtype or torch.float32, rows)
         else:
-            if gt == GGMLType.F32:
-                t = raw.view(torch.float32)
-            elif gt == GGMLType.F16:
-                t = raw.view(torch.float16)
-            elif gt == GGMLType.BF16:
-                t = raw.view(torch.bfloat16)
+            if gt in PLAIN_TYPES:
+                t = raw.view(getattr(torch, PLAIN_TYPES[gt][0]))
             elif gt == GGMLType.Q8_0:
                 b = raw.view(-1, 34)
                 t = b[:, :2].contiguous().view(torch.float16).float() * b[:, 2:].contiguous().view(torch.int8).float()

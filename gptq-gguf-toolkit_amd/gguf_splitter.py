@@ -15,25 +15,28 @@ sides write into `output_dir` itself and `--both` leaves the HF manifest as `man
 """
 import argparse
 import json
+import os
 import re
+import sys
 import time
 from pathlib import Path
 from typing import Dict, Iterable, Optional, Tuple, Union
 
 import numpy as np
 
-try:
-    from .gguf_writer import GGML_QUANT_SIZES, parse_gguf
-except ImportError:  # run as a script
-    import os
-    import sys
+if __package__ in (None, ""):  # run as a script: make the package importable under its alias
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from gptq_gguf_toolkit_amd.gguf_writer import GGML_QUANT_SIZES, parse_gguf
+    import gptq_gguf_toolkit_amd  # noqa: F401
+    __package__ = "gptq_gguf_toolkit_amd"
 
-TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 9: "Q8_1", 10: "Q2_K",
-              11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 15: "Q8_K", 30: "BF16"}  # gguf_splitter.py:42-50 (+BF16)
-EXACT_BITS = {"F32": 32.0, "F16": 16.0, "BF16": 16.0, "Q4_0": 4.5, "Q4_1": 5.0, "Q5_0": 5.5, "Q5_1": 6.0, "Q8_0": 8.5,
-              "Q8_1": 9.0, "Q2_K": 2.5625, "Q3_K": 3.4375, "Q4_K": 4.5, "Q5_K": 5.5, "Q6_K": 6.5625, "Q8_K": 8.5}  # :56-96
+from .gguf_writer import GGML_QUANT_SIZES, PLAIN_TYPES, parse_gguf  # noqa: E402
+from .level_db import BIT_WIDTHS, GGML_TYPE_IDS, level_stem  # noqa: E402
+
+# Views of level_db's tables on the types the reference's splitter names (gguf_splitter.py:42-50, :56-96; + BF16), narrow on
+# purpose: any other name ("IQ2_XS") keeps the exact width 32.0 here (resolve_hf_bitwidth with --exact), not the full table's.
+_TYPES = ("F32", "F16", "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1", "Q2_K", "Q3_K", "Q4_K", "Q5_K", "Q6_K", "Q8_K", "BF16")
+TYPE_NAMES = {GGML_TYPE_IDS[name]: name for name in _TYPES}
+EXACT_BITS = {name: BIT_WIDTHS[name] for name in _TYPES}
 
 
 class GGUFSplitter:
@@ -85,9 +88,7 @@ class GGUFSplitter:
         for name, shape, gt, off, nbytes, q, buf in self._entries():
             n += 1
             bitwidth = self.extract_bitwidth_from_quantization(q)
-            prefix = f"{bitwidth}" if isinstance(bitwidth, float) and bitwidth != int(bitwidth) else f"{int(bitwidth)}"
-            if self.use_exact_bitwidth:
-                prefix = f"{prefix}-{q}"
+            prefix = level_stem(bitwidth, q if self.use_exact_bitwidth else None)
             layer_dir = self.output_dir / name
             layer_dir.mkdir(parents=True, exist_ok=True)
             (layer_dir / f"{prefix}.pth").write_bytes(buf[off:off + nbytes])  # raw bytes, not a torch pickle (:378-380)
@@ -95,7 +96,7 @@ class GGUFSplitter:
             if bs > 1:
                 np_dtype, np_shape = "uint8", [*shape[:-1], shape[-1] // bs * ts]
             else:
-                np_dtype, np_shape = {0: "float32", 1: "float16", 30: "uint16"}[gt], list(shape)
+                np_dtype, np_shape = PLAIN_TYPES[gt][1], list(shape)
             common = {"type": gt, "quantization": q, "bitwidth": bitwidth, "exact_bitwidth": self.get_tensor_bit_width(q),
                       "shape": list(reversed(shape)), "n_elements": int(np.prod(shape))}
             (layer_dir / f"{prefix}-metadata.json").write_text(json.dumps({"tensor_info": {
@@ -118,10 +119,7 @@ class GGUFSplitter:
 
     def map_hf_to_gguf_name(self, hf_name: str) -> Optional[str]:
         """The GGUF tensor an HF parameter was written as, or None when the file has no such tensor (:148-282)."""
-        try:
-            from .pack_gptq_into_gguf import map_tensor_name
-        except ImportError:
-            from gptq_gguf_toolkit_amd.pack_gptq_into_gguf import map_tensor_name
+        from .pack_gptq_into_gguf import map_tensor_name
         try:
             name = map_tensor_name(hf_name)
         except ValueError:
@@ -147,12 +145,6 @@ class GGUFSplitter:
             return bitwidth, quantization, False
         return bitwidth, quantization, bool(self.gguf_layer_database[gguf_name]["bitwidth"] != bitwidth and bitwidth > 0)
 
-    @staticmethod
-    def bitwidth_prefix(bitwidth, quantization: Optional[str]) -> str:
-        """"4", "4.5", "4-Q4_K": the file-name stem of a layer (:560-566)."""
-        prefix = str(bitwidth) if isinstance(bitwidth, float) and bitwidth != int(bitwidth) else str(int(bitwidth))
-        return f"{prefix}-{quantization}" if quantization is not None else prefix
-
     def split_hf_model(self, dtype: str = "float16", overwrite_bitwidth=None, device: str = "cuda:0",
                        tensors: Optional[Iterable] = None):
         """Dequantize the file's decoder projections and write them, in HF layout and names, as the reference does.
@@ -162,10 +154,7 @@ class GGUFSplitter:
             self.build_gguf_layer_database()
         torch_dtype = torch.float16 if dtype == "float16" else torch.float32
         if tensors is None:
-            try:
-                from .gguf_loader import iter_gguf_tensors
-            except ImportError:
-                from gptq_gguf_toolkit_amd.gguf_loader import iter_gguf_tensors
+            from .gguf_loader import iter_gguf_tensors
             tensors = iter_gguf_tensors(str(self.model_path), device, torch_dtype, hf_layout=True)
         manifest = {"model_info": {"original_file": self.model_path.name, "dtype": dtype, "bitwidth": overwrite_bitwidth,
                                    "use_exact_bitwidth": self.use_exact_bitwidth, "split_timestamp": time.time()},
@@ -191,7 +180,7 @@ class GGUFSplitter:
             layer_dir_name = name.replace(".weight", "")
             layer_dir = self.output_dir / layer_dir_name
             layer_dir.mkdir(parents=True, exist_ok=True)
-            prefix = self.bitwidth_prefix(bitwidth, quantization)
+            prefix = level_stem(bitwidth, quantization)
             filename, metadata_filename = f"{prefix}.pth", f"{prefix}-metadata.json"
             torch.save(t, layer_dir / filename)
             n_bytes = t.numel() * t.element_size()

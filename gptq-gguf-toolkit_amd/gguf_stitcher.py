@@ -39,14 +39,13 @@ type (the IQ family, Q4_0, Q8_K, ...: known by name for the reports) is refused 
 
 `verify` (a keyword here, `--verify` on the command line) is the guarantee the reference does not give -- the file written is
 the model the search scored: the renamed file is read back through gguf_loader (mapped, decoded on the GPU by
-gq_dequantize_blocks) and every K-quant or plain tensor must equal, bit for bit, error_estimator.load_level of the level
+gq_dequantize_blocks) and every K-quant or plain tensor must equal, bit for bit, level_db.load_level of the level
 file the configuration chose -- the load path the search's LevelStore is tested against.  It adds no kernel.
 `--verify-only` checks a file stitched earlier against the same database and configuration and writes nothing.
 
 PARITY: gguf-py cannot be run here, so this module is checked against the reference by reading it (the citations above)
 and by an independent spec-level reader (tests/test_stitch_cpu.py), not by golden files."""
 import argparse
-import json
 import os
 import re
 import sys
@@ -55,24 +54,17 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-if __package__ in (None, ""):  # run as a script
+if __package__ in (None, ""):  # run as a script: make the package importable under its alias
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from gptq_gguf_toolkit_amd.config_converter import config_text as render_config, convert_hf_to_gguf_config, detect_moe_model, read_config_file
-    from gptq_gguf_toolkit_amd.gguf_writer import ALIGNMENT, GGML_QUANT_SIZES, GGUFValueType, GGUFWriter, parse_gguf
-else:
-    from .config_converter import config_text as render_config, convert_hf_to_gguf_config, detect_moe_model, read_config_file
-    from .gguf_writer import ALIGNMENT, GGML_QUANT_SIZES, GGUFValueType, GGUFWriter, parse_gguf
+    import gptq_gguf_toolkit_amd  # noqa: F401
+    __package__ = "gptq_gguf_toolkit_amd"
 
-# every type name the reference knows (:272-314) -> ggml type id; WRITABLE is what gguf_writer.py can write
-GGML_TYPE_IDS = {"F32": 0, "F16": 1, "Q4_0": 2, "Q4_1": 3, "Q5_0": 6, "Q5_1": 7, "Q8_0": 8, "Q8_1": 9, "Q2_K": 10, "Q3_K": 11,
-                 "Q4_K": 12, "Q5_K": 13, "Q6_K": 14, "Q8_K": 15, "IQ2_XXS": 16, "IQ2_XS": 17, "IQ3_XXS": 18, "IQ1_S": 19,
-                 "IQ4_NL": 20, "IQ3_S": 21, "IQ2_S": 22, "IQ4_XS": 23, "I8": 24, "I16": 25, "I32": 26, "I64": 27, "IQ1_M": 29,
-                 "BF16": 30, "IQ2_M": None, "IQ3_M": None}  # IQ2_M / IQ3_M are file types, not tensor types
-WRITABLE = {name: t for name, t in GGML_TYPE_IDS.items() if t in GGML_QUANT_SIZES}
-BIT_WIDTHS = {"F32": 32.0, "F16": 16.0, "BF16": 16.0, "I8": 8.0, "I16": 16.0, "I32": 32.0, "I64": 64.0, "Q4_0": 4.5, "Q4_1": 5.0,
-              "Q5_0": 5.5, "Q5_1": 6.0, "Q8_0": 8.5, "Q8_1": 9.0, "Q2_K": 2.5625, "Q3_K": 3.4375, "Q4_K": 4.5, "Q5_K": 5.5,
-              "Q6_K": 6.5625, "Q8_K": 8.5, "IQ2_XXS": 2.0625, "IQ2_XS": 2.3125, "IQ2_S": 2.5, "IQ2_M": 2.7, "IQ3_XXS": 3.0625,
-              "IQ3_S": 3.44, "IQ3_M": 3.66, "IQ4_NL": 4.56, "IQ4_XS": 4.25, "IQ1_S": 1.5625, "IQ1_M": 1.75}  # :232-268
+from . import level_db  # noqa: E402
+from .config_converter import config_text as render_config, convert_hf_to_gguf_config, detect_moe_model, read_config_file  # noqa: E402
+from .gguf_writer import ALIGNMENT, GGML_QUANT_SIZES, GGUFValueType, GGUFWriter, parse_gguf  # noqa: E402
+
+# WRITABLE is what gguf_writer.py can write of the type names the reference knows (level_db.GGML_TYPE_IDS)
+WRITABLE = {name: t for name, t in level_db.GGML_TYPE_IDS.items() if t in GGML_QUANT_SIZES}
 # the width-class table of :516-577: (low, high, {exact width: type}, (types kept when the level's own quantization names
 # them), type of the class); walked in this order, an integer width equal to `low` belongs to the class
 WIDTH_CLASSES = ((2.0, 2.7, {2.0625: "IQ2_XXS", 2.3125: "IQ2_XS", 2.5: "IQ2_S", 2.7: "IQ2_M"}, (), "Q2_K"),
@@ -87,10 +79,7 @@ LLAMA_FTYPE = {"F32": 0, "F16": 1, "Q8_0": 7, "Q2_K": 10, "Q3_K": 12, "Q4_K": 15
 LLAMA_FTYPE_MIXED = 15  # LLAMA_FTYPE_MOSTLY_Q4_K_M
 SKIP_KEYS = ("general.file_type", "general.quantization_version")  # re-added last (:679-682, :766-774)
 VALUE_TYPE_NAMES = {v: k for k, v in vars(GGUFValueType).items() if k.isupper()}
-NP_ITEMSIZE = {"uint8": 1, "int8": 1, "float16": 2, "uint16": 2, "float32": 4}
 
-_TYPED_FILE = re.compile(r"^([0-9.]+)-([^.]+)\.pth$")     # "<bw>-<type>.pth" (:89)
-_PLAIN_FILE = re.compile(r"^([0-9.]+)\.pth$")             # "<bw>.pth" (:99)
 _EXACT_LINE = re.compile(r"^([0-9.]+)\s*\(([0-9.]+-[^)]+\.pth)\)$")  # "bw (bw-TYPE.pth)" (:337)
 
 
@@ -102,10 +91,9 @@ class QuantizationConfig:
     """The level chosen for one tensor (:27-41): its bit width, file name and, when the file name carries one, its type."""
 
     def __init__(self, bitwidth: float, filename: str, quant_type: Optional[str] = None, metadata: Dict[str, Any] = None):
-        shown = int(bitwidth) if bitwidth == int(bitwidth) else bitwidth
         self.bitwidth = bitwidth
         self.filename = filename
-        self.filename_prefix = f"{shown}-{quant_type}" if quant_type else str(shown)
+        self.filename_prefix = level_db.level_stem(bitwidth, quant_type or None)
         self.meta_data = metadata or {}
         self.quant_type = quant_type
 
@@ -113,16 +101,6 @@ class QuantizationConfig:
 class _Planned:
     """One tensor as it will be written: resolved before the output is opened."""
     __slots__ = ("name", "shape", "type_name", "ggml_type", "path", "nbytes")
-
-
-def _parse_level_file(filename: str) -> Optional[Dict[str, Any]]:
-    m = _TYPED_FILE.match(filename)
-    if m:
-        return {"bitwidth": float(m.group(1)), "filename": filename, "quant_type": m.group(2)}
-    m = _PLAIN_FILE.match(filename)
-    if m:
-        return {"bitwidth": float(m.group(1)), "filename": filename, "quant_type": None}
-    return None
 
 
 class GGUFStitcher:
@@ -150,21 +128,23 @@ class GGUFStitcher:
 
     # ---- the database ----
     def _load_manifest(self) -> Dict[str, Any]:
-        path = self.split_dir / "manifest.json"
-        if not path.exists():
-            print(f"Warning: Manifest not found at {path}, creating minimal manifest from directory scan")
-            return {"layers": {d.name: {"bitwidths": {}} for d in sorted(self.split_dir.iterdir()) if d.is_dir()}}
         try:
-            with open(path, "r") as f:
-                manifest = json.load(f)
+            manifest = level_db.read_manifest(self.split_dir)
         except Exception as e:
             raise ValueError(f"Error loading manifest: {e}")
+        if manifest is None:
+            print(f"Warning: Manifest not found at {self.split_dir / 'manifest.json'}, creating minimal manifest from directory scan")
+            return {"layers": {d.name: {"bitwidths": {}} for d in sorted(self.split_dir.iterdir()) if d.is_dir()}}
         print(f"Loaded manifest with {len(manifest.get('layers', {}))} layers")
         return manifest
 
     def _scan_dir(self, layer_dir: Path) -> List[Dict[str, Any]]:
         """The levels one directory offers, ordered by bit width and name (the reference takes glob order)."""
-        found = [lv for lv in (_parse_level_file(p.name) for p in layer_dir.glob("*.pth")) if lv is not None]
+        found = []
+        for p in layer_dir.glob("*.pth"):
+            parsed = level_db.parse_level_name(p.name)
+            if parsed is not None:
+                found.append({"bitwidth": parsed[0], "filename": p.name, "quant_type": parsed[1]})
         return sorted(found, key=lambda lv: (lv["bitwidth"], lv["filename"]))
 
     def _discover_layers(self) -> Dict[str, List[Dict[str, Any]]]:
@@ -184,10 +164,9 @@ class GGUFStitcher:
             if levels:
                 discovered[name] = levels
         rest = sorted(d.name for d in self.split_dir.iterdir() if d.is_dir())
-        database = self.split_dir / "gguf_layer_database.json"
-        if database.exists():
-            with open(database, "r") as f:
-                order = {name: i for i, name in enumerate(json.load(f))}
+        database = level_db.read_manifest(self.split_dir, "gguf_layer_database.json")
+        if database is not None:
+            order = {name: i for i, name in enumerate(database)}
             rest.sort(key=lambda n: (order.get(n, len(order)), n))
         for name in rest:
             if name in discovered or name in hf_side:
@@ -237,8 +216,7 @@ class GGUFStitcher:
             exact = _EXACT_LINE.match(rest)
             if exact:
                 filename = exact.group(2)
-                typed = _TYPED_FILE.match(filename)
-                config[tensor_name] = QuantizationConfig(float(exact.group(1)), filename, typed.group(2) if typed else None)
+                config[tensor_name] = QuantizationConfig(float(exact.group(1)), filename, level_db.level_type(filename))
                 continue
             parts = rest.split()
             try:
@@ -284,7 +262,7 @@ class GGUFStitcher:
         return complete
 
     def get_tensor_bit_width(self, quantization: str) -> float:
-        return BIT_WIDTHS.get(quantization, 32.0)
+        return level_db.BIT_WIDTHS.get(quantization, 32.0)
 
     # ---- key/value data ----
     def _find_original_model(self) -> Optional[Path]:
@@ -375,7 +353,7 @@ class GGUFStitcher:
     def _get_quantization_type_from_config(self, config: QuantizationConfig, original_quantization: str = "") -> str:
         """The NAME of the type a tensor is written as (:504-577): the explicit type of the level's file name, else the
         class of its width, where the level's own quantization decides between the members of a class."""
-        if config.quant_type and config.quant_type in GGML_TYPE_IDS:
+        if config.quant_type and config.quant_type in level_db.GGML_TYPE_IDS:
             return config.quant_type
         bw = config.bitwidth
         if bw == 32:
@@ -413,32 +391,27 @@ class GGUFStitcher:
     def _resolve(self, tensor_name: str, config: QuantizationConfig) -> _Planned:
         """Files, type and byte counts of one tensor, all checked; raises with the file's name on any inconsistency."""
         tensor_file, metadata_file, fallback = self._level_files(tensor_name, config)
-        with open(metadata_file, "r") as f:
-            info = json.load(f)["tensor_info"]
-        if "np_dtype" not in info or "np_shape" not in info:
+        info = level_db.read_sidecar(tensor_file, metadata_file)
+        if info.ggml_type is None:
             raise StitchError(f"{metadata_file}: no np_dtype / np_shape -- not a level of the GGUF side of the splitter")
         if fallback:  # the payload is the F32 one, whatever the configuration asked for
             config = QuantizationConfig(32.0, "32-F32.pth", "F32")
-        type_name = self._get_quantization_type_from_config(config, info.get("quantization", ""))
+        type_name = self._get_quantization_type_from_config(config, info.quantization)
         if type_name not in WRITABLE:
             raise StitchError(f"tensor {tensor_name!r}: type {type_name} (level {tensor_file.name}) cannot be written; "
                               f"writable types are {sorted(WRITABLE)}")
         p = _Planned()
         p.name, p.type_name, p.ggml_type, p.path = tensor_name, type_name, WRITABLE[type_name], tensor_file
-        p.shape = tuple(int(n) for n in reversed(info["shape"]))  # "shape" is ggml's ne order, innermost first
-        if info["np_dtype"] not in NP_ITEMSIZE:
-            raise StitchError(f"{metadata_file}: np_dtype {info['np_dtype']!r} is not one of {sorted(NP_ITEMSIZE)}")
-        described = int(np.prod([int(n) for n in info["np_shape"]], dtype=np.int64)) * NP_ITEMSIZE[info["np_dtype"]]
+        p.shape = info.shape
+        if info.nbytes is None:
+            raise StitchError(f"{metadata_file}: np_dtype {info.np_dtype!r} is not one of {sorted(level_db.NP_ITEMSIZE)}")
         block, type_size = GGML_QUANT_SIZES[p.ggml_type]
         n_elements = int(np.prod(p.shape, dtype=np.int64))
         if not p.shape or p.shape[-1] % block:
             raise StitchError(f"{tensor_file}: rows of {p.shape[-1] if p.shape else 0} values are no multiple of {type_name}'s "
                               f"block of {block}")
         p.nbytes = n_elements // block * type_size
-        on_disk = os.path.getsize(tensor_file)
-        if on_disk != described:
-            raise StitchError(f"{tensor_file}: {on_disk} bytes on disk, np_shape {info['np_shape']} of {info['np_dtype']} "
-                              f"describes {described}")
+        on_disk = level_db.check_level_size(info, StitchError)
         if on_disk != p.nbytes:
             raise StitchError(f"{tensor_file}: {on_disk} bytes on disk, a {type_name} tensor of shape {p.shape} takes {p.nbytes}")
         return p
@@ -480,7 +453,7 @@ class GGUFStitcher:
     # ---- writing ----
     def _read_payload(self, planned: _Planned) -> np.ndarray:
         """A tensor's bytes, read when the writer's pipeline reaches it."""
-        return np.fromfile(planned.path, dtype=np.uint8)
+        return level_db.read_level_raw(planned)
 
     def stitch_model(self) -> Path:
         print(f"\n{'=' * 60}\nStarting model reconstruction...\n{'=' * 60}")
@@ -527,16 +500,11 @@ class GGUFStitcher:
 
     def verify(self, device="cuda") -> int:
         """The file at output_path against the level files the configuration chose: read back through gguf_loader (mapped,
-        decoded on the GPU) and compared bit for bit with error_estimator.load_level, tensor by tensor in file order.
+        decoded on the GPU) and compared bit for bit with level_db.load_level, tensor by tensor in file order.
         Raises StitchError naming the first tensor that differs; returns the number of tensors compared (Q8_0 tensors,
         which load_level does not decode, are compared as stored bytes)."""
         import torch
-        try:
-            from .error_estimator import load_level
-            from .gguf_loader import iter_gguf_tensors
-        except ImportError:
-            from gptq_gguf_toolkit_amd.error_estimator import load_level
-            from gptq_gguf_toolkit_amd.gguf_loader import iter_gguf_tensors
+        from .gguf_loader import iter_gguf_tensors
         planned = {p.name: p for p in self.plan()}
         _, tensors, buf = parse_gguf(str(self.output_path), mmap=True)
         names = [t[0] for t in tensors]
@@ -553,9 +521,9 @@ class GGUFStitcher:
                 raise StitchError(f"verify: tensor {name!r} is type {ggml_type} of shape {tuple(shape)} in {self.output_path}, "
                                   f"level {p.path.name} is {p.type_name} of shape {p.shape}")
             if p.type_name == "Q8_0":
-                same = bool(np.array_equal(np.asarray(buf[off:off + nbytes]), np.fromfile(p.path, dtype=np.uint8)))
+                same = bool(np.array_equal(np.asarray(buf[off:off + nbytes]), level_db.read_level_raw(p)))
             else:
-                want = load_level(str(p.path), got.device).reshape(got.shape)
+                want = level_db.load_level(str(p.path), got.device).reshape(got.shape)
                 same = want.dtype == got.dtype and torch.equal(got.view(as_int[got.element_size()]),
                                                                want.view(as_int[want.element_size()]))
             if not same:

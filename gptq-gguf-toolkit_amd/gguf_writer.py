@@ -57,6 +57,10 @@ GGML_QUANT_SIZES = {GGMLType.F32: (1, 4), GGMLType.F16: (1, 2), GGMLType.BF16: (
                     GGMLType.Q2_K: (256, 84),
                     GGMLType.Q3_K: (256, 110), GGMLType.Q4_K: (256, 144), GGMLType.Q5_K: (256, 176),
                     GGMLType.Q6_K: (256, 210)}
+K_QUANTS = (GGMLType.Q2_K, GGMLType.Q3_K, GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q6_K)
+# types stored as plain matrices: (torch dtype name, numpy dtype name -- numpy has no bf16 --, item size)
+PLAIN_TYPES = {GGMLType.F32: ("float32", "float32", 4), GGMLType.F16: ("float16", "float16", 2),
+               GGMLType.BF16: ("bfloat16", "uint16", 2)}
 
 
 def _s(b: str) -> bytes:

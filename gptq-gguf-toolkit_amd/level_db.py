@@ -1,0 +1,212 @@
+"""The per-layer level database that gguf_splitter.py writes, and the only module that knows how it is laid out and named:
+
+    <db>/<layer>/<bpw>[-<type>].pth      one level: a torch-saved dense tensor (--hf-layers) or raw GGUF bytes (--gguf-layers)
+    <db>/<layer>/<stem>-metadata.json    its sidecar; `np_dtype` / `np_shape` in it mean raw GGUF bytes
+    <db>/manifest.json                   the layers and the original file's key/value data
+    <db>/gguf_layer_database.json        tensor name -> type / bit width / shape / offset, in the file's tensor order
+
+Top to bottom: names -> directories -> sidecar -> manifest -> bytes on a device -> the ggml type tables.  torch, ops and
+gguf_loader are imported where a tensor is made, so the readers that only look at names and JSON (the stitcher's) need none."""
+import glob
+import json
+import os
+import re
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from .gguf_writer import PLAIN_TYPES
+
+# ------------------------------------------------------------------------------------------------ names
+# Two rules read a level's file name, kept apart on purpose.  They agree on every name the splitter writes and differ on
+# malformed ones only: level_key takes the float prefix of anything ("4-Q4_K.extra.pth" -> 4.0, "4..5.pth" -> 4.0, ".5.pth"
+# refused), parse_level_name whole names only ("4-Q4_K.extra.pth" -> None, "4..5.pth" -> float()'s ValueError, ".5.pth" -> 0.5).
+_NUM = re.compile(r"^[0-9]+(?:\.[0-9]+)?")
+_LEVEL_FILE = re.compile(r"^([0-9.]+)(?:-([^.]+))?\.pth$")  # "<bw>-<type>.pth" / "<bw>.pth" (reference mapper/gguf_stitcher.py:89,99)
+
+Levels = Dict[str, List[Tuple[float, str]]]
+
+
+def level_stem(bitwidth, quantization: Optional[str] = None) -> str:
+    """"4", "4.5", "4-Q4_K": the file-name stem of a level (reference mapper/gguf_splitter.py:560-566)."""
+    stem = str(int(bitwidth)) if bitwidth == int(bitwidth) else str(bitwidth)
+    return f"{stem}-{quantization}" if quantization is not None else stem
+
+
+def level_type(filename: str) -> Optional[str]:
+    """The type a typed level name carries ("4-Q4_K.pth" -> "Q4_K"), whatever its number is."""
+    m = _LEVEL_FILE.match(filename)
+    return m.group(2) if m else None
+
+
+def parse_level_name(filename: str) -> Optional[Tuple[float, Optional[str]]]:
+    """The stitcher's rule: (bit width, type or None) of "<bw>-<type>.pth" / "<bw>.pth", None for any other name."""
+    m = _LEVEL_FILE.match(filename)
+    return (float(m.group(1)), m.group(2)) if m else None
+
+
+def level_key(filename: str) -> float:
+    """The search's rule: the numeric prefix as a float, "4-Q4_K.pth" -> 4.0, "4.5-Q4_K.pth" -> 4.5, "3.pth" -> 3.0."""
+    m = _NUM.match(filename[:-4] if filename.endswith(".pth") else filename)
+    if not m:
+        raise ValueError(f"level file {filename!r} does not start with a number")
+    return float(m.group(0))
+
+
+def level_files(layer_dir: str) -> List[str]:
+    """The `.pth` files of one layer directory, ordered by numeric prefix (ties by name)."""
+    return sorted((f for f in os.listdir(layer_dir) if f.endswith(".pth")), key=lambda f: (level_key(f), f))
+
+
+def find_level_file(layer_dir: str, level) -> str:
+    """The weight file of `level` in one layer directory: `<level>.pth` as the reference reads it (eval/ppleval.py:138), else
+    level_stem's typed names.  `level` is a whole stem ("4-Q4_K") or a number alone ("4", 4, "4.5"), which must pick ONE file."""
+    stem = str(level).strip()
+    try:
+        stem = level_stem(float(stem))
+    except ValueError:
+        pass
+    exact = os.path.join(layer_dir, f"{stem}.pth")
+    if os.path.isfile(exact):
+        return exact
+    typed = sorted(glob.glob(os.path.join(glob.escape(layer_dir), f"{glob.escape(stem)}-*.pth")))
+    if len(typed) == 1:
+        return typed[0]
+    raise FileNotFoundError(f"{layer_dir}: no weight file for level {level!r} (looked for {stem}.pth and {stem}-<type>.pth, "
+                            f"found {[os.path.basename(f) for f in typed]})")
+
+
+def match_level(levels: Iterable[Tuple[float, object]], bitwidth: float):
+    """The item of the first (key, item) pair whose key is `bitwidth` (|difference| < 1e-6, the reference's rule), or None."""
+    return next((item for key, item in levels if abs(key - bitwidth) < 1e-6), None)
+
+
+def filename_of(available_bitwidths: Levels, layer_name: str, bitwidth: float) -> Optional[str]:
+    return match_level(available_bitwidths[layer_name], bitwidth)
+
+
+def scan_available_bitwidths(quant_weights_path: str, layer_names: Optional[Sequence[str]] = None) -> Levels:
+    """{layer name: [(bitwidth, file name), ...] sorted by bitwidth} (reference evopress/evo_quant_search.py:26-52).  Without
+    layer_names every directory of the database is a layer, named as the directory; with them (HF module names) the
+    directory is layer_dir's, which also finds the --gguf-layers layout."""
+    if layer_names is None:
+        layer_names = [n for n in os.listdir(quant_weights_path) if os.path.isdir(os.path.join(quant_weights_path, n))]
+    return {n: [(level_key(f), f) for f in level_files(layer_dir(quant_weights_path, n))] for n in layer_names}
+
+
+# ------------------------------------------------------------------------------------------------ directories
+def layer_dir(db: str, layer_name: str) -> str:
+    """<db>/<HF module name> (gguf_splitter --hf-layers), else <db>/<GGUF tensor name> (--gguf-layers)."""
+    d = os.path.join(db, layer_name)
+    if os.path.isdir(d):
+        return d
+    from .pack_gptq_into_gguf import map_tensor_name
+    try:
+        g = os.path.join(db, map_tensor_name(layer_name + ".weight"))
+    except ValueError:
+        g = d
+    if not os.path.isdir(g):
+        raise FileNotFoundError(f"{db}: no directory for {layer_name}")
+    return g
+
+
+def has_layer(db: str, layer_name: str) -> bool:
+    try:
+        layer_dir(db, layer_name)
+        return True
+    except FileNotFoundError:
+        return False
+
+
+# ------------------------------------------------------------------------------------------------ sidecar
+class LevelInfo:
+    """What `<stem>-metadata.json` says of a level file.  ggml_type None: a torch-saved tensor (no sidecar, or the HF side's,
+    without np_dtype / np_shape); the fields after it are unset then.  np_shape: the stored array, [R, C] values for plain
+    types, [R, C / block * type_size] bytes for block types; nbytes: what np_shape of np_dtype describes; shape: logical."""
+    __slots__ = ("path", "name", "quantization", "ggml_type", "np_dtype", "np_shape", "shape", "nbytes")
+
+
+def read_sidecar(path, meta_path=None) -> LevelInfo:
+    """The sidecar of level file `path` (`meta_path`: another file than `<stem>-metadata.json`, the stitcher's fallbacks)."""
+    path = str(path)
+    meta_path = str(meta_path) if meta_path is not None else path[:-4] + "-metadata.json"
+    info = {}
+    if os.path.isfile(meta_path):
+        with open(meta_path) as f:
+            info = json.load(f).get("tensor_info", {})
+    rec = LevelInfo()
+    rec.path, rec.name, rec.quantization = path, info.get("name", ""), info.get("quantization", "")  # name: the GGUF tensor's
+    rec.ggml_type = rec.np_dtype = rec.np_shape = rec.shape = rec.nbytes = None
+    if "np_dtype" in info and "np_shape" in info:
+        rec.ggml_type, rec.np_dtype = int(info["type"]), info["np_dtype"]
+        rec.np_shape = [int(n) for n in info["np_shape"]]
+        rec.shape = tuple(int(n) for n in reversed(info["shape"]))  # "shape" is ggml's ne order, innermost first
+        if rec.np_dtype in NP_ITEMSIZE:
+            rec.nbytes = int(np.prod(rec.np_shape, dtype=np.int64)) * NP_ITEMSIZE[rec.np_dtype]
+    return rec
+
+
+def check_level_size(rec: LevelInfo, error=ValueError) -> int:
+    """The size of a raw level file, which must be what its sidecar describes (else `error`)."""
+    on_disk = os.path.getsize(rec.path)
+    if on_disk != rec.nbytes:
+        raise error(f"{rec.path}: {on_disk} bytes on disk, np_shape {rec.np_shape} of {rec.np_dtype} describes {rec.nbytes}")
+    return on_disk
+
+
+# ------------------------------------------------------------------------------------------------ manifest
+def read_manifest(db, name: str = "manifest.json"):
+    """`manifest.json` (or `gguf_layer_database.json`) of the database, None where it cannot be opened."""
+    try:
+        with open(os.path.join(str(db), name)) as f:
+            return json.load(f)
+    except OSError:
+        return None
+
+
+def rotary_rows(db: str, gguf_name: str, R: int, device):
+    """gguf_loader.rotary_row_src with the manifest's architecture and head counts (opened for attn_q / attn_k only)."""
+    from .gguf_loader import ROTARY_TENSORS, kv_int, rotary_row_src
+    if not gguf_name.endswith(ROTARY_TENSORS):
+        return None
+    md = (read_manifest(db) or {}).get("metadata", {})
+    val = lambda k: md[k]["value"] if k in md else None  # noqa: E731
+    arch = val("general.architecture")
+    n_head, n_kv = (kv_int(val(k), k) for k in (f"{arch}.attention.head_count", f"{arch}.attention.head_count_kv"))
+    return rotary_row_src(gguf_name, R, arch, n_head, n_kv, device)
+
+
+# ------------------------------------------------------------------------------------------------ bytes on a device
+def read_level_raw(rec) -> np.ndarray:
+    """The bytes of a raw level file (`rec.path`), as they lie on disk."""
+    return np.fromfile(rec.path, dtype=np.uint8)
+
+
+def load_level(path: str, device, db: Optional[str] = None):
+    """One level's weight on `device`: a torch-saved tensor (--hf-layers) as it is; raw GGUF bytes (--gguf-layers) as a view
+    for plain types, decoded to fp16 by ops.dequantize_blocks for K-quants, with the manifest's q / k row gather if `db`."""
+    import torch
+    rec = read_sidecar(path)
+    if rec.ggml_type is None:
+        return torch.load(path, map_location=device)
+    from . import ops
+    raw = torch.from_numpy(read_level_raw(rec)).to(device)
+    rows = rotary_rows(db, rec.name, rec.np_shape[0], device) if db else None
+    if rec.ggml_type in PLAIN_TYPES:
+        w = raw.view(getattr(torch, PLAIN_TYPES[rec.ggml_type][0])).reshape(rec.np_shape)
+        return w[rows.long()] if rows is not None else w
+    return ops.dequantize_blocks(rec.ggml_type, raw.view(rec.np_shape[0], -1), torch.float16, rows)
+
+
+# ------------------------------------------------------------------------------------------------ ggml type tables
+# every type name the reference knows (mapper/gguf_stitcher.py:272-314) -> ggml type id
+GGML_TYPE_IDS = {"F32": 0, "F16": 1, "Q4_0": 2, "Q4_1": 3, "Q5_0": 6, "Q5_1": 7, "Q8_0": 8, "Q8_1": 9, "Q2_K": 10, "Q3_K": 11,
+                 "Q4_K": 12, "Q5_K": 13, "Q6_K": 14, "Q8_K": 15, "IQ2_XXS": 16, "IQ2_XS": 17, "IQ3_XXS": 18, "IQ1_S": 19,
+                 "IQ4_NL": 20, "IQ3_S": 21, "IQ2_S": 22, "IQ4_XS": 23, "I8": 24, "I16": 25, "I32": 26, "I64": 27, "IQ1_M": 29,
+                 "BF16": 30, "IQ2_M": None, "IQ3_M": None}  # IQ2_M / IQ3_M are file types, not tensor types
+BIT_WIDTHS = {"F32": 32.0, "F16": 16.0, "BF16": 16.0, "I8": 8.0, "I16": 16.0, "I32": 32.0, "I64": 64.0, "Q4_0": 4.5, "Q4_1": 5.0,
+              "Q5_0": 5.5, "Q5_1": 6.0, "Q8_0": 8.5, "Q8_1": 9.0, "Q2_K": 2.5625, "Q3_K": 3.4375, "Q4_K": 4.5, "Q5_K": 5.5,
+              "Q6_K": 6.5625, "Q8_K": 8.5, "IQ2_XXS": 2.0625, "IQ2_XS": 2.3125, "IQ2_S": 2.5, "IQ2_M": 2.7, "IQ3_XXS": 3.0625,
+              "IQ3_S": 3.44, "IQ3_M": 3.66, "IQ4_NL": 4.56, "IQ4_XS": 4.25, "IQ1_S": 1.5625, "IQ1_M": 1.75}  # :232-268
+# numpy dtype names a sidecar may carry -> item size: bytes of block types, and the plain types' own
+NP_ITEMSIZE = {"uint8": 1, "int8": 1, **{np_name: size for _, np_name, size in PLAIN_TYPES.values()}}

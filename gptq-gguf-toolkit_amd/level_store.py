@@ -8,47 +8,31 @@ The reference's load_layers (evopress/evo_quant_search.py:110-138) reads a dense
 candidate.  Here a switch reads the stored level where it lies on the device and writes the Linear's existing weight
 storage: no file, no host copy, no [R, C] temporary, no reallocation (weight.data_ptr() does not change).
 
-Both database layouts of gguf_splitter are read, through error_estimator.layer_dir / level_files / level_key:
+Both database layouts of gguf_splitter are read, through level_db:
   --hf-layers   <db>/<HF module name>/<bpw>-<Qn_K>.pth   torch-saved dense tensors: kept dense in their own dtype; a switch
                 is a cast copy with .to(dtype) rounding, so the weight equals torch.load(file).to(dtype) bit for bit;
   --gguf-layers <db>/<GGUF tensor name>/<bpw>.pth + -metadata.json   raw block bytes: kept packed; a switch decodes them
                 (with the q / k rotary row gather of the manifest) straight to the weight dtype.  For fp16 weights that is
-                error_estimator.load_level(file).to(dtype) bit for bit; for bf16 / fp32 weights the value is rounded ONCE
+                level_db.load_level(file).to(dtype) bit for bit; for bf16 / fp32 weights the value is rounded ONCE
                 from the fp32 decode, where load_level's fp16 tensor followed by .to(dtype) rounds twice.
 One rank, nn.Linear only."""
-import json
 import os
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
-import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
-from .error_estimator import _rotary_rows, layer_dir, level_files, level_key
+from . import level_db, ops
+from .gguf_writer import K_QUANTS, PLAIN_TYPES
 
-_PLAIN = {0: torch.float32, 1: torch.float16, 30: torch.bfloat16}  # ggml types stored as plain matrices
-_KQUANT = (10, 11, 12, 13, 14)
 _DENSE = (torch.float32, torch.float16, torch.bfloat16)
 
 State = Union[Dict[str, float], Sequence[Sequence[float]]]
 
 
 class _Level:
-    """One stored level: where it is on disk and, after upload, on the device."""
-    __slots__ = ("key", "file", "path", "kind", "nbytes", "np_shape", "dtype", "gguf_name", "data", "rows")
-
-
-def _describe(path: str) -> Tuple[Optional[int], Optional[list], Optional[str], str]:
-    """(ggml type or None for a torch-saved tensor, np_shape, np dtype name, gguf tensor name) of a level file."""
-    meta_path = path[:-4] + "-metadata.json"
-    info = None
-    if os.path.isfile(meta_path):
-        with open(meta_path) as f:
-            info = json.load(f).get("tensor_info", {})
-    if not info or "np_dtype" not in info:
-        return None, None, None, ""
-    return int(info["type"]), [int(n) for n in info["np_shape"]], info["np_dtype"], info.get("name", "")
+    """One stored level: what its sidecar says (`info`) and, after upload, where it is on the device."""
+    __slots__ = ("info", "key", "file", "kind", "nbytes", "dtype", "data", "rows")
 
 
 class LevelStore:
@@ -61,7 +45,7 @@ class LevelStore:
         if self.device.type == "cuda" and self.device.index is None:  # "cuda" -> the current device, as tensors report it
             self.device = torch.device("cuda", torch.cuda.current_device())
         if layer_names is None:
-            layer_names = [n for n, m in model.named_modules() if isinstance(m, nn.Linear) and self._has_dir(n)]
+            layer_names = [n for n, m in model.named_modules() if isinstance(m, nn.Linear) and level_db.has_layer(db, n)]
         self.layers: Dict[str, nn.Linear] = {}
         self.levels: Dict[str, List[_Level]] = {}
         need = 0
@@ -71,9 +55,9 @@ class LevelStore:
                 raise TypeError(f"LevelStore supports nn.Linear only, {name} is a {type(layer).__name__}")
             if layer.weight.dtype not in _DENSE:
                 raise TypeError(f"{name}: weight dtype {layer.weight.dtype} is not fp32 / fp16 / bf16")
-            ldir = layer_dir(db, name)
+            ldir = level_db.layer_dir(db, name)
             self.layers[name], self.levels[name] = layer, []
-            for f in level_files(ldir):
+            for f in level_db.level_files(ldir):
                 lv = self._inspect(os.path.join(ldir, f), name, layer)
                 self.levels[name].append(lv)
                 need += lv.nbytes
@@ -92,52 +76,40 @@ class LevelStore:
         self.jobs_issued = 0  # jobs of all switches so far (the diff is observable)
 
     # ---- construction ----
-    def _has_dir(self, name: str) -> bool:
-        try:
-            layer_dir(self.db, name)
-            return True
-        except FileNotFoundError:
-            return False
-
     def _inspect(self, path: str, name: str, layer: nn.Linear) -> _Level:
         lv = _Level()
-        lv.path, lv.file, lv.key = path, os.path.basename(path), level_key(os.path.basename(path))
-        lv.data = lv.rows = None
-        gt, lv.np_shape, np_dtype, lv.gguf_name = _describe(path)
-        want = tuple(layer.weight.shape)
+        lv.info, lv.file, lv.key = level_db.read_sidecar(path), os.path.basename(path), level_db.level_key(os.path.basename(path))
+        lv.data = lv.rows = lv.kind = lv.dtype = None
+        gt, want = lv.info.ggml_type, tuple(layer.weight.shape)
         if gt is None:  # torch-saved: the shape is only known after loading; the file size bounds the bytes
-            lv.kind, lv.dtype, lv.nbytes = None, None, os.path.getsize(path)
+            lv.nbytes = os.path.getsize(path)
             return lv
-        R = lv.np_shape[0]
-        if gt in _PLAIN:
-            lv.kind, lv.dtype, shape = None, _PLAIN[gt], tuple(lv.np_shape)
-        elif gt in _KQUANT:
-            ts = ops.type_info(gt)["type_size"]
-            lv.kind, lv.dtype, shape = gt, torch.uint8, (R, lv.np_shape[1] // ts * 256)
+        if gt in PLAIN_TYPES:
+            lv.dtype = getattr(torch, PLAIN_TYPES[gt][0])
+        elif gt in K_QUANTS:
+            lv.kind, lv.dtype = gt, torch.uint8
         else:
             raise ValueError(f"{path}: ggml type {gt} is not a K-quant or a plain fp32 / fp16 / bf16 matrix")
-        if shape != want:
-            raise ValueError(f"{name}: level {lv.file!r} has shape {shape}, the Linear {want}")
-        lv.nbytes = int(np.prod(lv.np_shape)) * (1 if gt in _KQUANT else torch.empty(0, dtype=lv.dtype).element_size())
-        if os.path.getsize(path) != lv.nbytes:
-            raise ValueError(f"{path}: {os.path.getsize(path)} bytes on disk, its metadata describes {lv.nbytes}")
+        if lv.info.shape != want:
+            raise ValueError(f"{name}: level {lv.file!r} has shape {lv.info.shape}, the Linear {want}")
+        lv.nbytes = level_db.check_level_size(lv.info)
         return lv
 
     def _upload(self, name: str, lv: _Level) -> None:
         want = tuple(self.layers[name].weight.shape)
-        if lv.np_shape is None:  # a torch-saved dense tensor (--hf-layers): kept as saved
-            t = torch.load(lv.path, map_location="cpu")
+        if lv.info.ggml_type is None:  # a torch-saved dense tensor (--hf-layers): kept as saved
+            t = torch.load(lv.info.path, map_location="cpu")
             if tuple(t.shape) != want:
                 raise ValueError(f"{name}: level {lv.file!r} has shape {tuple(t.shape)}, the Linear {want}")
             if t.dtype not in _DENSE:
                 t = t.float()
             lv.dtype, lv.data = t.dtype, t.contiguous().to(self.device)
-        else:
-            raw = torch.from_numpy(np.fromfile(lv.path, dtype=np.uint8)).to(self.device)
-            lv.data = raw if lv.kind is not None else raw.view(lv.dtype).reshape(lv.np_shape)
-            key = (lv.gguf_name.rsplit(".", 2)[-2] if lv.gguf_name.count(".") >= 2 else "", want[0])
+        else:  # raw bytes: packed levels stay packed, dense ones stay in their dtype
+            raw = torch.from_numpy(level_db.read_level_raw(lv.info)).to(self.device)
+            lv.data = raw if lv.kind is not None else raw.view(lv.dtype).reshape(lv.info.np_shape)
+            key = (lv.info.name.rsplit(".", 2)[-2] if lv.info.name.count(".") >= 2 else "", want[0])
             if key not in self._rows:  # the q / k row gather, built once per (tensor kind, R)
-                self._rows[key] = _rotary_rows(self.db, lv.gguf_name, want[0], self.device)
+                self._rows[key] = level_db.rotary_rows(self.db, lv.info.name, want[0], self.device)
             lv.rows = self._rows[key]
         lv.nbytes = lv.data.numel() * lv.data.element_size()
 
@@ -153,12 +125,10 @@ class LevelStore:
     def find(self, name: str, key) -> _Level:
         """The level of `name` whose numeric prefix is `key` (|difference| < 1e-6, as the reference matches bitwidths) or
         whose file name / stem is `key`."""
-        for lv in self.levels[name]:
-            if isinstance(key, str):
-                if key in (lv.file, lv.file[:-4]):
-                    return lv
-            elif abs(lv.key - float(key)) < 1e-6:
-                return lv
+        lv = (next((lv for lv in self.levels[name] if key in (lv.file, lv.file[:-4])), None) if isinstance(key, str)
+              else level_db.match_level(((lv.key, lv) for lv in self.levels[name]), float(key)))
+        if lv is not None:
+            return lv
         raise KeyError(f"{name}: no level {key!r} (have {[lv.file for lv in self.levels[name]]})")
 
     def flatten(self, state: State, grouped_layer_names=None) -> Dict[str, float]:
@@ -200,7 +170,7 @@ class LevelStore:
         return out
 
     def level_tensor(self, name: str, key) -> torch.Tensor:
-        """Level `key` of `name` as error_estimator.load_level returns it: the stored dense tensor itself (no copy), or
+        """Level `key` of `name` as level_db.load_level returns it: the stored dense tensor itself (no copy), or
         the packed blocks decoded to fp16."""
         lv = self.find(name, key)
         if lv.kind is None and lv.rows is None:

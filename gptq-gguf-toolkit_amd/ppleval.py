@@ -11,7 +11,6 @@ the sparse / drop-layer branches, the fast-tokenizer flag.  Beyond the reference
 gguf_loader) and --kl_against (dense KL of the scored model against the unmodified HF model or another .gguf; the target
 is evaluated first and its logits stay on the device in the model dtype)."""
 import argparse
-import glob
 import json
 import os
 import re
@@ -22,9 +21,9 @@ import torch
 if __package__ in (None, ""):  # run as a script: make the package importable under its alias
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import gptq_gguf_toolkit_amd  # noqa: F401
-    from gptq_gguf_toolkit_amd import gguf_loader, metrics
-else:
-    from . import gguf_loader, metrics
+    __package__ = "gptq_gguf_toolkit_amd"
+
+from . import gguf_loader, level_db, metrics  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -66,27 +65,6 @@ def parse_args(argv=None):
     return args
 
 
-def level_file(layer_dir: str, level) -> str:
-    """The weight file of `level` in one layer directory of the database.  `<level>.pth` as the reference writes and reads
-    it (ppleval.py:138), else the names gguf_splitter's HF side writes (GGUFSplitter.bitwidth_prefix): `<bpw>-<Qn_K>.pth`
-    with bpw an integer ("4-Q4_K") or, with --exact, a fraction ("4.5-Q4_K").  `level` may be the whole stem ("4-Q4_K") or
-    its number alone ("4", 4, "4.5"), which then has to pick exactly one file."""
-    stem = str(level).strip()
-    try:
-        num = float(stem)
-        stem = str(int(num)) if num == int(num) else str(num)
-    except ValueError:
-        pass
-    exact = os.path.join(layer_dir, f"{stem}.pth")
-    if os.path.isfile(exact):
-        return exact
-    typed = sorted(glob.glob(os.path.join(glob.escape(layer_dir), f"{glob.escape(stem)}-*.pth")))
-    if len(typed) == 1:
-        return typed[0]
-    raise FileNotFoundError(f"{layer_dir}: no weight file for level {level!r} (looked for {stem}.pth and {stem}-<type>.pth, "
-                            f"found {[os.path.basename(f) for f in typed]})")
-
-
 _CONFIG_FILE = re.compile(r"\(([^()]+\.pth)\)\s*$")  # evo_quant_search's `<bitwidth> (<file name>)`
 
 
@@ -111,7 +89,7 @@ def load_compressed_weights(model, compressed_weights_path, compressed_config_pa
             if not os.path.isfile(path):
                 raise FileNotFoundError(f"{path}: the weight file named by the configuration line of {layer_name}")
         else:
-            path = level_file(os.path.join(compressed_weights_path, layer_name), level)
+            path = level_db.find_level_file(os.path.join(compressed_weights_path, layer_name), level)
         w = load(path, layer.weight.device)
         if tuple(w.shape) != tuple(layer.weight.shape):
             raise ValueError(f"{layer_name}: level {level!r} has shape {tuple(w.shape)}, the model expects "

@@ -17,7 +17,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
-from gptq_gguf_toolkit_amd import error_estimator as ee, ops  # noqa: E402
+from gptq_gguf_toolkit_amd import error_estimator as ee, level_db, ops  # noqa: E402
 
 CFG = dict(hidden_size=4096, intermediate_size=14336, num_attention_heads=32, num_key_value_heads=8, vocab_size=128256,
            max_position_embeddings=8192, rope_theta=500000.0, rms_norm_eps=1e-5)
@@ -85,7 +85,7 @@ def main():
                 torch.save(ops.dequantize(qt, *ops.rtn_quantize(W, qt), out_dtype=torch.float16).cpu(), os.path.join(db, n, f))
         timed = Timed()
         ee._ops = timed
-        inner = ee.load_level
+        inner = level_db.load_level
 
         def load_level(*x, **k):
             t0 = time.perf_counter()
@@ -94,7 +94,7 @@ def main():
             timed.load_s += time.perf_counter() - t0
             return w
 
-        ee.load_level = load_level
+        level_db.load_level = load_level
         est = ee.ErrorEstimator(model, data, r".*layers.*((q|k|v|o|gate|up|down)_proj)$", ["model.embed_tokens", "model.rotary_emb"],
                                 "model.layers", db, device="cuda:0")
         torch.cuda.synchronize()

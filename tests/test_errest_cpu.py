@@ -223,7 +223,7 @@ def test_driver_shares_hessians_orders_levels_and_reads_once_per_linear(tiny, mo
 
 
 def test_level_key_is_the_float_prefix():
-    from gptq_gguf_toolkit_amd.error_estimator import level_key
+    from gptq_gguf_toolkit_amd.level_db import level_key
     assert level_key("4.5-Q4_K.pth") == 4.5 and level_key("4-Q4_K.pth") == 4.0 and level_key("3.pth") == 3.0
     assert level_key("10.pth") == 10.0 and level_key("2.5625-Q2_K.pth") == 2.5625
     with pytest.raises(ValueError):

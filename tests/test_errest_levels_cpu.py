@@ -1,6 +1,6 @@
 """Layer error estimator, the level loader (no GPU): a `--gguf-layers` database made by the package's own splitter from a
 GGUF with NON-SQUARE tensors -- a Q4_K attn_k (rotary row permutation), a Q4_K ffn_down, an F16 attn_q -- is read back by
-error_estimator.load_level / layer_dir and must equal what gguf_loader makes of the same file, with ops.dequantize_blocks
+level_db.load_level / layer_dir and must equal what gguf_loader makes of the same file, with ops.dequantize_blocks
 replaced in both by one stand-in that keeps every byte and the row gather visible.  Also the torch-saved (--hf-layers) side."""
 import os
 import sys
@@ -27,7 +27,7 @@ def _fake_dequantize_blocks(q_type, blocks, out_dtype=torch.float32, row_src=Non
 
 @pytest.fixture()
 def db(tmp_path, monkeypatch):
-    from gptq_gguf_toolkit_amd import error_estimator as ee, gguf_loader
+    from gptq_gguf_toolkit_amd import error_estimator as ee, gguf_loader, level_db as ldb, ops
     from gptq_gguf_toolkit_amd.gguf_splitter import main as split_main
     from gptq_gguf_toolkit_amd.gguf_writer import GGMLType, GGUFWriter
     rng = np.random.default_rng(18)
@@ -43,22 +43,22 @@ def db(tmp_path, monkeypatch):
     w.add_tensor("blk.0.attn_q.weight", q)
     w.write()
     split_main([str(tmp_path / "m.gguf"), str(tmp_path / "db"), "--exact", "--gguf-layers"])
-    monkeypatch.setattr(ee._ops, "dequantize_blocks", _fake_dequantize_blocks)  # ee._ops is gguf_loader.ops
-    assert gguf_loader.ops is ee._ops
+    monkeypatch.setattr(ops, "dequantize_blocks", _fake_dequantize_blocks)  # the ops level_db uses is gguf_loader.ops
+    assert gguf_loader.ops is ops
     want = dict(gguf_loader.iter_gguf_tensors(str(tmp_path / "m.gguf"), "cpu", torch.float16, hf_layout=True))
-    return ee, str(tmp_path / "db"), want, (k, d, q)
+    return ee, ldb, str(tmp_path / "db"), want, (k, d, q)
 
 
 def test_packed_gguf_levels_decode_as_the_loader_does(db):
-    ee, path, want, (k, d, q) = db
+    _, ldb, path, want, (k, d, q) = db
     for hf, gg, shape in (("model.layers.0.self_attn.k_proj", "blk.0.attn_k.weight", (R_K, C)),
                           ("model.layers.0.mlp.down_proj", "blk.0.ffn_down.weight", (R_D, C)),
                           ("model.layers.0.self_attn.q_proj", "blk.0.attn_q.weight", (R_Q, C))):
-        ldir = ee.layer_dir(path, hf)  # no directory under the HF name: the GGUF tensor's
+        ldir = ldb.layer_dir(path, hf)  # no directory under the HF name: the GGUF tensor's
         assert os.path.basename(ldir) == gg
-        files = ee.level_files(ldir)
+        files = ldb.level_files(ldir)
         assert len(files) == 1 and files[0].endswith(".pth")
-        got = ee.load_level(os.path.join(ldir, files[0]), "cpu", path)
+        got = ldb.load_level(os.path.join(ldir, files[0]), "cpu", path)
         assert tuple(got.shape) == shape and got.dtype == torch.float16
         assert torch.equal(got, want[hf + ".weight"]), hf
     # the rotary un-permute really moved rows of k and q, and left ffn_down alone
@@ -67,15 +67,15 @@ def test_packed_gguf_levels_decode_as_the_loader_does(db):
     assert torch.equal(want["model.layers.0.mlp.down_proj.weight"], _fake_dequantize_blocks(12, torch.from_numpy(d), torch.float16))
     assert not torch.equal(want["model.layers.0.self_attn.q_proj.weight"], torch.from_numpy(q))
     # without the manifest (db=None) the rows stay as stored
-    ldir = ee.layer_dir(path, "model.layers.0.self_attn.k_proj")
-    assert torch.equal(ee.load_level(os.path.join(ldir, ee.level_files(ldir)[0]), "cpu"), plain_k)
+    ldir = ldb.layer_dir(path, "model.layers.0.self_attn.k_proj")
+    assert torch.equal(ldb.load_level(os.path.join(ldir, ldb.level_files(ldir)[0]), "cpu"), plain_k)
     with pytest.raises(FileNotFoundError):
-        ee.layer_dir(path, "model.layers.0.mlp.up_proj")
+        ldb.layer_dir(path, "model.layers.0.mlp.up_proj")
 
 
 def test_packed_level_reaches_estimate_with_the_layers_shape(db):
     """A non-square packed level goes through LayerErrorEstimator.estimate (shape check included) on fp64 stand-ins."""
-    ee, path, want, _ = db
+    ee, ldb, path, want, _ = db
     import types
     calls = []
 
@@ -92,8 +92,8 @@ def test_packed_level_reaches_estimate_with_the_layers_shape(db):
         h = ee.LayerErrorEstimator(layer)
         h.update(torch.randn(1, 2 * C, C))
         h.pre_step()
-        ldir = ee.layer_dir(path, "model.layers.0.self_attn.k_proj")
-        w_c = ee.load_level(os.path.join(ldir, ee.level_files(ldir)[0]), "cpu", path)
+        ldir = ldb.layer_dir(path, "model.layers.0.self_attn.k_proj")
+        w_c = ldb.load_level(os.path.join(ldir, ldb.level_files(ldir)[0]), "cpu", path)
         v = h.estimate(w_c)
         assert v.dtype == torch.float64 and float(v) > 0 and calls == [(R_K, C), None]
     finally:
@@ -101,11 +101,11 @@ def test_packed_level_reaches_estimate_with_the_layers_shape(db):
 
 
 def test_torch_saved_levels_load_as_they_are(tmp_path):
-    from gptq_gguf_toolkit_amd import error_estimator as ee
+    from gptq_gguf_toolkit_amd import level_db as ldb
     d = tmp_path / "model.layers.0.mlp.up_proj"
     d.mkdir()
     w = torch.randn(6, 256).half()
     torch.save(w, str(d / "4-Q4_K.pth"))
     (d / "4-Q4_K-metadata.json").write_text('{"tensor_info": {"name": "model.layers.0.mlp.up_proj.weight", "shape": [6, 256]}}')
-    assert ee.layer_dir(str(tmp_path), "model.layers.0.mlp.up_proj") == str(d)
-    assert torch.equal(ee.load_level(str(d / "4-Q4_K.pth"), "cpu", str(tmp_path)), w)
+    assert ldb.layer_dir(str(tmp_path), "model.layers.0.mlp.up_proj") == str(d)
+    assert torch.equal(ldb.load_level(str(d / "4-Q4_K.pth"), "cpu", str(tmp_path)), w)

@@ -204,7 +204,7 @@ def test_ppleval_argument_rules(tmp_path, capsys):
 
 
 def test_load_compressed_weights_reads_both_file_name_forms(tmp_path):
-    from gptq_gguf_toolkit_amd import ppleval
+    from gptq_gguf_toolkit_amd import level_db, ppleval
     names = ["model.layers.0.q_proj", "model.layers.0.down_proj", "model.layers.1.q_proj"]
 
     def model():
@@ -242,13 +242,13 @@ def test_load_compressed_weights_reads_both_file_name_forms(tmp_path):
     assert torch.equal(m.get_submodule(names[0]).weight, w[names[0], 3].half())
     assert torch.equal(m.get_submodule(names[2]).weight, w[names[2], 4].half())
     assert torch.equal(m.get_submodule(names[1]).weight, before)  # a config loads the listed layers only
-    assert os.path.basename(ppleval.level_file(str(db / names[0]), "4.5")) == "4.5-Q4_K.pth"
-    assert os.path.basename(ppleval.level_file(str(db / names[0]), " 0 ")) == "0.pth"
+    assert os.path.basename(level_db.find_level_file(str(db / names[0]), "4.5")) == "4.5-Q4_K.pth"
+    assert os.path.basename(level_db.find_level_file(str(db / names[0]), " 0 ")) == "0.pth"
     with pytest.raises(FileNotFoundError):
-        ppleval.level_file(str(db / names[0]), 5)
+        level_db.find_level_file(str(db / names[0]), 5)
     torch.save(w[names[0], 3], db / names[0] / "3-Q3_K_S.pth")
     with pytest.raises(FileNotFoundError):  # two candidates: the number alone no longer picks one
-        ppleval.level_file(str(db / names[0]), 3)
+        level_db.find_level_file(str(db / names[0]), 3)
     torch.save(torch.zeros(2, 2), db / names[1] / "7.pth")
     with pytest.raises(ValueError, match="shape"):
         ppleval.load_compressed_weights(model(), str(db), default_level=7)

@@ -1,7 +1,7 @@
 """-m gpu: K18, the level switch of the bit-width search -- gq_level_switch through ops.level_switch, LevelStore on both
 database layouts, and evo_quant_search.search on the tiny Llama.  Every weight equality is on bits.  Anchors: the package's
 ops.dequantize_blocks (pinned to the reference by G6-G9), the independent ggml-layout decoder tests/ggml_spec.py, torch's
-.to(dtype), and error_estimator.load_level (the reference's load path)."""
+.to(dtype), and level_db.load_level (the reference's load path)."""
 import copy
 import json
 import os
@@ -164,7 +164,7 @@ def world(ops, tmp_path_factory):
 
 @pytest.mark.parametrize("layout", ["hf", "gg"])
 def test_store_switch_equals_the_reference_load_path(world, layout):
-    from gptq_gguf_toolkit_amd import error_estimator as ee
+    from gptq_gguf_toolkit_amd import level_db as ldb
     from gptq_gguf_toolkit_amd.level_store import LevelStore
     model, names, tmp, _ = world
     model = copy.deepcopy(model)
@@ -178,9 +178,9 @@ def test_store_switch_equals_the_reference_load_path(world, layout):
 
     def check(state):
         for n, key in state.items():
-            ldir = ee.layer_dir(db, n)
-            f = next(f for f in ee.level_files(ldir) if ee.level_key(f) == key)
-            want = ee.load_level(os.path.join(ldir, f), "cuda", db).to(F16)
+            ldir = ldb.layer_dir(db, n)
+            f = next(f for f in ldb.level_files(ldir) if ldb.level_key(f) == key)
+            want = ldb.load_level(os.path.join(ldir, f), "cuda", db).to(F16)
             w = model.get_submodule(n).weight
             assert torch.equal(bits(w.data), bits(want)), (n, key)
             assert w.data_ptr() == ptrs[n], n
@@ -232,7 +232,7 @@ def test_error_estimator_takes_the_store(world):
 
 # ------------------------------------------------------------------------------------------------ the search
 def test_search_on_the_tiny_llama(world, tmp_path):
-    from gptq_gguf_toolkit_amd import error_estimator as ee, evo_quant_search as S, metrics, ppleval
+    from gptq_gguf_toolkit_amd import evo_quant_search as S, level_db as ldb, metrics, ppleval
     from gptq_gguf_toolkit_amd.level_store import LevelStore
     base, names, tmp, calib = world
     db = str(tmp / "hf")
@@ -278,7 +278,7 @@ def test_search_on_the_tiny_llama(world, tmp_path):
     for n, bw in store.flatten(cand).items():
         f = S.filename_of(levels, n, bw)
         layer = ref.get_submodule(n)
-        layer.weight.data = ee.load_level(os.path.join(db, n, f), "cuda", db).to(layer.weight.dtype)
+        layer.weight.data = ldb.load_level(os.path.join(db, n, f), "cuda", db).to(layer.weight.dtype)
     want = [metrics.compute_kl_div(ref, data, tg) for _ in range(2)]
     spread = abs(want[0] - want[1])
     print(f"fitness through the store {got!r}, through the reference's path {want[0]!r}, {want[1]!r} (spread {spread!r})")
