@@ -26,6 +26,9 @@ EXPORTS_ERREST = ("gq_quad_form_workspace_bytes", "gq_quad_form")
 # include/gptq_gguf_search.h: the level switch of the bit-width search (additive in the same way)
 EXPORTS_SEARCH = ("gq_level_switch",)
 SWITCH_MAX_JOBS = 64  # GQ_SWITCH_MAX_JOBS: jobs of one launch (a longer list is cut by the library)
+# include/gptq_gguf_levels.h: the column walk over row bands of different types (additive in the same way)
+EXPORTS_LEVELS = ("gq_gptq_quantize_bands",)
+BANDS_MAX = 64  # GQ_BANDS_MAX: bands of one call (the caller cuts a longer list)
 
 
 class GQError(RuntimeError):
@@ -46,6 +49,11 @@ class SwitchJob(ctypes.Structure):
     """gq_switch_job_t"""
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("row_src", ctypes.c_void_p),
                 ("R", ctypes.c_int64), ("C", ctypes.c_int64), ("kind", ctypes.c_int32), ("out_dtype", ctypes.c_int32)]
+
+
+class Band(ctypes.Structure):
+    """gq_band_t"""
+    _fields_ = [("row_end", ctypes.c_int64), ("q_type", ctypes.c_int32)]
 
 
 def build(force: bool = False) -> str:
@@ -126,6 +134,7 @@ def lib():
     L.gq_quad_form_workspace_bytes.restype = sz
     L.gq_quad_form.argtypes = [vp, ci, i64, vp, ci, i64, vp, i64, i64, vp, vp, sz, vp]
     L.gq_level_switch.argtypes = [ctypes.POINTER(SwitchJob), ci, vp]
+    L.gq_gptq_quantize_bands.argtypes = [vp, vp, i64, i64, ctypes.POINTER(Band), ci, ci, sp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -133,7 +142,7 @@ def lib():
     L.gq_prof_collect.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
-    for name in EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH:
+    for name in EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS:
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

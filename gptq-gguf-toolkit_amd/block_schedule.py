@@ -458,6 +458,102 @@ class BlockSchedule:
         self.stats["own_U"] = len(call.results) - self.stats["reused_U"]
         return self._exchange_and_write_back(call)
 
+    # ------------------------------------------------------------------ level build
+    @torch.no_grad()
+    def quantize_levels(self, levels, propagate: Optional[GGMLQuantizationType],
+                        extra: Optional[Callable[[str, GPTQ, dict], Any]] = None) -> Dict[str, Dict[Any, Tuple[torch.Tensor, ...]]]:
+        """Every Linear of the block at every level of `levels` -> {name: {q_type: 5-tuple}}: the database the bit-width
+        search starts from, without a run per level.  The phases are quantize()'s -- the Hessians are folded once, one chain
+        per distinct Hessian on the same lanes, one factorisation per distinct (H, zero-column set) -- and a chain walks the
+        columns ONCE for all levels of all the Linears that share its factorisation (GPTQ.compute_levels).
+        `propagate`: one of `levels` -- that level's dequantized weights replace layer.weight.data, as
+        quantize(writeback=True) does with its one type, so the next block is calibrated on what an ordinary run of that
+        level feeds it -- or None: the weights stay as they are.  `extra(name, handle, {q_type: result})` runs on the
+        chain's stream.  Single rank only."""
+        handles = self.handles
+        levels = [GGMLQuantizationType(t) for t in levels]
+        if not levels or len(set(levels)) != len(levels):
+            raise ValueError("quantize_levels needs a non-empty list of distinct levels")
+        if propagate is not None:
+            propagate = GGMLQuantizationType(propagate)
+            if propagate not in levels:
+                raise ValueError(f"propagate={propagate.name} is not one of the levels {[t.name for t in levels]}")
+        if dist_utils.get_world_size() > 1:
+            raise NotImplementedError("quantize_levels runs on one rank (multi-rank level builds are not built)")
+        for n, h in handles.items():
+            if h.act_order or h.static_groups:
+                raise ValueError(f"{n}: act_order / static_groups handles have no level build")
+        dev = next(iter(handles.values())).W_device
+        on_gpu = torch.device(dev).type == "cuda"
+        main = torch.cuda.current_stream(dev) if on_gpu else None
+        ready, start = self._reduce_hessians(1, main)
+        order = self._chains(0)
+        own = self._needs_own_factorisation()
+        lent = 1 if on_gpu and 2 < self.n_streams and len(order) <= self.n_streams and any(
+            _ops.uses_helper_stream(len(levels) * h.d_row, h.d_col, h.block_size) for h in handles.values()) else 0
+        streams = [None] + _chain_streams(dev, min(self.n_streams - lent, len(order)) - 1)
+        lane_of, enq = _plan_lanes([_lane_load([handles[n] for n in names]) for names in order], len(streams))
+        results: Dict[str, Dict[Any, tuple]] = {}
+        deq: Dict[str, torch.Tensor] = {}
+        with _far_helper_lease(bool(lent)) if on_gpu else contextlib.nullcontext():
+            lanes = []
+            for k in enq:
+                lane = _Lane(streams[lane_of[k]], main)
+                lane.wait(start)
+                lanes.append((lane, self._run_level_chain(order[k], levels, propagate, own, extra, results, deq, lane)))
+            for lane, born in lanes:
+                lane.join(born)
+        self.stats["own_U"] = len(results) - self.stats["reused_U"]
+        for n, h in handles.items():
+            if propagate is not None:
+                h.layer.weight.data = deq[n]
+            h.reset()
+        return {n: results[n] for n in handles}
+
+    def _run_level_chain(self, names: List[str], levels, propagate, own: Dict[str, bool], extra, results, deq,
+                         lane: _Lane) -> List[torch.Tensor]:
+        """Enqueue one chain of a level build on its lane -> the tensors born there.  The leader and the followers KNOWN to
+        share its factorisation build their levels in one walk; a follower with a column set of its own, or one whose
+        sharing became known too late to be checked (MoE experts), factorises for itself and walks alone -- the same
+        results either way, and no host read."""
+        handles = self.handles
+        born: List[torch.Tensor] = []
+        names = sorted(names, key=lambda n: handles[n].shared_H_with is not None)
+        together = [n for n in names if handles[n].shared_H_with is None or (n in own and not own[n])]
+        alone = [n for n in names if n not in together]
+        with lane.run():
+            for grp in ([together] if self.stack else [[n] for n in together]):
+                if not grp:
+                    continue
+                if self.verbose:
+                    print(f"[rank 0] Quantizing {grp} with {[t.name for t in levels]}.")
+                hs = [handles[n] for n in grp]
+                if len(grp) > 1:
+                    self.stats["stacked"] = self.stats.get("stacked", 0) + len(grp)
+                res = GPTQ.compute_levels(hs, levels, defer_check=True)
+                for n, h in zip(grp, hs):
+                    if h._pending_mismatch is not None:  # a reused factorisation: the flag is asserted by verify()
+                        BlockSchedule.unverified.append(h._pending_mismatch)
+                        h._pending_mismatch = None
+                        self.stats["reused_U"] += 1
+                    results[n] = res[h]
+            for n in alone:
+                h = handles[n]
+                self.stats["refactorised"] += 1
+                results[n] = GPTQ.compute_levels([h], levels, own_U=True)[h]
+            for n in names:
+                h = handles[n]
+                for res in results[n].values():
+                    born.extend(res)
+                born.extend(t for t in (h._last_U, h._last_cf) if torch.is_tensor(t))
+                if propagate is not None:
+                    deq[n] = dequantize_linear_weight(propagate, *results[n][propagate], out_dtype=h.layer.weight.data.dtype)
+                    born.append(deq[n])
+                if extra is not None:
+                    out = extra(n, h, results[n])
+                    born.extend(t for t in (out if isinstance(out, (tuple, list)) else (out,)) if torch.is_tensor(t))
+        return born
+
     def _assign_ranks(self, world: int) -> None:
         """[N>1] Who computes what: the row-split matrices, the owners of the others, `self.owners`, and where every
         Hessian is needed (`reduce_to`).  Holds a collective (_agree_on_sharing): runs before the Hessians' on every rank."""

@@ -1,5 +1,6 @@
 // gq_api.hip -- extern "C" surface of libgptqgguf_hip.so (see include/gptq_gguf.h).
 #include "gq_common.hpp"
+#include "../../include/gptq_gguf_levels.h"
 
 namespace gq {
 thread_local char g_err[512] = "";
@@ -31,6 +32,8 @@ size_t h_prepare_workspace_bytes(int64_t, int64_t);
 int h_prepare(float*, float*, int64_t, int64_t, float, float*, int*, uint8_t*, void*, size_t, hipStream_t, bool);
 int obq_quantize(float*, const float*, int64_t, int64_t, int, int, int, int, uint8_t*, float*, float*, void*, size_t,
                  hipStream_t);
+int gptq_quantize_bands(float*, const float*, int64_t, int64_t, const gq_band_t*, int, int, const gq_search_t*, uint8_t*,
+                        uint16_t*, uint8_t*, uint16_t*, uint8_t*, void*, size_t, hipStream_t);
 int gptq_uses_helper_stream(int64_t, int64_t, int);
 int far_helper_enable(int);
 int w_prepare(const uint8_t*, float*, int64_t, int64_t, int*, hipStream_t);
@@ -350,6 +353,14 @@ int gq_gptq_quantize_stacked(float* W, const float* U, int64_t R, int64_t C, int
     if (n_stacked < 1 || (n_stacked > 1 && !row_ends_host)) GQ_FAIL(GQ_E_NULL, "gq_gptq_quantize_stacked: n_stacked=%d without row_ends", n_stacked);
     return gptq_quantize(W, U, R, C, q_type, block_size, static_groups, p, qweight, d, s, dmin, m, ws, ws_bytes,
                          (hipStream_t)stream, nullptr, row_ends_host, n_stacked);
+}
+
+int gq_gptq_quantize_bands(float* W, const float* U, int64_t R, int64_t C, const gq_band_t* bands_host, int n_bands,
+                           int block_size, const gq_search_t* p_host, uint8_t* qweight, uint16_t* d, uint8_t* s, uint16_t* dmin,
+                           uint8_t* m, void* ws, size_t ws_bytes, void* stream) {
+    GQ_OPTIONS_OK();
+    return gptq_quantize_bands(W, U, R, C, bands_host, n_bands, block_size, p_host, qweight, d, s, dmin, m, ws, ws_bytes,
+                               (hipStream_t)stream);
 }
 
 int gq_gptq_quantize_perm(float* W, const float* U, int64_t R, int64_t C, int q_type, int block_size, const int32_t* perm,

@@ -11,6 +11,7 @@
 #include <mutex>
 #include "gq_common.hpp"
 #include "gq_gemm32.hpp"
+#include "../../include/gptq_gguf_levels.h"
 #include <stdlib.h>
 
 namespace gq {
@@ -43,10 +44,23 @@ constexpr int SEG_LDS_BYTES = (SEG * 64 + SEG * SEG + 2 * SB * 64) * 4 + SEG * 8
 // column loop performs two divisions per column and is bound by exactly that chain.
 __device__ __forceinline__ float div_rcp64(float n, double rd) { return (float)((double)n * rd); }
 
+// BANDS (gq_gptq_quantize_bands): the rows are bands of different K-quant types that share U.  A workgroup owns 64 rows
+// and band boundaries are multiples of 64, so it lies in exactly one band: it looks its band up in this table (it travels
+// in the kernel arguments: wave-uniform scalar loads, no staging copy) and takes the type constants and its s / m base
+// from there instead of from the launch-uniform arguments.  Everything per row is the code of the <false> instantiation.
+struct BandTable {
+    int32_t n;
+    int32_t end64[GQ_BANDS_MAX];   // row_end / 64, ascending
+    uint32_t info[GQ_BANDS_MAX];   // group | is_signed << 8 | (uint8_t)qmin << 16 | qmax << 24
+    int64_t sm_off[GQ_BANDS_MAX];  // first byte of the band's [rows, C / group] block in s and in m
+};
+template <bool BANDS> struct BandArg {};
+template <> struct BandArg<true> { BandTable t; };
+
 // UNI: the uniform grid of EvoPress' FastOBQ (evopress/src/quant_utils.py:23-29) instead of a K-quant:
 //   q = clamp(round(w / max(scale, 1e-9) + zero), 0, maxq),  w_hat = scale * (q - zero)
 // with scale / zero fp32 [R, C / G] (uscale / uzero; d, s, dmin, m unused).
-template <bool PERM, bool UNI = false>
+template <bool PERM, bool UNI = false, bool BANDS = false>
 __global__ __launch_bounds__(SEG_WAVES * 64) void gptq_segment_kernel(
     float* W, int64_t C, const float* src, int64_t ld_src,  // may alias (single-segment blocks)
     const float* __restrict__ U, int64_t a, int len, int64_t R,
@@ -57,9 +71,10 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void gptq_segment_kernel(
     const float* __restrict__ uzero = nullptr,  // PERM (act_order, gptq.py:211-216): column j takes the parameters of
                                                 // the group of its ORIGINAL column perm[j]
     const float* __restrict__ Unext = nullptr,  // != nullptr: U[a .. a+127][a+128 .. a+255]; epilogue below
-    int npair = 1) {  // 2 (r05; needs Unext, src == W + a): this launch ALSO walks the partner block a+128 .. a+255 once its
+    int npair = 1,    // 2 (r05; needs Unext, src == W + a): this launch ALSO walks the partner block a+128 .. a+255 once its
                       // epilogue has brought this block's errors there -- every workgroup owns its 64 rows in both blocks, so
                       // nothing but the workgroup's own stores has to be visible: one launch per 256-column group instead of two
+    BandArg<BANDS> bands = {}) {
     // One workgroup = 64 rows (lane = row) x SEG_WAVES waves.  Wave 0 walks the columns (the dependent chain) one
     // 16-column sub-block ("tile") at a time; the rank-1 updates of the later tiles run UNDER the next chain:
     //   iteration t:  wave 0: chain(t) -> -err of tile t into ne[t & 1]
@@ -79,6 +94,21 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void gptq_segment_kernel(
     const int64_t row = (int64_t)blockIdx.x * 64 + lane;
     const bool live = row < R;
     const int64_t r = live ? row : 0;
+    int64_t band_row0 = 0;  // BANDS: s / m are indexed by the row inside the band
+    if constexpr (BANDS) {
+        static_assert(!PERM && !UNI, "bands are K-quants in natural column order");
+        const BandTable& bt = bands.t;
+        int k = 0;
+        while (k + 1 < bt.n && (int)blockIdx.x >= bt.end64[k]) ++k;
+        const uint32_t info = bt.info[k];
+        G = (int)(info & 0xffu);
+        is_signed = (int)((info >> 8) & 1u);
+        qmin = (float)(int8_t)((info >> 16) & 0xffu);
+        qmax = (float)(info >> 24);
+        band_row0 = k ? (int64_t)bt.end64[k - 1] * 64 : 0;
+        s += bt.sm_off[k];
+        m += bt.sm_off[k];
+    }
     for (int half = 0; half < npair; ++half) {
     if (half) {  // the partner block: same rows, next 128 columns; the epilogue's stores of this workgroup are complete
         __syncthreads();
@@ -126,6 +156,10 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void gptq_segment_kernel(
                 if constexpr (UNI) {
                     dst[t] = uscale[r * ng + col0 / G];
                     dmt[t] = uzero[r * ng + col0 / G];
+                } else if constexpr (BANDS) {
+                    const int64_t rb = r - band_row0;
+                    dst[t] = h2f(d[r * nsg + col0 / 256]) * ival(s[rb * ng + col0 / G], is_signed);
+                    dmt[t] = h2f(dmin[r * nsg + col0 / 256]) * ival(m[rb * ng + col0 / G], is_signed);
                 } else {
                     dst[t] = h2f(d[r * nsg + col0 / 256]) * ival(s[r * ng + col0 / G], is_signed);
                     dmt[t] = h2f(dmin[r * nsg + col0 / 256]) * ival(m[r * ng + col0 / G], is_signed);
@@ -454,12 +488,18 @@ int gptq_uses_helper_stream(int64_t R, int64_t C, int block_size) {
     return !opt(OPT_no_lookahead) && far_async_shape(R, C, B, la);
 }
 
+// Does some block of B columns live in the block scratch?  Wider than a segment, or -- B not dividing 256 -- a block that
+// straddles a 256-column super-group and is therefore walked in two segments (column_loop: `single`).
+static bool needs_block_scratch(int64_t B) { return B > SEG || 256 % B != 0; }
+
 size_t gptq_workspace_bytes(int64_t R, int64_t C, int block_size) {
     int64_t B = block_size <= 0 || block_size > C ? C : block_size;
     size_t err = (size_t)R * (size_t)B * sizeof(float);
     if (B == LA_B) err *= LA;  // super-block error buffer [R, LA * B]
     if (B == LA_B) err *= 2;   // ... doubled for the far update next to the loop (far_async_shape)
-    size_t blk = B > SEG ? (size_t)R * (size_t)B * sizeof(float) : 0;
+    // (a block <= 128 columns that straddles a super-group used the scratch without its room being counted here: the copy
+    // wrote R * B floats past the workspace, e.g. block_size 48 or 96 at C = 512)
+    size_t blk = needs_block_scratch(B) ? (size_t)R * (size_t)B * sizeof(float) : 0;
     return err + blk + 256 + 256;  // + the panel word of the scale searches (quant_utils.py:250-252)
 }
 
@@ -475,10 +515,20 @@ struct UniformSpec {
     float *scale, *zero;   // [R, C / group]
 };
 
+// bands != nullptr (gq_gptq_quantize_bands): band k is rows [row_end[k-1], row_end[k]) and has its own K-quant type.  The
+// walk -- segment launches, near and far updates -- is that of one matrix [R, C]; only the lazy scale search is per band
+// (one launch each, on that band's rows of W as they are at that column), and the segment kernel reads the band table.
+struct BandPlan {
+    BandTable tbl;
+    int q_type[GQ_BANDS_MAX];
+    int64_t row_end[GQ_BANDS_MAX];
+};
+
 static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_type, int block_size, int static_groups,
                        const gq_search_t* p, uint8_t* qweight, uint16_t* d, uint8_t* s, uint16_t* dmin, uint8_t* m,
                        void* ws, size_t ws_bytes, hipStream_t st, const int32_t* perm, const UniformSpec* uni,
-                       const int64_t* row_ends = nullptr, int nstack = 1, int32_t* researches_out = nullptr) {
+                       const int64_t* row_ends = nullptr, int nstack = 1, int32_t* researches_out = nullptr,
+                       const BandPlan* bands = nullptr) {
     // row_ends / nstack: W is several matrices that share U, one under the other (rows never mix: gptq.py:222-270);
     // only the scale searches need to know where one ends and the next begins (their panel-wide `continue`)
     TypeInfo ti;
@@ -492,6 +542,14 @@ static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_typ
         static_groups = 2;  // no K-quant scale search
         d = dmin = reinterpret_cast<uint16_t*>(qweight);  // unused by the UNI kernel; keeps the null check below simple
         s = m = qweight;
+    } else if (bands) {
+        ti = TypeInfo{};
+        ti.group = 16;  // unused: every band brings its own
+        for (int k = 0; k < bands->tbl.n; ++k) {
+            TypeInfo tk;
+            type_info(bands->q_type[k], tk);
+            ti.k_search |= tk.k_search;
+        }
     } else if (!type_info(q_type, ti)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_gptq_quantize: unknown q_type %d", q_type);
     if (R <= 0 || C <= 0 || C % 256) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gptq_quantize: R=%ld C=%ld (C %% 256 != 0)", (long)R, (long)C);
     if (!W || !U || !qweight || !d || !s || !dmin || !m) GQ_FAIL(GQ_E_NULL, "gq_gptq_quantize: null pointer");
@@ -545,7 +603,7 @@ static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_typ
     int ev_i = 0;
     // one device word shared by all scale-search launches of this call (each leaves it at zero)
     unsigned* panel = reinterpret_cast<unsigned*>(
-        (reinterpret_cast<uintptr_t>(Wblk + ((B > SEG) ? (size_t)R * B : 0)) + 255) & ~(uintptr_t)255);
+        (reinterpret_cast<uintptr_t>(Wblk + (needs_block_scratch(B) ? (size_t)R * B : 0)) + 255) & ~(uintptr_t)255);
     if ((ti.k_search && static_groups != 2) || researches_out) GQ_HIP(hipMemsetAsync(panel, 0, 256, st));
     const int64_t ng = C / ti.group, nsg = C / 256;
     const int gps = uni ? 1 : 256 / ti.group;
@@ -572,6 +630,8 @@ static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_typ
         GQ_HIP(hipFuncSetAttribute((const void*)gptq_segment_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    SEG_LDS_BYTES));
         GQ_HIP(hipFuncSetAttribute((const void*)gptq_segment_kernel<false, true>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, SEG_LDS_BYTES));
+        GQ_HIP(hipFuncSetAttribute((const void*)gptq_segment_kernel<false, false, true>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, SEG_LDS_BYTES));
         seg_attr = true;
     }
@@ -610,7 +670,17 @@ static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_typ
                 // reads w (global), NOT w_blk: with block_size > 256 these columns
                 // are stale by design
                 const int64_t sg = a / 256;
-                if ((rc = launch_scale_search(W + a, R, C, q_type, p, d + sg, nsg, s + sg * gps, ng, dmin + sg, nsg,
+                if (bands) {
+                    for (int k = 0; k < bands->tbl.n; ++k) {
+                        const int64_t r0 = k ? bands->row_end[k - 1] : 0, rows = bands->row_end[k] - r0;
+                        const int gk = (int)(bands->tbl.info[k] & 0xffu), gpsk = 256 / gk;
+                        const int64_t ngk = C / gk;
+                        uint8_t *sk = s + bands->tbl.sm_off[k] + sg * gpsk, *mk = m + bands->tbl.sm_off[k] + sg * gpsk;
+                        if ((rc = launch_scale_search(W + r0 * C + a, rows, C, bands->q_type[k], p, d + r0 * nsg + sg, nsg, sk,
+                                                      ngk, dmin + r0 * nsg + sg, nsg, mk, ngk, st, panel)))
+                            return rc;
+                    }
+                } else if ((rc = launch_scale_search(W + a, R, C, q_type, p, d + sg, nsg, s + sg * gps, ng, dmin + sg, nsg,
                                               m + sg * gps, ng, st, panel, row_ends, nstack)))
                     return rc;
             }
@@ -623,7 +693,11 @@ static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_typ
             walked_by_partner = npair == 2;
             {
                 ProfScope ps(PT_GPTQ_SEGMENT, st);
-                if (uni)
+                if (bands)
+                    hipLaunchKernelGGL((gptq_segment_kernel<false, false, true>), seg_grid, seg_block, SEG_LDS_BYTES, st, W, C,
+                                       srcp, ld_src, U, a, len, R, d, s, dmin, m, 0, 0, 0.0f, 0.0f, qweight, Err, ldE,
+                                       pos * B + (a - c1), perm, nullptr, nullptr, unext, npair, BandArg<true>{bands->tbl});
+                else if (uni)
                     hipLaunchKernelGGL((gptq_segment_kernel<false, true>), seg_grid, seg_block, SEG_LDS_BYTES, st, W, C, srcp,
                                        ld_src, U, a, len, R, d, s, dmin, m, ti.group, 0, 0.0f, (float)ti.qmax, qweight, Err,
                                        ldE, pos * B + (a - c1), perm, uni->scale, uni->zero, unext);
@@ -731,6 +805,39 @@ int gptq_quantize(float* W, const float* U, int64_t R, int64_t C, int q_type, in
     if (nstack > 1 && perm) GQ_FAIL(GQ_E_UNSUPPORTED, "gq_gptq_quantize_stacked: act_order matrices are not stacked");
     return column_loop(W, U, R, C, q_type, block_size, static_groups, p, qweight, d, s, dmin, m, ws, ws_bytes, st, perm,
                        nullptr, row_ends, nstack, researches_out);
+}
+
+// gq_gptq_quantize_bands (include/gptq_gguf_levels.h): every check of the band table before the first HIP call.
+int gptq_quantize_bands(float* W, const float* U, int64_t R, int64_t C, const gq_band_t* bands_host, int n_bands,
+                        int block_size, const gq_search_t* p, uint8_t* qweight, uint16_t* d, uint8_t* s, uint16_t* dmin,
+                        uint8_t* m, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (!bands_host) GQ_FAIL(GQ_E_NULL, "gq_gptq_quantize_bands: null band table");
+    if (n_bands < 1 || n_bands > GQ_BANDS_MAX)
+        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gptq_quantize_bands: %d bands (1..%d)", n_bands, GQ_BANDS_MAX);
+    if (R <= 0 || C <= 0 || C % 256) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gptq_quantize_bands: R=%ld C=%ld (C %% 256 != 0)", (long)R, (long)C);
+    BandPlan bp{};
+    bp.tbl.n = n_bands;
+    int64_t prev = 0, off = 0;
+    for (int k = 0; k < n_bands; ++k) {
+        const int64_t e = bands_host[k].row_end;
+        TypeInfo tk;
+        if (!type_info(bands_host[k].q_type, tk))
+            GQ_FAIL(GQ_E_BAD_TYPE, "gq_gptq_quantize_bands: band %d has unknown q_type %d", k, (int)bands_host[k].q_type);
+        if (e % 64 || e <= prev || e > R || e / 64 > INT32_MAX)
+            GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gptq_quantize_bands: band %d ends at row %ld (ascending multiples of 64 up to R=%ld)", k,
+                    (long)e, (long)R);
+        bp.q_type[k] = bands_host[k].q_type;
+        bp.row_end[k] = e;
+        bp.tbl.end64[k] = (int32_t)(e / 64);
+        bp.tbl.info[k] = (uint32_t)tk.group | (uint32_t)tk.is_signed << 8 | (uint32_t)(uint8_t)(int8_t)tk.qmin << 16 |
+                         (uint32_t)tk.qmax << 24;
+        bp.tbl.sm_off[k] = off;
+        off += (e - prev) * (C / tk.group);
+        prev = e;
+    }
+    if (prev != R) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gptq_quantize_bands: the last band ends at row %ld, R=%ld", (long)prev, (long)R);
+    return column_loop(W, U, R, C, -1, block_size, 0, p, qweight, d, s, dmin, m, ws, ws_bytes, st, nullptr, nullptr, nullptr, 1,
+                       nullptr, &bp);
 }
 
 // EvoPress FastOBQ.step for one bit width (evopress/src/fast_obq.py:146-200) given U.

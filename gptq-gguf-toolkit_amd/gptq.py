@@ -421,6 +421,88 @@ class GPTQ:
             h.W = None
         return [tuple(t[r1 - n:r1] for t in res) for r1, n in zip(ends, rows)]
 
+    def levels_key(self):
+        """stack_key without the type: handles with equal keys that share a factorisation may build their levels in ONE
+        walk (compute_levels); None: this handle's rows cannot lie in a band (its levels walk one after another)."""
+        key = self.stack_key(GGMLQuantizationType.Q4_K)
+        return None if key is None else key[1:]
+
+    @staticmethod
+    @torch.no_grad()
+    def compute_levels(hs: Sequence["GPTQ"], q_types: Sequence[GGMLQuantizationType], own_U: bool = False,
+                       defer_check: bool = False):
+        """Every handle of `hs` at every level of `q_types` from ONE factorisation and ONE walk over the columns: the
+        Hessian, the Cholesky chain and the C dependent steps of the column loop do not depend on the level, so the
+        working copies -- Linear-major, then level -- are stacked by rows and each band is rounded to its own grid
+        (gq_gptq_quantize_bands).  `hs`: a leader and followers of its input tensor (the precondition of compute_stacked,
+        whatever the type), or one handle alone (`own_U`: a follower that factorises for itself).  Every result equals
+        quantize(q_type) of a fresh handle fed the same tensors, bit for bit.  -> {handle: {q_type: 5-tuple}}.
+
+        A follower whose dead / zero-column set turns out to differ from the leader's is walked again with a
+        factorisation of its own (one host read of the flags); with `defer_check` the flags stay on the device in
+        `_pending_mismatch`, as compute_stacked leaves them, and the caller answers for them.  A handle's W is None
+        afterwards.  A group that needs more than GQ_BANDS_MAX bands is cut into several calls; a handle whose rows are
+        no multiple of 64 (levels_key() is None) walks its levels one after another with the one U."""
+        q_types = [GGMLQuantizationType(t) for t in q_types]
+        if not hs or not q_types or len(set(q_types)) != len(q_types):
+            raise ValueError("compute_levels needs at least one handle and distinct levels")
+        for h in hs:
+            if h.act_order or h.static_groups:
+                raise ValueError("compute_levels: act_order / static_groups handles have no level build")
+            if h._row_split_active():
+                raise NotImplementedError("compute_levels: row-split (multi-rank) handles")
+        out = {h: {} for h in hs}
+        h0, L = hs[0], len(q_types)
+        mq = dict(quant_scale=h0.quant_scale.value, grid=h0.grid)
+        banded = [h for h in hs if h.levels_key() is not None]
+        assert all(h.levels_key() == banded[0].levels_key() for h in banded), "banded handles must share one grid setup"
+        U = None
+
+        def prepare(h):
+            nonlocal U
+            Uh = h._prepare(defer_check=True, own_U=own_U)
+            assert U is None or Uh is U, "the handles of a level build must share one factorisation"
+            U = h._last_U = Uh
+
+        per_call = max(1, _ops.BANDS_MAX // L)
+        for i in range(0, len(banded), per_call):
+            grp = banded[i:i + per_call]
+            C = grp[0].d_col
+            Wf = torch.empty((L * sum(h.d_row for h in grp), C), device=grp[0].W_device, dtype=torch.float32)
+            bands, r0 = [], 0
+            for h in grp:
+                h.make_working_copy(out=Wf[r0:r0 + h.d_row])
+                prepare(h)  # masks the dead columns of the first copy; the other levels start from that copy
+                for k, t in enumerate(q_types):
+                    if k:
+                        Wf[r0 + k * h.d_row:r0 + (k + 1) * h.d_row].copy_(Wf[r0:r0 + h.d_row])
+                    bands.append((r0 + (k + 1) * h.d_row, int(t)))
+                r0 += L * h.d_row
+            res = _ops.gptq_quantize_bands(Wf, U, bands, h0.block_size, h0.rmin, h0.rdelta, h0.nstep, **mq)
+            for j, h in enumerate(grp):
+                out[h] = {t: res[j * L + k] for k, t in enumerate(q_types)}
+                h.W = None  # the contract of compute_stacked: no handle pins the stack
+        for h in hs:
+            if h.levels_key() is not None:
+                continue
+            for k, t in enumerate(q_types):
+                h.make_working_copy()
+                if k == 0:
+                    prepare(h)
+                else:
+                    _ops.w_prepare(h._last_cf, h.W)  # the dead / all-zero columns _prepare zeroed in the first copy
+                out[h][t] = _ops.gptq_quantize(h.W, U, int(t), h.block_size, False, h.rmin, h.rdelta, h.nstep, **mq)
+            h.W = None
+        if not defer_check:
+            pending = [h for h in hs if h._pending_mismatch is not None]
+            if pending:
+                flags = torch.cat([h._pending_mismatch.reshape(1) for h in pending]).tolist()
+                for h, bad in zip(pending, flags):
+                    h._pending_mismatch = None
+                    if bad:
+                        out[h] = GPTQ.compute_levels([h], q_types, own_U=True)[h]
+        return out
+
     def _row_split_active(self) -> bool:
         return bool(self.row_split) and not self.act_order and dist_utils.get_world_size() > 1
 

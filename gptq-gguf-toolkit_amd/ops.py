@@ -309,6 +309,67 @@ def gptq_quantize(W: torch.Tensor, U: torch.Tensor, q_type: int, block_size=128,
     return q.view(t), d, s.view(t), dmin, m.view(t)
 
 
+BANDS_MAX = _cabi.BANDS_MAX
+_K_GROUP = {10: 16, 11: 16, 12: 32, 13: 32, 14: 16}   # group size of Q2_K .. Q6_K (quant_utils.py:19-26)
+_K_SIGNED = {10: False, 11: True, 12: False, 13: False, 14: True}
+
+
+def band_layout(bands: Sequence[Tuple[int, int]], C: int):
+    """Pure: where the bands of a gq_gptq_quantize_bands call lie.  `bands` is the call's table, (row_end, q_type) per band,
+    ascending.  -> [(row0, row1, q_type, group, sm_off)] per band and the total bytes of s (and of m): band k's
+    [rows_k, C / group_k] array starts at byte sm_off = sum_{j<k} rows_j * C / group_j.  Raises ValueError for a table the
+    library would refuse (so that a caller's mistake shows before any allocation)."""
+    if not 1 <= len(bands) <= BANDS_MAX:
+        raise ValueError(f"{len(bands)} bands (1..{BANDS_MAX})")
+    out, r0, off = [], 0, 0
+    for k, (r1, t) in enumerate(bands):
+        r1, t = int(r1), int(t)
+        if t not in _K_GROUP:
+            raise ValueError(f"band {k} has unknown q_type {t}")
+        if r1 % 64 or r1 <= r0:
+            raise ValueError(f"band {k} ends at row {r1} (ascending multiples of 64)")
+        g = _K_GROUP[t]
+        out.append((r0, r1, t, g, off))
+        off += (r1 - r0) * (C // g)
+        r0 = r1
+    return out, off
+
+
+def gptq_quantize_bands(W: torch.Tensor, U: torch.Tensor, bands: Sequence[Tuple[int, int]], block_size=128, rmin=-1.0,
+                        rdelta=0.1, nstep=20, ws: Optional[torch.Tensor] = None, **mq):
+    """The column walk of gptq_quantize over row bands of DIFFERENT K-quant types that share U (gq_gptq_quantize_bands):
+    W (fp32, contiguous) holds several working copies one under the other, band k = rows [row_end[k-1], row_end[k]) is
+    quantized to q_type[k]; `bands` = [(row_end, q_type)], row ends ascending multiples of 64, the last one == R.  One
+    walk over the columns for all bands; every band's rows equal gptq_quantize on those rows alone with that type, bit
+    for bit.  W is updated IN PLACE.  Returns one (qweight, d, s, dmin, m) per band: views into the stacked outputs."""
+    _need_cuda(W, U)
+    assert W.dtype == torch.float32 and U.dtype == torch.float32 and W.is_contiguous() and U.is_contiguous()
+    R, C = W.shape
+    n = len(bands)
+    tbl = (_cabi.Band * max(n, 1))(*[_cabi.Band(int(e), int(t)) for e, t in bands])
+    dev = W.device
+    q = torch.empty(R, C, dtype=torch.uint8, device=dev)
+    d = torch.empty(R, C // 256, dtype=torch.float16, device=dev)
+    dmin = torch.empty(R, C // 256, dtype=torch.float16, device=dev)
+    s = torch.empty(R * (C // 16), dtype=torch.uint8, device=dev)  # G >= 16: room for any table
+    m = torch.empty(R * (C // 16), dtype=torch.uint8, device=dev)
+    bs = int(block_size or 0)
+    need = workspace_bytes(_cabi.WS_GPTQ_QUANTIZE, R, C, 0, bs)
+    if ws is None:
+        ws = _ws(need, dev)
+    check(lib().gq_gptq_quantize_bands(_ptr(W), _ptr(U), R, C, tbl, n, bs, _search(rmin, rdelta, nstep, **mq), _ptr(q),
+                                       _ptr(d), _ptr(s), _ptr(dmin), _ptr(m), _ptr(ws), ws.numel(), _stream(W)),
+          "gq_gptq_quantize_bands")
+    lay, _ = band_layout(bands, C)
+    out = []
+    for r0, r1, t, g, off in lay:
+        it = torch.int8 if _K_SIGNED[t] else torch.uint8
+        nb = (r1 - r0) * (C // g)
+        out.append((q[r0:r1].view(it), d[r0:r1], s[off:off + nb].view(r1 - r0, C // g).view(it), dmin[r0:r1],
+                    m[off:off + nb].view(r1 - r0, C // g).view(it)))
+    return out
+
+
 def uses_helper_stream(R: int, C: int, block_size) -> bool:
     """Will the column loop of an R x C matrix run its far updates on the library's helper stream (gq_gptq_uses_helper_stream)?"""
     return bool(lib().gq_gptq_uses_helper_stream(int(R), int(C), int(block_size or 0)))

@@ -86,7 +86,39 @@ def parse_args(argv=None):
     p.add_argument("--eval_data", type=str, default=None,
                    help="a .pt file of [1, L] token-id tensors: what --eval_perplexity scores the quantized model on (the "
                         "reference downloads WikiText-2 there)")
-    return p.parse_args(argv)
+    p.add_argument("--levels", nargs="+", type=str, default=None, choices=Q_NAMES,
+                   help="beyond the reference: build every listed level in ONE pass (one calibration, one Hessian, one "
+                        "factorisation and one column walk per Linear) and write one ordinary tree per level, "
+                        "<save_dir>/<LEVEL>/<module>/data.pth; needs --propagate_level")
+    p.add_argument("--propagate_level", type=str, default=None, choices=Q_NAMES + ["none"],
+                   help="with --levels: the level whose quantized weights the later blocks are calibrated on (that level's "
+                        "tree equals its ordinary run), or none: every block sees full-precision activations")
+    args = p.parse_args(argv)
+    problem = levels_problem(args)
+    if problem:
+        p.error(problem)
+    return args
+
+
+def levels_problem(args, world_size=None):
+    """Why this combination of flags cannot run as a level build (None: it can, or --levels is not given)."""
+    if args.levels is None:
+        return "--propagate_level needs --levels" if args.propagate_level is not None else None
+    if args.propagate_level is None:
+        return "--levels needs --propagate_level (one of the levels, or none): which level the later blocks are calibrated on"
+    if len(set(args.levels)) != len(args.levels):
+        return "--levels lists a level twice"
+    if args.propagate_level != "none" and args.propagate_level not in args.levels:
+        return f"--propagate_level {args.propagate_level} is not one of --levels {' '.join(args.levels)}"
+    if args.bit_width_configuration is not None:
+        return "--levels builds every module at every level: --bit_width_configuration does not apply"
+    if args.act_order or args.static_groups:
+        return "--levels does not support --act_order / --static_groups"
+    if world_size is None:
+        world_size = int(os.environ.get("WORLD_SIZE", "1"))
+    if world_size > 1:
+        return f"--levels runs on one rank (WORLD_SIZE={world_size}): multi-rank level builds are not built"
+    return None
 
 
 def build_quant_config(default_bit_width, bit_width_configuration):
@@ -179,7 +211,11 @@ def _run(args):
     dist_utils.barrier()
 
     t1 = time.perf_counter()
-    quantizer.quantize(quant_config)
+    if args.levels is not None:
+        quantizer.quantize_levels([GGMLQuantizationType[n] for n in args.levels],
+                                  None if args.propagate_level == "none" else GGMLQuantizationType[args.propagate_level])
+    else:
+        quantizer.quantize(quant_config)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     dist_utils.print_on_main(f"Quantization took {(t2 - t1)} s.")

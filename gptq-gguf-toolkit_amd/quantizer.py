@@ -548,6 +548,25 @@ def _first(x):
     return x[0] if isinstance(x, (tuple, list)) else x
 
 
+def level_tree_name(level, module: str) -> str:
+    """Where a module's data.pth of a level build lies under save_dir: <LEVEL>/<module> (the level's type name, e.g.
+    Q4_K/model.layers.0.mlp.up_proj) -- <save_dir>/<LEVEL> is an ordinary tree, a valid --dir_model_quant of the packer."""
+    return f"{GGMLQuantizationType(level).name}/{module}"
+
+
+def check_levels(levels, propagate):
+    """-> (levels, propagate) as GGMLQuantizationType (propagate None stays None); ValueError for an empty or repeated
+    list or a propagate level that is not built."""
+    levels = [GGMLQuantizationType(t) for t in levels]
+    if not levels or len(set(levels)) != len(levels):
+        raise ValueError("levels must be a non-empty list of distinct K-quant types")
+    if propagate is not None:
+        propagate = GGMLQuantizationType(propagate)
+        if propagate not in levels:
+            raise ValueError(f"propagate level {propagate.name} is not one of the levels {[t.name for t in levels]}")
+    return levels, propagate
+
+
 class Quantizer:
     def __init__(self, model: nn.Module, data_loader: Iterable, quantizable_modules: str,
                  quantizer_kwargs: Dict[str, Any], pre_block_modules: List[str], post_block_modules: List[str],
@@ -585,6 +604,26 @@ class Quantizer:
         self.fused_forward = level_of(os.environ.get("GQ_FUSED_FORWARD", fused_forward))
 
     # ------------------------------------------------------------------ walk
+    @torch.no_grad()
+    def quantize_levels(self, levels, propagate) -> None:
+        """The level database in one pass: every quantizable module at every level of `levels`, one ordinary tree per level
+        under <save_dir>/<LEVEL>/ (level_tree_name; same schema, same writer as quantize()).  The calibration forwards, the
+        Hessians, the factorisations and the column walk are those of ONE run (BlockSchedule.quantize_levels).
+        `propagate`: the level whose dequantized weights replace the model's -- every later block is calibrated on what an
+        ordinary all-<propagate> run feeds it, so that level's tree and the model afterwards are that run's -- or None:
+        the model stays untouched and every block is calibrated on full-precision activations.  With
+        quant_non_block_modules, embed / lm_head are RTN-quantized per level (what --default_bit_width LEVEL writes)."""
+        levels, propagate = check_levels(levels, propagate)
+        if dist_utils.get_world_size() > 1:
+            raise NotImplementedError("quantize_levels runs on one rank (multi-rank level builds are not built)")
+        if self.quantizer_kwargs.get("act_order") or self.quantizer_kwargs.get("static_groups"):
+            raise ValueError("quantize_levels: act_order / static_groups have no level build")
+        self._levels, self._level_src = (levels, propagate), {}
+        try:
+            self.quantize({})
+        finally:
+            self._levels, self._level_src = None, {}
+
     @torch.no_grad()
     def quantize(self, quant_config: Dict[str, GGMLQuantizationType]) -> None:
         device = self.device or next(self.model.parameters()).device
@@ -722,7 +761,8 @@ class Quantizer:
             for name, module in post_blocks:
                 self._quant_and_save_non_block(name, module.to(device), quant_config)
         if self.quant_non_block_modules:  # wherever they ran, they ran: the packer would silently write a missing one as f16
-            missing = [n for n, _ in pre_blocks + post_blocks if n not in self._saved_names]
+            saved = {n.rsplit("/", 1)[-1] for n in self._saved_names}  # (a level build saves <LEVEL>/<module>)
+            missing = [n for n, _ in pre_blocks + post_blocks if n not in saved]
             assert not missing, f"non-block modules never quantized: {missing}"
         if use_cache is not None:
             self.model.config.use_cache = use_cache
@@ -783,6 +823,16 @@ class Quantizer:
         sched = self._schedule
         assert sched is not None and sched.handles is handles
         batch = []
+        if getattr(self, "_levels", None) is not None:
+            levels, propagate = self._levels
+            for n, per_level in sched.quantize_levels(levels, propagate).items():
+                for t in levels:
+                    item = self._save(level_tree_name(t, n), t, *per_level[t], defer=True)
+                    if item is not None:
+                        batch.append(item)
+            self._saver.put_many(batch)
+            self.schedule_stats = sched.stats
+            return
         for n, res in sched.quantize(qtypes, writeback=True).items():
             item = self._save(n, qtypes[n], *res, defer=True)
             if item is not None:
@@ -814,8 +864,31 @@ class Quantizer:
     def _quant_and_save_non_block(self, name, module, quant_config):
         if self.verbose:
             dist_utils.print_on_main(f"Processing {name}.")
+        if getattr(self, "_levels", None) is not None:
+            return self._quant_and_save_non_block_levels(name, module)
         q_type = quant_config.get(name.split(".")[-1], GGMLQuantizationType.Q6_K)  # quantizer.py:107,192
         qweight, d, s, dmin, m = self._quant_non_block_module(module.weight, q_type)
         module.weight.data = dequantize_linear_weight(q_type, qweight, d, s, dmin, m,
                                                       out_dtype=module.weight.data.dtype)
         self._save(name, q_type, qweight, d, s, dmin, m)
+
+    def _quant_and_save_non_block_levels(self, name, module):
+        """embed / lm_head of a level build: RTN per level, each what an all-<level> run writes; only the propagated level is
+        written back.  A module whose weight an earlier non-block module already went through (a tied lm_head) sees, per
+        level, that level's dequantized weight -- as it does in the all-<level> run, where embed_tokens' write-back comes
+        first."""
+        levels, propagate = self._levels
+        key = id(module.weight)
+        tied = key in self._level_src
+        src = self._level_src.setdefault(key, module.weight.data)  # the weight before any write-back (kept alive here)
+        back = None
+        for t in levels:
+            w = src
+            if tied:
+                w = dequantize_linear_weight(t, *self._quant_non_block_module(src, t), out_dtype=src.dtype)
+            res = self._quant_non_block_module(w, t)
+            if t == propagate:
+                back = dequantize_linear_weight(t, *res, out_dtype=module.weight.data.dtype)
+            self._save(level_tree_name(t, name), t, *res)
+        if back is not None:
+            module.weight.data = back

@@ -30,6 +30,8 @@ python -m torch.distributed.run --nnodes=1 --nproc-per-node="$NUM_GPUS" --master
     --block_size "${BLOCK_SIZE:-128}" \
     --default_bit_width "${BITS:-Q4_K}" \
     ${BIT_WIDTH_CONFIGURATION:+--bit_width_configuration "$BIT_WIDTH_CONFIGURATION"} \
+    ${LEVELS:+--levels $LEVELS} \
+    ${PROPAGATE_LEVEL:+--propagate_level "$PROPAGATE_LEVEL"} \
     --rmin "${RMIN:--1.0}" \
     --rdelta "${RDELTA:-0.1}" \
     --nstep "${NSTEP:-20}" \
