@@ -1,13 +1,10 @@
 // gq_api.hip -- extern "C" surface of libgptqgguf_hip.so (see include/gptq_gguf.h).
 #include "gq_common.hpp"
-#include "../../include/gptq_gguf_levels.h"
+#include "gq_walk.hpp"  // the column walk's host interface and launch_scale_search
 
 namespace gq {
 thread_local char g_err[512] = "";
 
-int launch_scale_search(const float*, int64_t, int64_t, int, const gq_search_t*, uint16_t*, int64_t, uint8_t*, int64_t,
-                        uint16_t*, int64_t, uint8_t*, int64_t, hipStream_t, unsigned* panel = nullptr,
-                        const int64_t* row_ends = nullptr, int nstack = 1);
 int launch_dequantize(int, const uint8_t*, const uint16_t*, const uint8_t*, const uint16_t*, const uint8_t*, int64_t,
                       int64_t, void*, int, hipStream_t);
 int launch_rtn_elementwise(const void*, int, const uint16_t*, const uint8_t*, const uint16_t*, const uint8_t*, int64_t,
@@ -20,22 +17,12 @@ int launch_pack(int, const uint8_t*, const uint16_t*, const uint8_t*, const uint
                 uint8_t*, hipStream_t);
 int launch_trailing_update(float*, int64_t, const float*, int64_t, const float*, int64_t, int64_t, int64_t, int64_t,
                            hipStream_t);
-size_t gptq_workspace_bytes(int64_t, int64_t, int);
-int gptq_quantize(float*, const float*, int64_t, int64_t, int, int, int, const gq_search_t*, uint8_t*, uint16_t*,
-                  uint8_t*, uint16_t*, uint8_t*, void*, size_t, hipStream_t, const int32_t*, const int64_t* = nullptr, int = 1,
-                  int32_t* = nullptr);
 size_t h_accumulate_workspace_bytes(int64_t, int64_t);
 int h_accumulate(float*, const void*, int, int64_t, int64_t, float, float, void*, size_t, hipStream_t);
 int h_accumulate_grouped(int, float* const*, const void* const*, const int64_t*, const int64_t*, const float*, const float*,
                          int, void*, size_t, hipStream_t, const void* const* const*, const int64_t*);
 size_t h_prepare_workspace_bytes(int64_t, int64_t);
 int h_prepare(float*, float*, int64_t, int64_t, float, float*, int*, uint8_t*, void*, size_t, hipStream_t, bool);
-int obq_quantize(float*, const float*, int64_t, int64_t, int, int, int, int, uint8_t*, float*, float*, void*, size_t,
-                 hipStream_t);
-int gptq_quantize_bands(float*, const float*, int64_t, int64_t, const gq_band_t*, int, int, const gq_search_t*, uint8_t*,
-                        uint16_t*, uint8_t*, uint16_t*, uint8_t*, void*, size_t, hipStream_t);
-int gptq_uses_helper_stream(int64_t, int64_t, int);
-int far_helper_enable(int);
 int w_prepare(const uint8_t*, float*, int64_t, int64_t, int*, hipStream_t);
 int h_pack_upper(const float*, int64_t, float*, hipStream_t);
 int h_unpack_upper(const float*, int64_t, float*, hipStream_t);

@@ -11,15 +11,10 @@
 #include <mutex>
 #include "gq_common.hpp"
 #include "gq_gemm32.hpp"
-#include "../../include/gptq_gguf_levels.h"
+#include "gq_walk.hpp"
 #include <stdlib.h>
 
 namespace gq {
-
-int launch_scale_search(const float* x, int64_t rows, int64_t ld, int q_type, const gq_search_t* p,
-                        uint16_t* d, int64_t d_stride, uint8_t* s, int64_t s_ld, uint16_t* dmin,
-                        int64_t dmin_stride, uint8_t* m, int64_t m_ld, hipStream_t st, unsigned* panel = nullptr,
-                        const int64_t* row_ends = nullptr, int nstack = 1);
 
 // ---------------------------------------------------------------- K5 segment
 // Processes columns [a, a+len) (len <= 128, a % 16 == 0, len % 16 == 0) of the
@@ -405,29 +400,305 @@ int launch_trailing_update(float* Cmat, int64_t ldc, const float* A, int64_t lda
 }
 
 // ------------------------------------------------------------- orchestration
-// Look-ahead depth of the trailing update (blocks of 128 columns per super-block), see gptq_quantize.
-constexpr int LA = 8;
+// One walk over the columns of W for every entry point (gq_walk.hpp): the entry points fill a
+// WalkCall, walk_plan turns shape and options into the schedule and the workspace layout, and column_walk runs the
+// named steps below block after block.
+constexpr int LA = 8;      // look-ahead depth of the trailing update: blocks of 128 columns per super-block
 constexpr int LA_B = 128;  // only this block size takes the look-ahead path (the chain length is a template constant)
 
-// ---- the far update next to the column loop (single-Linear look-ahead pipeline) ----
-// The far update of super-block s (everything beyond it) is one MFMA-bound GEMM; the column loop of super-block s+1
-// is a string of small latency-bound launches that needs the far update on ITS OWN 1024 columns only.  So the far
-// update is cut by column groups (g = 1024-column group index; F_s[g] = super-block s's update of group g):
-//   caller's stream:  loop(s) | F_s[s+1] | loop(s+1) | F_{s+1}[s+2] | ...
-//   helper stream:             F_s[s+2] , F_s[s+3..] | F_{s+1}[s+3] , F_{s+1}[s+4..] | ...
-// F_s[s+1] waits for F_{s-1}[s+1] (an event after that small launch); the helper launches are PERSISTENT with a
-// bounded number of workgroups, so the loop's kernels always find free CUs instead of queueing behind 56-us GEMM
-// tiles.  Every element of W still sees ((w - E_0 U_0) - E_1 U_1) - ... in the same order: results are unchanged.
-// The error buffer is doubled (the helper may still read super-block s's errors while the loop fills s+1's).
 static std::atomic<int> g_far_enabled{1};
 int far_helper_enable(int on) { return g_far_enabled.exchange(on ? 1 : 0); }
-static bool far_async_shape(int64_t R, int64_t C, int64_t B, int la) {
-    if (!g_far_enabled.load()) return false;
-    // options are read per call: tests and A/B runs flip them inside one process
-    const bool off = opt(OPT_far_sync) != 0;
-    const int64_t max_rows = opt(OPT_far_async_max_rows), min_sb = opt(OPT_far_async_min_sb);
-    return !off && B == LA_B && R % 128 == 0 && C % 128 == 0 && R <= max_rows && C >= min_sb * (int64_t)la * B;
+
+// options are read per call: tests and A/B runs flip them inside one process
+WalkOptions walk_options() {
+    return WalkOptions{opt(OPT_la), opt(OPT_no_lookahead), opt(OPT_far_sync), opt(OPT_far_async_max_rows),
+                       opt(OPT_far_async_min_sb), opt(OPT_far_wgs), opt(OPT_near64_maxn), g_far_enabled.load() != 0};
 }
+
+WalkPlan walk_plan(int64_t R, int64_t C, int block_size, WalkKind kind, int uniform_group, const WalkOptions& o) {
+    WalkPlan p{};
+    const int64_t B = p.B = block_size <= 0 || block_size > C ? C : block_size;  // gptq.py:54
+    // tuning knob; even only: a 256-column scale-search group must not straddle two super-blocks
+    p.la = (o.la >= 2 && o.la <= LA && o.la % 2 == 0) ? (int)o.la : LA;
+    const int ug = kind == WalkKind::Uniform && uniform_group > 0 ? uniform_group : 0;
+    // Look-ahead (B == 128): the blocks of a super-block of `la` blocks write their errors side by side into one
+    // [R, LA * 128] buffer.  After a block only the REST OF THE SUPER-BLOCK is updated; at the end of the super-block
+    // everything beyond it is updated by ONE chained GEMM (CHAIN = 128): per element ((w - E_0 U_0) - E_1 U_1) - ..., the
+    // same operations in the same order as gptq.py:270 applied block after block, with one read and one write of W
+    // instead of `la`.  A uniform group must lie inside one super-block as well: its grid is found from columns that
+    // every earlier block has already updated.
+    p.lookahead = B == LA_B && !o.no_lookahead && (!ug || (p.la * B) % ug == 0);
+    // Near updates at the granularity of the 256-column scale-search groups: an even block hands its errors to its
+    // partner (the odd block of the group) in the segment kernel's epilogue; after the odd block ONE chained launch
+    // (K = 256, chain 128) brings both blocks' errors to the rest of the super-block.  Per element the same subtractions
+    // in the same order as after-every-block updates; 3 launches per super-block instead of 7.  One launch after every
+    // block remains for uniform groups that do not divide 256.
+    p.pair_look = p.lookahead && p.la % 2 == 0 && (!ug || 256 % ug == 0);
+    p.ldE = p.lookahead ? (int64_t)LA * B : B;
+    p.helper_ok = p.lookahead && o.helper_enabled && !o.far_sync && R % 128 == 0 && C % 128 == 0 &&
+                  R <= o.far_async_max_rows && C >= o.far_async_min_sb * (int64_t)p.la * B;
+    p.far_wgs = (int)o.far_wgs;
+    p.near64_maxn = o.near64_maxn;
+    // The layout depends on R and B alone, never on the kind or the options: a caller sizes the workspace once.
+    const size_t blk = (size_t)R * (size_t)B * sizeof(float);   // one block of errors, or of working values
+    const size_t err = blk * (B == LA_B ? 2 * (size_t)LA : 1);  // super-block error buffer [R, LA * B], twice
+    // wider than a segment, or -- B not dividing 256 -- a block that straddles a 256-column super-group and is therefore
+    // walked in two segments
+    p.needs_blk = B > SEG || (B > 0 && 256 % B != 0);
+    p.err_off[0] = 0;
+    p.err_off[1] = B == LA_B ? blk * LA : 0;
+    p.blk_off = err;
+    p.panel_off = (err + (p.needs_blk ? blk : 0) + 255) & ~(size_t)255;
+    p.total = err + (p.needs_blk ? blk : 0) + 256 + 256;  // rounding up the workspace pointer, then the panel block
+    return p;
+}
+
+size_t gptq_workspace_bytes(int64_t R, int64_t C, int block_size) {
+    return walk_plan(R, C, block_size, WalkKind::KQuant, 0, walk_options()).total;
+}
+int gptq_uses_helper_stream(int64_t R, int64_t C, int block_size) {
+    return walk_plan(R, C, block_size, WalkKind::KQuant, 0, walk_options()).helper_ok;
+}
+
+// band k is rows [row_end[k-1], row_end[k]) and has its own K-quant type
+struct BandPlan {
+    BandTable tbl;
+    int q_type[GQ_BANDS_MAX];
+    int64_t row_end[GQ_BANDS_MAX];
+};
+
+// when the K-quant scales of a 256-column group are found
+enum class ScaleSearch {
+    None,     // never: they are inputs (ActOrder), or there are none (Uniform)
+    UpFront,  // gptq.py:184-196: all from the ORIGINAL W, before the first block
+    Lazy,     // gptq.py:240-245: from W as it is when the walk reaches the group
+};
+
+struct Walk {  // a checked call: the record, its plan and the pointers both imply
+    const WalkCall& c;
+    WalkPlan p;
+    TypeInfo ti;
+    ScaleSearch search;
+    float *err[2], *Wblk;
+    unsigned* panel;  // one device word block shared by all scale-search launches of this call (each leaves it at zero)
+    int64_t ng, nsg;  // groups / 256-column super-groups per row
+    int gps;          // groups per super-group
+    bool helper;      // far updates go through the helper stream: the plan admits it and the lease was granted
+};
+struct Block {  // gptq.py:222
+    int64_t c1, c2;  // columns
+    int64_t sb, pos;  // super-block and slot in it (0 without look-ahead)
+    int64_t S0, S1;   // columns of the super-block
+    bool single;      // one segment: the block fits in LDS and stays inside one 256-column super-group; else it lives
+                      // in the block scratch
+    float* Err;       // [R, ldE]
+};
+
+// Every check of a call, in the order the error messages have always had, then the plan and the workspace carve-up.
+static int walk_open(const WalkCall& c, Walk& w) {
+    const bool uni = c.kind == WalkKind::Uniform;
+    w.ti = TypeInfo{};
+    if (uni) {
+        w.ti.group = c.uni.group > 0 ? c.uni.group : (int)c.C;
+        w.ti.qmax = (1 << c.uni.bits) - 1;
+    } else if (c.kind == WalkKind::Bands) {
+        w.ti.group = 16;  // unused: every band brings its own
+        for (int k = 0; k < c.bands->tbl.n; ++k) {
+            TypeInfo tk;
+            type_info(c.bands->q_type[k], tk);
+            w.ti.k_search |= tk.k_search;
+        }
+    } else if (!type_info(c.q_type, w.ti)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_gptq_quantize: unknown q_type %d", c.q_type);
+    if (c.R <= 0 || c.C <= 0 || c.C % 256)
+        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gptq_quantize: R=%ld C=%ld (C %% 256 != 0)", (long)c.R, (long)c.C);
+    if (!c.W || !c.U || !c.qweight || (!uni && (!c.d || !c.s || !c.dmin || !c.m)))
+        GQ_FAIL(GQ_E_NULL, "gq_gptq_quantize: null pointer");
+    w.p = walk_plan(c.R, c.C, c.block_size, c.kind, c.uni.group, walk_options());
+    if (w.p.B % SB) GQ_FAIL(GQ_E_UNSUPPORTED, "gq_gptq_quantize: block_size %ld is not a multiple of 16", (long)w.p.B);
+    if (c.kind == WalkKind::ActOrder && c.q_type == GQ_Q3_K)
+        GQ_FAIL(GQ_E_UNSUPPORTED, "gq_gptq_quantize_perm: Q3_K forces act_order off (gptq.py:204-206)");
+    if (c.kind == WalkKind::Bands) w.search = ScaleSearch::Lazy;
+    else if (c.kind != WalkKind::KQuant) w.search = ScaleSearch::None;
+    else w.search = c.static_groups && c.q_type != GQ_Q3_K ? ScaleSearch::UpFront : ScaleSearch::Lazy;  // gptq.py:204-206
+    if (!c.ws || c.ws_bytes < w.p.total)
+        GQ_FAIL(GQ_E_WORKSPACE, "gq_gptq_quantize: workspace %zu < %zu bytes", c.ws_bytes, w.p.total);
+    char* base = reinterpret_cast<char*>(((uintptr_t)c.ws + 255) & ~(uintptr_t)255);
+    w.err[0] = reinterpret_cast<float*>(base + w.p.err_off[0]);
+    w.err[1] = reinterpret_cast<float*>(base + w.p.err_off[1]);
+    w.Wblk = reinterpret_cast<float*>(base + w.p.blk_off);
+    w.panel = reinterpret_cast<unsigned*>(base + w.p.panel_off);
+    w.ng = c.C / w.ti.group;
+    w.nsg = c.C / 256;
+    w.gps = uni ? 1 : 256 / w.ti.group;
+    w.helper = false;
+    return GQ_OK;
+}
+
+// quant_utils.py:57-106 for the [R, G] panel at column `col`: grid g of every row
+static void uniform_params(const Walk& w, int64_t col, int G, int64_t g) {
+    const WalkCall& c = w.c;
+    hipLaunchKernelGGL(uniform_params_kernel, dim3((unsigned)((c.R + 3) / 4)), dim3(256), 0, c.st, c.W + col, c.R, c.C, G,
+                       (float)w.ti.qmax, c.uni.sym, c.uni.scale + g, c.uni.zero + g, w.ng);
+}
+
+// Uniform: fast_obq.py:168-171 for every group that starts inside this block
+static int uniform_grids(const Walk& w, const Block& b) {
+    const int64_t G = w.c.uni.group;
+    ProfScope ps(PT_SCALE_SEARCH, w.c.st);
+    for (int64_t g = (b.c1 + G - 1) / G; g * G < b.c2; ++g) uniform_params(w, g * G, (int)G, g);
+    GQ_LAUNCH_CHECK();
+    return GQ_OK;
+}
+
+// gptq.py:184-196: all scales from the ORIGINAL W
+static int up_front_search(const Walk& w) {
+    const WalkCall& c = w.c;
+    int rc;
+    for (int64_t col = 0; col < c.C; col += 256)
+        if ((rc = launch_scale_search(c.W + col, c.R, c.C, c.q_type, c.p, c.d + col / 256, w.nsg, c.s + (col / 256) * w.gps,
+                                      w.ng, c.dmin + col / 256, w.nsg, c.m + (col / 256) * w.gps, w.ng, c.st, w.panel,
+                                      c.row_ends, c.nstack)))
+            return rc;
+    return GQ_OK;
+}
+
+// gptq.py:240-245 for the 256-column group that starts at column a.  Reads w (global), NOT w_blk: with block_size > 256
+// these columns are stale by design.  Bands: one launch per band, on that band's rows.
+static int lazy_search(const Walk& w, int64_t a) {
+    const WalkCall& c = w.c;
+    const int64_t sg = a / 256, nsg = w.nsg;
+    if (c.kind != WalkKind::Bands)
+        return launch_scale_search(c.W + a, c.R, c.C, c.q_type, c.p, c.d + sg, nsg, c.s + sg * w.gps, w.ng, c.dmin + sg, nsg,
+                                   c.m + sg * w.gps, w.ng, c.st, w.panel, c.row_ends, c.nstack);
+    const BandPlan& bp = *c.bands;
+    int rc;
+    for (int k = 0; k < bp.tbl.n; ++k) {
+        const int64_t r0 = k ? bp.row_end[k - 1] : 0, rows = bp.row_end[k] - r0;
+        const int gk = (int)(bp.tbl.info[k] & 0xffu), gpsk = 256 / gk;
+        const int64_t ngk = c.C / gk;
+        uint8_t *sk = c.s + bp.tbl.sm_off[k] + sg * gpsk, *mk = c.m + bp.tbl.sm_off[k] + sg * gpsk;
+        if ((rc = launch_scale_search(c.W + r0 * c.C + a, rows, c.C, bp.q_type[k], c.p, c.d + r0 * nsg + sg, nsg, sk, ngk,
+                                      c.dmin + r0 * nsg + sg, nsg, mk, ngk, c.st, w.panel)))
+            return rc;
+    }
+    return GQ_OK;
+}
+
+static int segment_attributes() {
+    static std::atomic<bool> seg_attr{false};  // guards an idempotent call: a race sets the same value twice
+    if (seg_attr) return GQ_OK;
+    for (const void* k : {(const void*)gptq_segment_kernel<false>, (const void*)gptq_segment_kernel<true>,
+                          (const void*)gptq_segment_kernel<false, true>, (const void*)gptq_segment_kernel<false, false, true>})
+        GQ_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, SEG_LDS_BYTES));
+    seg_attr = true;
+    return GQ_OK;
+}
+
+// K5 for columns [a, a + len) of block b: the one place that picks the kernel instantiation of a kind.
+// unext != nullptr: the partner's columns are updated in the epilogue; npair == 2: and walked in the same launch.
+static int launch_segment(const Walk& w, const Block& b, int64_t a, int len, const float* unext, int npair) {
+    const WalkCall& c = w.c;
+    const TypeInfo& ti = w.ti;
+    const dim3 grid((unsigned)((c.R + 63) / 64)), block(SEG_WAVES * 64);
+    const float* src = b.single ? c.W + a : w.Wblk + (a - b.c1);
+    const int64_t ld_src = b.single ? c.C : w.p.B, ldE = w.p.ldE, err_col0 = b.pos * w.p.B + (a - b.c1);
+    ProfScope ps(PT_GPTQ_SEGMENT, c.st);
+    switch (c.kind) {
+    case WalkKind::Bands:
+        hipLaunchKernelGGL((gptq_segment_kernel<false, false, true>), grid, block, SEG_LDS_BYTES, c.st, c.W, c.C, src, ld_src,
+                           c.U, a, len, c.R, c.d, c.s, c.dmin, c.m, 0, 0, 0.0f, 0.0f, c.qweight, b.Err, ldE, err_col0, nullptr,
+                           nullptr, nullptr, unext, npair, BandArg<true>{c.bands->tbl});
+        break;
+    case WalkKind::Uniform:  // d, s, dmin, m are null: the UNI instantiation never reads them
+        hipLaunchKernelGGL((gptq_segment_kernel<false, true>), grid, block, SEG_LDS_BYTES, c.st, c.W, c.C, src, ld_src, c.U, a,
+                           len, c.R, c.d, c.s, c.dmin, c.m, ti.group, 0, 0.0f, (float)ti.qmax, c.qweight, b.Err, ldE, err_col0,
+                           nullptr, c.uni.scale, c.uni.zero, unext);
+        break;
+    case WalkKind::ActOrder:
+        hipLaunchKernelGGL(gptq_segment_kernel<true>, grid, block, SEG_LDS_BYTES, c.st, c.W, c.C, src, ld_src, c.U, a, len, c.R,
+                           c.d, c.s, c.dmin, c.m, ti.group, ti.is_signed, (float)ti.qmin, (float)ti.qmax, c.qweight, b.Err, ldE,
+                           err_col0, c.perm, nullptr, nullptr, unext, npair);
+        break;
+    case WalkKind::KQuant:
+        hipLaunchKernelGGL(gptq_segment_kernel<false>, grid, block, SEG_LDS_BYTES, c.st, c.W, c.C, src, ld_src, c.U, a, len, c.R,
+                           c.d, c.s, c.dmin, c.m, ti.group, ti.is_signed, (float)ti.qmin, (float)ti.qmax, c.qweight, b.Err, ldE,
+                           err_col0, nullptr, nullptr, nullptr, unext, npair);
+        break;
+    }
+    GQ_LAUNCH_CHECK();
+    return GQ_OK;
+}
+
+// The columns of block b, segment after segment.  walked_by_partner: in, this block's columns were already walked by the
+// previous (even) block's launch; out, this block's last launch walked the next block as well.
+static int walk_block(const Walk& w, const Block& b, bool& walked_by_partner) {
+    const WalkCall& c = w.c;
+    const int64_t B = w.p.B;
+    int rc;
+    if (!b.single) {  // w_blk lives in scratch
+        ProfScope ps(PT_BLOCK_FAR, c.st);
+        hipLaunchKernelGGL(copy2d_kernel, dim3(2048), dim3(256), 0, c.st, w.Wblk, B, c.W + b.c1, c.C, c.R, b.c2 - b.c1);
+        GQ_LAUNCH_CHECK();
+    }
+    int64_t a = walked_by_partner ? b.c2 : b.c1;
+    walked_by_partner = false;
+    while (a < b.c2) {
+        // a segment never crosses a 256-column super-group boundary: the lazy
+        // scale search (gptq.py:240-245) must see W as it is at that column.
+        int64_t e = a + SEG < b.c2 ? a + SEG : b.c2;
+        const int64_t next_sg = (a / 256 + 1) * 256;
+        if (e > next_sg) e = next_sg;
+        const int len = (int)(e - a);
+        if (w.search == ScaleSearch::Lazy && (a % 256) == 0 && (rc = lazy_search(w, a))) return rc;
+        // an even block of a 256-group: its partner's columns are updated in this kernel's epilogue
+        const float* unext =
+            (w.p.pair_look && b.single && len == SEG && !(b.pos & 1) && b.c2 + B <= c.C) ? c.U + a * c.C + a + SEG : nullptr;
+        // the partner block in the same launch (it is a whole single segment too: B == SEG, c2 + B <= C)
+        const int npair = (unext && c.kind != WalkKind::Uniform && B == SEG) ? 2 : 1;
+        walked_by_partner = npair == 2;
+        if ((rc = launch_segment(w, b, a, len, unext, npair))) return rc;
+        if (e < b.c2) {  // push this segment's rank-1 updates into the rest of the block
+            ProfScope ps(PT_BLOCK_FAR, c.st);
+            hipLaunchKernelGGL(block_far_update_kernel, dim3(2048), dim3(256), 0, c.st, w.Wblk + (e - b.c1), B, b.c2 - e, c.R,
+                               b.Err, w.p.ldE, a - b.c1, len, c.U, c.C, a, e);
+            GQ_LAUNCH_CHECK();
+        }
+        a = e;
+    }
+    return GQ_OK;
+}
+
+// ---- after a block: gptq.py:270, W[:, c2:] -= Err @ U[c1:c2, c2:], cut four ways ----
+
+// this block's errors to the columns [c2, end): every later column without look-ahead, else the rest of the super-block
+static int block_trailing_update(const Walk& w, const Block& b, int64_t end) {
+    const WalkCall& c = w.c;
+    return launch_trailing_update(c.W + b.c2, c.C, b.Err + b.pos * w.p.B, w.p.ldE, c.U + b.c1 * c.C + b.c2, c.C, c.R,
+                                  end - b.c2, b.c2 - b.c1, c.st);
+}
+
+// pair_look, after the odd block of a 256-group: both blocks' errors, in order, to the rest of the super-block (the even
+// block reached its partner in the segment kernel).  What was measured against this form: DESIGN.md K6.
+static int pair_near_update(const Walk& w, const Block& b) {
+    if (!(b.pos & 1)) return GQ_OK;
+    const WalkCall& c = w.c;
+    const int64_t B = w.p.B, n = b.S1 - b.c2;
+    const float *E = b.Err + (b.pos - 1) * B, *Up = c.U + (b.c1 - B) * c.C + b.c2;
+    ProfScope ps(PT_TRAILING, c.st);
+    // up to near64_maxn columns: 64x64 tiles with the K = 256 panels whole in LDS (gemm32_near256_kernel)
+    if (n <= w.p.near64_maxn && c.R % 64 == 0) return launch_gemm32_near256(c.W + b.c2, c.C, E, w.p.ldE, Up, c.C, c.R, n, c.st);
+    return launch_gemm32<false, 0, false, 0, LA_B>(c.W + b.c2, c.C, E, w.p.ldE, Up, c.C, c.R, n, 2 * B, c.st);
+}
+
+// end of a super-block, caller's stream only: all its blocks at once, every later column
+static int far_update(const Walk& w, const Block& b) {
+    const WalkCall& c = w.c;
+    ProfScope ps(PT_TRAILING_FAR, c.st);
+    return launch_gemm32<false, 0, false, 0, LA_B>(c.W + b.S1, c.C, b.Err, w.p.ldE, c.U + b.S0 * c.C + b.S1, c.C, c.R,
+                                                   c.C - b.S1, b.S1 - b.S0, c.st);
+}
+
+// ---- the far update next to the walk (single-Linear look-ahead pipeline) ----
 // One helper stream per device, held by ONE call at a time: from the start of its enqueue until its last helper launch
 // has finished on the device.  A call that finds it taken runs the one-stream schedule (same results) -- several
 // chains funnelled through one in-order helper stream would wait for each other's GEMMs (measured: 103 -> 112 ms
@@ -445,10 +716,7 @@ static int far_helper_acquire(FarHelper** out) {
     GQ_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_far_mu);
     FarHelper& h = g_far[dev & 63];
-    if (!h.st) {
-        // (Measured and dropped: a helper stream confined to 192 CUs by hipExtStreamCreateWithCUMask -- the first n mask
-        // bits are n CUs, n/8 per XCD, profiles/micro/cu_mask_probe.hip -- with plain launches instead of persistent
-        // ones: the 4096 x 14336 loop takes 20.4 ms against 12.5, a block step 109 ms against 97.)
+    if (!h.st) {  // a plain stream with persistent launches; a CU-masked one was measured and dropped
         GQ_HIP(hipStreamCreateWithFlags(&h.st, hipStreamNonBlocking));
         GQ_HIP(hipEventCreateWithFlags(&h.done, hipEventDisableTiming));
     }
@@ -467,7 +735,7 @@ static void far_helper_release(FarHelper* h) {
     h->recorded = hipEventRecord(h->done, h->st) == hipSuccess;
     h->enqueueing = false;
 }
-struct FarHold {  // releases on every return path of the column loop
+struct FarHold {  // releases on every return path of the walk
     FarHelper* h = nullptr;
     ~FarHold() { far_helper_release(h); }
 };
@@ -480,322 +748,132 @@ static int far_event(int i, hipEvent_t* out) {
     return GQ_OK;
 }
 
-// does gq_gptq_quantize(R, C, block_size) put its far updates on the library's helper stream?
-int gptq_uses_helper_stream(int64_t R, int64_t C, int block_size) {
-    const int64_t B = block_size <= 0 || block_size > C ? C : block_size;
-    int la = LA;
-    if (const int64_t e = opt(OPT_la)) la = (e >= 2 && e <= LA && e % 2 == 0) ? (int)e : LA;
-    return !opt(OPT_no_lookahead) && far_async_shape(R, C, B, la);
-}
-
-// Does some block of B columns live in the block scratch?  Wider than a segment, or -- B not dividing 256 -- a block that
-// straddles a 256-column super-group and is therefore walked in two segments (column_loop: `single`).
-static bool needs_block_scratch(int64_t B) { return B > SEG || 256 % B != 0; }
-
-size_t gptq_workspace_bytes(int64_t R, int64_t C, int block_size) {
-    int64_t B = block_size <= 0 || block_size > C ? C : block_size;
-    size_t err = (size_t)R * (size_t)B * sizeof(float);
-    if (B == LA_B) err *= LA;  // super-block error buffer [R, LA * B]
-    if (B == LA_B) err *= 2;   // ... doubled for the far update next to the loop (far_async_shape)
-    // (a block <= 128 columns that straddles a super-group used the scratch without its room being counted here: the copy
-    // wrote R * B floats past the workspace, e.g. block_size 48 or 96 at C = 512)
-    size_t blk = needs_block_scratch(B) ? (size_t)R * (size_t)B * sizeof(float) : 0;
-    return err + blk + 256 + 256;  // + the panel word of the scale searches (quant_utils.py:250-252)
-}
-
-// perm != nullptr: act_order (gptq.py:208-216, 233-235, 272-276).  W and U are already in permuted
-// order, d/s/dmin/m are INPUTS (the static scales of the original column groups, gptq.py:184-196) and
-// qweight comes back in permuted positions; the caller un-permutes it.
-//
-// uni != nullptr: the uniform grids of EvoPress' FastOBQ (evopress/src/fast_obq.py:146-200) instead of a K-quant --
-// the same column loop and trailing updates; the grid of a group is found from W as it is when the block holding
-// the group's first column starts (fast_obq.py:168-171 reads w, which the in-block feedback never touches).
-struct UniformSpec {
-    int bits, group, sym;  // group == 0: one grid per row, from the original W (fast_obq.py:153-154)
-    float *scale, *zero;   // [R, C / group]
-};
-
-// bands != nullptr (gq_gptq_quantize_bands): band k is rows [row_end[k-1], row_end[k]) and has its own K-quant type.  The
-// walk -- segment launches, near and far updates -- is that of one matrix [R, C]; only the lazy scale search is per band
-// (one launch each, on that band's rows of W as they are at that column), and the segment kernel reads the band table.
-struct BandPlan {
-    BandTable tbl;
-    int q_type[GQ_BANDS_MAX];
-    int64_t row_end[GQ_BANDS_MAX];
-};
-
-static int column_loop(float* W, const float* U, int64_t R, int64_t C, int q_type, int block_size, int static_groups,
-                       const gq_search_t* p, uint8_t* qweight, uint16_t* d, uint8_t* s, uint16_t* dmin, uint8_t* m,
-                       void* ws, size_t ws_bytes, hipStream_t st, const int32_t* perm, const UniformSpec* uni,
-                       const int64_t* row_ends = nullptr, int nstack = 1, int32_t* researches_out = nullptr,
-                       const BandPlan* bands = nullptr) {
-    // row_ends / nstack: W is several matrices that share U, one under the other (rows never mix: gptq.py:222-270);
-    // only the scale searches need to know where one ends and the next begins (their panel-wide `continue`)
-    TypeInfo ti;
-    if (uni) {
-        ti = TypeInfo{};
-        ti.group = uni->group > 0 ? uni->group : (int)C;
-        ti.is_signed = 0;
-        ti.qmin = 0;
-        ti.qmax = (1 << uni->bits) - 1;
-        ti.k_search = false;
-        static_groups = 2;  // no K-quant scale search
-        d = dmin = reinterpret_cast<uint16_t*>(qweight);  // unused by the UNI kernel; keeps the null check below simple
-        s = m = qweight;
-    } else if (bands) {
-        ti = TypeInfo{};
-        ti.group = 16;  // unused: every band brings its own
-        for (int k = 0; k < bands->tbl.n; ++k) {
-            TypeInfo tk;
-            type_info(bands->q_type[k], tk);
-            ti.k_search |= tk.k_search;
-        }
-    } else if (!type_info(q_type, ti)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_gptq_quantize: unknown q_type %d", q_type);
-    if (R <= 0 || C <= 0 || C % 256) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gptq_quantize: R=%ld C=%ld (C %% 256 != 0)", (long)R, (long)C);
-    if (!W || !U || !qweight || !d || !s || !dmin || !m) GQ_FAIL(GQ_E_NULL, "gq_gptq_quantize: null pointer");
-    const int64_t B = block_size <= 0 || block_size > C ? C : block_size;  // gptq.py:54
-    int rc;
-    if (B % SB) GQ_FAIL(GQ_E_UNSUPPORTED, "gq_gptq_quantize: block_size %ld is not a multiple of 16", (long)B);
-    if (q_type == GQ_Q3_K && perm) GQ_FAIL(GQ_E_UNSUPPORTED, "gq_gptq_quantize_perm: Q3_K forces act_order off (gptq.py:204-206)");
-    if (q_type == GQ_Q3_K) static_groups = 0;  // gptq.py:204-206
-    if (perm) static_groups = 2;  // scales are inputs: neither the up-front nor the lazy search runs
-    const size_t need = gptq_workspace_bytes(R, C, (int)B);
-    if (!ws || ws_bytes < need) GQ_FAIL(GQ_E_WORKSPACE, "gq_gptq_quantize: workspace %zu < %zu bytes", ws_bytes, need);
-    // Look-ahead trailing update (B == 128): the blocks of a super-block of LA blocks write their errors
-    // side by side into one [R, LA*128] buffer.  After each block only the REST OF THE SUPER-BLOCK is
-    // updated (a small GEMM); at the end of the super-block everything beyond it is updated by ONE chained
-    // GEMM (CHAIN = 128): per element ((w - E_0 U_0) - E_1 U_1) - ..., the same operations in the same
-    // order as gptq.py:270 applied block after block, with one read and one write of W instead of LA.
-    // (Deferring the far part to a helper stream, to overlap it with the next super-block's column loop,
-    // measured no gain alone and -8 % inside a block's multi-stream schedule: its long K = 1024 tiles keep
-    // the column-loop workgroups, which need a whole CU's LDS, waiting.)
-    int la = LA;
-    // tuning knob; even only: a 256-column scale-search group must not straddle two super-blocks
-    if (const int64_t e = opt(OPT_la)) la = (e >= 2 && e <= LA && e % 2 == 0) ? (int)e : LA;
-    // a uniform group must lie inside one super-block as well: its grid is found from columns that every earlier
-    // block has already updated
-    const bool lookahead = (B == LA_B) && !opt(OPT_no_lookahead) &&
-                           (!uni || uni->group <= 0 || (la * B) % uni->group == 0);
-    // (Measured and removed, r03: a LEFT-looking form of the near updates -- before block b its columns receive the errors of
-    // the super-block's earlier blocks in one chained 64-tile launch with K = 128 b: a quarter of the traffic on W, bit-identical,
-    // and no faster (2.33 vs 2.30 ms of near updates in the 4096 x 14336 loop))
-    // r03, default: near updates at the granularity of the 256-column scale-search groups.  An even block hands its
-    // errors to its partner (the odd block of the group) in the column-loop kernel's epilogue; after the odd block ONE
-    // chained launch (K = 256, chain 128) brings both blocks' errors to the rest of the super-block.  Per element the
-    // same subtractions in the same order as after-every-block updates (bit-identical: the parity tests run both);
-    // 3 launches per super-block instead of 7.  One launch after every block (r02) remains for uniform groups that do not
-    // divide 256.
-    const bool pair_look = lookahead && la % 2 == 0 &&
-                           (!uni || uni->group <= 0 || 256 % uni->group == 0);
-    const int64_t ldE = lookahead ? (int64_t)LA * B : B;
-    float* Err0 = reinterpret_cast<float*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    float* Wblk = Err0 + (size_t)R * B * (B == LA_B ? 2 * LA : 1);
-    bool far_async = lookahead && far_async_shape(R, C, B, la);
-    const int far_wgs = (int)opt(OPT_far_wgs);
+// The far update of super-block s (everything beyond it) is one MFMA-bound GEMM; the walk of super-block s+1 is a string
+// of small latency-bound launches that needs the far update on ITS OWN G = la * 128 columns only.  So the far update is
+// cut by column groups (g = index of a group of G columns; F_s[g] = super-block s's update of group g):
+//   caller's stream:  walk(s) | F_s[s+1] | walk(s+1) | F_{s+1}[s+2] | ...
+//   helper stream:             F_s[s+2] , F_s[s+3..] | F_{s+1}[s+3] , F_{s+1}[s+4..] | ...
+// F_s[s+1] waits for F_{s-1}[s+1] (an event after that small launch); the helper launches are PERSISTENT with a
+// bounded number of workgroups, so the walk's kernels always find free CUs instead of queueing behind 56-us GEMM
+// tiles.  Every element of W still sees ((w - E_0 U_0) - E_1 U_1) - ... in the same order: results are unchanged.
+// The error buffer is doubled (the helper may still read super-block s's errors while the walk fills s+1's).
+struct FarPipeline {
     FarHold hold;
     hipStream_t helper = nullptr;
-    hipEvent_t ev_small_prev = nullptr, ev_bulk[2] = {nullptr, nullptr}, ev_last = nullptr;
-    if (far_async) {
+    hipEvent_t ev_small_prev = nullptr;         // behind F_{s-1}[s+1]
+    hipEvent_t ev_bulk[2] = {nullptr, nullptr}; // behind the helper's last read of each half of the error buffer
+    hipEvent_t ev_last = nullptr;               // behind the helper's last launch
+    int ev_i = 0;                               // events taken from far_event so far
+
+    // helper stays null when another call holds the stream: that call runs the one-stream schedule
+    int lease() {
+        int rc;
         if ((rc = far_helper_acquire(&hold.h))) return rc;
         if (hold.h) helper = hold.h->st;
-        else far_async = false;  // taken by another call: the one-stream schedule
+        return GQ_OK;
     }
-    int ev_i = 0;
-    // one device word shared by all scale-search launches of this call (each leaves it at zero)
-    unsigned* panel = reinterpret_cast<unsigned*>(
-        (reinterpret_cast<uintptr_t>(Wblk + (needs_block_scratch(B) ? (size_t)R * B : 0)) + 255) & ~(uintptr_t)255);
-    if ((ti.k_search && static_groups != 2) || researches_out) GQ_HIP(hipMemsetAsync(panel, 0, 256, st));
-    const int64_t ng = C / ti.group, nsg = C / 256;
-    const int gps = uni ? 1 : 256 / ti.group;
-    auto uniform_params = [&](int64_t col, int G, int64_t g) {
-        hipLaunchKernelGGL(uniform_params_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, W + col, R, C, G,
-                           (float)ti.qmax, uni->sym, uni->scale + g, uni->zero + g, ng);
-    };
-    if (uni && uni->group <= 0) {
-        uniform_params(0, (int)C, 0);
+    // before super-block sb writes its half of the error buffer: the helper is done with it
+    int wait_for_half(hipStream_t st, int64_t sb) {
+        if (!ev_bulk[sb & 1]) return GQ_OK;
+        GQ_HIP(hipStreamWaitEvent(st, ev_bulk[sb & 1], 0));
+        ev_bulk[sb & 1] = nullptr;
+        return GQ_OK;
+    }
+    // end of super-block b.sb: F_s[s+1] on the caller's stream, F_s[s+2] and F_s[s+3..] on the helper
+    int far_update(const Walk& w, const Block& b) {
+        const WalkCall& c = w.c;
+        const int64_t C = c.C, S0 = b.S0, S1 = b.S1, ldE = w.p.ldE, K = S1 - S0;
+        const int64_t G = (int64_t)w.p.la * w.p.B, g1 = S1 + G < C ? S1 + G : C, g2 = g1 + G < C ? g1 + G : C;
+        const float* Us = c.U + S0 * C;
+        hipEvent_t ready = nullptr, ev = nullptr;
+        int rc;
+        if (g1 < C) {  // the helper may start on this super-block's errors
+            if ((rc = far_event(ev_i++, &ready))) return rc;
+            GQ_HIP(hipEventRecord(ready, c.st));
+        }
+        if (ev_small_prev) GQ_HIP(hipStreamWaitEvent(c.st, ev_small_prev, 0));  // F_{s-1}[s+1] is in
+        ev_small_prev = nullptr;
+        {
+            ProfScope ps(PT_TRAILING_FAR, c.st);
+            if ((rc = launch_gemm32_chain_full<LA_B>(c.W + S1, C, b.Err, ldE, Us + S1, C, c.R, g1 - S1, K, c.st))) return rc;
+        }
+        if (g1 >= C) return GQ_OK;
+        GQ_HIP(hipStreamWaitEvent(helper, ready, 0));
+        ProfScope ps(PT_TRAILING_FAR, helper);
+        if ((rc = launch_gemm32_chain_full<LA_B>(c.W + g1, C, b.Err, ldE, Us + g1, C, c.R, g2 - g1, K, helper, w.p.far_wgs)))
+            return rc;
+        if ((rc = far_event(ev_i++, &ev))) return rc;
+        GQ_HIP(hipEventRecord(ev, helper));
+        ev_small_prev = ev;
+        if (g2 < C &&
+            (rc = launch_gemm32_chain_full<LA_B>(c.W + g2, C, b.Err, ldE, Us + g2, C, c.R, C - g2, K, helper, w.p.far_wgs)))
+            return rc;
+        if ((rc = far_event(ev_i++, &ev))) return rc;
+        GQ_HIP(hipEventRecord(ev, helper));
+        ev_bulk[b.sb & 1] = ev;
+        ev_last = ev;
+        return GQ_OK;
+    }
+    // the caller's stream sees the helper's last write
+    int final_wait(hipStream_t st) {
+        if (ev_last) GQ_HIP(hipStreamWaitEvent(st, ev_last, 0));
+        return GQ_OK;
+    }
+};
+
+static int column_walk(const WalkCall& c) {
+    Walk w{c};
+    int rc;
+    if ((rc = walk_open(c, w))) return rc;
+    const WalkPlan& p = w.p;
+    FarPipeline far;
+    if (p.helper_ok) {
+        if ((rc = far.lease())) return rc;
+        w.helper = far.helper != nullptr;
+    }
+    if ((w.ti.k_search && w.search != ScaleSearch::None) || c.researches_out) GQ_HIP(hipMemsetAsync(w.panel, 0, 256, c.st));
+    if (c.kind == WalkKind::Uniform && c.uni.group <= 0) {
+        uniform_params(w, 0, (int)c.C, 0);
         GQ_LAUNCH_CHECK();
     }
+    if (w.search == ScaleSearch::UpFront && (rc = up_front_search(w))) return rc;
+    if ((rc = segment_attributes())) return rc;
 
-    if (static_groups == 1) {  // gptq.py:184-196: all scales from the ORIGINAL W
-        for (int64_t c = 0; c < C; c += 256)
-            if ((rc = launch_scale_search(W + c, R, C, q_type, p, d + c / 256, nsg, s + (c / 256) * gps, ng,
-                                          dmin + c / 256, nsg, m + (c / 256) * gps, ng, st, panel, row_ends, nstack)))
-                return rc;
+    bool walked_by_partner = false;
+    for (int64_t c1 = 0; c1 < c.C; c1 += p.B) {  // gptq.py:222
+        Block b;
+        b.c1 = c1;
+        b.c2 = c1 + p.B < c.C ? c1 + p.B : c.C;
+        b.single = (b.c2 - b.c1) <= SEG && (b.c1 / 256 == (b.c2 - 1) / 256);
+        const int64_t bi = c1 / p.B;
+        b.sb = bi / p.la;
+        b.pos = p.lookahead ? bi % p.la : 0;
+        b.S0 = b.sb * p.la * p.B;
+        b.S1 = b.S0 + p.la * p.B < c.C ? b.S0 + p.la * p.B : c.C;
+        b.Err = w.err[w.helper ? b.sb & 1 : 0];
+        if (w.helper && b.pos == 0 && (rc = far.wait_for_half(c.st, b.sb))) return rc;
+        if (c.kind == WalkKind::Uniform && c.uni.group > 0 && (rc = uniform_grids(w, b))) return rc;
+        if ((rc = walk_block(w, b, walked_by_partner))) return rc;
+        if (b.c2 >= c.C) break;
+        if (!p.lookahead) rc = block_trailing_update(w, b, c.C);
+        else if (b.c2 < b.S1) rc = p.pair_look ? pair_near_update(w, b) : block_trailing_update(w, b, b.S1);
+        else rc = w.helper ? far.far_update(w, b) : far_update(w, b);
+        if (rc) return rc;
     }
-    const dim3 seg_grid((unsigned)((R + 63) / 64)), seg_block(SEG_WAVES * 64);
-    static std::atomic<bool> seg_attr{false};  // guards an idempotent call: a race sets the same value twice
-    if (!seg_attr) {
-        GQ_HIP(hipFuncSetAttribute((const void*)gptq_segment_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   SEG_LDS_BYTES));
-        GQ_HIP(hipFuncSetAttribute((const void*)gptq_segment_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   SEG_LDS_BYTES));
-        GQ_HIP(hipFuncSetAttribute((const void*)gptq_segment_kernel<false, true>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, SEG_LDS_BYTES));
-        GQ_HIP(hipFuncSetAttribute((const void*)gptq_segment_kernel<false, false, true>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, SEG_LDS_BYTES));
-        seg_attr = true;
-    }
-    bool walked_by_partner = false;  // this block's columns were walked by the previous (even) block's launch
-    for (int64_t c1 = 0; c1 < C; c1 += B) {  // gptq.py:222
-        const int64_t c2 = c1 + B < C ? c1 + B : C;
-        // one segment iff the block fits in LDS and stays inside one 256-column super-group
-        const bool single = (c2 - c1) <= SEG && (c1 / 256 == (c2 - 1) / 256);
-        const int64_t ncols = c2 - c1;
-        const int64_t bi = c1 / B, sb = bi / la, pos = lookahead ? bi % la : 0;  // block, super-block, slot
-        float* Err = far_async ? Err0 + (sb & 1) * (size_t)R * ldE : Err0;
-        if (far_async && pos == 0 && ev_bulk[sb & 1]) {  // this half of the error buffer: the helper is done with it
-            GQ_HIP(hipStreamWaitEvent(st, ev_bulk[sb & 1], 0));
-            ev_bulk[sb & 1] = nullptr;
-        }
-        if (uni && uni->group > 0) {  // fast_obq.py:168-171 for every group that starts inside this block
-            ProfScope ps(PT_SCALE_SEARCH, st);
-            for (int64_t g = (c1 + uni->group - 1) / uni->group; g * uni->group < c2; ++g) uniform_params(g * uni->group, uni->group, g);
-            GQ_LAUNCH_CHECK();
-        }
-        if (!single) {  // w_blk lives in scratch
-            ProfScope ps(PT_BLOCK_FAR, st);
-            hipLaunchKernelGGL(copy2d_kernel, dim3(2048), dim3(256), 0, st, Wblk, B, W + c1, C, R, ncols);
-            GQ_LAUNCH_CHECK();
-        }
-        int64_t a = walked_by_partner ? c2 : c1;
-        walked_by_partner = false;
-        while (a < c2) {
-            // a segment never crosses a 256-column super-group boundary: the lazy
-            // scale search (gptq.py:240-245) must see W as it is at that column.
-            int64_t e = a + SEG < c2 ? a + SEG : c2;
-            const int64_t next_sg = (a / 256 + 1) * 256;
-            if (e > next_sg) e = next_sg;
-            const int len = (int)(e - a);
-            if (!static_groups && (a % 256) == 0) {
-                // reads w (global), NOT w_blk: with block_size > 256 these columns
-                // are stale by design
-                const int64_t sg = a / 256;
-                if (bands) {
-                    for (int k = 0; k < bands->tbl.n; ++k) {
-                        const int64_t r0 = k ? bands->row_end[k - 1] : 0, rows = bands->row_end[k] - r0;
-                        const int gk = (int)(bands->tbl.info[k] & 0xffu), gpsk = 256 / gk;
-                        const int64_t ngk = C / gk;
-                        uint8_t *sk = s + bands->tbl.sm_off[k] + sg * gpsk, *mk = m + bands->tbl.sm_off[k] + sg * gpsk;
-                        if ((rc = launch_scale_search(W + r0 * C + a, rows, C, bands->q_type[k], p, d + r0 * nsg + sg, nsg, sk,
-                                                      ngk, dmin + r0 * nsg + sg, nsg, mk, ngk, st, panel)))
-                            return rc;
-                    }
-                } else if ((rc = launch_scale_search(W + a, R, C, q_type, p, d + sg, nsg, s + sg * gps, ng, dmin + sg, nsg,
-                                              m + sg * gps, ng, st, panel, row_ends, nstack)))
-                    return rc;
-            }
-            // an even block of a 256-group: its partner's columns are updated in this kernel's epilogue
-            const float* unext = (pair_look && single && len == SEG && !(pos & 1) && c2 + B <= C) ? U + a * C + a + SEG : nullptr;
-            const float* srcp = single ? (W + a) : (Wblk + (a - c1));
-            const int64_t ld_src = single ? C : B;
-            // the partner block in the same launch (it is a whole single segment too: B == SEG, c2 + B <= C)
-            const int npair = (unext && !uni && B == SEG) ? 2 : 1;
-            walked_by_partner = npair == 2;
-            {
-                ProfScope ps(PT_GPTQ_SEGMENT, st);
-                if (bands)
-                    hipLaunchKernelGGL((gptq_segment_kernel<false, false, true>), seg_grid, seg_block, SEG_LDS_BYTES, st, W, C,
-                                       srcp, ld_src, U, a, len, R, d, s, dmin, m, 0, 0, 0.0f, 0.0f, qweight, Err, ldE,
-                                       pos * B + (a - c1), perm, nullptr, nullptr, unext, npair, BandArg<true>{bands->tbl});
-                else if (uni)
-                    hipLaunchKernelGGL((gptq_segment_kernel<false, true>), seg_grid, seg_block, SEG_LDS_BYTES, st, W, C, srcp,
-                                       ld_src, U, a, len, R, d, s, dmin, m, ti.group, 0, 0.0f, (float)ti.qmax, qweight, Err,
-                                       ldE, pos * B + (a - c1), perm, uni->scale, uni->zero, unext);
-                else if (perm)
-                    hipLaunchKernelGGL(gptq_segment_kernel<true>, seg_grid, seg_block, SEG_LDS_BYTES, st, W, C, srcp, ld_src, U, a,
-                                       len, R, d, s, dmin, m, ti.group, ti.is_signed, (float)ti.qmin, (float)ti.qmax, qweight, Err,
-                                       ldE, pos * B + (a - c1), perm, nullptr, nullptr, unext, npair);
-                else
-                    hipLaunchKernelGGL(gptq_segment_kernel<false>, seg_grid, seg_block, SEG_LDS_BYTES, st, W, C, srcp, ld_src, U, a,
-                                       len, R, d, s, dmin, m, ti.group, ti.is_signed, (float)ti.qmin, (float)ti.qmax, qweight, Err,
-                                       ldE, pos * B + (a - c1), perm, nullptr, nullptr, unext, npair);
-                GQ_LAUNCH_CHECK();
-            }
-            if (e < c2) {  // push this segment's rank-1 updates into the rest of the block
-                ProfScope ps(PT_BLOCK_FAR, st);
-                hipLaunchKernelGGL(block_far_update_kernel, dim3(2048), dim3(256), 0, st, Wblk + (e - c1), B,
-                                   c2 - e, R, Err, ldE, a - c1, len, U, C, a, e);
-                GQ_LAUNCH_CHECK();
-            }
-            a = e;
-        }
-        // gptq.py:270
-        if (c2 >= C) break;
-        if (!lookahead) {
-            if ((rc = launch_trailing_update(W + c2, C, Err, B, U + c1 * C + c2, C, R, C - c2, ncols, st))) return rc;
-            continue;
-        }
-        const int64_t S0 = sb * la * B, S1 = (S0 + la * B < C) ? S0 + la * B : C;  // this super-block
-        if (c2 < S1) {  // rest of the super-block, this block's errors only
-            // (measured and dropped: applying the blocks in pairs -- an even block updates its partner only, the odd
-            // block the rest with both in one chained K = 256 launch -- gives 4 tiny + 3 deeper launches instead of 7
-            // thin ones, bit-identical, but no faster: 1.79 vs 1.71 ms for 4096 x 14336; every launch is latency.
-            // Also dropped: a dedicated K = 128 kernel, one workgroup per CU with the whole K of both operands in LDS
-            // (23.5 vs 17.3 us per launch).  A rank-128 update moves 16 B of operands L2 -> LDS per output element for
-            // 256 flops at 64 x 64 tiles: it is L2-bandwidth-bound near 50 TFLOP/s whatever the schedule.)
-            if (pair_look) {
-                // (measured, 1.24 vs 1.05 ms of near launches for 4096 x 14336, removed: a third level -- pair -> the
-                // quad's other pair (K = 256, N = 256), quad -> the rest of the super-block (K = 512, N = 512): same flops,
-                // deeper K on fewer tiles)
-                if (pos & 1) {  // end of a 256-group: both blocks' errors, in order, to the rest of the super-block
-                    ProfScope ps(PT_TRAILING, st);
-                    // up to GQ_NEAR64_MAXN columns: 64x64 tiles with the K = 256 panels whole in LDS (gemm32_near256_kernel)
-                    const int64_t near64_maxn = opt(OPT_near64_maxn);
-                    if (S1 - c2 <= near64_maxn && R % 64 == 0) {
-                        if ((rc = launch_gemm32_near256(W + c2, C, Err + (pos - 1) * B, ldE, U + (c1 - B) * C + c2, C, R, S1 - c2, st)))
-                            return rc;
-                    } else if ((rc = launch_gemm32<false, 0, false, 0, LA_B>(W + c2, C, Err + (pos - 1) * B, ldE,
-                                                                             U + (c1 - B) * C + c2, C, R, S1 - c2, 2 * B, st)))
-                        return rc;
-                }
-                continue;
-            }
-            if ((rc = launch_trailing_update(W + c2, C, Err + pos * B, ldE, U + c1 * C + c2, C, R, S1 - c2, ncols, st)))
-                return rc;
-            continue;
-        }
-        // end of the super-block: all its blocks at once, every later column
-        if (!far_async) {
-            ProfScope ps(PT_TRAILING_FAR, st);
-            if ((rc = launch_gemm32<false, 0, false, 0, LA_B>(W + S1, C, Err, ldE, U + S0 * C + S1, C, R, C - S1, S1 - S0, st)))
-                return rc;
-            continue;
-        }
-        {
-            const int64_t G = (int64_t)la * B, g1 = S1 + G < C ? S1 + G : C, g2 = g1 + G < C ? g1 + G : C;
-            hipEvent_t ready = nullptr, ev = nullptr;
-            if (g1 < C) {  // the helper may start on this super-block's errors
-                if ((rc = far_event(ev_i++, &ready))) return rc;
-                GQ_HIP(hipEventRecord(ready, st));
-            }
-            if (ev_small_prev) GQ_HIP(hipStreamWaitEvent(st, ev_small_prev, 0));  // F_{s-1}[s+1] is in
-            ev_small_prev = nullptr;
-            {
-                ProfScope ps(PT_TRAILING_FAR, st);
-                if ((rc = launch_gemm32_chain_full<LA_B>(W + S1, C, Err, ldE, U + S0 * C + S1, C, R, g1 - S1, S1 - S0, st)))
-                    return rc;
-            }
-            if (g1 < C) {
-                GQ_HIP(hipStreamWaitEvent(helper, ready, 0));
-                ProfScope ps(PT_TRAILING_FAR, helper);
-                if ((rc = launch_gemm32_chain_full<LA_B>(W + g1, C, Err, ldE, U + S0 * C + g1, C, R, g2 - g1, S1 - S0, helper, far_wgs)))
-                    return rc;
-                if ((rc = far_event(ev_i++, &ev))) return rc;
-                GQ_HIP(hipEventRecord(ev, helper));
-                ev_small_prev = ev;
-                if (g2 < C && (rc = launch_gemm32_chain_full<LA_B>(W + g2, C, Err, ldE, U + S0 * C + g2, C, R, C - g2, S1 - S0, helper, far_wgs)))
-                    return rc;
-                if ((rc = far_event(ev_i++, &ev))) return rc;
-                GQ_HIP(hipEventRecord(ev, helper));
-                ev_bulk[sb & 1] = ev;
-                ev_last = ev;
-            }
-        }
-    }
-    if (ev_last) GQ_HIP(hipStreamWaitEvent(st, ev_last, 0));  // the caller's stream sees the helper's last write
-    if (researches_out)  // every scale search of this call ran on `st`: the count is final here
-        GQ_HIP(hipMemcpyAsync(researches_out, panel + GQ_PANEL_RESEARCH, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    if ((rc = far.final_wait(c.st))) return rc;
+    if (c.researches_out)  // every scale search of this call ran on `st`: the count is final here
+        GQ_HIP(hipMemcpyAsync(c.researches_out, w.panel + GQ_PANEL_RESEARCH, sizeof(int32_t), hipMemcpyDeviceToDevice, c.st));
     return GQ_OK;
+}
+
+static WalkCall walk_call(WalkKind kind, float* W, const float* U, int64_t R, int64_t C, int block_size, uint8_t* qweight,
+                          void* ws, size_t ws_bytes, hipStream_t st) {
+    WalkCall c;
+    c.kind = kind;
+    c.W = W, c.U = U, c.R = R, c.C = C, c.block_size = block_size;
+    c.qweight = qweight;
+    c.ws = ws, c.ws_bytes = ws_bytes, c.st = st;
+    return c;
 }
 
 int gptq_quantize(float* W, const float* U, int64_t R, int64_t C, int q_type, int block_size, int static_groups,
@@ -803,8 +881,14 @@ int gptq_quantize(float* W, const float* U, int64_t R, int64_t C, int q_type, in
                   void* ws, size_t ws_bytes, hipStream_t st, const int32_t* perm, const int64_t* row_ends, int nstack,
                   int32_t* researches_out) {
     if (nstack > 1 && perm) GQ_FAIL(GQ_E_UNSUPPORTED, "gq_gptq_quantize_stacked: act_order matrices are not stacked");
-    return column_loop(W, U, R, C, q_type, block_size, static_groups, p, qweight, d, s, dmin, m, ws, ws_bytes, st, perm,
-                       nullptr, row_ends, nstack, researches_out);
+    WalkCall c = walk_call(perm ? WalkKind::ActOrder : WalkKind::KQuant, W, U, R, C, block_size, qweight, ws, ws_bytes, st);
+    c.d = d, c.s = s, c.dmin = dmin, c.m = m;
+    c.q_type = q_type;
+    c.static_groups = static_groups != 0;
+    c.p = p;
+    c.row_ends = row_ends, c.nstack = nstack, c.researches_out = researches_out;
+    c.perm = perm;
+    return column_walk(c);
 }
 
 // gq_gptq_quantize_bands (include/gptq_gguf_levels.h): every check of the band table before the first HIP call.
@@ -836,8 +920,11 @@ int gptq_quantize_bands(float* W, const float* U, int64_t R, int64_t C, const gq
         prev = e;
     }
     if (prev != R) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gptq_quantize_bands: the last band ends at row %ld, R=%ld", (long)prev, (long)R);
-    return column_loop(W, U, R, C, -1, block_size, 0, p, qweight, d, s, dmin, m, ws, ws_bytes, st, nullptr, nullptr, nullptr, 1,
-                       nullptr, &bp);
+    WalkCall c = walk_call(WalkKind::Bands, W, U, R, C, block_size, qweight, ws, ws_bytes, st);
+    c.d = d, c.s = s, c.dmin = dmin, c.m = m;
+    c.p = p;
+    c.bands = &bp;
+    return column_walk(c);
 }
 
 // EvoPress FastOBQ.step for one bit width (evopress/src/fast_obq.py:146-200) given U.
@@ -847,9 +934,9 @@ int obq_quantize(float* W, const float* U, int64_t R, int64_t C, int bits, int g
     if (!scale || !zero) GQ_FAIL(GQ_E_NULL, "gq_obq_quantize: null pointer");
     if (group_size < 0 || (group_size > 0 && (group_size % SB || C % group_size)))
         GQ_FAIL(GQ_E_UNSUPPORTED, "gq_obq_quantize: group_size %d must be 0 or a multiple of 16 that divides C=%ld", group_size, (long)C);
-    UniformSpec u{bits, group_size, sym ? 1 : 0, scale, zero};
-    return column_loop(W, U, R, C, -1, block_size, 2, nullptr, qweight, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes,
-                       st, nullptr, &u);
+    WalkCall c = walk_call(WalkKind::Uniform, W, U, R, C, block_size, qweight, ws, ws_bytes, st);
+    c.uni = UniformSpec{bits, group_size, sym ? 1 : 0, scale, zero};
+    return column_walk(c);
 }
 
 }  // namespace gq

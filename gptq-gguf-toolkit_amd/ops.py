@@ -214,6 +214,17 @@ def _alloc_outs(R, C, q_type, dev):
             torch.empty(R, C // G, dtype=torch.uint8, device=dev))
 
 
+def _walk_ws(ws: Optional[torch.Tensor], R, C, bs, device) -> torch.Tensor:
+    """The column walk's workspace: the caller's when it is at least the needed size, else a fresh one."""
+    need = workspace_bytes(_cabi.WS_GPTQ_QUANTIZE, R, C, 0, bs)
+    return ws if ws is not None and ws.numel() >= need else _ws(need, device)
+
+
+def _kquant_outs(q_type, q, d, s, dmin, m):
+    t = _idt(q_type)
+    return q.view(t), d, s.view(t), dmin, m.view(t)
+
+
 _side_streams = {}
 
 
@@ -254,41 +265,22 @@ def gptq_quantize(W: torch.Tensor, U: torch.Tensor, q_type: int, block_size=128,
     if row_chunks > 1 and (R % (64 * row_chunks) or ws is not None):
         row_chunks = 1
 
-    if row_ends is not None and len(row_ends) > 1:
-        ends = (ctypes.c_int64 * len(row_ends))(*[int(e) for e in row_ends])
-        need = workspace_bytes(_cabi.WS_GPTQ_QUANTIZE, R, C, 0, bs)
-        if ws is None or ws.numel() < need:
-            ws = _ws(need, W.device)
-        check(lib().gq_gptq_quantize_stacked(_ptr(W), _ptr(U), R, C, int(q_type), bs, int(bool(static_groups)),
-                                             _search(rmin, rdelta, nstep, **mq), _ptr(q), _ptr(d), _ptr(s), _ptr(dmin),
-                                             _ptr(m), ends, len(row_ends), _ptr(ws), ws.numel(), _stream(W)),
-              "gq_gptq_quantize_stacked")
-        t = _idt(q_type)
-        return q.view(t), d, s.view(t), dmin, m.view(t)
-
-    if panel_researches is not None:
-        assert panel_researches.dtype == torch.int32 and panel_researches.is_cuda and panel_researches.numel() >= 1
-        need = workspace_bytes(_cabi.WS_GPTQ_QUANTIZE, R, C, 0, bs)
-        if ws is None or ws.numel() < need:
-            ws = _ws(need, W.device)
-        check(lib().gq_gptq_quantize_slice(_ptr(W), _ptr(U), R, C, int(q_type), bs, int(bool(static_groups)),
-                                           _search(rmin, rdelta, nstep, **mq), _ptr(q), _ptr(d), _ptr(s), _ptr(dmin), _ptr(m),
-                                           _ptr(panel_researches), _ptr(ws), ws.numel(), _stream(W)), "gq_gptq_quantize_slice")
-        t = _idt(q_type)
-        return q.view(t), d, s.view(t), dmin, m.view(t)
-
-    def one(r0, r1, wsbuf):
+    def one(r0, r1, wsbuf, entry="gq_gptq_quantize", extra=()):
+        """rows [r0, r1) through one entry point: all three take `extra` between the outputs and the workspace"""
         n = r1 - r0
-        need = workspace_bytes(_cabi.WS_GPTQ_QUANTIZE, n, C, 0, bs)
-        if wsbuf is None or wsbuf.numel() < need:
-            wsbuf = _ws(need, W.device)
-        check(lib().gq_gptq_quantize(_ptr(W[r0:r1]), _ptr(U), n, C, int(q_type), bs, int(bool(static_groups)),
-                                     _search(rmin, rdelta, nstep, **mq), _ptr(q[r0:r1]), _ptr(d[r0:r1]), _ptr(s[r0:r1]),
-                                     _ptr(dmin[r0:r1]), _ptr(m[r0:r1]), _ptr(wsbuf), wsbuf.numel(), _stream(W)),
-              "gq_gptq_quantize")
+        wsbuf = _walk_ws(wsbuf, n, C, bs, W.device)
+        check(getattr(lib(), entry)(_ptr(W[r0:r1]), _ptr(U), n, C, int(q_type), bs, int(bool(static_groups)),
+                                    _search(rmin, rdelta, nstep, **mq), _ptr(q[r0:r1]), _ptr(d[r0:r1]), _ptr(s[r0:r1]),
+                                    _ptr(dmin[r0:r1]), _ptr(m[r0:r1]), *extra, _ptr(wsbuf), wsbuf.numel(), _stream(W)), entry)
         return wsbuf
 
-    if row_chunks == 1:
+    if row_ends is not None and len(row_ends) > 1:
+        ends = (ctypes.c_int64 * len(row_ends))(*[int(e) for e in row_ends])
+        one(0, R, ws, "gq_gptq_quantize_stacked", (ends, len(row_ends)))
+    elif panel_researches is not None:
+        assert panel_researches.dtype == torch.int32 and panel_researches.is_cuda and panel_researches.numel() >= 1
+        one(0, R, ws, "gq_gptq_quantize_slice", (_ptr(panel_researches),))
+    elif row_chunks == 1:
         one(0, R, ws)
     else:
         cur = torch.cuda.current_stream(W.device)
@@ -305,8 +297,7 @@ def gptq_quantize(W: torch.Tensor, U: torch.Tensor, q_type: int, block_size=128,
             cur.wait_event(ev)
         for b in keep:  # scratch was allocated on side streams; it is dead once `cur` has passed the joins
             b.record_stream(cur)
-    t = _idt(q_type)
-    return q.view(t), d, s.view(t), dmin, m.view(t)
+    return _kquant_outs(q_type, q, d, s, dmin, m)
 
 
 BANDS_MAX = _cabi.BANDS_MAX
@@ -354,9 +345,8 @@ def gptq_quantize_bands(W: torch.Tensor, U: torch.Tensor, bands: Sequence[Tuple[
     s = torch.empty(R * (C // 16), dtype=torch.uint8, device=dev)  # G >= 16: room for any table
     m = torch.empty(R * (C // 16), dtype=torch.uint8, device=dev)
     bs = int(block_size or 0)
-    need = workspace_bytes(_cabi.WS_GPTQ_QUANTIZE, R, C, 0, bs)
-    if ws is None:
-        ws = _ws(need, dev)
+    if ws is None:  # a caller's own workspace goes to the library as it is: a short one is the library's to refuse
+        ws = _walk_ws(None, R, C, bs, dev)
     check(lib().gq_gptq_quantize_bands(_ptr(W), _ptr(U), R, C, tbl, n, bs, _search(rmin, rdelta, nstep, **mq), _ptr(q),
                                        _ptr(d), _ptr(s), _ptr(dmin), _ptr(m), _ptr(ws), ws.numel(), _stream(W)),
           "gq_gptq_quantize_bands")
@@ -391,9 +381,7 @@ def gptq_quantize_perm(W: torch.Tensor, U: torch.Tensor, q_type: int, perm: torc
     R, C = W.shape
     q = torch.empty(R, C, dtype=torch.uint8, device=W.device)
     bs = int(block_size or 0)
-    need = workspace_bytes(_cabi.WS_GPTQ_QUANTIZE, R, C, 0, bs)
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, W.device)
+    ws = _walk_ws(ws, R, C, bs, W.device)
     check(lib().gq_gptq_quantize_perm(_ptr(W), _ptr(U), R, C, int(q_type), bs, _ptr(perm), _ptr(d.contiguous()),
                                       _ptr(s.contiguous()), _ptr(dmin.contiguous()), _ptr(m.contiguous()), _ptr(q),
                                       _ptr(ws), ws.numel(), _stream(W)), "gq_gptq_quantize_perm")
@@ -412,9 +400,7 @@ def obq_quantize(W: torch.Tensor, U: torch.Tensor, bits: int, group_size: int = 
     scale = torch.empty(R, ng, dtype=torch.float32, device=W.device)
     zero = torch.empty(R, ng, dtype=torch.float32, device=W.device)
     bs = int(block_size or 0)
-    need = workspace_bytes(_cabi.WS_GPTQ_QUANTIZE, R, C, 0, bs)
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, W.device)
+    ws = _walk_ws(ws, R, C, bs, W.device)
     check(lib().gq_obq_quantize(_ptr(W), _ptr(U), R, C, int(bits), int(group_size or 0), int(bool(sym)), bs, _ptr(q),
                                 _ptr(scale), _ptr(zero), _ptr(ws), ws.numel(), _stream(W)), "gq_obq_quantize")
     return q, scale, zero

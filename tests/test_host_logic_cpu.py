@@ -1632,3 +1632,49 @@ def test_gguf_writer_lazy_tensors_are_written_in_order_and_errors_surface(tmp_pa
         w.write()
     with pytest.raises(ValueError, match="Duplicated tensor name"):
         w.add_tensor_lazy("t", (4, 256), GGMLType.Q4_K, lambda: blobs[0])
+
+
+# --------------------------------------------------------------------------- the column walk's pure plan
+# gq_workspace_bytes(GQ_WS_GPTQ_QUANTIZE, R, C, 0, block), recorded from the library before the walk's workspace layout
+# and schedule became one function (walk_plan): (R, C, block) -> bytes
+_RECORDED_WALK_WS = {
+    (64, 512, 128): 524800, (64, 512, 48): 25088, (64, 512, 96): 49664, (64, 512, 256): 131584, (64, 512, 0): 262656,
+    (128, 9472, 128): 1049088, (192, 512, 64): 49664,
+    # more of the same: block > C is the whole row, 16 and 32 divide 256 (no block scratch), 512 and 768 do not fit a segment
+    (64, 512, 1024): 262656, (64, 512, 16): 4608, (64, 512, 32): 8704, (64, 1024, 512): 262656, (100, 1536, 768): 614912,
+    (128, 2304, 128): 1049088, (1, 256, 128): 8704, (4096, 14336, 128): 33554944,
+}
+# the options the walk reads, each away from its default (la and far_async_min_sb twice)
+_WALK_OPTION_SETTINGS = [dict(la=2), dict(la=4, far_async_min_sb=2), dict(no_lookahead=1), dict(far_sync=1),
+                         dict(far_async_max_rows=0), dict(far_async_min_sb=0), dict(far_wgs=24), dict(near64_maxn=0),
+                         dict(la=6, no_lookahead=1, far_sync=1, far_async_max_rows=64, far_async_min_sb=1, far_wgs=1,
+                              near64_maxn=1048576)]
+
+
+def test_walk_workspace_is_the_recorded_table_under_every_option():
+    from gptq_gguf_toolkit_amd import _cabi
+
+    def table():
+        return {k: int(_cabi.lib().gq_workspace_bytes(_cabi.WS_GPTQ_QUANTIZE, k[0], k[1], 0, k[2])) for k in _RECORDED_WALK_WS}
+    assert table() == _RECORDED_WALK_WS
+    for kv in _WALK_OPTION_SETTINGS:
+        with _cabi.options(**kv):
+            assert table() == _RECORDED_WALK_WS, kv
+
+
+def test_walk_helper_stream_eligibility():
+    from gptq_gguf_toolkit_amd import _cabi
+
+    def helper(R, C, block):
+        return int(_cabi.lib().gq_gptq_uses_helper_stream(R, C, block))
+    # defaults: la 8, at least 8 super-blocks (8192 columns), R and C multiples of 128, block 128
+    default = {(128, 9472, 128): 1, (64, 9472, 128): 0, (128, 4096, 128): 0, (128, 9472, 64): 0}
+    assert {k: helper(*k) for k in default} == default
+    small = {(128, 2304, 128): 1, (128, 1024, 128): 1, (128, 768, 128): 0, (192, 2304, 128): 0}
+    with _cabi.options(la=4, far_async_min_sb=2):
+        assert {k: helper(*k) for k in small} == small
+    for base, rows in (({}, default), (dict(la=4, far_async_min_sb=2), small)):
+        for off in (dict(far_sync=1), dict(no_lookahead=1)):
+            with _cabi.options(**base, **off):
+                assert [helper(*k) for k, v in rows.items() if v] == [0] * sum(rows.values()), (base, off)
+    assert {k: helper(*k) for k in default} == default  # the options are back
