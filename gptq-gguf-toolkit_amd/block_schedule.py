@@ -461,7 +461,8 @@ class BlockSchedule:
     # ------------------------------------------------------------------ level build
     @torch.no_grad()
     def quantize_levels(self, levels, propagate: Optional[GGMLQuantizationType],
-                        extra: Optional[Callable[[str, GPTQ, dict], Any]] = None) -> Dict[str, Dict[Any, Tuple[torch.Tensor, ...]]]:
+                        extra: Optional[Callable[[str, GPTQ, dict], Any]] = None,
+                        pack: Optional[Callable[[tuple, list, list], Any]] = None) -> Dict[str, Dict[Any, Tuple[torch.Tensor, ...]]]:
         """Every Linear of the block at every level of `levels` -> {name: {q_type: 5-tuple}}: the database the bit-width
         search starts from, without a run per level.  The phases are quantize()'s -- the Hessians are folded once, one chain
         per distinct Hessian on the same lanes, one factorisation per distinct (H, zero-column set) -- and a chain walks the
@@ -469,7 +470,9 @@ class BlockSchedule:
         `propagate`: one of `levels` -- that level's dequantized weights replace layer.weight.data, as
         quantize(writeback=True) does with its one type, so the next block is calibrated on what an ordinary run of that
         level feeds it -- or None: the weights stay as they are.  `extra(name, handle, {q_type: result})` runs on the
-        chain's stream.  Single rank only."""
+        chain's stream; so does `pack(stacked, bands, members)`, once per walk (GPTQ.compute_levels' `walks`, members as
+        (Linear name, q_type) or None): the place for work on a whole walk's device buffers, the level database's one
+        gq_pack_bands launch.  Tensors either returns are kept valid for the caller's stream.  Single rank only."""
         handles = self.handles
         levels = [GGMLQuantizationType(t) for t in levels]
         if not levels or len(set(levels)) != len(levels):
@@ -500,7 +503,7 @@ class BlockSchedule:
             for k in enq:
                 lane = _Lane(streams[lane_of[k]], main)
                 lane.wait(start)
-                lanes.append((lane, self._run_level_chain(order[k], levels, propagate, own, extra, results, deq, lane)))
+                lanes.append((lane, self._run_level_chain(order[k], levels, propagate, own, extra, results, deq, lane, pack)))
             for lane, born in lanes:
                 lane.join(born)
         self.stats["own_U"] = len(results) - self.stats["reused_U"]
@@ -511,7 +514,7 @@ class BlockSchedule:
         return {n: results[n] for n in handles}
 
     def _run_level_chain(self, names: List[str], levels, propagate, own: Dict[str, bool], extra, results, deq,
-                         lane: _Lane) -> List[torch.Tensor]:
+                         lane: _Lane, pack=None) -> List[torch.Tensor]:
         """Enqueue one chain of a level build on its lane -> the tensors born there.  The leader and the followers KNOWN to
         share its factorisation build their levels in one walk; a follower with a column set of its own, or one whose
         sharing became known too late to be checked (MoE experts), factorises for itself and walks alone -- the same
@@ -521,6 +524,8 @@ class BlockSchedule:
         names = sorted(names, key=lambda n: handles[n].shared_H_with is not None)
         together = [n for n in names if handles[n].shared_H_with is None or (n in own and not own[n])]
         alone = [n for n in names if n not in together]
+        walks = [] if pack is not None else None
+        name_of = {handles[n]: n for n in names}
         with lane.run():
             for grp in ([together] if self.stack else [[n] for n in together]):
                 if not grp:
@@ -530,7 +535,7 @@ class BlockSchedule:
                 hs = [handles[n] for n in grp]
                 if len(grp) > 1:
                     self.stats["stacked"] = self.stats.get("stacked", 0) + len(grp)
-                res = GPTQ.compute_levels(hs, levels, defer_check=True)
+                res = GPTQ.compute_levels(hs, levels, defer_check=True, walks=walks)
                 for n, h in zip(grp, hs):
                     if h._pending_mismatch is not None:  # a reused factorisation: the flag is asserted by verify()
                         BlockSchedule.unverified.append(h._pending_mismatch)
@@ -540,7 +545,7 @@ class BlockSchedule:
             for n in alone:
                 h = handles[n]
                 self.stats["refactorised"] += 1
-                results[n] = GPTQ.compute_levels([h], levels, own_U=True)[h]
+                results[n] = GPTQ.compute_levels([h], levels, own_U=True, walks=walks)[h]
             for n in names:
                 h = handles[n]
                 for res in results[n].values():
@@ -552,6 +557,9 @@ class BlockSchedule:
                 if extra is not None:
                     out = extra(n, h, results[n])
                     born.extend(t for t in (out if isinstance(out, (tuple, list)) else (out,)) if torch.is_tensor(t))
+            for stacked, bands, members in walks or ():
+                out = pack(stacked, bands, [None if mem is None else (name_of[mem[0]], mem[1]) for mem in members])
+                born.extend(t for t in (out if isinstance(out, (tuple, list)) else (out,)) if torch.is_tensor(t))
         return born
 
     def _assign_ranks(self, world: int) -> None:

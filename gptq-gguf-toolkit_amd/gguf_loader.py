@@ -46,6 +46,25 @@ def rotary_row_src(name: str, R: int, arch, n_head, n_head_kv, device) -> Option
     return unpermute_rows(R, n_head, n_head if name.endswith(".attn_q.weight") else n_head_kv).to(device)
 
 
+_ROW_DST: Dict[tuple, torch.Tensor] = {}  # (q or k, R, heads, device) -> rotary_row_dst's index
+
+
+def rotary_row_dst(gguf_name: str, R: int, n_head, n_kv, device) -> Optional[torch.Tensor]:
+    """The other direction, HF -> GGUF, as an index: int32 [R] on `device` with x[rotary_row_dst(...)] == permute(x, ...) of
+    pack_gptq_into_gguf for attn_q / attn_k (None for any other tensor) -- the `row_src` of ops.pack_bands, which packs an
+    HF-ordered band straight into GGUF row order.  rotary_row_src of the same tensor undoes it: either composition is the
+    identity.  One tensor per (q or k, R, heads, device), kept for the process."""
+    if not n_head or not gguf_name.endswith(ROTARY_TENSORS):
+        return None
+    from .pack_gptq_into_gguf import permute
+    is_q = gguf_name.endswith(".attn_q.weight")
+    heads = int(n_head if is_q or n_kv is None else n_kv)
+    key = ("q" if is_q else "k", int(R), heads, str(device))
+    if key not in _ROW_DST:
+        _ROW_DST[key] = permute(torch.arange(R, dtype=torch.int32), heads, heads).contiguous().to(device)
+    return _ROW_DST[key]
+
+
 def hf_tensor_name(gguf_name: str) -> str:
     """Inverse of pack_gptq_into_gguf.map_tensor_name for the dense Llama table (and Mixtral's router)."""
     if gguf_name in _TOP:

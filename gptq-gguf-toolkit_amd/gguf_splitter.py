@@ -22,21 +22,16 @@ import time
 from pathlib import Path
 from typing import Dict, Iterable, Optional, Tuple, Union
 
-import numpy as np
 
 if __package__ in (None, ""):  # run as a script: make the package importable under its alias
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import gptq_gguf_toolkit_amd  # noqa: F401
     __package__ = "gptq_gguf_toolkit_amd"
 
-from .gguf_writer import GGML_QUANT_SIZES, PLAIN_TYPES, parse_gguf  # noqa: E402
-from .level_db import BIT_WIDTHS, GGML_TYPE_IDS, level_stem  # noqa: E402
-
-# Views of level_db's tables on the types the reference's splitter names (gguf_splitter.py:42-50, :56-96; + BF16), narrow on
-# purpose: any other name ("IQ2_XS") keeps the exact width 32.0 here (resolve_hf_bitwidth with --exact), not the full table's.
-_TYPES = ("F32", "F16", "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1", "Q2_K", "Q3_K", "Q4_K", "Q5_K", "Q6_K", "Q8_K", "BF16")
-TYPE_NAMES = {GGML_TYPE_IDS[name]: name for name in _TYPES}
-EXACT_BITS = {name: BIT_WIDTHS[name] for name in _TYPES}
+from .gguf_writer import parse_gguf  # noqa: E402
+# TYPE_NAMES / EXACT_BITS: level_db's narrow views on the types the reference's splitter names; level_records: the JSON
+# records of a level, shared with level_db.LevelDbWriter
+from .level_db import EXACT_BITS, TYPE_NAMES, level_records, level_stem, write_manifests, write_sidecar  # noqa: E402
 
 
 class GGUFSplitter:
@@ -73,9 +68,8 @@ class GGUFSplitter:
     def build_gguf_layer_database(self) -> Dict[str, dict]:
         db = {}
         for name, shape, gt, off, nbytes, q, _ in self._entries():
-            db[name] = {"tensor_type": gt, "quantization": q, "bitwidth": self.extract_bitwidth_from_quantization(q),
-                        "exact_bitwidth": self.get_tensor_bit_width(q), "shape": list(reversed(shape)),  # ggml ne order
-                        "n_elements": int(np.prod(shape)), "n_bytes": nbytes, "data_offset": off}
+            db[name] = level_records(name, shape, gt, q, self.extract_bitwidth_from_quantization(q), self.get_tensor_bit_width(q),
+                                     nbytes, "", off)[2]
         self.gguf_layer_database = db
         return db
 
@@ -92,25 +86,15 @@ class GGUFSplitter:
             layer_dir = self.output_dir / name
             layer_dir.mkdir(parents=True, exist_ok=True)
             (layer_dir / f"{prefix}.pth").write_bytes(buf[off:off + nbytes])  # raw bytes, not a torch pickle (:378-380)
-            bs, ts = GGML_QUANT_SIZES[gt]
-            if bs > 1:
-                np_dtype, np_shape = "uint8", [*shape[:-1], shape[-1] // bs * ts]
-            else:
-                np_dtype, np_shape = PLAIN_TYPES[gt][1], list(shape)
-            common = {"type": gt, "quantization": q, "bitwidth": bitwidth, "exact_bitwidth": self.get_tensor_bit_width(q),
-                      "shape": list(reversed(shape)), "n_elements": int(np.prod(shape))}
-            (layer_dir / f"{prefix}-metadata.json").write_text(json.dumps({"tensor_info": {
-                "name": name, **common, "n_bytes": nbytes, "data_offset_original": off, "data_filename": f"{prefix}.pth",
-                "np_dtype": np_dtype, "np_shape": np_shape}}, indent=2))
+            sidecar, level, _ = level_records(name, shape, gt, q, bitwidth, self.get_tensor_bit_width(q), nbytes, prefix, off)
+            write_sidecar(layer_dir / f"{prefix}-metadata.json", sidecar)
             layer = manifest["layers"].setdefault(name, {"original_name": name, "dims": list(reversed(shape)), "bitwidths": {}})
-            layer["bitwidths"][str(bitwidth)] = {"filename": f"{prefix}.pth", "metadata_filename": f"{prefix}-metadata.json",
-                                                 **common, "size_bytes": nbytes, "data_offset": off}
+            layer["bitwidths"][str(bitwidth)] = level
         for key, (value, types) in self._kv.items():
             manifest["metadata"][key] = {"types": types, "value": value}
         manifest["model_info"]["split_timestamp"] = time.time()
         manifest["model_info"]["processed_tensors"] = n
-        (self.output_dir / "manifest.json").write_text(json.dumps(manifest, indent=2))
-        (self.output_dir / "gguf_layer_database.json").write_text(json.dumps(self.gguf_layer_database, indent=2))
+        write_manifests(self.output_dir, manifest, self.gguf_layer_database)
         return manifest
 
 

@@ -252,6 +252,21 @@ class GGUFWriter:
             timing["wait"] = timing.get("wait", 0.0) + t_wait
 
 
+def kv_records(kv: Sequence[Tuple[str, int, Any, int]]):
+    """A writer's key/value list (`GGUFWriter.kv`) as parse_gguf reads it back from the written file: {key: (value,
+    [value type ids])}, every scalar taken through its wire format (a FLOAT32 comes back as the nearest float32, an integer
+    that does not fit its type raises as write() would) -- so a database written without a file carries the `metadata` a
+    split of the file carries."""
+    def wire(t, v):
+        if t == GGUFValueType.STRING:
+            return bytes(v).decode("utf-8") if isinstance(v, (bytes, bytearray)) else v
+        return struct.unpack(_SCALAR_FMT[t], struct.pack(_SCALAR_FMT[t], v))[0]
+    out = {}
+    for key, t, v, sub in kv:
+        out[key] = ([wire(sub, x) for x in v], [t, sub]) if t == GGUFValueType.ARRAY else (wire(t, v), [t])
+    return out
+
+
 class _Lazy:
     def __init__(self, producer, nbytes):
         self.producer, self.nbytes = producer, nbytes

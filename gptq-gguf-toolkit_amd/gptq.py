@@ -430,7 +430,7 @@ class GPTQ:
     @staticmethod
     @torch.no_grad()
     def compute_levels(hs: Sequence["GPTQ"], q_types: Sequence[GGMLQuantizationType], own_U: bool = False,
-                       defer_check: bool = False):
+                       defer_check: bool = False, walks: Optional[list] = None):
         """Every handle of `hs` at every level of `q_types` from ONE factorisation and ONE walk over the columns: the
         Hessian, the Cholesky chain and the C dependent steps of the column loop do not depend on the level, so the
         working copies -- Linear-major, then level -- are stacked by rows and each band is rounded to its own grid
@@ -442,7 +442,12 @@ class GPTQ:
         factorisation of its own (one host read of the flags); with `defer_check` the flags stay on the device in
         `_pending_mismatch`, as compute_stacked leaves them, and the caller answers for them.  A handle's W is None
         afterwards.  A group that needs more than GQ_BANDS_MAX bands is cut into several calls; a handle whose rows are
-        no multiple of 64 (levels_key() is None) walks its levels one after another with the one U."""
+        no multiple of 64 (levels_key() is None) walks its levels one after another with the one U.
+
+        `walks` (a list, appended to): what each walk left on the device, for a consumer of whole walks (ops.pack_bands) --
+        (stacked, bands, members): the stacked (qweight, d, s, dmin, m) buffers of a gq_gptq_quantize_bands call, its band
+        table, and per band the (handle, q_type) it holds (None for a band whose handle was walked again: its bytes are
+        stale); a level-after-level walk is a one-band entry whose `stacked` is the call's result tuple."""
         q_types = [GGMLQuantizationType(t) for t in q_types]
         if not hs or not q_types or len(set(q_types)) != len(q_types):
             raise ValueError("compute_levels needs at least one handle and distinct levels")
@@ -478,7 +483,12 @@ class GPTQ:
                         Wf[r0 + k * h.d_row:r0 + (k + 1) * h.d_row].copy_(Wf[r0:r0 + h.d_row])
                     bands.append((r0 + (k + 1) * h.d_row, int(t)))
                 r0 += L * h.d_row
-            res = _ops.gptq_quantize_bands(Wf, U, bands, h0.block_size, h0.rmin, h0.rdelta, h0.nstep, **mq)
+            if walks is None:
+                res = _ops.gptq_quantize_bands(Wf, U, bands, h0.block_size, h0.rmin, h0.rdelta, h0.nstep, **mq)
+            else:
+                res, stacked = _ops.gptq_quantize_bands(Wf, U, bands, h0.block_size, h0.rmin, h0.rdelta, h0.nstep,
+                                                        return_stacked=True, **mq)
+                walks.append((stacked, bands, [(h, t) for h in grp for t in q_types]))
             for j, h in enumerate(grp):
                 out[h] = {t: res[j * L + k] for k, t in enumerate(q_types)}
                 h.W = None  # the contract of compute_stacked: no handle pins the stack
@@ -492,6 +502,8 @@ class GPTQ:
                 else:
                     _ops.w_prepare(h._last_cf, h.W)  # the dead / all-zero columns _prepare zeroed in the first copy
                 out[h][t] = _ops.gptq_quantize(h.W, U, int(t), h.block_size, False, h.rmin, h.rdelta, h.nstep, **mq)
+                if walks is not None:
+                    walks.append((out[h][t], [(h.d_row, int(t))], [(h, t)]))
             h.W = None
         if not defer_check:
             pending = [h for h in hs if h._pending_mismatch is not None]
@@ -500,7 +512,10 @@ class GPTQ:
                 for h, bad in zip(pending, flags):
                     h._pending_mismatch = None
                     if bad:
-                        out[h] = GPTQ.compute_levels([h], q_types, own_U=True)[h]
+                        if walks is not None:  # what the shared walk left of this handle is not its result
+                            for _, _, members in walks:
+                                members[:] = [None if mem is not None and mem[0] is h else mem for mem in members]
+                        out[h] = GPTQ.compute_levels([h], q_types, own_U=True, walks=walks)[h]
         return out
 
     def _row_split_active(self) -> bool:

@@ -5,17 +5,33 @@
     <db>/manifest.json                   the layers and the original file's key/value data
     <db>/gguf_layer_database.json        tensor name -> type / bit width / shape / offset, in the file's tensor order
 
-Top to bottom: names -> directories -> sidecar -> manifest -> bytes on a device -> the ggml type tables.  torch, ops and
-gguf_loader are imported where a tensor is made, so the readers that only look at names and JSON (the stitcher's) need none."""
+Top to bottom: names -> directories -> sidecar -> manifest -> bytes on a device -> the ggml type tables -> the records and the
+writer.  torch, ops and gguf_loader are imported where a tensor is made, so the readers that only look at names and JSON (the
+stitcher's) need none.
+
+The database has two producers.  gguf_splitter.py cuts a finished .gguf; LevelDbWriter (the one-pass level build,
+quant.py --level_db) writes the same files without a .gguf in between.  Both take every JSON record from level_records, so
+a reader cannot tell them apart -- except for what a database that never was a file cannot say:
+  * no `original_file` in model_info and no `data_offset` / `data_offset_original` anywhere: there is no source file.  Nothing
+    in the package reads the offsets; the stitcher, not finding an original model, takes the manifest's `metadata`;
+  * layers[name]["bitwidths"] holds ALL levels of a tensor (splitting one file per level into one directory rewrites the
+    manifest each time and leaves the last level only);
+  * gguf_layer_database.json carries, per tensor, the record of the level registered LAST (the last level of --levels: what
+    splitting the per-level files in that order leaves); its tensor order and manifest.json's are set_order's -- the order the
+    converter writes for the model -- whatever order the tensors arrived in;
+  * nothing is visible under <db> before close(): files are written under <db>.partial, which close() renames."""
 import glob
 import json
 import os
 import re
+import shutil
+import threading
+import time
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .gguf_writer import PLAIN_TYPES
+from .gguf_writer import GGML_QUANT_SIZES, PLAIN_TYPES
 
 # ------------------------------------------------------------------------------------------------ names
 # Two rules read a level's file name, kept apart on purpose.  They agree on every name the splitter writes and differ on
@@ -210,3 +226,155 @@ BIT_WIDTHS = {"F32": 32.0, "F16": 16.0, "BF16": 16.0, "I8": 8.0, "I16": 16.0, "I
               "IQ3_S": 3.44, "IQ3_M": 3.66, "IQ4_NL": 4.56, "IQ4_XS": 4.25, "IQ1_S": 1.5625, "IQ1_M": 1.75}  # :232-268
 # numpy dtype names a sidecar may carry -> item size: bytes of block types, and the plain types' own
 NP_ITEMSIZE = {"uint8": 1, "int8": 1, **{np_name: size for _, np_name, size in PLAIN_TYPES.values()}}
+
+
+# Views of the tables on the types the reference's splitter names (mapper/gguf_splitter.py:42-50, :56-96; + BF16), narrow on
+# purpose: any other name ("IQ2_XS") keeps the exact width 32.0 there (resolve_hf_bitwidth with --exact), not the full table's.
+SPLIT_TYPES = ("F32", "F16", "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1", "Q2_K", "Q3_K", "Q4_K", "Q5_K", "Q6_K", "Q8_K", "BF16")
+TYPE_NAMES = {GGML_TYPE_IDS[name]: name for name in SPLIT_TYPES}
+EXACT_BITS = {name: BIT_WIDTHS[name] for name in SPLIT_TYPES}
+
+
+# ------------------------------------------------------------------------------------------------ records
+def level_records(name: str, shape: Sequence[int], ggml_type: int, quantization: str, bitwidth, exact_bitwidth: float,
+                  nbytes: int, stem: str, data_offset: Optional[int] = None):
+    """The three JSON records of one level of one tensor -- the ONE definition the splitter and the writer share:
+    (sidecar `tensor_info`, its entry of manifest layers[name]["bitwidths"], its gguf_layer_database.json record).  `shape` is
+    logical, outermost first; `data_offset` (the splitter's: where the bytes lay in the source file) is left out when None."""
+    shape = [int(n) for n in shape]
+    bs, ts = GGML_QUANT_SIZES[ggml_type]
+    if bs > 1:
+        np_dtype, np_shape = "uint8", [*shape[:-1], shape[-1] // bs * ts]
+    else:
+        np_dtype, np_shape = PLAIN_TYPES[ggml_type][1], list(shape)
+    off = lambda key: {} if data_offset is None else {key: data_offset}  # noqa: E731
+    common = {"type": ggml_type, "quantization": quantization, "bitwidth": bitwidth, "exact_bitwidth": exact_bitwidth,
+              "shape": list(reversed(shape)), "n_elements": int(np.prod(shape))}  # "shape": ggml ne order
+    sidecar = {"name": name, **common, "n_bytes": nbytes, **off("data_offset_original"), "data_filename": f"{stem}.pth",
+               "np_dtype": np_dtype, "np_shape": np_shape}
+    level = {"filename": f"{stem}.pth", "metadata_filename": f"{stem}-metadata.json", **common, "size_bytes": nbytes,
+             **off("data_offset")}
+    record = {"tensor_type": ggml_type, "quantization": quantization, "bitwidth": bitwidth, "exact_bitwidth": exact_bitwidth,
+              "shape": list(reversed(shape)), "n_elements": int(np.prod(shape)), "n_bytes": nbytes, **off("data_offset")}
+    return sidecar, level, record
+
+
+def write_sidecar(path, sidecar: dict) -> None:
+    with open(path, "w") as f:
+        f.write(json.dumps({"tensor_info": sidecar}, indent=2))
+
+
+def write_manifests(db, manifest: dict, database: dict) -> None:
+    with open(os.path.join(str(db), "manifest.json"), "w") as f:
+        f.write(json.dumps(manifest, indent=2))
+    with open(os.path.join(str(db), "gguf_layer_database.json"), "w") as f:
+        f.write(json.dumps(database, indent=2))
+
+
+# ------------------------------------------------------------------------------------------------ writer
+class LevelDbWriter:
+    """Writes what `GGUFSplitter(..., use_exact_bitwidth=True).split_gguf_model()` writes, level by level and without a
+    .gguf (the differences: module docstring).  register() books one level and returns where its bytes go -- the driver's
+    writer process fills the file --, add_level() also writes them; set_metadata / set_order may come at any time before
+    close(), which checks every file against its sidecar, writes manifest.json and gguf_layer_database.json in set_order's
+    order and renames <db>.partial to <db>.  abort() (and leaving a `with` block by an exception) removes the partial
+    directory: a failed run leaves nothing that looks like a database.  Thread-safe."""
+
+    def __init__(self, db):
+        self.db = os.path.abspath(str(db))
+        self.tmp = self.db + ".partial"
+        if os.path.lexists(self.db):
+            raise FileExistsError(f"{self.db} exists: a level database is written whole (remove it, or name another directory)")
+        if os.path.isdir(self.tmp):
+            shutil.rmtree(self.tmp)  # what a failed run left
+        os.makedirs(self.tmp)
+        self._layers: Dict[str, dict] = {}    # tensor -> manifest layer record, in arrival order
+        self._records: Dict[str, dict] = {}   # tensor -> database record of its last level
+        self._files: List[str] = []
+        self._order: List[str] = []
+        self._metadata: Dict[str, dict] = {}
+        self._lock = threading.Lock()
+        self._closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, *_):
+        if exc_type is not None:
+            self.abort()
+        elif not self._closed:
+            self.close()
+        return False
+
+    def set_metadata(self, kv) -> None:
+        """The key/value data: {key: (value, [value type ids])} as gguf_writer.parse_gguf / kv_records give it."""
+        self._metadata = {key: {"types": list(types), "value": value} for key, (value, types) in kv.items()}
+
+    def set_order(self, names: Iterable[str]) -> None:
+        """Tensor names in the file's order; tensors it does not name follow in arrival order."""
+        self._order = list(names)
+
+    def register(self, name: str, shape: Sequence[int], ggml_type: int) -> str:
+        """Book one level of GGUF tensor `name` (logical `shape`, outermost first) and write its sidecar -> the path its raw
+        bytes belong at (under <db>.partial).  A tensor's levels are registered in the order of --levels: the last one is its
+        gguf_layer_database.json record."""
+        if self._closed:
+            raise RuntimeError("LevelDbWriter is closed")
+        ggml_type = int(ggml_type)
+        if ggml_type not in TYPE_NAMES or ggml_type not in GGML_QUANT_SIZES:
+            raise ValueError(f"tensor {name!r}: ggml type {ggml_type} cannot be a level")
+        shape = [int(n) for n in shape]
+        bs, ts = GGML_QUANT_SIZES[ggml_type]
+        if not shape or shape[-1] % bs:
+            raise ValueError(f"tensor {name!r}: rows of {shape[-1] if shape else 0} values are no multiple of the block of {bs}")
+        q = TYPE_NAMES[ggml_type]
+        bitwidth = EXACT_BITS[q]
+        stem = level_stem(bitwidth, q)
+        nbytes = int(np.prod(shape, dtype=np.int64)) // bs * ts
+        sidecar, level, record = level_records(name, shape, ggml_type, q, bitwidth, bitwidth, nbytes, stem)
+        d = os.path.join(self.tmp, name)
+        with self._lock:
+            os.makedirs(d, exist_ok=True)
+            layer = self._layers.setdefault(name, {"original_name": name, "dims": list(reversed(shape)), "bitwidths": {}})
+            if str(bitwidth) in layer["bitwidths"]:
+                raise ValueError(f"tensor {name!r}: level {stem} registered twice")
+            layer["bitwidths"][str(bitwidth)] = level
+            self._records[name] = record
+            path = os.path.join(d, f"{stem}.pth")
+            self._files.append(path)
+        write_sidecar(os.path.join(d, f"{stem}-metadata.json"), sidecar)
+        return path
+
+    def add_level(self, name: str, shape: Sequence[int], ggml_type: int, data) -> str:
+        """register() and write the bytes: `data` is bytes-like or a C-contiguous numpy array of the level's byte count."""
+        path = self.register(name, shape, ggml_type)
+        buf = memoryview(np.ascontiguousarray(data)).cast("B") if isinstance(data, np.ndarray) else memoryview(data)
+        with open(path, "wb") as f:
+            f.write(buf)
+        return path
+
+    def abort(self) -> None:
+        self._closed = True
+        shutil.rmtree(self.tmp, ignore_errors=True)
+
+    def close(self) -> str:
+        """Check, write the two manifests, rename -> <db>.  Any failure aborts: no <db> appears."""
+        if self._closed:
+            raise RuntimeError("LevelDbWriter is closed")
+        try:
+            for path in self._files:  # every booked file is there and as long as its sidecar says
+                if not os.path.isfile(path):
+                    raise FileNotFoundError(f"{path}: registered, never written")
+                check_level_size(read_sidecar(path))
+            rank = {n: i for i, n in enumerate(self._order)}
+            names = sorted(self._layers, key=lambda n: rank.get(n, len(rank)))  # stable: the rest keeps arrival order
+            manifest = {"model_info": {"total_tensors": len(names), "split_timestamp": time.time(), "use_exact_bitwidth": True,
+                                       "processed_tensors": len(names)},
+                        "metadata": self._metadata, "layers": {n: self._layers[n] for n in names}}
+            write_manifests(self.tmp, manifest, {n: self._records[n] for n in names})
+            os.rename(self.tmp, self.db)
+        except BaseException:
+            self.abort()
+            raise
+        self._closed = True
+        return self.db

@@ -327,12 +327,13 @@ def band_layout(bands: Sequence[Tuple[int, int]], C: int):
 
 
 def gptq_quantize_bands(W: torch.Tensor, U: torch.Tensor, bands: Sequence[Tuple[int, int]], block_size=128, rmin=-1.0,
-                        rdelta=0.1, nstep=20, ws: Optional[torch.Tensor] = None, **mq):
+                        rdelta=0.1, nstep=20, ws: Optional[torch.Tensor] = None, return_stacked: bool = False, **mq):
     """The column walk of gptq_quantize over row bands of DIFFERENT K-quant types that share U (gq_gptq_quantize_bands):
     W (fp32, contiguous) holds several working copies one under the other, band k = rows [row_end[k-1], row_end[k]) is
     quantized to q_type[k]; `bands` = [(row_end, q_type)], row ends ascending multiples of 64, the last one == R.  One
     walk over the columns for all bands; every band's rows equal gptq_quantize on those rows alone with that type, bit
-    for bit.  W is updated IN PLACE.  Returns one (qweight, d, s, dmin, m) per band: views into the stacked outputs."""
+    for bit.  W is updated IN PLACE.  Returns one (qweight, d, s, dmin, m) per band: views into the stacked outputs; with
+    `return_stacked` also the stacked outputs themselves, (views, (qweight, d, s, dmin, m)), as pack_bands takes them."""
     _need_cuda(W, U)
     assert W.dtype == torch.float32 and U.dtype == torch.float32 and W.is_contiguous() and U.is_contiguous()
     R, C = W.shape
@@ -357,7 +358,98 @@ def gptq_quantize_bands(W: torch.Tensor, U: torch.Tensor, bands: Sequence[Tuple[
         nb = (r1 - r0) * (C // g)
         out.append((q[r0:r1].view(it), d[r0:r1], s[off:off + nb].view(r1 - r0, C // g).view(it), dmin[r0:r1],
                     m[off:off + nb].view(r1 - r0, C // g).view(it)))
-    return out
+    return (out, (q, d, s, dmin, m)) if return_stacked else out
+
+
+# ---- the bands of a walk as GGUF block bytes (gq_pack_bands) ----
+_K_TYPE_SIZE = {10: 84, 11: 110, 12: 144, 13: 176, 14: 210}  # bytes of a 256-value block of Q2_K .. Q6_K
+
+
+def pack_bands_plan(bands: Sequence[Tuple[int, int]], C: int):
+    """Pure: what a gq_pack_bands call over `bands` (the table of band_layout) writes.  -> [(row0, row1, q_type, row_bytes,
+    nbytes, off)] per band and the total: band k packs to [rows_k, row_bytes] = nbytes bytes, and `off` is where it lies when
+    all bands share one buffer (the prefix sum: every nbytes is a multiple of 64 * type_size, so every band starts 16-byte
+    aligned).  Raises ValueError for what the library would refuse."""
+    C = int(C)
+    if C <= 0 or C % 256:
+        raise ValueError(f"C={C} (a positive multiple of 256)")
+    lay, _ = band_layout(bands, C)
+    out, off = [], 0
+    for r0, r1, t, _, _ in lay:
+        row_bytes = C // 256 * _K_TYPE_SIZE[t]
+        out.append((r0, r1, t, row_bytes, (r1 - r0) * row_bytes, off))
+        off += (r1 - r0) * row_bytes
+    return out, off
+
+
+def _stacked_of(results, lay, C):
+    """The stacked (q, d, s, dmin, m) buffers behind per-band views (what gptq_quantize_bands returns), as raw pointers."""
+    es = {0: 1, 1: 2, 2: 1, 3: 2, 4: 1}
+    base = [results[0][i].data_ptr() for i in range(5)]
+    for (r0, r1, t, g, off), res in zip(lay, results):
+        want = (r0 * C, r0 * (C // 256) * 2, off, r0 * (C // 256) * 2, off)
+        for i in range(5):
+            if not res[i].is_contiguous() or res[i].data_ptr() != base[i] + want[i] or \
+                    res[i].numel() * es[i] != (r1 - r0) * (C, C // 256 * 2, C // g, C // 256 * 2, C // g)[i]:
+                raise _cabi.GQError("pack_bands: the per-band results are not views into one set of stacked buffers in "
+                                    "band order (pass gptq_quantize_bands' results, or the stacked tensors themselves)")
+    return base
+
+
+def pack_bands(results, bands: Sequence[Tuple[int, int]], outs: Optional[Sequence[torch.Tensor]] = None,
+               row_srcs: Optional[Sequence[Optional[torch.Tensor]]] = None):
+    """The outputs of ONE gptq_quantize_bands call as GGUF block bytes, every band into a buffer of its own, in one launch
+    (gq_pack_bands).  `results`: that call's per-band views, or its stacked (qweight [R, C], d, s, dmin, m) tensors
+    (return_stacked); `bands`: its table.  outs[k]: contiguous uint8 of pack_bands_plan's nbytes, 16-byte aligned (None:
+    allocated here, one buffer cut by the plan's offsets).  row_srcs[k]: None or int32 [rows_k] on the device, output row r
+    of band k is packed from band row row_srcs[k][r]; indices are trusted.  Band k's bytes equal
+    pack(q_type_k, *[t[row_srcs[k]] for t in band k]) bit for bit.  -> the outs as [rows_k, row_bytes] views.  Inputs are
+    not modified; no host read."""
+    n = len(bands)
+    stacked = len(results) == 5 and all(torch.is_tensor(t) for t in results)
+    q0 = results[0] if stacked else results[0][0]
+    _need_cuda(q0)
+    dev = q0.device
+    C = int(q0.shape[1])
+    plan, total = pack_bands_plan(bands, C)
+    lay, _ = band_layout(bands, C)
+    R = plan[-1][1]
+    if stacked:
+        q, d, s, dmin, m = results
+        _need_cuda(q, d, s, dmin, m)
+        if not all(t.is_contiguous() for t in results) or tuple(q.shape) != (R, C) or d.numel() != R * (C // 256) \
+                or dmin.numel() != d.numel() or s.numel() < lay[-1][4] + (R - lay[-1][0]) * (C // lay[-1][3]) or m.numel() < s.numel():
+            raise _cabi.GQError(f"pack_bands: stacked inputs do not fit the table (R={R}, C={C})")
+        base = [t.data_ptr() for t in results]
+    else:
+        if len(results) != n:
+            raise _cabi.GQError(f"pack_bands: {len(results)} results for {n} bands")
+        _need_cuda(*[t for res in results for t in res])
+        base = _stacked_of(results, lay, C)
+    if outs is None:
+        buf = torch.empty(total, dtype=torch.uint8, device=dev)
+        outs = [buf[off:off + nb] for _, _, _, _, nb, off in plan]
+    if len(outs) != n or (row_srcs is not None and len(row_srcs) != n):
+        raise _cabi.GQError(f"pack_bands: outs / row_srcs must have one entry per band ({n})")
+    vp = ctypes.c_void_p
+    op, rp = (vp * n)(), (vp * n)()
+    for k, (r0, r1, t, row_bytes, nb, _) in enumerate(plan):
+        o = outs[k]
+        _need_cuda(o)
+        if o.dtype != torch.uint8 or not o.is_contiguous() or o.numel() != nb or o.device != dev:
+            raise _cabi.GQError(f"pack_bands: outs[{k}] must be a contiguous uint8 tensor of {nb} bytes on {dev}; got {o.dtype} "
+                                f"{tuple(o.shape)}")
+        op[k] = o.data_ptr()
+        rs = row_srcs[k] if row_srcs is not None else None
+        if rs is not None:
+            _need_cuda(rs)
+            if rs.dtype != torch.int32 or rs.numel() != r1 - r0 or not rs.is_contiguous() or rs.device != dev:
+                raise _cabi.GQError(f"pack_bands: row_srcs[{k}] must be a contiguous int32 [{r1 - r0}] tensor on {dev}")
+            rp[k] = rs.data_ptr()
+    tbl = (_cabi.Band * n)(*[_cabi.Band(int(e), int(t)) for e, t in bands])
+    check(lib().gq_pack_bands(vp(base[0]), vp(base[1]), vp(base[2]), vp(base[3]), vp(base[4]), R, C, tbl, n, op, rp,
+                              _stream(q0)), "gq_pack_bands")
+    return [o.view(r1 - r0, row_bytes) for o, (r0, r1, _, row_bytes, _, _) in zip(outs, plan)]
 
 
 def uses_helper_stream(R: int, C: int, block_size) -> bool:

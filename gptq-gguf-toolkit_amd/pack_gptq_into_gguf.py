@@ -340,6 +340,73 @@ def rope_freqs_llama3(hp: dict):
     return torch.tensor(out, dtype=torch.float32)
 
 
+def plain_tensor(new_name: str, data: torch.Tensor, outtype: str):
+    """The type rule for a tensor GPTQ did not quantize -> (array, raw_dtype or None) as GGUFWriter.add_tensor takes them:
+    n_dims <= 1, norms and the MoE router stay F32 (reference :355-376); the rest takes --outtype (:395-410)."""
+    if data.dtype not in (torch.float16, torch.float32):
+        data = data.to(torch.float32)
+    if data.dim() <= 1 or new_name.endswith("_norm.weight") or new_name.endswith("ffn_gate_inp.weight") \
+            or not new_name.endswith(".weight") or outtype == "f32":
+        return data.to(torch.float32).numpy(), None
+    if outtype == "f16":
+        return data.to(torch.float16).numpy(), None
+    if outtype == "q8_0":
+        try:
+            return quantize_q8_0(data.numpy()), GGMLType.Q8_0
+        except QuantError as e:  # :419-424: a row length that is no multiple of 32 falls back to F16
+            print(f"{e}, falling back to F16", file=sys.stderr)
+            return data.to(torch.float16).numpy(), None
+    bf = data.to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+    return bf.view(np.uint8).reshape(*bf.shape[:-1], -1), FTYPE[outtype][1]
+
+
+def rope_setup(hp: dict):
+    """-> (rope_scaling dict, rope type in lower case); NotImplementedError for what the reference's LlamaModel does not write."""
+    rope_scaling = hp.get("rope_scaling") or {}
+    rope_type = str(rope_scaling.get("rope_type", rope_scaling.get("type", ""))).lower()
+    if rope_type not in ("", "default", "linear", "llama3"):
+        raise NotImplementedError(f"rope_scaling type {rope_type!r}: the reference's LlamaModel writes linear scaling "
+                                  "keys and llama3 rope_freqs only (:2172-2175, :2259-2287); nothing else is reproduced")
+    return rope_scaling, rope_type
+
+
+def add_model_metadata(w, hp: dict, dir_model: Path, file_type: int, total_params: int, expert_params: int = 0,
+                       vocab: bool = True) -> None:
+    """The key/value data of a converted model, into any object with GGUFWriter's add_* interface (the converter's writer,
+    or one that only collects them: the level build's database has no file).  The reference's order: prepare_metadata
+    (:412-441) -> set_gguf_parameters (:594-638, :2160-2175) -> quantization version -> set_vocab (:590-592)."""
+    n_head = hp["num_attention_heads"]
+    n_experts = hp.get("num_local_experts")
+    rope_scaling, rope_type = rope_setup(hp)
+    w.add_string("general.type", "model")
+    w.add_string("general.name", hp.get("_name_or_path") or dir_model.name)
+    if total_params > 0:
+        w.add_string("general.size_label", size_label(total_params, expert_params, n_experts or 0))
+    w.add_uint32("llama.block_count", hp["num_hidden_layers"])
+    for key, gg, kind in (("max_position_embeddings", "llama.context_length", "u"), ("hidden_size", "llama.embedding_length", "u"),
+                          ("intermediate_size", "llama.feed_forward_length", "u"), ("num_attention_heads", "llama.attention.head_count", "u"),
+                          ("num_key_value_heads", "llama.attention.head_count_kv", "u"), ("rope_theta", "llama.rope.freq_base", "f"),
+                          ("rms_norm_eps", "llama.attention.layer_norm_rms_epsilon", "f"),
+                          ("num_local_experts", "llama.expert_count", "u"), ("num_experts_per_tok", "llama.expert_used_count", "u")):
+        if hp.get(key) is not None:
+            (w.add_uint32 if kind == "u" else w.add_float32)(gg, hp[key])
+    if hp.get("head_dim") is not None:
+        w.add_uint32("llama.attention.key_length", hp["head_dim"])
+        w.add_uint32("llama.attention.value_length", hp["head_dim"])
+    w.add_uint32("general.file_type", file_type)
+    w.add_uint32("llama.vocab_size", hp["vocab_size"])
+    w.add_uint32("llama.rope.dimension_count", hp.get("head_dim") or hp["hidden_size"] // n_head)
+    if rope_type == "linear" and "factor" in rope_scaling:
+        w.add_string("llama.rope.scaling.type", "linear")
+        w.add_float32("llama.rope.scaling.factor", rope_scaling["factor"])
+    w.add_uint32("general.quantization_version", 2)
+    if vocab:
+        add_tokenizer(w, dir_model, hp["vocab_size"])
+
+
+SKIPPED_HF_TENSORS = (".attention.masked_bias", ".attention.bias", ".rotary_emb.inv_freq")  # never written (reference :296-298)
+
+
 def convert(dir_model: Path, dir_model_quant: Path, outfile: Path, outtype: str = "f16", verbose: bool = False,
             vocab: bool = True, pipelined: bool = True, timing: Optional[dict] = None):
     """pipelined (default): a quantized Linear's five tensors are mapped from data.pth (torch.load(mmap=True): no read), and its
@@ -373,12 +440,8 @@ def convert(dir_model: Path, dir_model_quant: Path, outfile: Path, outtype: str 
         outtype = "f16" if first.dtype == torch.float16 else "bf16"
         if verbose:
             print(f"choosing --outtype {outtype} from first tensor type ({first.dtype})")
-    file_type, out_ggml = FTYPE[outtype]
-    rope_scaling = hp.get("rope_scaling") or {}
-    rope_type = str(rope_scaling.get("rope_type", rope_scaling.get("type", ""))).lower()
-    if rope_type not in ("", "default", "linear", "llama3"):
-        raise NotImplementedError(f"rope_scaling type {rope_type!r}: the reference's LlamaModel writes linear scaling "
-                                  "keys and llama3 rope_freqs only (:2172-2175, :2259-2287); nothing else is reproduced")
+    file_type, _ = FTYPE[outtype]
+    _, rope_type = rope_setup(hp)
 
     # ---- tensors first (the reference prepares them before the metadata: write() :444-447), extra tensors lead
     w = GGUFWriter(str(outfile), "llama")
@@ -389,29 +452,13 @@ def convert(dir_model: Path, dir_model_quant: Path, outfile: Path, outtype: str 
     experts = {}  # (bid, wid) -> {expert id: (payload or tensor, q_type or None)}
 
     def add_plain(new_name, data):
-        if data.dtype not in (torch.float16, torch.float32):
-            data = data.to(torch.float32)
-        # n_dims <= 1, norms and the MoE router stay F32 (:355-376); the rest takes --outtype (:395-410)
-        if data.dim() <= 1 or new_name.endswith("_norm.weight") or new_name.endswith("ffn_gate_inp.weight") \
-                or not new_name.endswith(".weight") or outtype == "f32":
-            w.add_tensor(new_name, data.to(torch.float32).numpy())
-        elif outtype == "f16":
-            w.add_tensor(new_name, data.to(torch.float16).numpy())
-        elif outtype == "q8_0":
-            try:
-                w.add_tensor(new_name, quantize_q8_0(data.numpy()), raw_dtype=GGMLType.Q8_0)
-            except QuantError as e:  # :419-424: a row length that is no multiple of 32 falls back to F16
-                print(f"{e}, falling back to F16", file=sys.stderr)
-                w.add_tensor(new_name, data.to(torch.float16).numpy())
-        else:
-            bf = data.to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
-            w.add_tensor(new_name, bf.view(np.uint8).reshape(*bf.shape[:-1], -1), raw_dtype=out_ggml)
+        w.add_tensor(new_name, *plain_tensor(new_name, data, outtype))
 
     if rope_type == "llama3":
         w.add_tensor("rope_freqs.weight", rope_freqs_llama3(hp).numpy())
     FIVE = ("qweight", "super_group_scale", "group_scale_quant", "super_group_zero", "group_zero_quant")
     for name, shape, get in iter_hf_entries(dir_model):
-        if name.endswith((".attention.masked_bias", ".attention.bias", ".rotary_emb.inv_freq")):
+        if name.endswith(SKIPPED_HF_TENSORS):
             continue
         names_seen.add(name)
         numel = int(np.prod(shape)) if len(shape) else 1
@@ -508,32 +555,7 @@ def convert(dir_model: Path, dir_model_quant: Path, outfile: Path, outtype: str 
     if "lm_head.weight" not in names_seen and not tied:
         print("warning: no lm_head.weight in the checkpoint and tie_word_embeddings is false", file=sys.stderr)
 
-    # ---- metadata in the reference's order: prepare_metadata (:412-441) -> set_gguf_parameters (:594-638,
-    # :2160-2175) -> quantization version -> set_vocab (:590-592)
-    w.add_string("general.type", "model")
-    w.add_string("general.name", hp.get("_name_or_path") or dir_model.name)
-    if total_params > 0:
-        w.add_string("general.size_label", size_label(total_params, expert_params, n_experts or 0))
-    w.add_uint32("llama.block_count", hp["num_hidden_layers"])
-    for key, gg, kind in (("max_position_embeddings", "llama.context_length", "u"), ("hidden_size", "llama.embedding_length", "u"),
-                          ("intermediate_size", "llama.feed_forward_length", "u"), ("num_attention_heads", "llama.attention.head_count", "u"),
-                          ("num_key_value_heads", "llama.attention.head_count_kv", "u"), ("rope_theta", "llama.rope.freq_base", "f"),
-                          ("rms_norm_eps", "llama.attention.layer_norm_rms_epsilon", "f"),
-                          ("num_local_experts", "llama.expert_count", "u"), ("num_experts_per_tok", "llama.expert_used_count", "u")):
-        if hp.get(key) is not None:
-            (w.add_uint32 if kind == "u" else w.add_float32)(gg, hp[key])
-    if hp.get("head_dim") is not None:
-        w.add_uint32("llama.attention.key_length", hp["head_dim"])
-        w.add_uint32("llama.attention.value_length", hp["head_dim"])
-    w.add_uint32("general.file_type", file_type)
-    w.add_uint32("llama.vocab_size", hp["vocab_size"])
-    w.add_uint32("llama.rope.dimension_count", hp.get("head_dim") or hp["hidden_size"] // n_head)
-    if rope_type == "linear" and "factor" in rope_scaling:
-        w.add_string("llama.rope.scaling.type", "linear")
-        w.add_float32("llama.rope.scaling.factor", rope_scaling["factor"])
-    w.add_uint32("general.quantization_version", 2)
-    if vocab:
-        add_tokenizer(w, dir_model, hp["vocab_size"])
+    add_model_metadata(w, hp, dir_model, file_type, total_params, expert_params, vocab)
     t0 = time.perf_counter()
     w.write(tm)
     clock("write_call", t0)

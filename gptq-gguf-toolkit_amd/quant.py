@@ -93,6 +93,14 @@ def parse_args(argv=None):
     p.add_argument("--propagate_level", type=str, default=None, choices=Q_NAMES + ["none"],
                    help="with --levels: the level whose quantized weights the later blocks are calibrated on (that level's "
                         "tree equals its ordinary run), or none: every block sees full-precision activations")
+    p.add_argument("--level_db", type=str, default=None, metavar="DIR",
+                   help="with --levels: also write the level database -- what pack_gptq_into_gguf.py + gguf_splitter.py "
+                        "--gguf-layers --exact leave of the per-level trees: <DIR>/<gguf tensor>/<bits>-<TYPE>.pth with sidecars, "
+                        "manifest.json and gguf_layer_database.json -- straight from the walk, packed on the GPU.  The packed "
+                        "(GGUF) side only: the dense --hf-layers side is NOT written (the search, the estimator and the "
+                        "stitcher read the packed side).  --model_name_or_path must be a local directory; DIR must not exist")
+    p.add_argument("--level_db_only", action="store_true",
+                   help="with --level_db: do not write the <save_dir>/<LEVEL> trees")
     args = p.parse_args(argv)
     problem = levels_problem(args)
     if problem:
@@ -102,7 +110,12 @@ def parse_args(argv=None):
 
 def levels_problem(args, world_size=None):
     """Why this combination of flags cannot run as a level build (None: it can, or --levels is not given)."""
+    level_db = getattr(args, "level_db", None)
+    if getattr(args, "level_db_only", False) and level_db is None:
+        return "--level_db_only needs --level_db"
     if args.levels is None:
+        if level_db is not None:
+            return "--level_db needs --levels: the level database is written by the one-pass level build"
         return "--propagate_level needs --levels" if args.propagate_level is not None else None
     if args.propagate_level is None:
         return "--levels needs --propagate_level (one of the levels, or none): which level the later blocks are calibrated on"
@@ -114,6 +127,12 @@ def levels_problem(args, world_size=None):
         return "--levels builds every module at every level: --bit_width_configuration does not apply"
     if args.act_order or args.static_groups:
         return "--levels does not support --act_order / --static_groups"
+    if level_db is not None:
+        if not os.path.isdir(args.model_name_or_path):
+            return (f"--level_db needs --model_name_or_path to be a local directory (got {args.model_name_or_path!r}): the "
+                    "database's key/value data and plain tensors are read from its config.json, tokenizer and *.safetensors")
+        if os.path.lexists(level_db):
+            return f"--level_db {level_db} exists: a level database is written whole (remove it, or name another directory)"
     if world_size is None:
         world_size = int(os.environ.get("WORLD_SIZE", "1"))
     if world_size > 1:
@@ -213,7 +232,8 @@ def _run(args):
     t1 = time.perf_counter()
     if args.levels is not None:
         quantizer.quantize_levels([GGMLQuantizationType[n] for n in args.levels],
-                                  None if args.propagate_level == "none" else GGMLQuantizationType[args.propagate_level])
+                                  None if args.propagate_level == "none" else GGMLQuantizationType[args.propagate_level],
+                                  level_db=args.level_db, trees=not args.level_db_only, level_db_model=args.model_name_or_path)
     else:
         quantizer.quantize(quant_config)
     torch.cuda.synchronize()

@@ -25,6 +25,7 @@ import threading
 import time
 from typing import Any, Dict, Iterable, List, Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -90,7 +91,13 @@ def _own_storage(t):
     return t if t.untyped_storage().nbytes() == t.numel() * t.element_size() else t.clone()
 
 
-def _write_data_pth(save_dir, name, q_type, qweight, d, s, dmin, m):
+RAW_BYTES = -1  # the q_type of a saver item that is ONE uint8 tensor, written as it is to the absolute path `name`
+
+
+def _write_data_pth(save_dir, name, q_type, qweight, d=None, s=None, dmin=None, m=None):
+    if q_type == RAW_BYTES:  # a level of the level database: raw GGUF block bytes, no pickle (level_db.LevelDbWriter.register)
+        qweight.contiguous().numpy().tofile(name)
+        return
     os.makedirs(os.path.join(save_dir, name), exist_ok=True)
     qweight, d, s, dmin, m = (_own_storage(t) for t in (qweight, d, s, dmin, m))
     torch.save({"q_type": int(q_type), "qweight": qweight, "super_group_scale": d, "super_group_zero": dmin,
@@ -567,6 +574,110 @@ def check_levels(levels, propagate):
     return levels, propagate
 
 
+class _LevelDbSink:
+    """The level-database side of a level build (quant.py --level_db): packs every walk's bands into GGUF block bytes with
+    ONE gq_pack_bands launch on the walk's stream -- q / k rows gathered into GGUF's rotary order on the way -- and books the
+    files with level_db.LevelDbWriter; the bytes travel through the _Saver like a tree's tensors (RAW_BYTES items).  The
+    key/value data and the tensors GPTQ does not quantize come from the model directory, by the converter's own rules
+    (pack_gptq_into_gguf.add_model_metadata / plain_tensor with --outtype f16): the database is what converting every
+    level's tree and splitting the files with --exact leaves.  Dense Llama family only; the HF side is not written."""
+
+    def __init__(self, db: str, dir_model: str, vocab: bool = True):
+        import json
+        from pathlib import Path
+        from . import level_db
+        from .pack_gptq_into_gguf import SKIPPED_HF_TENSORS, iter_hf_entries, map_tensor_name, rope_setup
+        if not dir_model or not os.path.isdir(dir_model) or not os.path.isfile(os.path.join(dir_model, "config.json")):
+            raise ValueError(f"level_db needs the model as a local directory with config.json and *.safetensors (got "
+                             f"{dir_model!r}): the key/value data and the plain tensors are read from it")
+        self.dir_model, self.vocab = Path(dir_model), vocab
+        self.hp = json.load(open(self.dir_model / "config.json"))
+        arch = self.hp.get("architectures", ["LlamaForCausalLM"])[0]
+        if arch not in ("LlamaForCausalLM", "LLaMAForCausalLM", "MistralForCausalLM") or self.hp.get("num_local_experts"):
+            raise NotImplementedError(f"level_db: {arch} (dense Llama family only; expert stacking in the database is not built)")
+        self.n_head = self.hp["num_attention_heads"]
+        self.n_kv = self.hp.get("num_key_value_heads", self.n_head)
+        _, self.rope_type = rope_setup(self.hp)
+        self.tensor_of: Dict[str, str] = {}  # HF module name -> GGUF tensor name, for what the checkpoint holds
+        order = ["rope_freqs.weight"] if self.rope_type == "llama3" else []
+        self.total_params = 0
+        for name, shape, _ in iter_hf_entries(self.dir_model):
+            if name.endswith(SKIPPED_HF_TENSORS):
+                continue
+            self.total_params += int(np.prod(shape)) if len(shape) else 1
+            self.tensor_of[name.removesuffix(".weight")] = map_tensor_name(name)
+            order.append(map_tensor_name(name))
+        self.writer = level_db.LevelDbWriter(db)
+        self.writer.set_order(order)
+        self.packed = set()   # HF module names whose levels are in the database
+        self.items: List[tuple] = []  # saver items of the walks packed since the last take()
+
+    def _row_src(self, tensor: str, rows: int, device):
+        from .gguf_loader import rotary_row_dst
+        return rotary_row_dst(tensor, rows, self.n_head, self.n_kv, device)
+
+    def pack_walk(self, stacked, bands, members):
+        """One walk -> one launch (BlockSchedule.quantize_levels' `pack`; also the one-band calls of embed / lm_head and of
+        the level-after-level walks).  members[k]: (HF module name, q_type) of band k, or None (stale: packed, not kept).
+        Rows that are no multiple of 64 cannot lie in a band table: such a one-band walk takes gq_pack, its rows gathered
+        first."""
+        q = stacked[0]
+        dev, C = q.device, q.shape[1]
+        tensors = [None if mem is None else self.tensor_of.get(mem[0]) for mem in members]
+        if all(t is None for t in tensors):
+            return []
+        r0, srcs = 0, []
+        for (r1, _), t in zip(bands, tensors):
+            srcs.append(self._row_src(t, r1 - r0, dev) if t is not None else None)
+            r0 = r1
+        if len(bands) == 1 and bands[0][0] % 64:
+            five = stacked if srcs[0] is None else [x.index_select(0, srcs[0].long()) for x in stacked]
+            outs = [_ops.pack(bands[0][1], *five)]
+        else:
+            outs = _ops.pack_bands(stacked, bands, None, srcs)
+        r0 = 0
+        for (r1, t), mem, tensor, out in zip(bands, members, tensors, outs):
+            if tensor is not None:
+                path = self.writer.register(tensor, (r1 - r0, C), int(t))
+                self.items.append((path, RAW_BYTES, (out.view(-1),)))
+                self.packed.add(mem[0])
+            r0 = r1
+        return outs
+
+    def take(self) -> List[tuple]:
+        items, self.items = self.items, []
+        return items
+
+    def finish(self) -> str:
+        """Every level file is on disk (the saver is closed): the key/value data, the plain tensors, close()."""
+        from .gguf_writer import GGMLType, GGUFWriter, kv_records
+        from .pack_gptq_into_gguf import (FTYPE, SKIPPED_HF_TENSORS, add_model_metadata, iter_hf_entries, permute, plain_tensor,
+                                          rope_freqs_llama3)
+        w = self.writer
+        kv = GGUFWriter(None, "llama")  # collects the key/value data; never written
+        add_model_metadata(kv, self.hp, self.dir_model, FTYPE["f16"][0], self.total_params, 0, self.vocab)
+        w.set_metadata(kv_records(kv.kv))
+
+        def plain(tensor, data):
+            arr, raw = plain_tensor(tensor, data, "f16")
+            arr = np.ascontiguousarray(arr)
+            w.add_level(tensor, arr.shape, raw if raw is not None else (GGMLType.F32 if arr.dtype == np.float32 else GGMLType.F16), arr)
+
+        if self.rope_type == "llama3":
+            plain("rope_freqs.weight", rope_freqs_llama3(self.hp))
+        for name, _, get in iter_hf_entries(self.dir_model):
+            base = name.removesuffix(".weight")
+            if name.endswith(SKIPPED_HF_TENSORS) or base in self.packed:
+                continue
+            data = get()
+            if name.endswith("q_proj.weight"):
+                data = permute(data, self.n_head, self.n_head)
+            elif name.endswith("k_proj.weight"):
+                data = permute(data, self.n_head, self.n_kv)
+            plain(self.tensor_of[base], data)
+        return w.close()
+
+
 class Quantizer:
     def __init__(self, model: nn.Module, data_loader: Iterable, quantizable_modules: str,
                  quantizer_kwargs: Dict[str, Any], pre_block_modules: List[str], post_block_modules: List[str],
@@ -605,24 +716,45 @@ class Quantizer:
 
     # ------------------------------------------------------------------ walk
     @torch.no_grad()
-    def quantize_levels(self, levels, propagate) -> None:
+    def quantize_levels(self, levels, propagate, level_db: Optional[str] = None, trees: bool = True,
+                        level_db_model: Optional[str] = None, level_db_vocab: bool = True) -> None:
         """The level database in one pass: every quantizable module at every level of `levels`, one ordinary tree per level
         under <save_dir>/<LEVEL>/ (level_tree_name; same schema, same writer as quantize()).  The calibration forwards, the
         Hessians, the factorisations and the column walk are those of ONE run (BlockSchedule.quantize_levels).
         `propagate`: the level whose dequantized weights replace the model's -- every later block is calibrated on what an
         ordinary all-<propagate> run feeds it, so that level's tree and the model afterwards are that run's -- or None:
         the model stays untouched and every block is calibrated on full-precision activations.  With
-        quant_non_block_modules, embed / lm_head are RTN-quantized per level (what --default_bit_width LEVEL writes)."""
+        quant_non_block_modules, embed / lm_head are RTN-quantized per level (what --default_bit_width LEVEL writes).
+
+        `level_db`: also write the level database there (a directory that does not exist yet) -- what converting every
+        level's tree and splitting the files with --exact leaves, packed on the GPU with one gq_pack_bands launch per walk
+        (_LevelDbSink; level_db.py lists how it differs from a split).  `level_db_model`: the model's directory (default: the
+        model's own name_or_path, which must be a local directory), `level_db_vocab`: write the tokenizer keys, as
+        convert(vocab=...).  `trees=False` (with level_db): the per-level trees are not written.  Everything is refused
+        before any work; a failed run leaves no database."""
         levels, propagate = check_levels(levels, propagate)
         if dist_utils.get_world_size() > 1:
             raise NotImplementedError("quantize_levels runs on one rank (multi-rank level builds are not built)")
         if self.quantizer_kwargs.get("act_order") or self.quantizer_kwargs.get("static_groups"):
             raise ValueError("quantize_levels: act_order / static_groups have no level build")
-        self._levels, self._level_src = (levels, propagate), {}
+        if level_db is None and not trees:
+            raise ValueError("quantize_levels: trees=False needs level_db (nothing would be written)")
+        sink = None
+        if level_db is not None:
+            if os.environ.get("GQ_SAVE_SKIP") == "1":
+                raise ValueError("quantize_levels: GQ_SAVE_SKIP=1 writes no files, a level database cannot be completed")
+            sink = _LevelDbSink(level_db, level_db_model or getattr(self.model.config, "_name_or_path", None), level_db_vocab)
+        self._levels, self._level_src, self._level_sink, self._level_trees = (levels, propagate), {}, sink, bool(trees)
         try:
             self.quantize({})
+            if sink is not None:
+                sink.finish()
+        except BaseException:
+            if sink is not None:
+                sink.writer.abort()
+            raise
         finally:
-            self._levels, self._level_src = None, {}
+            self._levels, self._level_src, self._level_sink, self._level_trees = None, {}, None, True
 
     @torch.no_grad()
     def quantize(self, quant_config: Dict[str, GGMLQuantizationType]) -> None:
@@ -762,6 +894,9 @@ class Quantizer:
                 self._quant_and_save_non_block(name, module.to(device), quant_config)
         if self.quant_non_block_modules:  # wherever they ran, they ran: the packer would silently write a missing one as f16
             saved = {n.rsplit("/", 1)[-1] for n in self._saved_names}  # (a level build saves <LEVEL>/<module>)
+            sink = getattr(self, "_level_sink", None)
+            if sink is not None and not getattr(self, "_level_trees", True):  # no trees: what the database holds instead, and
+                saved |= sink.packed | {n for n, _ in pre_blocks + post_blocks if n not in sink.tensor_of}  # (a tied lm_head)
             missing = [n for n, _ in pre_blocks + post_blocks if n not in saved]
             assert not missing, f"non-block modules never quantized: {missing}"
         if use_cache is not None:
@@ -825,11 +960,14 @@ class Quantizer:
         batch = []
         if getattr(self, "_levels", None) is not None:
             levels, propagate = self._levels
-            for n, per_level in sched.quantize_levels(levels, propagate).items():
-                for t in levels:
+            sink = getattr(self, "_level_sink", None)
+            for n, per_level in sched.quantize_levels(levels, propagate, pack=sink.pack_walk if sink else None).items():
+                for t in levels if getattr(self, "_level_trees", True) else ():
                     item = self._save(level_tree_name(t, n), t, *per_level[t], defer=True)
                     if item is not None:
                         batch.append(item)
+            if sink is not None and os.environ.get("GQ_SAVE_SKIP") != "1":
+                batch.extend(sink.take())
             self._saver.put_many(batch)
             self.schedule_stats = sched.stats
             return
@@ -889,6 +1027,11 @@ class Quantizer:
             res = self._quant_non_block_module(w, t)
             if t == propagate:
                 back = dequantize_linear_weight(t, *res, out_dtype=module.weight.data.dtype)
-            self._save(level_tree_name(t, name), t, *res)
+            if getattr(self, "_level_trees", True):
+                self._save(level_tree_name(t, name), t, *res)
+            sink = getattr(self, "_level_sink", None)
+            if sink is not None:
+                sink.pack_walk(res, [(res[0].shape[0], int(t))], [(name, t)])
+                self._saver.put_many(sink.take())
         if back is not None:
             module.weight.data = back
