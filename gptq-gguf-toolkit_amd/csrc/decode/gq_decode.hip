@@ -17,6 +17,10 @@
 // operation rounded on its own (-ffp-contract=off), then one round-to-nearest-even cast: dequantize1 of gq_common.hpp on
 // the decoded fields.  Q3_K / Q6_K have no minimum: dm = 0 * 0 = +0 and x - (+0) == x for every x, -0 included.
 // Layouts: llama.cpp ggml-quants.c dequantize_row_q{2,3,4,5,6}_K and get_scale_min_k4.
+//
+// Q8_0 (include/gptq_gguf_q8.h; dequantize_row_q8_0) takes the same route through gq_dequantize_blocks: a turn is 128 blocks of
+// 32 values, staged by 2-byte loads into 48-byte LDS slots, half a block per thread, w = f32(d) * f32(q) and one cast
+// (blockdec::decode_turn_q8_0).  gq_unpack has no Q8_0 form: the five data.pth tensors are a K-quant notion.
 #include "../search/gq_block_decode.hpp"  // Lay, stage_blocks, codes16, group_scale, decode_turn: shared with search/gq_switch.hip
 
 namespace gq {
@@ -39,6 +43,20 @@ __global__ __launch_bounds__(256) void dequantize_blocks_kernel(const uint8_t* _
     for (int64_t b0 = (int64_t)blockIdx.x * DB; b0 < nblocks; b0 += (int64_t)gridDim.x * DB) {
         const int nb = (int)((nblocks - b0) < DB ? (nblocks - b0) : DB);
         decode_turn<QT, OutT>(blocks, row_src, b0, nb, nbr, out, sb, ssrc);
+        __syncthreads();
+    }
+}
+
+// Q8_0 (include/gptq_gguf_q8.h): the same loop over turns of 128 blocks of 32 values, w = f32(d) * f32(q) and one cast
+template <typename OutT>
+__global__ __launch_bounds__(256) void dequantize_q8_0_kernel(const uint8_t* __restrict__ blocks,
+                                                              const int32_t* __restrict__ row_src, int64_t nblocks,
+                                                              int64_t nbr, OutT* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) uint8_t sb[Q8_DB * Q8_SLOT];
+    __shared__ int64_t ssrc[Q8_DB];
+    for (int64_t b0 = (int64_t)blockIdx.x * Q8_DB; b0 < nblocks; b0 += (int64_t)gridDim.x * Q8_DB) {
+        const int nb = (int)((nblocks - b0) < Q8_DB ? (nblocks - b0) : Q8_DB);
+        decode_turn_q8_0<OutT>(blocks, row_src, b0, nb, nbr, out, sb, ssrc);
         __syncthreads();
     }
 }
@@ -89,8 +107,8 @@ __global__ __launch_bounds__(256) void unpack_kernel(const uint8_t* __restrict__
     }
 }
 
-unsigned turns_grid(int64_t nblocks) {
-    const int64_t g = (nblocks + DB - 1) / DB;
+unsigned turns_grid(int64_t nblocks, int per_turn = DB) {
+    const int64_t g = (nblocks + per_turn - 1) / per_turn;
     return (unsigned)(g < 16384 ? g : 16384);
 }
 
@@ -112,6 +130,24 @@ int launch_dequantize_blocks_t(const uint8_t* blocks, const int32_t* row_src, in
     default:
         hipLaunchKernelGGL((dequantize_blocks_kernel<QT, bf16_bits>), grid, block, 0, st, blocks, row_src, nblocks, nbr,
                            (bf16_bits*)out);
+        break;
+    }
+    GQ_LAUNCH_CHECK();
+    return GQ_OK;
+}
+
+int launch_dequantize_q8_0(const uint8_t* blocks, const int32_t* row_src, int64_t nblocks, int64_t nbr, void* out,
+                           int out_dtype, hipStream_t st) {
+    dim3 grid(turns_grid(nblocks, Q8_DB)), block(256);
+    switch (out_dtype) {
+    case GQ_F32:
+        hipLaunchKernelGGL((dequantize_q8_0_kernel<float>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (float*)out);
+        break;
+    case GQ_F16:
+        hipLaunchKernelGGL((dequantize_q8_0_kernel<half_bits>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (half_bits*)out);
+        break;
+    default:
+        hipLaunchKernelGGL((dequantize_q8_0_kernel<bf16_bits>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (bf16_bits*)out);
         break;
     }
     GQ_LAUNCH_CHECK();
@@ -159,16 +195,20 @@ int gq_dequantize_blocks(int q_type, const uint8_t* blocks, int64_t R, int64_t C
                          int out_dtype, void* stream) {
     if (int rc = options_ok()) return rc;
     TypeInfo ti;
-    if (!type_info(q_type, ti)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_dequantize_blocks: unknown q_type %d", q_type);
+    const int bs = q_type == GQ_Q8_0 ? 32 : 256;  // values per block
+    if (q_type != GQ_Q8_0 && !type_info(q_type, ti)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_dequantize_blocks: unknown q_type %d", q_type);
     if (out_dtype != GQ_F32 && out_dtype != GQ_F16 && out_dtype != GQ_BF16)
         GQ_FAIL(GQ_E_BAD_TYPE, "gq_dequantize_blocks: unknown out_dtype %d", out_dtype);
-    if (R <= 0 || C <= 0 || C % 256)
-        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_dequantize_blocks: R=%ld C=%ld (C %% 256 != 0)", (long)R, (long)C);
+    if (R <= 0 || C <= 0 || C % bs)
+        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_dequantize_blocks: R=%ld C=%ld (C %% %d != 0)", (long)R, (long)C, bs);
     if (!blocks || !out) GQ_FAIL(GQ_E_NULL, "gq_dequantize_blocks: null pointer");
     if (!aligned(out, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_dequantize_blocks: out must be 16-byte aligned");
-    const int64_t nbr = C / 256, nblocks = R * nbr;
+    const int64_t nbr = C / bs, nblocks = R * nbr;
     hipStream_t st = (hipStream_t)stream;
     switch (q_type) {
+    case GQ_Q8_0:
+        if (!aligned(blocks, 2)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_dequantize_blocks: blocks not 2-byte aligned");
+        return launch_dequantize_q8_0(blocks, row_src, nblocks, nbr, out, out_dtype, st);
     case GQ_Q2_K: return launch_dequantize_blocks_t<GQ_Q2_K>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
     case GQ_Q3_K: return launch_dequantize_blocks_t<GQ_Q3_K>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
     case GQ_Q4_K: return launch_dequantize_blocks_t<GQ_Q4_K>(blocks, row_src, nblocks, nbr, out, out_dtype, st);

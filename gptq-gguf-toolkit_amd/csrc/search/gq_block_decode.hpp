@@ -1,10 +1,11 @@
-// gq_block_decode.hpp -- the device side of the K-quant block decoder, shared by decode/gq_decode.hip (K15: one matrix per
-// launch) and search/gq_switch.hip (K18: a table of matrices per launch).  One text, so the two entry points cannot drift
-// apart: a turn of either kernel is decode_turn() below.  Layouts, staging widths and the numerical contract are
-// described at the top of decode/gq_decode.hip.
+// gq_block_decode.hpp -- the device side of the block decoder (K-quants and Q8_0), shared by decode/gq_decode.hip (K15: one
+// matrix per launch) and search/gq_switch.hip (K18: a table of matrices per launch).  One text, so the two entry points
+// cannot drift apart: a turn of either kernel is decode_turn() (K-quants) or decode_turn_q8_0() below.  Layouts, staging
+// widths and the numerical contract are described at the top of decode/gq_decode.hip.
 #pragma once
 
 #include "../gq_common.hpp"
+#include "../../../include/gptq_gguf_q8.h"
 
 namespace gq {
 namespace blockdec {
@@ -168,6 +169,56 @@ __device__ __forceinline__ void decode_turn(const uint8_t* __restrict__ blocks, 
             o[k] = cvt_out<OutT>(dequantize1(code, ds, dm));
         }
         uint4* op = reinterpret_cast<uint4*>(out + (b0 + b) * 256 + 16 * g16);
+#pragma unroll
+        for (int k = 0; k < (int)sizeof(OutT) * 16 / 16; ++k) op[k] = reinterpret_cast<const uint4*>(o)[k];
+    }
+}
+
+// ---- Q8_0: block_q8_0 { fp16 d; int8 qs[32]; }, 34 bytes per 32 values, 2-byte aligned.  A turn is Q8_DB = 128 consecutive
+// output blocks -- the 4096 values of a K-quant turn -- and a thread produces half a block.  Block b of the turn lies in
+// the LDS slot of Q8_SLOT = 48 bytes at sb + 48 b with d at byte 14 and the 32 codes at bytes 16 .. 47: staging unit u
+// (2 bytes, u = 0 .. 16) of a block goes to byte 14 + 2 u, so that each half of the codes is one aligned 16-byte LDS read.
+constexpr int Q8_DB = 128, Q8_TS = 34, Q8_SLOT = 48, Q8_UPB = Q8_TS / 2;
+constexpr int SB_BYTES = Q8_DB * Q8_SLOT > DB * TSP_MAX ? Q8_DB * Q8_SLOT : DB * TSP_MAX;  // LDS of a kernel that takes any turn
+constexpr int SSRC_N = Q8_DB > DB ? Q8_DB : DB;
+
+// One turn of a workgroup of 256 threads: output blocks b0 .. b0 + nb - 1 (nb <= Q8_DB) of a matrix with nbr = C / 32 blocks
+// per row, decoded to out + b0 * 32: w = f32(d) * f32(q), one cast.  Output block L comes from packed block
+// row_src[L / nbr] * nbr + L % nbr; a turn may straddle rows.  sb: Q8_DB * Q8_SLOT bytes, 16-byte aligned; ssrc: Q8_DB
+// entries.  The caller puts a barrier between two turns that use the same sb / ssrc.
+template <typename OutT>
+__device__ __forceinline__ void decode_turn_q8_0(const uint8_t* __restrict__ blocks, const int32_t* __restrict__ row_src,
+                                                 int64_t b0, int nb, int64_t nbr, OutT* __restrict__ out, uint8_t* sb,
+                                                 int64_t* ssrc) {
+    constexpr int NIT = (Q8_DB * Q8_UPB + 255) / 256;
+    const int tid = threadIdx.x;
+    if (tid < nb) {
+        const int64_t o = b0 + tid, r = o / nbr, j = o - r * nbr;
+        ssrc[tid] = (row_src ? (int64_t)row_src[r] : r) * nbr + j;
+    }
+    __syncthreads();
+    uint16_t v[NIT] = {};
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {  // 2-byte loads of exactly the blocks' bytes, all in flight before the first LDS write
+        const int u = tid + 256 * it, b = u / Q8_UPB, o = u - b * Q8_UPB;
+        if (u < nb * Q8_UPB) v[it] = ld2(blocks + ssrc[b] * Q8_TS + o * 2);
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int u = tid + 256 * it, b = u / Q8_UPB, o = u - b * Q8_UPB;
+        if (u < nb * Q8_UPB) *reinterpret_cast<uint16_t*>(sb + b * Q8_SLOT + 14 + o * 2) = v[it];
+    }
+    __syncthreads();
+    const int b = tid >> 1, h = tid & 1;
+    if (b < nb) {
+        const uint8_t* B = sb + b * Q8_SLOT;
+        const float d = h2f(ld2(B + 14));
+        uint32_t c[4];
+        ld16(B + 16 + 16 * h, c);
+        alignas(16) OutT o[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) o[k] = cvt_out<OutT>(d * (float)(int8_t)((c[k >> 2] >> (8 * (k & 3))) & 0xffu));
+        uint4* op = reinterpret_cast<uint4*>(out + (b0 + b) * 32 + 16 * h);
 #pragma unroll
         for (int k = 0; k < (int)sizeof(OutT) * 16 / 16; ++k) op[k] = reinterpret_cast<const uint4*>(o)[k];
     }

@@ -13,9 +13,11 @@
 //   dense : 512 chunks of 16 output bytes, two per thread, chunk k = (row k / cpr, 16 / elsize columns): one 8- / 16- /
 //           32-byte load of the (gathered) source row, exact widening to fp32, one RNE cast (f2h / f2bf: torch's
 //           .to(dtype)), one 16-byte store.
+//   Q8_0  : blockdec::decode_turn_q8_0<OutT>, gq_dequantize_blocks' turn for that type: 128 blocks of 32 values -- the same
+//           4096 values per unit --, 2-byte staging loads, half a block per thread.
 // The kind / out_dtype dispatch is a switch on block-uniform values: a workgroup executes one arm.  HBM-bound like K15:
 // 0.33-0.82 B/param in, 2 or 4 B/param out; the unit is K15's turn so that the per-byte rate is K15's.
-#include "../../../include/gptq_gguf_search.h"
+#include "../../../include/gptq_gguf_q8.h"  // (includes gptq_gguf_search.h)
 #include "gq_block_decode.hpp"
 
 namespace gq {
@@ -29,7 +31,7 @@ struct SwitchEntry {
     const uint8_t* src;
     uint8_t* dst;
     const int32_t* row_src;
-    int64_t n;          // packed: blocks of the job (R * C / 256); dense: 16-byte output chunks (R * cpr)
+    int64_t n;          // packed: blocks of the job (R * C / 256; Q8_0: R * C / 32); dense: 16-byte output chunks (R * cpr)
     int32_t per_row;    // packed: blocks per row; dense: chunks per row (cpr)
     uint32_t unit_end;  // work units of entries 0 .. this one
     int32_t kind, out_dtype;
@@ -48,6 +50,15 @@ __device__ __forceinline__ void packed_unit(const SwitchEntry& J, int64_t b0, ui
     case GQ_F32: decode_turn<QT, float>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<float*>(J.dst), sb, ssrc); break;
     case GQ_F16: decode_turn<QT, half_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<half_bits*>(J.dst), sb, ssrc); break;
     default: decode_turn<QT, bf16_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<bf16_bits*>(J.dst), sb, ssrc); break;
+    }
+}
+
+__device__ __forceinline__ void q8_0_unit(const SwitchEntry& J, int64_t b0, uint8_t* sb, int64_t* ssrc) {
+    const int nb = (int)((J.n - b0) < Q8_DB ? (J.n - b0) : Q8_DB);
+    switch (J.out_dtype) {
+    case GQ_F32: decode_turn_q8_0<float>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<float*>(J.dst), sb, ssrc); break;
+    case GQ_F16: decode_turn_q8_0<half_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<half_bits*>(J.dst), sb, ssrc); break;
+    default: decode_turn_q8_0<bf16_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<bf16_bits*>(J.dst), sb, ssrc); break;
     }
 }
 
@@ -103,8 +114,8 @@ __device__ __forceinline__ void dense_unit_from(const SwitchEntry& J, int64_t k0
 }
 
 __global__ __launch_bounds__(256) void level_switch_kernel(const SwitchTable t) {
-    __shared__ __attribute__((aligned(16))) uint8_t sb[DB * TSP_MAX];
-    __shared__ int64_t ssrc[DB];
+    __shared__ __attribute__((aligned(16))) uint8_t sb[SB_BYTES];
+    __shared__ int64_t ssrc[SSRC_N];
     const uint32_t u = blockIdx.x;
     int lo = 0, hi = t.n - 1;  // the first entry whose unit_end exceeds u (the grid is e[n - 1].unit_end: it exists)
     while (lo < hi) {
@@ -120,6 +131,7 @@ __global__ __launch_bounds__(256) void level_switch_kernel(const SwitchTable t) 
     case GQ_Q4_K: packed_unit<GQ_Q4_K>(J, ul * DB, sb, ssrc); break;
     case GQ_Q5_K: packed_unit<GQ_Q5_K>(J, ul * DB, sb, ssrc); break;
     case GQ_Q6_K: packed_unit<GQ_Q6_K>(J, ul * DB, sb, ssrc); break;
+    case GQ_Q8_0: q8_0_unit(J, ul * Q8_DB, sb, ssrc); break;
     case GQ_F32: dense_unit_from<GQ_F32>(J, ul * DENSE_CHUNKS); break;
     case GQ_F16: dense_unit_from<GQ_F16>(J, ul * DENSE_CHUNKS); break;
     default: dense_unit_from<GQ_BF16>(J, ul * DENSE_CHUNKS); break;
@@ -135,8 +147,8 @@ constexpr int64_t MAX_UNITS = 0x7fffffff;  // of one launch (the grid's x extent
 
 // every check of job i; fills the job's table entry except unit_end, and its unit count
 int check_job(const gq_switch_job_t& j, int i, SwitchEntry& e, int64_t& units) {
-    const bool packed = j.kind >= GQ_Q2_K && j.kind <= GQ_Q6_K;
-    if (!packed && !is_dtype(j.kind)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_level_switch: job %d: unknown kind %d", i, j.kind);
+    const bool packed = j.kind >= GQ_Q2_K && j.kind <= GQ_Q6_K, q8 = j.kind == GQ_Q8_0;
+    if (!packed && !q8 && !is_dtype(j.kind)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_level_switch: job %d: unknown kind %d", i, j.kind);
     if (!is_dtype(j.out_dtype)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_level_switch: job %d: unknown out_dtype %d", i, j.out_dtype);
     if (!j.src) GQ_FAIL(GQ_E_NULL, "gq_level_switch: job %d: src is NULL", i);
     if (!j.dst) GQ_FAIL(GQ_E_NULL, "gq_level_switch: job %d: dst is NULL", i);
@@ -151,6 +163,10 @@ int check_job(const gq_switch_job_t& j, int i, SwitchEntry& e, int64_t& units) {
         if (!aligned(j.src, block_align(j.kind)))
             GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: src not %d-byte aligned", i, block_align(j.kind));
         e.per_row = (int32_t)(j.C / 256), per_unit = DB;
+    } else if (q8) {
+        if (j.C % 32) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: C=%ld (C %% 32 != 0)", i, (long)j.C);
+        if (!aligned(j.src, 2)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: src not 2-byte aligned", i);
+        e.per_row = (int32_t)(j.C / 32), per_unit = Q8_DB;
     } else {
         const int ses = elsize(j.kind);
         if (j.C * ses % 16 || j.C * des % 16)

@@ -439,6 +439,12 @@ def main(argv=None):
     if not available or not all(_is_module(model, n) for n in available):
         names = [n for n, m in model.named_modules()
                  if isinstance(m, torch.nn.Linear) and has_layer(args.quant_weights_path, n)]
+        # a database cut from a whole model also holds output.weight: lm_head is no Linear of a block (layer_order_fn has
+        # no place for it) and is not searched -- it keeps the model's own weights
+        outside = [n for n in names if not _in_a_block(n)]
+        if outside:
+            print(f"not searched (no Linear of a block): {outside}")
+        names = [n for n in names if n not in outside]
         available = scan_available_bitwidths(args.quant_weights_path, names)
     print("Available bitwidths:")
     for layer_name, bitwidths in available.items():
@@ -502,6 +508,14 @@ def main(argv=None):
     if args.log_wandb:
         wandb.log(log_dict)
     return parent, out
+
+
+def _in_a_block(name: str) -> bool:
+    try:
+        layer_order_fn(name)
+        return True
+    except (IndexError, ValueError):
+        return False
 
 
 def _is_module(model, name) -> bool:

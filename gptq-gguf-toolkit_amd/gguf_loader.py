@@ -1,12 +1,13 @@
 """GGUF -> HF tensors on the GPU: the inverse of pack_gptq_into_gguf.py for the dense Llama family.
 
 The reference reads a .gguf back through transformers' GGUF loader (mapper/gguf_splitter.py:469-474), which needs gguf-py;
-that package is not installable here, so the file is parsed by gguf_writer.parse_gguf (spec level) and the K-quant payloads
-are decoded by this package's own kernel: bytes are uploaded as they lie in the file and `ops.dequantize_blocks` writes the
+that package is not installable here, so the file is parsed by gguf_writer.parse_gguf (spec level) and the K-quant and Q8_0
+payloads are decoded by this package's own kernel: bytes are uploaded as they lie in the file and `ops.dequantize_blocks` writes the
 weights in one pass.  The q_proj / k_proj rotary row permutation the converter applied (reference
 pack_gptq_into_gguf.py:2177-2183) is undone inside that pass by a row gather (`row_src`), for architecture "llama" only.
-F32 / F16 / BF16 tensors pass through with a cast; Q8_0 (`--outtype q8_0` writes it for the tensors GPTQ did not quantize)
-is two torch ops (d * q, ggml-quants.c dequantize_row_q8_0) and not a hot path.  The file is mapped, never read whole.
+F32 / F16 / BF16 tensors pass through with a cast.  Q8_0 (`--outtype q8_0` writes it for the tensors GPTQ did not quantize, and
+it may be a level of the search) takes the same one call as the K-quants: d * q of ggml-quants.c dequantize_row_q8_0, the row
+gather folded in, one cast to `dtype`.  The file is mapped, never read whole.
 Merged 3-D expert tensors (`*_exps`) are refused: splitting them back into per-expert HF names belongs to the MoE path.
 """
 from typing import Dict, Iterator, Optional, Tuple
@@ -113,15 +114,12 @@ def iter_gguf_tensors(path: str, device="cuda:0", dtype: Optional[torch.dtype] =
         raw = _host(buf, off, nbytes).to(device)
         if gt in K_QUANTS:
             t = ops.dequantize_blocks(gt, raw.view(shape[0], -1), dtype or quant_dtype or torch.float32, rows)
+        elif gt == GGMLType.Q8_0:  # (quant_dtype is the K-quants' alone)
+            t = ops.dequantize_blocks(gt, raw.view(shape[0], -1), dtype or torch.float32, rows)
         else:
-            if gt in PLAIN_TYPES:
-                t = raw.view(getattr(torch, PLAIN_TYPES[gt][0]))
-            elif gt == GGMLType.Q8_0:
-                b = raw.view(-1, 34)
-                t = b[:, :2].contiguous().view(torch.float16).float() * b[:, 2:].contiguous().view(torch.int8).float()
-            else:
+            if gt not in PLAIN_TYPES:
                 raise ValueError(f"tensor {name!r}: ggml type {gt} is not supported")
-            t = t.reshape(shape)
+            t = raw.view(getattr(torch, PLAIN_TYPES[gt][0])).reshape(shape)
             if dtype is not None:
                 t = t.to(dtype)
             if rows is not None:

@@ -501,8 +501,9 @@ class GGUFStitcher:
     def verify(self, device="cuda") -> int:
         """The file at output_path against the level files the configuration chose: read back through gguf_loader (mapped,
         decoded on the GPU) and compared bit for bit with level_db.load_level, tensor by tensor in file order.
-        Raises StitchError naming the first tensor that differs; returns the number of tensors compared (Q8_0 tensors,
-        which load_level does not decode, are compared as stored bytes)."""
+        Raises StitchError naming the first tensor that differs; returns the number of tensors compared (Q8_0 tensors are
+        compared as stored bytes: the loader decodes them to fp32 and load_level to fp16, and equal bytes are the stricter
+        check of the two)."""
         import torch
         from .gguf_loader import iter_gguf_tensors
         planned = {p.name: p for p in self.plan()}

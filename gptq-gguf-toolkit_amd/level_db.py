@@ -200,7 +200,8 @@ def read_level_raw(rec) -> np.ndarray:
 
 def load_level(path: str, device, db: Optional[str] = None):
     """One level's weight on `device`: a torch-saved tensor (--hf-layers) as it is; raw GGUF bytes (--gguf-layers) as a view
-    for plain types, decoded to fp16 by ops.dequantize_blocks for K-quants, with the manifest's q / k row gather if `db`."""
+    for plain types, decoded to fp16 by ops.dequantize_blocks for K-quants and Q8_0, with the manifest's q / k row gather if
+    `db`."""
     import torch
     rec = read_sidecar(path)
     if rec.ggml_type is None:

@@ -546,22 +546,52 @@ def unpack(q_type: int, blocks: torch.Tensor):
     return q.view(t), d, s.view(t), dmin, m.view(t)
 
 
+def block_geometry(q_type: int) -> Tuple[int, int]:
+    """(values per block, bytes per block) of a type gq_dequantize_blocks / gq_level_switch decode: the K-quants' 256-value
+    blocks, Q8_0's 32 values in 34 bytes.  Any other type is the library's refusal (gq_type_info)."""
+    if int(q_type) == _cabi.Q8_0:
+        return 32, 34
+    return 256, type_info(q_type)["type_size"]
+
+
 def dequantize_blocks(q_type: int, blocks: torch.Tensor, out_dtype=torch.float32,
                       row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Packed blocks uint8 [R, C/256*type_size] -> weights [R, C] in one pass (gq_dequantize_blocks): bit for bit
-    dequantize(*unpack(blocks)).  row_src (int32 [R] on the device): out[r] = decode(blocks[row_src[r]]); every index
-    must lie in [0, R) -- the kernel does not check."""
+    """Packed blocks uint8 [R, C/block*type_size] -> weights [R, C] in one pass (gq_dequantize_blocks): for a K-quant bit
+    for bit dequantize(*unpack(blocks)), for Q8_0 (blocks of 32 values in 34 bytes) `d.float() * q.float()` and one cast.
+    row_src (int32 [R] on the device): out[r] = decode(blocks[row_src[r]]); every index must lie in [0, R) -- the kernel
+    does not check."""
     _need_cuda(blocks, row_src)
-    ts = type_info(q_type)["type_size"]
-    assert blocks.dtype == torch.uint8 and blocks.dim() == 2 and blocks.shape[1] % ts == 0
+    bs, ts = block_geometry(q_type)
+    if blocks.dtype != torch.uint8 or blocks.dim() != 2 or blocks.shape[1] % ts:
+        raise _cabi.GQError(f"dequantize_blocks: packed blocks of q_type {int(q_type)} must be uint8 [R, C/{bs}*{ts}]; got "
+                            f"{blocks.dtype} {tuple(blocks.shape)}")
     blocks = blocks.contiguous()
-    R, C = blocks.shape[0], blocks.shape[1] // ts * 256
+    R, C = blocks.shape[0], blocks.shape[1] // ts * bs
     if row_src is not None:
         assert row_src.dtype == torch.int32 and row_src.numel() == R and row_src.device == blocks.device
         row_src = row_src.contiguous()
     out = torch.empty(R, C, dtype=out_dtype, device=blocks.device)
     check(lib().gq_dequantize_blocks(int(q_type), _ptr(blocks), R, C, _ptr(row_src), _ptr(out), _DT[out_dtype],
                                      _stream(blocks)), "gq_dequantize_blocks")
+    return out
+
+
+def quantize_q8_0(x: torch.Tensor, row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[R, C] fp32 / fp16 / bf16 on the device -> Q8_0 blocks uint8 [R, C/32*34] (gq_quantize_q8_0): bit for bit
+    gguf_writer.quantize_q8_0 of x widened to fp32.  row_src (int32 [R] on the device): out[r] = encode(x[row_src[r]]);
+    every index must lie in [0, R) -- the kernel does not check."""
+    _need_cuda(x, row_src)
+    if x.dim() != 2 or x.dtype not in _DT or x.shape[1] % 32 or x.shape[0] < 1 or x.shape[1] < 32:
+        raise _cabi.GQError(f"quantize_q8_0: x must be a [R, C] fp32 / fp16 / bf16 tensor with C % 32 == 0; got {x.dtype} "
+                            f"{tuple(x.shape)}")
+    x = x.contiguous()
+    R, C = x.shape
+    if row_src is not None:
+        if row_src.dtype != torch.int32 or row_src.numel() != R or row_src.device != x.device:
+            raise _cabi.GQError(f"quantize_q8_0: row_src must be an int32 [{R}] tensor on {x.device}")
+        row_src = row_src.contiguous()
+    out = torch.empty(R, C // 32 * 34, dtype=torch.uint8, device=x.device)
+    check(lib().gq_quantize_q8_0(_ptr(x), _DT[x.dtype], R, C, _ptr(row_src), _ptr(out), _stream(x)), "gq_quantize_q8_0")
     return out
 
 
@@ -803,8 +833,8 @@ def quad_form(A: torch.Tensor, H: torch.Tensor, B: Optional[torch.Tensor] = None
 # ---- level switch of the bit-width search (gq_level_switch): stored levels -> live weights, one call ----
 def level_switch(jobs) -> None:
     """Apply a list of jobs (src, dst, kind, row_src) in ONE gq_level_switch call on the current stream of their device.
-    dst: contiguous [R, C] fp32 / fp16 / bf16, written in place.  kind a K-quant q_type (10..14): src uint8, R rows of
-    C / 256 packed blocks (any 1-D / 2-D contiguous view of R * C / 256 * type_size bytes); kind None: src a dense
+    dst: contiguous [R, C] fp32 / fp16 / bf16, written in place.  kind a K-quant q_type (10..14) or Q8_0 (8): src uint8, R rows
+    of C / 256 packed blocks (Q8_0: C / 32 blocks of 34 bytes; any 1-D / 2-D contiguous view of exactly those bytes); kind None: src a dense
     contiguous [R, C] tensor, cast as .to(dst.dtype).  row_src: None or int32 [R], dst[r] = f(src[row_src[r]]); every index
     must lie in [0, R) -- the kernel does not check.  Returns None; no host read, no allocation on the device."""
     jobs = list(jobs)
@@ -830,8 +860,9 @@ def level_switch(jobs) -> None:
             k = _DT[src.dtype]
         else:
             k = int(kind)
-            need = R * (C // 256) * type_info(k)["type_size"]
-            if src.dtype != torch.uint8 or C % 256 or src.numel() != need:
+            bs, ts = block_geometry(k)
+            need = R * (C // bs) * ts
+            if src.dtype != torch.uint8 or C % bs or src.numel() != need:
                 raise _cabi.GQError(f"level_switch: job {i}: packed src of q_type {k} for {(R, C)} must be {need} uint8; got "
                                     f"{src.dtype} {tuple(src.shape)}")
         if row_src is not None and (row_src.dtype != torch.int32 or row_src.numel() != R or not row_src.is_contiguous()):

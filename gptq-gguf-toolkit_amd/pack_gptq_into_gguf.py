@@ -98,6 +98,18 @@ def iter_hf_entries(dir_model: Path):
                 yield k, tuple(f.get_slice(k).get_shape()), (lambda f=f, k=k: f.get_tensor(k))
 
 
+def hf_tensor_files(dir_model: Path) -> dict:
+    """{tensor name: the *.safetensors file that holds it} (headers only): for a reader that comes back to a tensor after
+    iter_hf_entries has moved on and closed the file."""
+    from safetensors import safe_open
+    where = {}
+    for fn in sorted(dir_model.glob("*.safetensors")):
+        with safe_open(str(fn), framework="pt", device="cpu") as f:
+            for k in f.keys():
+                where[k] = fn
+    return where
+
+
 # llama.cpp token types (reference pack_gptq_into_gguf.py:47-53)
 TOK_NORMAL, TOK_UNKNOWN, TOK_CONTROL, TOK_USER_DEFINED, TOK_UNUSED, TOK_BYTE = 1, 2, 3, 4, 5, 6
 _SPECIAL_TYPES = ("bos", "eos", "unk", "sep", "pad", "cls", "mask")
@@ -412,7 +424,9 @@ def convert(dir_model: Path, dir_model_quant: Path, outfile: Path, outtype: str 
     """pipelined (default): a quantized Linear's five tensors are mapped from data.pth (torch.load(mmap=True): no read), and its
     payload is made WHEN THE FILE IS WRITTEN, on a producer thread a few tensors ahead of the file writes -- one upload, the q / k
     row un-permute and gq_pack on the GPU, one download (GGUFWriter.add_tensor_lazy) -- instead of five uploads, a CPU permute
-    and ~5 GB of payloads held until write() (pipelined=False: that flow, the reference's :282-349 order of operations).  Same
+    and ~5 GB of payloads held until write() (pipelined=False: that flow, the reference's :282-349 order of operations).  With
+    --outtype q8_0 and a GPU, a plain tensor that plain_tensor's rule sends to Q8_0 takes the same pipeline: read, upload,
+    ops.quantize_q8_0 with the q / k permute as its row gather, download -- instead of numpy's six fp32 temporaries.  Same
     file bytes either way (tests/test_host_logic_cpu.py::test_pack_into_gguf...).  `timing` receives seconds per stage."""
     import threading
     import time
@@ -454,6 +468,15 @@ def convert(dir_model: Path, dir_model_quant: Path, outfile: Path, outtype: str 
     def add_plain(new_name, data):
         w.add_tensor(new_name, *plain_tensor(new_name, data, outtype))
 
+    q8_gpu = pipelined and outtype == "q8_0" and torch.cuda.is_available()
+    files = hf_tensor_files(dir_model) if q8_gpu else {}
+
+    def q8_0_on_gpu(new_name, shape):
+        """Does plain_tensor's rule send this tensor to Q8_0 (asked of the rule itself, on a one-block stand-in of the same
+        rank), and is it a matrix the encoder takes?  Rows that are no multiple of 32 keep the host path and its F16 fallback."""
+        return (q8_gpu and len(shape) == 2 and shape[0] >= 1 and shape[1] >= 32 and shape[1] % 32 == 0
+                and plain_tensor(new_name, torch.zeros(1, 32), outtype)[1] == GGMLType.Q8_0)
+
     if rope_type == "llama3":
         w.add_tensor("rope_freqs.weight", rope_freqs_llama3(hp).numpy())
     FIVE = ("qweight", "super_group_scale", "group_scale_quant", "super_group_zero", "group_zero_quant")
@@ -493,6 +516,34 @@ def convert(dir_model: Path, dir_model_quant: Path, outfile: Path, outtype: str 
             if verbose:
                 print(f"{new_name:28s} {tuple(shape)} --> ggml type {q_type}")
             w.add_tensor_lazy(new_name, tuple(qd["qweight"].shape), q_type, producer)       # :344-348
+            continue
+        if base not in index_map and not is_expert and q8_0_on_gpu(map_tensor_name(name), shape):
+            def q8_producer(name=name, new_name=map_tensor_name(name)):
+                from safetensors import safe_open
+                from . import ops
+                from .gguf_loader import rotary_row_dst
+                t0 = time.perf_counter()
+                with safe_open(str(files[name]), framework="pt", device="cpu") as f:
+                    x = f.get_tensor(name)
+                clock("hf_read", t0)
+                if x.dtype not in (torch.float16, torch.float32, torch.bfloat16):
+                    x = x.to(torch.float32)
+                t0 = time.perf_counter()
+                x = x.contiguous().cuda()
+                clock("h2d", t0)
+                t0 = time.perf_counter()
+                out = ops.quantize_q8_0(x, rotary_row_dst(new_name, x.shape[0], n_head, n_kv, x.device))  # the q / k permute
+                torch.cuda.synchronize()
+                clock("q8_0", t0)
+                t0 = time.perf_counter()
+                host = out.cpu().numpy()
+                clock("d2h", t0)
+                return host
+
+            new_name = map_tensor_name(name)
+            if verbose:
+                print(f"{new_name:28s} {tuple(shape)} --> ggml type {int(GGMLType.Q8_0)}")
+            w.add_tensor_lazy(new_name, tuple(shape), GGMLType.Q8_0, q8_producer)
             continue
         t0 = time.perf_counter()
         data = get()

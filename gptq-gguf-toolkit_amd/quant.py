@@ -101,6 +101,10 @@ def parse_args(argv=None):
                         "stitcher read the packed side).  --model_name_or_path must be a local directory; DIR must not exist")
     p.add_argument("--level_db_only", action="store_true",
                    help="with --level_db: do not write the <save_dir>/<LEVEL> trees")
+    p.add_argument("--level_db_q8_0", action="store_true",
+                   help="with --level_db: every tensor that has K-quant levels also gets the 8.5-bit level 8.5-Q8_0.pth, encoded "
+                        "on the GPU.  This is round-to-nearest of the UNMODIFIED weights -- what llama-quantize Q8_0 followed by "
+                        "the splitter would leave --, not a GPTQ result")
     args = p.parse_args(argv)
     problem = levels_problem(args)
     if problem:
@@ -113,6 +117,8 @@ def levels_problem(args, world_size=None):
     level_db = getattr(args, "level_db", None)
     if getattr(args, "level_db_only", False) and level_db is None:
         return "--level_db_only needs --level_db"
+    if getattr(args, "level_db_q8_0", False) and level_db is None:
+        return "--level_db_q8_0 needs --level_db: the Q8_0 level is a level of the database"
     if args.levels is None:
         if level_db is not None:
             return "--level_db needs --levels: the level database is written by the one-pass level build"
@@ -233,7 +239,8 @@ def _run(args):
     if args.levels is not None:
         quantizer.quantize_levels([GGMLQuantizationType[n] for n in args.levels],
                                   None if args.propagate_level == "none" else GGMLQuantizationType[args.propagate_level],
-                                  level_db=args.level_db, trees=not args.level_db_only, level_db_model=args.model_name_or_path)
+                                  level_db=args.level_db, trees=not args.level_db_only, level_db_model=args.model_name_or_path,
+                                  level_db_q8_0=args.level_db_q8_0)
     else:
         quantizer.quantize(quant_config)
     torch.cuda.synchronize()

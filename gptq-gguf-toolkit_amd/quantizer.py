@@ -580,9 +580,12 @@ class _LevelDbSink:
     files with level_db.LevelDbWriter; the bytes travel through the _Saver like a tree's tensors (RAW_BYTES items).  The
     key/value data and the tensors GPTQ does not quantize come from the model directory, by the converter's own rules
     (pack_gptq_into_gguf.add_model_metadata / plain_tensor with --outtype f16): the database is what converting every
-    level's tree and splitting the files with --exact leaves.  Dense Llama family only; the HF side is not written."""
+    level's tree and splitting the files with --exact leaves.  Dense Llama family only; the HF side is not written.
+    `q8_0`: every tensor whose K-quant levels were packed also gets the 8.5-bit level 8.5-Q8_0.pth -- round-to-nearest of
+    the checkpoint's unmodified weights (gq_quantize_q8_0, q / k rows gathered on the way), what `llama-quantize Q8_0` and
+    the splitter would leave; GPTQ has no part in it."""
 
-    def __init__(self, db: str, dir_model: str, vocab: bool = True):
+    def __init__(self, db: str, dir_model: str, vocab: bool = True, q8_0: bool = False):
         import json
         from pathlib import Path
         from . import level_db
@@ -590,7 +593,7 @@ class _LevelDbSink:
         if not dir_model or not os.path.isdir(dir_model) or not os.path.isfile(os.path.join(dir_model, "config.json")):
             raise ValueError(f"level_db needs the model as a local directory with config.json and *.safetensors (got "
                              f"{dir_model!r}): the key/value data and the plain tensors are read from it")
-        self.dir_model, self.vocab = Path(dir_model), vocab
+        self.dir_model, self.vocab, self.q8_0 = Path(dir_model), vocab, bool(q8_0)
         self.hp = json.load(open(self.dir_model / "config.json"))
         arch = self.hp.get("architectures", ["LlamaForCausalLM"])[0]
         if arch not in ("LlamaForCausalLM", "LLaMAForCausalLM", "MistralForCausalLM") or self.hp.get("num_local_experts"):
@@ -623,6 +626,7 @@ class _LevelDbSink:
         first."""
         q = stacked[0]
         dev, C = q.device, q.shape[1]
+        self.device = dev  # (finish() encodes the Q8_0 level where the walks ran)
         tensors = [None if mem is None else self.tensor_of.get(mem[0]) for mem in members]
         if all(t is None for t in tensors):
             return []
@@ -667,7 +671,16 @@ class _LevelDbSink:
             plain("rope_freqs.weight", rope_freqs_llama3(self.hp))
         for name, _, get in iter_hf_entries(self.dir_model):
             base = name.removesuffix(".weight")
-            if name.endswith(SKIPPED_HF_TENSORS) or base in self.packed:
+            if name.endswith(SKIPPED_HF_TENSORS):
+                continue
+            if base in self.packed:
+                if self.q8_0:  # the 8.5-bit level: RTN of the checkpoint's own weights, registered after the K-quant levels
+                    x = get().to(self.device)
+                    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+                        x = x.float()
+                    tensor = self.tensor_of[base]
+                    blocks = _ops.quantize_q8_0(x, self._row_src(tensor, x.shape[0], x.device))
+                    w.add_level(tensor, tuple(x.shape), GGMLType.Q8_0, blocks.cpu().numpy())
                 continue
             data = get()
             if name.endswith("q_proj.weight"):
@@ -717,7 +730,7 @@ class Quantizer:
     # ------------------------------------------------------------------ walk
     @torch.no_grad()
     def quantize_levels(self, levels, propagate, level_db: Optional[str] = None, trees: bool = True,
-                        level_db_model: Optional[str] = None, level_db_vocab: bool = True) -> None:
+                        level_db_model: Optional[str] = None, level_db_vocab: bool = True, level_db_q8_0: bool = False) -> None:
         """The level database in one pass: every quantizable module at every level of `levels`, one ordinary tree per level
         under <save_dir>/<LEVEL>/ (level_tree_name; same schema, same writer as quantize()).  The calibration forwards, the
         Hessians, the factorisations and the column walk are those of ONE run (BlockSchedule.quantize_levels).
@@ -730,8 +743,9 @@ class Quantizer:
         level's tree and splitting the files with --exact leaves, packed on the GPU with one gq_pack_bands launch per walk
         (_LevelDbSink; level_db.py lists how it differs from a split).  `level_db_model`: the model's directory (default: the
         model's own name_or_path, which must be a local directory), `level_db_vocab`: write the tokenizer keys, as
-        convert(vocab=...).  `trees=False` (with level_db): the per-level trees are not written.  Everything is refused
-        before any work; a failed run leaves no database."""
+        convert(vocab=...).  `trees=False` (with level_db): the per-level trees are not written.  `level_db_q8_0` (with
+        level_db): every tensor that has K-quant levels also gets the 8.5-bit level 8.5-Q8_0.pth, round-to-nearest of its
+        unmodified weights.  Everything is refused before any work; a failed run leaves no database."""
         levels, propagate = check_levels(levels, propagate)
         if dist_utils.get_world_size() > 1:
             raise NotImplementedError("quantize_levels runs on one rank (multi-rank level builds are not built)")
@@ -739,11 +753,14 @@ class Quantizer:
             raise ValueError("quantize_levels: act_order / static_groups have no level build")
         if level_db is None and not trees:
             raise ValueError("quantize_levels: trees=False needs level_db (nothing would be written)")
+        if level_db is None and level_db_q8_0:
+            raise ValueError("quantize_levels: level_db_q8_0 needs level_db (the Q8_0 level is a level of the database)")
         sink = None
         if level_db is not None:
             if os.environ.get("GQ_SAVE_SKIP") == "1":
                 raise ValueError("quantize_levels: GQ_SAVE_SKIP=1 writes no files, a level database cannot be completed")
-            sink = _LevelDbSink(level_db, level_db_model or getattr(self.model.config, "_name_or_path", None), level_db_vocab)
+            sink = _LevelDbSink(level_db, level_db_model or getattr(self.model.config, "_name_or_path", None), level_db_vocab,
+                                q8_0=level_db_q8_0)
         self._levels, self._level_src, self._level_sink, self._level_trees = (levels, propagate), {}, sink, bool(trees)
         try:
             self.quantize({})
