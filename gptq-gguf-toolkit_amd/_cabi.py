@@ -35,6 +35,8 @@ PACK_BANDS_ALIGN = 16  # GQ_PACK_BANDS_ALIGN: alignment of every band's output b
 # include/gptq_gguf_q8.h: the Q8_0 encoder; gq_dequantize_blocks / gq_level_switch take the type (additive in the same way)
 EXPORTS_Q8 = ("gq_quantize_q8_0",)
 Q8_0 = 8  # GQ_Q8_0: the ggml type id
+# include/gptq_gguf_qgemm.h: the packed-weight forward, a GEMM that reads block bytes as its weight operand (additive in the same way)
+EXPORTS_QGEMM = ("gq_linear_packed",)
 
 
 class GQError(RuntimeError):
@@ -143,6 +145,7 @@ def lib():
     L.gq_gptq_quantize_bands.argtypes = [vp, vp, i64, i64, ctypes.POINTER(Band), ci, ci, sp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.gq_pack_bands.argtypes = [vp, vp, vp, vp, vp, i64, i64, ctypes.POINTER(Band), ci, ctypes.POINTER(vp), ctypes.POINTER(vp), vp]
     L.gq_quantize_q8_0.argtypes = [vp, ci, i64, i64, vp, vp, vp]
+    L.gq_linear_packed.argtypes = [ci, vp, vp, i64, i64, vp, i64, ci, vp, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -150,7 +153,7 @@ def lib():
     L.gq_prof_collect.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
-    for name in EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8:
+    for name in EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_QGEMM:
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

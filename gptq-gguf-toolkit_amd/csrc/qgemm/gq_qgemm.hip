@@ -1,0 +1,295 @@
+// gq_qgemm.hip -- K21: y = x W^T for a Linear whose weight [R, C] exists only as GGUF block bytes (K-quants, Q8_0).
+// gq_linear_packed is the forward of packed residency: the search and ppleval keep every level packed and no dense copy.
+//
+// Regime: T >= 256 tokens per call (calibration batches of the search, perplexity windows); small T is correct, not fast.
+// Both operands are K-contiguous -- x rows and W rows --, so with v_mfma_f32_16x16x32_{f16,bf16} and A = W, B = x a lane's two
+// fragments are each 8 consecutive k (16 bytes) of one row: lane l holds W[r = l & 15][8 (l >> 4) + j] and
+// x[t = l & 15][8 (l >> 4) + j]; D[r = 4 (l >> 4) + i][t = l & 15] in register i.
+//
+// A workgroup of 4 waves owns the output tile [TT tokens, TR = 128 rows] and walks C in whole superblocks of 256.  TT = 256
+// when that grid has at least 512 workgroups (two per CU), else TT = 128 (measured: the wide tile is 15-35 % faster where it
+// fills the device and 15-25 % slower at [4096 x C] x 2048 tokens, 256 workgroups); the figures below are TT = 256's.
+//   * the 128 rows' packed bytes of the superblock are staged in LDS with loads of the type's natural alignment that cover
+//     exactly the blocks' bytes (as blockdec::stage_blocks), one slot per row;
+//   * x is staged in four chunks of 64 k ([256, 64], 32 KB), the next chunk's global loads in flight during the MFMAs;
+//   * wave w owns rows 32 w .. 32 w + 31 (two 16-row tiles) and all 256 tokens (sixteen tiles): 128 accumulator registers.
+//     Per chunk a lane decodes, for each of its two rows, the 16 consecutive values 64 c + 16 (l >> 4) .. + 15 with
+//     block_d / group_scale / codes16 / dequantize1 / cvt_out -- the text of decode_turn, so the operand bits are
+//     gq_dequantize_blocks' -- and uses values 8 s .. 8 s + 7 as its fragment of MFMA step s = 0, 1.  (The k order
+//     inside a chunk is thus permuted, identically for both operands.)  Only the wave that owns a row decodes it: a weight
+//     is decoded once per workgroup and used 256 times (the decode is VALU work on the critical path: at a token tile
+//     of 128 it weighs twice as much); no decoded [rows, K] tile exists anywhere.
+// LDS: x chunk as 8 planes (one per 8-k piece u = 2 (l >> 4) + s) of 256 slots of 16 bytes: the 16 lanes of a quarter wave
+// read 256 contiguous bytes, and the lane groups of ds_read_b128 ({0-3, 12-15, 20-27}, ...) take slots {0-3, 12-15} of one
+// plane and {4-11} of another, planes 4096 bytes apart: conflict-free.  Packed slots have an odd number of 16-byte units
+// (Q2_K / Q3_K 112, Q4_K 144, Q5_K 176, Q6_K 240, Q8_0 304 bytes) so that 16 rows' reads at the same offset fall on 16
+// different 16-byte bank groups.  Budget: 32 KB + 128 slots + 1 KB of row offsets = 47 KB (Q2_K) .. 63 KB (Q6_K), 71 KB (Q8_0): two workgroups
+// per CU, which is also what ~220 VGPRs allow; the staging latency of one is covered by the MFMAs of the other.
+// Rows >= R and tokens >= T of an edge tile: the rows are not staged (their LDS slots hold stale bytes, decoded to values
+// that only reach output elements that are never stored), the tokens are staged as zeros; nothing is read or written
+// outside the arguments' extents.
+#include "../../../include/gptq_gguf_qgemm.h"
+#include <type_traits>
+
+#include "../search/gq_block_decode.hpp"
+
+namespace gq {
+namespace {
+
+using namespace blockdec;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int TR = 128, KC = 64;  // tile of rows; k of an x chunk (the token tile TT = 256 or 128 is a template parameter)
+constexpr int64_t WIDE_TILES = 512;  // two workgroups on each of the 256 CUs: from there on the 256-token tile is used
+
+// the staging of one row's share of a superblock: UPR units of AL bytes, unit o at LDS byte lds_off(o) of the row's slot
+template <int QT> struct QL {
+    using L = Lay<QT>;
+    static constexpr int AL = L::AL, UPR = L::TS / L::AL, ROWB = L::TS;
+    static constexpr int SLOT = ((L::TS + 15) / 16 | 1) * 16;
+    static __device__ __forceinline__ int lds_off(int o) { return o * AL; }
+};
+template <> struct QL<GQ_Q8_0> {  // 8 blocks of 34 bytes: the eight d at bytes 0 .. 15, block b's 32 codes at 16 + 32 b
+    static constexpr int AL = 2, UPR = 8 * Q8_UPB, ROWB = 8 * Q8_TS;
+    static constexpr int SLOT = 16 + 8 * 32 + 32;
+    static __device__ __forceinline__ int lds_off(int o) {
+        const int b = o / Q8_UPB, w = o - b * Q8_UPB;
+        return w == 0 ? 2 * b : 16 + 32 * b + 2 * (w - 1);
+    }
+};
+static_assert(QL<GQ_Q8_0>::SLOT / 16 % 2 == 1, "an odd number of 16-byte units");
+
+// Stage superblock j of the tile's nr rows: sbase[r] = byte offset of the row's first block.  The caller has a barrier before
+// (sb free) and after.
+template <int QT>
+__device__ __forceinline__ void stage_rows(const uint8_t* __restrict__ blocks, const int64_t* sbase, int64_t j, int nr,
+                                           uint8_t* sb) {
+    using Q = QL<QT>;
+    using U = typename Unit<Q::AL>::T;
+    constexpr int NIT = (TR * Q::UPR + 255) / 256, GRP = 8;
+    const int tid = threadIdx.x, n = nr * Q::UPR;
+#pragma unroll 1
+    for (int it0 = 0; it0 < NIT; it0 += GRP) {
+        if (tid + 256 * it0 >= n) break;
+        U v[GRP] = {};
+#pragma unroll
+        for (int g = 0; g < GRP; ++g) {
+            const int u = tid + 256 * (it0 + g), r = u / Q::UPR, o = u - r * Q::UPR;
+            if (u < n) v[g] = *reinterpret_cast<const U*>(blocks + sbase[r] + j * Q::ROWB + o * Q::AL);
+        }
+#pragma unroll
+        for (int g = 0; g < GRP; ++g) {
+            const int u = tid + 256 * (it0 + g), r = u / Q::UPR, o = u - r * Q::UPR;
+            if (u < n) *reinterpret_cast<U*>(sb + r * Q::SLOT + Q::lds_off(o)) = v[g];
+        }
+    }
+}
+
+// The 16 values 64 c + 16 q .. + 15 of the superblock in slot B, as 8 words of two OutT bit patterns: decode_turn's text.
+template <int QT, typename OutT>
+__device__ __forceinline__ void decode16(const uint8_t* B, int c, int q, uint32_t w[8]) {
+    uint32_t cd[4];
+    uint16_t o[16];
+    if constexpr (QT == GQ_Q8_0) {
+        const int b = 2 * c + (q >> 1);
+        const float d = h2f(ld2(B + 2 * b));
+        ld16(B + 16 + 32 * b + 16 * (q & 1), cd);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) o[k] = cvt_out<OutT>(q8_0_dequantize1(d, (cd[k >> 2] >> (8 * (k & 3))) & 0xffu)).b;
+    } else {
+        using L = Lay<QT>;
+        const int g16 = 4 * c + q;
+        uint16_t d, dmin;
+        int sc, mn;
+        block_d<QT>(B, d, dmin);
+        group_scale<QT>(B, g16 * L::NG / 16, sc, mn);
+        const float ds = h2f(d) * (float)sc, dm = h2f(dmin) * (float)mn;
+        codes16<QT>(B, g16, cd);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const float code = (float)((cd[k >> 2] >> (8 * (k & 3))) & 0xffu) - (float)L::OFF;
+            o[k] = cvt_out<OutT>(dequantize1(code, ds, dm)).b;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[k] = (uint32_t)o[2 * k] | ((uint32_t)o[2 * k + 1] << 16);
+}
+
+template <bool BF16>
+__device__ __forceinline__ f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
+    if constexpr (BF16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
+// the XP 16-byte pieces of a thread of x chunk (k0 .. k0 + 63) of tokens t0 .. t0 + TT - 1: piece p = tid + 256 i is
+// token p >> 3, 8-k piece p & 7 (a token's 128 bytes are read by 8 consecutive lanes)
+template <int XP>
+__device__ __forceinline__ void load_x(const uint8_t* __restrict__ x, int64_t C, int64_t T, int64_t t0, int64_t k0, u32x4 xr[XP]) {
+#pragma unroll
+    for (int i = 0; i < XP; ++i) {
+        const int p = threadIdx.x + 256 * i;
+        const int64_t t = t0 + (p >> 3);
+        xr[i] = t < T ? *reinterpret_cast<const u32x4*>(x + (t * C + k0 + 8 * (p & 7)) * 2) : u32x4{0, 0, 0, 0};
+    }
+}
+
+template <int QT, bool BF16, int TT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void linear_packed_kernel(const uint8_t* __restrict__ blocks, const int32_t* __restrict__ row_src,
+                                                            int64_t R, int64_t C, const uint8_t* __restrict__ x, int64_t T,
+                                                            uint16_t* __restrict__ y, uint32_t n_rt) {
+    using Q = QL<QT>;
+    using OutT = typename std::conditional<BF16, bf16_bits, half_bits>::type;
+    constexpr int XP = TT * 8 / 256;
+    __shared__ __attribute__((aligned(16))) uint8_t sb[TR * Q::SLOT];
+    __shared__ __attribute__((aligned(16))) uint8_t sx[TT * KC * 2];
+    __shared__ int64_t sbase[TR];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, q = lane >> 4;
+    const int64_t r0 = (int64_t)(blockIdx.x % n_rt) * TR, t0 = (int64_t)(blockIdx.x / n_rt) * TT;  // row tiles fastest: they share x
+    const int nr = (int)((R - r0) < TR ? (R - r0) : TR), nt = (int)((T - t0) < TT ? (T - t0) : TT), ntt = (nt + 15) >> 4;
+    const int64_t nsb = C / 256;
+    if (tid < nr) sbase[tid] = (row_src ? (int64_t)row_src[r0 + tid] : r0 + tid) * nsb * Q::ROWB;
+
+    f32x4 acc[2][TT / 16];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int tt = 0; tt < TT / 16; ++tt) acc[a][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    u32x4 xr[XP];
+    load_x<XP>(x, C, T, t0, 0, xr);
+    __syncthreads();  // sbase
+    const uint8_t* B0 = sb + (32 * wave + l15) * Q::SLOT;
+#pragma unroll 1
+    for (int64_t j = 0; j < nsb; ++j) {
+        stage_rows<QT>(blocks, sbase, j, nr, sb);  // (the barrier that ended the previous chunk freed sb)
+#pragma unroll 1
+        for (int c = 0; c < 256 / KC; ++c) {
+#pragma unroll
+            for (int i = 0; i < XP; ++i) {
+                const int p = tid + 256 * i;
+                *reinterpret_cast<u32x4*>(sx + ((p & 7) * TT + (p >> 3)) * 16) = xr[i];
+            }
+            __syncthreads();
+            const int64_t kn = 256 * j + KC * (c + 1);
+            if (kn < C) load_x<XP>(x, C, T, t0, kn, xr);
+            uint32_t w[2][8];
+            decode16<QT, OutT>(B0, c, q, w[0]);
+            decode16<QT, OutT>(B0 + 16 * Q::SLOT, c, q, w[1]);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const u32x4 wa = {w[0][4 * s], w[0][4 * s + 1], w[0][4 * s + 2], w[0][4 * s + 3]};
+                const u32x4 wb = {w[1][4 * s], w[1][4 * s + 1], w[1][4 * s + 2], w[1][4 * s + 3]};
+                const uint8_t* px = sx + ((2 * q + s) * TT + l15) * 16;
+#pragma unroll
+                for (int tt = 0; tt < TT / 16; ++tt)
+                    if (tt < ntt) {
+                        const u32x4 xa = *reinterpret_cast<const u32x4*>(px + tt * 256);
+                        acc[0][tt] = mfma<BF16>(wa, xa, acc[0][tt]);
+                        acc[1][tt] = mfma<BF16>(wb, xa, acc[1][tt]);
+                    }
+            }
+            __syncthreads();  // sx (and after the last chunk sb) may be overwritten
+        }
+    }
+
+    const bool vec = (R & 3) == 0;  // then (t R + r) * 2 is 8-byte aligned for r % 4 == 0
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const int64_t r = r0 + 32 * wave + 16 * a + 4 * q;
+#pragma unroll
+        for (int tt = 0; tt < TT / 16; ++tt) {
+            const int64_t t = t0 + 16 * tt + l15;
+            if (t >= T || r >= R) continue;
+            uint16_t o[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = cvt_out<OutT>(acc[a][tt][i]).b;
+            uint16_t* py = y + t * R + r;
+            if (vec) {
+                *reinterpret_cast<uint2*>(py) = make_uint2((uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16));
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (r + i < R) py[i] = o[i];
+            }
+        }
+    }
+}
+
+bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+int block_align(int q) { return q == GQ_Q2_K ? 4 : (q == GQ_Q4_K || q == GQ_Q5_K) ? 16 : 2; }
+
+// the grid of token tile tt; 0 when it is more than one launch takes
+int64_t tiles(int64_t R, int64_t T, int tt) {
+    const int64_t n_rt = (R + TR - 1) / TR, n_tt = (T + tt - 1) / tt;
+    return n_tt > 0x7fffffff / n_rt ? 0 : n_rt * n_tt;
+}
+
+template <int QT, bool BF16>
+void launch_dt(bool wide, dim3 grid, hipStream_t st, const uint8_t* blocks, const int32_t* row_src, int64_t R, int64_t C,
+               const uint8_t* x, int64_t T, uint16_t* y, uint32_t n_rt) {
+    if (wide) hipLaunchKernelGGL((linear_packed_kernel<QT, BF16, 256>), grid, dim3(256), 0, st, blocks, row_src, R, C, x, T, y, n_rt);
+    else hipLaunchKernelGGL((linear_packed_kernel<QT, BF16, 128>), grid, dim3(256), 0, st, blocks, row_src, R, C, x, T, y, n_rt);
+}
+
+template <int QT>
+void launch(bool bf16, bool wide, dim3 grid, hipStream_t st, const uint8_t* blocks, const int32_t* row_src, int64_t R, int64_t C,
+            const uint8_t* x, int64_t T, uint16_t* y, uint32_t n_rt) {
+    if (bf16) launch_dt<QT, true>(wide, grid, st, blocks, row_src, R, C, x, T, y, n_rt);
+    else launch_dt<QT, false>(wide, grid, st, blocks, row_src, R, C, x, T, y, n_rt);
+}
+
+}  // namespace
+}  // namespace gq
+
+using namespace gq;
+
+extern "C" {
+
+int gq_linear_packed(int q_type, const void* blocks, const int32_t* row_src, int64_t R, int64_t C, const void* x, int64_t T,
+                     int x_dtype, void* y, void* stream) {
+    if (int rc = options_ok()) return rc;
+    const bool kq = q_type >= GQ_Q2_K && q_type <= GQ_Q6_K;
+    if (!kq && q_type != GQ_Q8_0) GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed: unknown q_type %d (a K-quant or GQ_Q8_0)", q_type);
+    if (x_dtype != GQ_F16 && x_dtype != GQ_BF16)
+        GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed: x_dtype %d (GQ_F16 or GQ_BF16; there is no fp32 path)", x_dtype);
+    if (!blocks) GQ_FAIL(GQ_E_NULL, "gq_linear_packed: blocks is NULL");
+    if (!x) GQ_FAIL(GQ_E_NULL, "gq_linear_packed: x is NULL");
+    if (!y) GQ_FAIL(GQ_E_NULL, "gq_linear_packed: y is NULL");
+    if (R < 1 || R > 0x7fffffff) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: R=%ld (not in [1, 2^31))", (long)R);
+    if (T < 1 || T > 0x7fffffff) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: T=%ld (not in [1, 2^31))", (long)T);
+    if (C < 256 || C > 0x7fffffff || C % 256)
+        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 included)", (long)C);
+    const int al = kq ? block_align(q_type) : 2;
+    if (!aligned(blocks, al)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: blocks not %d-byte aligned", al);
+    if (!aligned(row_src, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: row_src not 4-byte aligned");
+    if (!aligned(x, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: x not 16-byte aligned");
+    if (!aligned(y, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: y not 16-byte aligned");
+    // the 256-token tile halves the decode work per output, the 128-token one fills the device at small shapes
+    const bool wide = tiles(R, T, 256) >= WIDE_TILES;
+    const int64_t n_rt = (R + TR - 1) / TR, n_wg = tiles(R, T, wide ? 256 : 128);
+    if (!n_wg) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: R=%ld T=%ld is more than one launch takes", (long)R, (long)T);
+    const dim3 grid((unsigned)n_wg);
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* b = static_cast<const uint8_t*>(blocks);
+    const uint8_t* xp = static_cast<const uint8_t*>(x);
+    uint16_t* yp = static_cast<uint16_t*>(y);
+    const bool bf = x_dtype == GQ_BF16;
+    switch (q_type) {
+    case GQ_Q2_K: launch<GQ_Q2_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
+    case GQ_Q3_K: launch<GQ_Q3_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
+    case GQ_Q4_K: launch<GQ_Q4_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
+    case GQ_Q5_K: launch<GQ_Q5_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
+    case GQ_Q6_K: launch<GQ_Q6_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
+    default: launch<GQ_Q8_0>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
+    }
+    GQ_LAUNCH_CHECK();
+    return GQ_OK;
+}
+
+}  // extern "C"

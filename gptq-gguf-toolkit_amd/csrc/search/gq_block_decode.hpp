@@ -1,5 +1,6 @@
 // gq_block_decode.hpp -- the device side of the block decoder (K-quants and Q8_0), shared by decode/gq_decode.hip (K15: one
-// matrix per launch) and search/gq_switch.hip (K18: a table of matrices per launch).  One text, so the two entry points
+// matrix per launch), search/gq_switch.hip (K18: a table of matrices per launch) and qgemm/gq_qgemm.hip (K21: the pieces below
+// decode_turn, as the weight operand of a GEMM).  One text, so the two entry points
 // cannot drift apart: a turn of either kernel is decode_turn() (K-quants) or decode_turn_q8_0() below.  Layouts, staging
 // widths and the numerical contract are described at the top of decode/gq_decode.hip.
 #pragma once
@@ -182,6 +183,9 @@ constexpr int Q8_DB = 128, Q8_TS = 34, Q8_SLOT = 48, Q8_UPB = Q8_TS / 2;
 constexpr int SB_BYTES = Q8_DB * Q8_SLOT > DB * TSP_MAX ? Q8_DB * Q8_SLOT : DB * TSP_MAX;  // LDS of a kernel that takes any turn
 constexpr int SSRC_N = Q8_DB > DB ? Q8_DB : DB;
 
+// one value: the stored byte as int8, times d -- exact in fp32 (shared with qgemm/gq_qgemm.hip)
+__device__ __forceinline__ float q8_0_dequantize1(float d, uint32_t byte) { return d * (float)(int8_t)byte; }
+
 // One turn of a workgroup of 256 threads: output blocks b0 .. b0 + nb - 1 (nb <= Q8_DB) of a matrix with nbr = C / 32 blocks
 // per row, decoded to out + b0 * 32: w = f32(d) * f32(q), one cast.  Output block L comes from packed block
 // row_src[L / nbr] * nbr + L % nbr; a turn may straddle rows.  sb: Q8_DB * Q8_SLOT bytes, 16-byte aligned; ssrc: Q8_DB
@@ -217,7 +221,7 @@ __device__ __forceinline__ void decode_turn_q8_0(const uint8_t* __restrict__ blo
         ld16(B + 16 + 16 * h, c);
         alignas(16) OutT o[16];
 #pragma unroll
-        for (int k = 0; k < 16; ++k) o[k] = cvt_out<OutT>(d * (float)(int8_t)((c[k >> 2] >> (8 * (k & 3))) & 0xffu));
+        for (int k = 0; k < 16; ++k) o[k] = cvt_out<OutT>(q8_0_dequantize1(d, (c[k >> 2] >> (8 * (k & 3))) & 0xffu));
         uint4* op = reinterpret_cast<uint4*>(out + (b0 + b) * 32 + 16 * h);
 #pragma unroll
         for (int k = 0; k < (int)sizeof(OutT) * 16 / 16; ++k) op[k] = reinterpret_cast<const uint4*>(o)[k];

@@ -128,6 +128,9 @@ class ErrorEstimator:
     ) -> None:
         """level_store: an optional level_store.LevelStore holding the database on the device; the levels are then read
         from it instead of from the files (the values are the same)."""
+        if getattr(level_store, "resident", "dense") != "dense":
+            raise ValueError("ErrorEstimator needs the model's dense Linears: it cannot work on a packed-resident LevelStore "
+                             "(resident='packed'); build the store with resident='dense'")
         self.level_store = level_store
         self.model = model
         self.data_loader = data_loader

@@ -4,7 +4,7 @@
     python -m gptq_gguf_toolkit_amd.evo_quant_search --model_name_or_path HF_DIR --quant_weights_path DB \
         --calibration_data ids.pt --eval_datasets eval.pt --generations G --offspring N --target_bitwidth B \
         --survivors_per_selection 4 1 --tokens_per_selection 2048 16384 [--group_rule size|name|none] \
-        [--fitness_fn kl|ppl|sparse_kl] [--targets_on device|cpu]
+        [--fitness_fn kl|ppl|sparse_kl] [--targets_on device|cpu] [--resident dense|packed]
 
 The loop of the reference's main() (:401-779) is restated as functions of their arguments -- scan_available_bitwidths (level_db's),
 calculate_total_bits, get_next_bitwidth, initial_parent / initial_candidates, mutate, make_offspring, minibatch, selection,
@@ -21,6 +21,10 @@ What differs from the reference, on purpose:
   * level files are recognised by level_db.level_key ("4.pth" and "4-Q4_K.pth" both count; the reference's
     filename.split('-')[0] drops the former with a warning), and the --gguf-layers layout is read too;
   * the reference's progress prints inside the mutation ("Can't decrease bits, continue ...") are not made.
+  * --resident packed: no dense live copy of the searched Linears (level_store / packed_linear): the forward reads the
+    current level's block bytes, a switch launches nothing.  The KL targets are then collected BEFORE the store is built
+    (they need the unmodified dense model, which the store frees).  Fitnesses differ from dense residency by fp32
+    summation order only, so a trajectory may differ where two candidates are that close.
 One rank, nn.Linear only."""
 import argparse
 import copy
@@ -357,6 +361,9 @@ def parse_args(argv=None):
                    help="Attention implementation: eager, sdpa, or flash_attention_2")
     p.add_argument("--targets_on", type=str, default="device", choices=["cpu", "device"],
                    help="where the KL targets are kept: on the device when they fit (default), or on the host as the reference")
+    p.add_argument("--resident", type=str, default="dense", choices=["dense", "packed"],
+                   help="dense (default): the model keeps a dense live weight per Linear and a switch decodes into it; packed: "
+                        "no dense copy, the forward reads the stored block bytes (fp16 / bf16 models, packed levels)")
     args = p.parse_args(argv)
     # every refusal BEFORE any work
     for what, names in (("calibration_data", [args.calibration_data]), ("eval_datasets", args.eval_datasets)):
@@ -452,10 +459,15 @@ def main(argv=None):
     layer_names = sorted(available, key=layer_order_fn)
     grouped = group_layers(model, layer_names, args.group_rule)
     print(grouped)
-    store = LevelStore(model, args.quant_weights_path, device, layer_names)  # refuses what does not fit before uploading
+    if args.resident == "packed":  # the targets need the unmodified dense model: first, before the store frees it
+        target_logits, where = collect_targets(model, calibration_data, args.fitness_fn, args.kl_topk, args.targets_on)
+    # refuses what does not fit before uploading
+    store = LevelStore(model, args.quant_weights_path, device, layer_names, resident=args.resident)
     store.grouped_layer_names = grouped
-    print(f"level store: {store.bytes()} bytes on {device}")
-    target_logits, where = collect_targets(model, calibration_data, args.fitness_fn, args.kl_topk, args.targets_on)
+    print(f"level store: {store.bytes()} bytes on {device}" +
+          (f", {store.freed_bytes} bytes of dense weights freed" if args.resident == "packed" else ""))
+    if args.resident != "packed":
+        target_logits, where = collect_targets(model, calibration_data, args.fitness_fn, args.kl_topk, args.targets_on)
     if args.fitness_fn != "ppl":
         print(f"targets on: {where}")
 

@@ -95,7 +95,8 @@ def _host(buf, off: int, nbytes: int) -> torch.Tensor:
 
 
 def iter_gguf_tensors(path: str, device="cuda:0", dtype: Optional[torch.dtype] = None,
-                      hf_layout: bool = True, quant_dtype: Optional[torch.dtype] = None) -> Iterator[Tuple[str, torch.Tensor]]:
+                      hf_layout: bool = True, quant_dtype: Optional[torch.dtype] = None,
+                      skip=()) -> Iterator[Tuple[str, torch.Tensor]]:
     """Yield (name, tensor on `device`) for every tensor of the file, in file order.  hf_layout: HF names and HF row order
     of attn_q / attn_k (`rope_freqs.weight`, which no HF module owns, is left out); otherwise GGUF names and rows as stored.
     dtype None: fp32 for quantized tensors (`quant_dtype` for the K-quants when given), the stored dtype for F32 / F16 / BF16."""
@@ -108,7 +109,7 @@ def iter_gguf_tensors(path: str, device="cuda:0", dtype: Optional[torch.dtype] =
         if name.endswith("_exps.weight") or len(shape) > 2:
             raise NotImplementedError(f"tensor {name!r} (shape {tuple(shape)}): merged expert tensors are not split back into "
                                       f"per-expert HF tensors")
-        if hf_layout and name == "rope_freqs.weight":
+        if (hf_layout and name == "rope_freqs.weight") or name in skip:  # (skip: GGUF names the caller handles itself)
             continue
         rows = rotary_row_src(name, shape[0], arch, n_head, n_kv, device) if hf_layout else None
         raw = _host(buf, off, nbytes).to(device)
@@ -132,11 +133,58 @@ def load_state_dict(path: str, device="cuda:0", dtype: Optional[torch.dtype] = N
     return dict(iter_gguf_tensors(path, device, dtype, hf_layout=True))
 
 
-def load_into_model(model: torch.nn.Module, path: str) -> torch.nn.Module:
+def packed_linear_tensors(model: torch.nn.Module, path: str) -> Dict[str, tuple]:
+    """{HF module name: (GGUF tensor name, ggml type)} of the file's K-quant / Q8_0 tensors that are the weight of an
+    nn.Linear of a block of `model` with in_features % 256 == 0 -- what load_into_model(packed=True) keeps packed.
+    lm_head, embeddings and norms are not among them."""
+    _, tensors, _ = parse_gguf(str(path), mmap=True)
+    out = {}
+    for name, shape, gt, _, _ in tensors:
+        if not (gt in K_QUANTS or gt == GGMLType.Q8_0) or len(shape) != 2 or not name.startswith("blk."):
+            continue
+        hf = hf_tensor_name(name)
+        mod = hf[:-len(".weight")] if hf.endswith(".weight") else None
+        try:
+            layer = model.get_submodule(mod) if mod else None
+        except AttributeError:
+            layer = None
+        if isinstance(layer, torch.nn.Linear) and tuple(layer.weight.shape) == tuple(shape) and shape[1] % 256 == 0:
+            out[mod] = (name, gt)
+    return out
+
+
+def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The packed half of load_into_model: the Linears of packed_linear_tensors become PackedLinear holding the file's
+    block bytes (with the rotary row gather of attn_q / attn_k as row_src) -> the state dict of everything else."""
+    from .packed_linear import replace_linear
+    if ref.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"load_into_model(packed=True) computes in fp16 / bf16, the model is {ref.dtype}")
+    keep = packed_linear_tensors(model, path)
+    by_gguf = {g: m for m, (g, _) in keep.items()}
+    kv, tensors, buf = parse_gguf(str(path), mmap=True)
+    arch = kv["general.architecture"][0] if "general.architecture" in kv else None
+    n_head, n_kv = (kv_int(kv[k][0] if k in kv else None, k)
+                    for k in (f"{arch}.attention.head_count", f"{arch}.attention.head_count_kv"))
+    rows: Dict[tuple, Optional[torch.Tensor]] = {}  # one gather per (q or k, R)
+    for name, shape, gt, off, nbytes in tensors:
+        if name in by_gguf:
+            key = (name.rsplit(".", 2)[-2], shape[0])
+            if key not in rows:
+                rows[key] = rotary_row_src(name, shape[0], arch, n_head, n_kv, ref.device)
+            packed = replace_linear(model, by_gguf[name])
+            packed.set_level(_host(buf, off, nbytes).to(ref.device), int(gt), rows[key])
+    skip = {m + ".weight" for m in keep}
+    return {k: t for k, t in iter_gguf_tensors(path, ref.device, ref.dtype, hf_layout=True, skip=by_gguf) if k not in skip}
+
+
+def load_into_model(model: torch.nn.Module, path: str, packed: bool = False) -> torch.nn.Module:
     """Load the file's weights into `model` (parameters on a GPU), strict on names and shapes.  A tied lm_head (no
-    `output.weight` in the file) follows token_embd."""
+    `output.weight` in the file) follows token_embd.
+    packed=True: the K-quant and Q8_0 tensors of the blocks' nn.Linear modules stay packed on the device -- each such Linear
+    becomes a packed_linear.PackedLinear whose forward reads the block bytes (the q / k rotary permutation undone by its
+    row_src), about 4.5 bits per parameter for a Q4_K file instead of 16; embeddings, norms and lm_head load as without it."""
     ref = next(model.parameters())
-    sd = load_state_dict(path, ref.device, ref.dtype)
+    sd = _load_packed(model, path, ref) if packed else load_state_dict(path, ref.device, ref.dtype)
     want = model.state_dict()
     if "lm_head.weight" in want and "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:
         sd["lm_head.weight"] = sd["model.embed_tokens.weight"]

@@ -15,6 +15,11 @@ Both database layouts of gguf_splitter are read, through level_db:
                 (with the q / k rotary row gather of the manifest) straight to the weight dtype.  For fp16 weights that is
                 level_db.load_level(file).to(dtype) bit for bit; for bf16 / fp32 weights the value is rounded ONCE
                 from the fp32 decode, where load_level's fp16 tensor followed by .to(dtype) rounds twice.
+
+resident="packed" (default "dense") keeps NO dense live copy: every held Linear becomes a packed_linear.PackedLinear whose
+forward reads the current level's block bytes (ops.linear_packed), its dense storage is freed, and a switch is a change of
+references -- no launch, no device memory moves.  The levels must then be packed (K-quants, Q8_0) or dense in the model's
+dtype; fp16 / bf16 models only.
 One rank, nn.Linear only."""
 import os
 from typing import Dict, List, Optional, Sequence, Tuple, Union
@@ -22,7 +27,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import torch
 import torch.nn as nn
 
-from . import level_db, ops
+from . import level_db, ops, packed_linear
 from .gguf_writer import K_QUANTS, PLAIN_TYPES, GGMLType
 
 _DENSE = (torch.float32, torch.float16, torch.bfloat16)
@@ -35,12 +40,34 @@ class _Level:
     __slots__ = ("info", "key", "file", "kind", "nbytes", "dtype", "data", "rows")
 
 
+def packed_peak_bytes(level_bytes: Sequence[int], dense_bytes: Sequence[int]) -> int:
+    """The most device memory packed residency takes beyond what is held at its start: Linear i (in upload order) first
+    frees dense_bytes[i] -- its dense weight --, then level_bytes[i] -- all its levels -- are uploaded.  Negative when
+    the model shrinks from the first Linear on.  Pure arithmetic."""
+    held, peak = 0, None
+    for lv, dn in zip(level_bytes, dense_bytes):
+        held += int(lv) - int(dn)
+        peak = held if peak is None else max(peak, held)
+    return 0 if peak is None else peak
+
+
+def packed_fits(level_bytes: Sequence[int], dense_bytes: Sequence[int], capacity_bytes: int) -> bool:
+    """Whether the levels fit `capacity_bytes` of free device memory once the bytes that installing PackedLinear frees are
+    credited (packed_peak_bytes)."""
+    return packed_peak_bytes(level_bytes, dense_bytes) <= int(capacity_bytes)
+
+
 class LevelStore:
 
     def __init__(self, model: nn.Module, db: str, device, layer_names: Optional[Sequence[str]] = None,
-                 capacity_bytes: Optional[int] = None):
+                 capacity_bytes: Optional[int] = None, resident: str = "dense"):
         """layer_names: the Linears to hold (default: every nn.Linear of the model that has a directory in `db`).
-        capacity_bytes: the device memory the levels may take (default: what torch reports free on `device`)."""
+        capacity_bytes: the device memory the levels may take (default: what torch reports free on `device`).
+        resident: "dense" -- the model keeps its nn.Linear weights and a switch decodes into them; "packed" -- the Linears
+        become PackedLinear, their dense weights are freed (credited in the capacity check) and a switch swaps references."""
+        if resident not in ("dense", "packed"):
+            raise ValueError(f"resident must be 'dense' or 'packed', got {resident!r}")
+        self.resident, self.freed_bytes = resident, 0
         self.model, self.db, self.device = model, db, torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:  # "cuda" -> the current device, as tensors report it
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -48,7 +75,7 @@ class LevelStore:
             layer_names = [n for n, m in model.named_modules() if isinstance(m, nn.Linear) and level_db.has_layer(db, n)]
         self.layers: Dict[str, nn.Linear] = {}
         self.levels: Dict[str, List[_Level]] = {}
-        need = 0
+        need, per_layer, layer = 0, [], None
         for name in layer_names:  # pass 1: the files only -- every refusal comes before the first upload
             layer = model.get_submodule(name)
             if not isinstance(layer, nn.Linear):
@@ -57,19 +84,39 @@ class LevelStore:
                 raise TypeError(f"{name}: weight dtype {layer.weight.dtype} is not fp32 / fp16 / bf16")
             ldir = level_db.layer_dir(db, name)
             self.layers[name], self.levels[name] = layer, []
+            if resident == "packed" and layer.weight.dtype not in (torch.float16, torch.bfloat16):
+                raise TypeError(f"{name}: packed residency computes in fp16 / bf16, the weight is {layer.weight.dtype}: use "
+                                f"dense residency")
             for f in level_db.level_files(ldir):
                 lv = self._inspect(os.path.join(ldir, f), name, layer)
+                if resident == "packed" and lv.kind is None and lv.dtype != layer.weight.dtype:
+                    what = "a torch-saved dense tensor" if lv.info.ggml_type is None else f"a plain {lv.dtype} matrix"
+                    raise ValueError(f"{os.path.join(ldir, f)}: {what}, neither packed blocks nor dense in the model's dtype "
+                                     f"({layer.weight.dtype}): packed residency cannot hold this level of {name}, use dense "
+                                     f"residency")
                 self.levels[name].append(lv)
                 need += lv.nbytes
             if not self.levels[name]:
                 raise FileNotFoundError(f"{ldir}: no level file for {name}")
+            per_layer.append((sum(lv.nbytes for lv in self.levels[name]), packed_linear.dense_bytes(layer)))
+        del layer
         if capacity_bytes is None:
             capacity_bytes = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else None
-        if capacity_bytes is not None and need > capacity_bytes:
+        if resident == "packed":
+            lvb, dnb = [a for a, _ in per_layer], [b for _, b in per_layer]
+            if capacity_bytes is not None and not packed_fits(lvb, dnb, capacity_bytes):
+                raise MemoryError(f"the levels of {db} need {need} bytes on {self.device}, at most "
+                                  f"{packed_peak_bytes(lvb, dnb)} beyond what is held now once the {sum(dnb)} bytes of the "
+                                  f"dense weights are freed; {capacity_bytes} are available "
+                                  f"({sum(len(v) for v in self.levels.values())} levels of {len(self.levels)} Linears)")
+        elif capacity_bytes is not None and need > capacity_bytes:
             raise MemoryError(f"the levels of {db} need {need} bytes on {self.device}, {capacity_bytes} are available "
                               f"({sum(len(v) for v in self.levels.values())} levels of {len(self.levels)} Linears)")
         self._rows: Dict[Tuple[str, int], Optional[torch.Tensor]] = {}
         for name, lvs in self.levels.items():  # pass 2: upload, each level once
+            if resident == "packed":  # the dense weight goes first, so that the peak is packed_peak_bytes'
+                self.freed_bytes += packed_linear.dense_bytes(self.layers[name])
+                self.layers[name] = packed_linear.replace_linear(model, name)
             for lv in lvs:
                 self._upload(name, lv)
         self.state: Dict[str, Optional[float]] = {name: None for name in self.layers}
@@ -111,6 +158,8 @@ class LevelStore:
             if key not in self._rows:  # the q / k row gather, built once per (tensor kind, R)
                 self._rows[key] = level_db.rotary_rows(self.db, lv.info.name, want[0], self.device)
             lv.rows = self._rows[key]
+        if self.resident == "packed" and lv.kind is None and lv.rows is not None:
+            lv.data, lv.rows = lv.data[lv.rows.long()].contiguous(), None  # F.linear takes the level as it lies: gather once
         lv.nbytes = lv.data.numel() * lv.data.element_size()
 
     # ---- use ----
@@ -146,6 +195,8 @@ class LevelStore:
         from the recorded one are rewritten, in place, by ONE ops.level_switch call.  Layers the state does not name keep
         their level.  Returns the number of Linears rewritten; no host read."""
         flat = self.flatten(state)
+        if self.resident == "packed":
+            return self._switch_packed(flat)
         jobs, new = [], {}
         for name, key in flat.items():
             lv = self.find(name, key)
@@ -160,6 +211,19 @@ class LevelStore:
         self.state.update(new)
         self.jobs_issued += len(jobs)
         return len(jobs)
+
+    def _switch_packed(self, flat: Dict[str, float]) -> int:
+        """Packed residency: the Linears whose level differs get references to the stored level (PackedLinear.set_level).
+        No launch (jobs_issued does not move), no allocation."""
+        n = 0
+        for name, key in flat.items():
+            lv = self.find(name, key)
+            if self.state[name] is not None and self.state[name] == lv.key:
+                continue
+            self.layers[name].set_level(lv.data, lv.kind, lv.rows)
+            self.state[name] = lv.key
+            n += 1
+        return n
 
     def weight_of(self, name: str, key, dtype=None) -> torch.Tensor:
         """A fresh tensor holding level `key` of `name` in `dtype` (default: the Linear's), decoded by the same call

@@ -3,7 +3,7 @@
 eval/ppleval.py (:25-120 flags, :124-152 load_compressed_weights, :207-229 the result JSON) on the gq_eval_* kernels.
 
     python -m gptq_gguf_toolkit_amd.ppleval --model_name_or_path HF_DIR --eval_datasets ids.pt --output_file out.json \
-        [--quant_weights_path DB [--quant_config_path FILE] [--quant_default_level N] | --gguf FILE] \
+        [--quant_weights_path DB [--quant_config_path FILE] [--quant_default_level N] | --gguf FILE [--packed]] \
         [--kl_against none|model|gguf:FILE]
 
 Evaluation data are `.pt` files of [1, L] id tensors (no tokenizer, no download).  Left out: --memory_efficient, wandb,
@@ -53,7 +53,12 @@ def parse_args(argv=None):
     p.add_argument("--kl_against", type=str, default="none",
                    help="none | model | gguf:FILE -- also report the dense KL of the scored model against the unmodified "
                         "HF model or against another .gguf")
+    p.add_argument("--packed", default=False, action="store_true",
+                   help="with --gguf: keep the K-quant / Q8_0 weights of the blocks' Linears packed on the device and compute "
+                        "with the block bytes (no dense copy; fp16 / bf16)")
     args = p.parse_args(argv)
+    if args.packed and not args.gguf:
+        p.error("--packed needs --gguf")
     if args.gguf and args.quant_weights_path:
         p.error("--gguf and --quant_weights_path are mutually exclusive")
     if args.kl_against not in ("none", "model") and not (args.kl_against.startswith("gguf:") and args.kl_against[5:]):
@@ -112,7 +117,7 @@ def load_hf_model(args, device):
 def apply_weights(model, args):
     """The scored model: --gguf, the level database, or the HF weights as loaded."""
     if args.gguf:
-        gguf_loader.load_into_model(model, args.gguf)
+        gguf_loader.load_into_model(model, args.gguf, packed=getattr(args, "packed", False))
     elif args.quant_weights_path:
         load_compressed_weights(model, args.quant_weights_path, args.quant_config_path, args.quant_default_level)
     return model
