@@ -25,7 +25,11 @@ What differs from the reference, on purpose:
     current level's block bytes, a switch launches nothing.  The KL targets are then collected BEFORE the store is built
     (they need the unmodified dense model, which the store frees).  Fitnesses differ from dense residency by fp32
     summation order only, so a trajectory may differ where two candidates are that close.
-One rank, nn.Linear only."""
+  * --reuse_prefix on: the parent is run once per minibatch and a candidate from its first changed block on (suffix_forward);
+    under `python -m torch.distributed.run --nproc-per-node N -m gptq_gguf_toolkit_amd.evo_quant_search ...` a selection's
+    candidates are dealt to the N ranks and the fitnesses all-gathered.  Both keep the trajectory of a seed; [--backend],
+    [--reuse_prefix_bytes], [--trace_out FILE].
+nn.Linear only."""
 import argparse
 import copy
 import math
@@ -264,11 +268,21 @@ def minibatch(calibration_data, num_tokens: int, rng: random.Random, fitness_fn:
 
 
 def selection(evaluate: Callable, candidates: List[State], num_survive: int, calibration_data, num_tokens: int,
-              rng: random.Random, fitness_fn: str = "ppl", target_logits=None, trace: Optional[list] = None):
+              rng: random.Random, fitness_fn: str = "ppl", target_logits=None, trace: Optional[list] = None, *,
+              parent: Optional[State] = None, reuse=None, ranks=None):
     """:150-199: one minibatch, every candidate evaluated on it as evaluate(candidate, data, targets) -> float, the
-    num_survive fittest kept -> (survivors, their fitnesses)."""
+    num_survive fittest kept -> (survivors, their fitnesses).
+
+    ranks (suffix_forward.Ranks): the candidates are dealt to the ranks by cost (assign_candidates), each rank evaluates its
+    share, and ONE all-gather of fp64 puts every fitness on every rank in candidate order.
+    reuse (suffix_forward.StageReuse) and parent: this process's share is planned (plan_stage); where it reuses, the parent is
+    captured on the minibatch and a candidate is evaluated as evaluate(candidate, data, targets, start_block).  Neither draws from rng nor
+    changes the order of the list; with both absent this is the loop above."""
     data, ids, targets = minibatch(calibration_data, num_tokens, rng, fitness_fn, target_logits)
-    fitnesses = [evaluate(c, data, targets) for c in candidates]
+    if reuse is None and ranks is None:
+        fitnesses = [evaluate(c, data, targets) for c in candidates]
+    else:
+        fitnesses = _evaluate_stage(evaluate, candidates, data, targets, parent, reuse, ranks)
     best_ids = np.argsort(fitnesses)[:num_survive]
     if trace is not None:
         trace.append({"num_tokens": num_tokens, "minibatch_ids": ids, "candidates": copy.deepcopy(candidates),
@@ -276,13 +290,48 @@ def selection(evaluate: Callable, candidates: List[State], num_survive: int, cal
     return [candidates[i] for i in best_ids], [fitnesses[i] for i in best_ids]
 
 
+def _evaluate_stage(evaluate: Callable, candidates: List[State], data, targets, parent, reuse, ranks) -> List[float]:
+    """selection()'s fitness list with a stage plan and / or ranks: the same numbers in the same order.
+
+    The candidate-to-rank map is computed from the candidates and the parent alone (reuse.costs: blocks from the first changed
+    block; equal costs without reuse or parent), so it is the same on every rank.  What depends on a rank's free memory -- the
+    stride, and whether reusing pays for ITS share -- is decided by that rank for itself after the map is fixed: a rank that
+    declines runs its share in full, which gives the same numbers."""
+    from .suffix_forward import assign_candidates
+    world, rank = (ranks.world_size, ranks.rank) if ranks is not None else (1, 0)
+    n = len(candidates)
+    costs = reuse.costs(candidates, parent) if reuse is not None and parent is not None else [1.0] * n
+    owner = assign_candidates(costs, world)
+    mine = [i for i, r in enumerate(owner) if r == rank]
+    starts = reuse.begin_stage([candidates[i] for i in mine], parent, data) if reuse is not None else None
+    out, done = [0.0] * n, [0.0] * n
+    try:
+        if starts is not None:
+            reuse.capture(parent, data)
+        for k, i in enumerate(mine):
+            c = candidates[i]
+            out[i] = float(evaluate(c, data, targets) if starts is None else evaluate(c, data, targets, starts[k]))
+            done[i] = 1.0
+    finally:
+        if reuse is not None:
+            reuse.end_stage()
+    if ranks is None:
+        return out
+    rows = ranks.gather(out + done)  # the one collective of the loop: every rank's fitnesses and which ones it computed
+    for i in range(n):  # every candidate by its owner and by nobody else: the ranks agreed on the map
+        who = [r for r in range(world) if rows[r][n + i] == 1.0]
+        assert who == [owner[i]], f"candidate {i} belongs to rank {owner[i]} and was evaluated by ranks {who}"
+    return [rows[owner[i]][i] for i in range(n)]
+
+
 def search(ctx: _Ctx, evaluate: Callable, calibration_data, rng: random.Random, *, generations: int, offspring: int,
            target_bitwidth: float, survivors_per_selection: Sequence[int], tokens_per_selection: Sequence[int],
            group_rule: str = "size", fitness_fn: str = "ppl", target_logits=None, initially_generated: Optional[int] = None,
-           initial_tokens: Optional[int] = None, on_generation: Optional[Callable] = None):
+           initial_tokens: Optional[int] = None, on_generation: Optional[Callable] = None, reuse=None, ranks=None):
     """The loop of main() (:401-779) -> (final parent, its last train fitness, trace).  trace: one dict per generation,
     {"parent", "offspring", "stages": [selection's record per stage]} (and "initial" for a fractional target).
-    on_generation(generation, parent, parent_bits, train_fitness) is called before each generation's offspring are made."""
+    on_generation(generation, parent, parent_bits, train_fitness) is called before each generation's offspring are made.
+    reuse / ranks: handed to every selection() (the initial one of a fractional target has no parent and reuses nothing)."""
     assert len(survivors_per_selection) == len(tokens_per_selection), "Must have same number of stages"
     assert survivors_per_selection[-1] == 1, "Last stage should have only one survivor"
     trace = []
@@ -293,7 +342,7 @@ def search(ctx: _Ctx, evaluate: Callable, calibration_data, rng: random.Random, 
         assert initial_tokens is not None, "Need initial_tokens for non-integer initial level"
         stage = []
         cands, fits = selection(evaluate, initial_candidates(ctx, target_bitwidth, initially_generated, rng), 1,
-                                calibration_data, initial_tokens, rng, fitness_fn, target_logits, stage)
+                                calibration_data, initial_tokens, rng, fitness_fn, target_logits, stage, ranks=ranks)
         parent, train_fitness = cands[0], fits[0]
         trace.append({"initial": stage[0]})
     for generation in range(generations):
@@ -306,7 +355,8 @@ def search(ctx: _Ctx, evaluate: Callable, calibration_data, rng: random.Random, 
                 if parent not in offspring_list:  # elitist: the parent competes in the last stage
                     offspring_list.append(parent)
             offspring_list, train_fitnesses = selection(evaluate, offspring_list, num_survive, calibration_data, num_tokens,
-                                                        rng, fitness_fn, target_logits, rec["stages"])
+                                                        rng, fitness_fn, target_logits, rec["stages"], parent=parent,
+                                                        reuse=reuse, ranks=ranks)
         train_fitness, parent = train_fitnesses[0], offspring_list[0]
         trace.append(rec)
     return parent, train_fitness, trace
@@ -364,6 +414,15 @@ def parse_args(argv=None):
     p.add_argument("--resident", type=str, default="dense", choices=["dense", "packed"],
                    help="dense (default): the model keeps a dense live weight per Linear and a switch decodes into it; packed: "
                         "no dense copy, the forward reads the stored block bytes (fp16 / bf16 models, packed levels)")
+    p.add_argument("--reuse_prefix", type=str, default="off", choices=["off", "on"],
+                   help="on: run the parent once per minibatch and evaluate every candidate from its first changed block "
+                        "(suffix_forward); the trajectory is the one of `off`")
+    p.add_argument("--reuse_prefix_bytes", type=int, default=None,
+                   help="device memory the cached hidden states may take (default: what is free, less a reserve)")
+    p.add_argument("--backend", type=str, default=None, choices=["nccl", "gloo"],
+                   help="under torch.distributed.run: nccl (= RCCL; default with one GPU per rank) or gloo (default "
+                        "otherwise: the ranks share the visible GPUs)")
+    p.add_argument("--trace_out", type=str, default=None, help="write search()'s trace to this file as JSON (rank 0)")
     args = p.parse_args(argv)
     # every refusal BEFORE any work
     for what, names in (("calibration_data", [args.calibration_data]), ("eval_datasets", args.eval_datasets)):
@@ -387,14 +446,57 @@ def parse_args(argv=None):
     return args
 
 
-def compute_fitness(model, data, fitness_fn: str, target_logits=None) -> float:
-    """:141-147"""
+def compute_fitness(model, data, fitness_fn: str, target_logits=None, logits_fn=None) -> float:
+    """:141-147.  logits_fn: metrics' way to take a sequence's logits from something other than model(inputs)."""
     from . import metrics
     if fitness_fn == "ppl":
-        return metrics.compute_perplexity(model, data)
+        return metrics.compute_perplexity(model, data, logits_fn=logits_fn)
     if fitness_fn == "kl":
-        return metrics.compute_kl_div(model, data, target_logits)
-    return metrics.compute_sparse_kl_div(model, data, target_logits)
+        return metrics.compute_kl_div(model, data, target_logits, logits_fn=logits_fn)
+    return metrics.compute_sparse_kl_div(model, data, target_logits, logits_fn=logits_fn)
+
+
+def suffix_evaluate(store, runner, model, fitness_fn: str) -> Callable:
+    """evaluate(candidate, data, targets[, start_block]) on a level store: the plain evaluation, or with start_block the
+    logits of every sequence from the runner's cached boundary."""
+    def evaluate(candidate, data, targets, start_block=None):
+        store.switch(candidate)
+        if start_block is None:
+            return compute_fitness(model, data, fitness_fn, targets)
+        return compute_fitness(model, data, fitness_fn, targets,
+                               logits_fn=lambda i, inputs: runner.logits(i, start_block, inputs))
+    return evaluate
+
+
+def sharded_perplexity(model, data, ranks) -> float:
+    """compute_perplexity with the sequences dealt to the ranks (sequence i to rank i % world_size): every rank sums the
+    fp32 per-row NLL of its share in fp64, one gather of (sum, rows) per rank, exp(total / rows).  Reporting only: the last
+    digits may differ from one rank's compute_perplexity (another order of the fp64 sum)."""
+    import torch
+    from . import metrics
+    mine = data[ranks.rank::ranks.world_size]
+    rows = metrics.nll_rows(model, mine)
+    parts = ranks.gather([float(rows.sum(dtype=torch.float64).item()), float(rows.numel())])
+    return math.exp(sum(p[0] for p in parts) / sum(p[1] for p in parts))
+
+
+def init_ranks(backend: Optional[str]):
+    """Under torch.distributed.run: join the process group -> (Ranks, device); otherwise (None, cuda)."""
+    import torch
+    if "RANK" not in os.environ or not torch.distributed.is_available():
+        return None, torch.device("cuda")
+    import torch.distributed as dist
+    from .suffix_forward import Ranks
+    world, local = int(os.environ["WORLD_SIZE"]), int(os.environ.get("LOCAL_RANK", os.environ["RANK"]))
+    own_gpu = torch.cuda.device_count() >= int(os.environ.get("LOCAL_WORLD_SIZE", world))
+    backend = backend or ("nccl" if own_gpu else "gloo")
+    device = torch.device("cuda", local if own_gpu else local % torch.cuda.device_count())
+    torch.cuda.set_device(device)
+    if backend == "nccl":
+        dist.init_process_group("nccl", device_id=device)  # nccl == RCCL on ROCm
+    else:
+        dist.init_process_group("gloo")
+    return Ranks(device if backend == "nccl" else "cpu"), device
 
 
 def collect_targets(model, calibration_data, fitness_fn: str, kl_topk: int, targets_on: str, reserve_bytes: int = 0):
@@ -423,14 +525,30 @@ def collect_targets(model, calibration_data, fitness_fn: str, kl_topk: int, targ
 def main(argv=None):
     args = parse_args(argv)
     import torch
+    assert torch.cuda.is_available(), "evo_quant_search needs a GPU (there is no CPU path)"
+    ranks, device = init_ranks(args.backend)
+    try:
+        return _run(args, ranks, device)
+    finally:  # also when the run raises: the launcher then reports the real error, not a hung rendezvous
+        if ranks is not None:
+            torch.distributed.destroy_process_group()
+
+
+def _run(args, ranks, device):
+    """Every rank loads the model, builds its own level store, holds all targets and seeds the same random.Random: the host
+    decisions of the trajectory are replicated (a rank's cache stride is its own and decides nothing shared: _evaluate_stage).
+    Rank 0 alone prints the report, logs and writes."""
+    import json
+    import torch
     from . import metrics
+    from . import dist_utils
     from .level_store import LevelStore
     from .ppleval import load_hf_model
-    assert torch.cuda.is_available(), "evo_quant_search needs a GPU (there is no CPU path)"
-    device = torch.device("cuda")
+    main_rank = ranks is None or ranks.rank == 0
+    say = dist_utils.print_on_main  # every line of the run's report is rank 0's
     metrics.fix_seed(args.seed)
     rng = random.Random(args.seed)
-    if args.log_wandb:
+    if args.log_wandb and main_rank:
         import wandb
         wandb.init(config=args)
     model = load_hf_model(args, device)
@@ -450,74 +568,93 @@ def main(argv=None):
         # no place for it) and is not searched -- it keeps the model's own weights
         outside = [n for n in names if not _in_a_block(n)]
         if outside:
-            print(f"not searched (no Linear of a block): {outside}")
+            say(f"not searched (no Linear of a block): {outside}")
         names = [n for n in names if n not in outside]
         available = scan_available_bitwidths(args.quant_weights_path, names)
-    print("Available bitwidths:")
+    say("Available bitwidths:")
     for layer_name, bitwidths in available.items():
-        print(f"{layer_name}: {[bw for bw, _ in bitwidths]}")
+        say(f"{layer_name}: {[bw for bw, _ in bitwidths]}")
     layer_names = sorted(available, key=layer_order_fn)
     grouped = group_layers(model, layer_names, args.group_rule)
-    print(grouped)
+    say(grouped)
     if args.resident == "packed":  # the targets need the unmodified dense model: first, before the store frees it
         target_logits, where = collect_targets(model, calibration_data, args.fitness_fn, args.kl_topk, args.targets_on)
     # refuses what does not fit before uploading
     store = LevelStore(model, args.quant_weights_path, device, layer_names, resident=args.resident)
     store.grouped_layer_names = grouped
-    print(f"level store: {store.bytes()} bytes on {device}" +
+    say(f"level store: {store.bytes()} bytes on {device}" +
           (f", {store.freed_bytes} bytes of dense weights freed" if args.resident == "packed" else ""))
     if args.resident != "packed":
         target_logits, where = collect_targets(model, calibration_data, args.fitness_fn, args.kl_topk, args.targets_on)
     if args.fitness_fn != "ppl":
-        print(f"targets on: {where}")
+        say(f"targets on: {where}")
 
     ctx = _Ctx(model, grouped, available, target_bits_of(grouped, model, args.target_bitwidth))
     quantizable_weights = sum(model.get_submodule(n).weight.numel() for n in layer_names)
     log_dict = {}
 
-    def evaluate(candidate, data, targets):
-        store.switch(candidate)
-        return compute_fitness(model, data, args.fitness_fn, targets)
+    reuse = runner = None
+    if args.reuse_prefix == "on":
+        from .suffix_forward import StageReuse, SuffixRunner
+        # (a stage that does not fit is a rank's own finding: that message comes from the rank it concerns)
+        log = say if ranks is None else (lambda msg: print(f"[rank {ranks.rank}] {msg}"))
+        runner = SuffixRunner(model, budget_bytes=args.reuse_prefix_bytes, log=log)
+        reuse = StageReuse(runner, store)
+    evaluate = suffix_evaluate(store, runner, model, args.fitness_fn)
 
-    def evaluate_parent(tag=""):
+    def perplexity(data):
+        return metrics.compute_perplexity(model, data) if ranks is None else sharded_perplexity(model, data, ranks)
+
+    def evaluate_parent(tag=""):  # (the store's state is the caller's; a stage's cache never outlives its stage)
         for name, data in zip(args.eval_datasets, eval_datasets):
-            ppl = metrics.compute_perplexity(model, data)
-            print(f"{name}: {ppl:.2f}")
+            ppl = perplexity(data)
+            say(f"{name}: {ppl:.2f}")
             log_dict[f"ppl_eval/{name}"] = ppl
-        ppl_train = metrics.compute_perplexity(model, calibration_data)
-        print(f"ppl_train: {ppl_train:.2f}")
+        ppl_train = perplexity(calibration_data)
+        say(f"ppl_train: {ppl_train:.2f}")
         log_dict["ppl_train"] = ppl_train
 
     def on_generation(generation, parent, parent_bits, train_fitness):
-        print(f"Generation {generation + 1}/{args.generations}")
-        print("Current search point:")
+        say(f"Generation {generation + 1}/{args.generations}")
+        say("Current search point:")
         for group in parent:
-            print(group)
-        print(f"Parent bits: {parent_bits}")
-        print(f"Bit average: {parent_bits / quantizable_weights:.4e}")
-        print(f"Train fitness: {train_fitness:.4e}")
+            say(group)
+        say(f"Parent bits: {parent_bits}")
+        say(f"Bit average: {parent_bits / quantizable_weights:.4e}")
+        say(f"Train fitness: {train_fitness:.4e}")
+        if runner is not None:
+            runner.invalidate()
         store.switch(parent)
         if generation % args.eval_every == 0:
             evaluate_parent()
-        if args.log_wandb:
+        if args.log_wandb and main_rank:
             wandb.log(log_dict)
 
-    parent, train_fitness, _ = search(
+    parent, train_fitness, trace = search(
         ctx, evaluate, calibration_data, rng, generations=args.generations, offspring=args.offspring,
         target_bitwidth=args.target_bitwidth, survivors_per_selection=args.survivors_per_selection,
         tokens_per_selection=args.tokens_per_selection, group_rule=args.group_rule, fitness_fn=args.fitness_fn,
         target_logits=target_logits, initially_generated=args.initially_generated, initial_tokens=args.initial_tokens,
-        on_generation=on_generation)
+        on_generation=on_generation, reuse=reuse, ranks=ranks)
     log_dict["train_fitness"] = train_fitness
+    if reuse is not None:
+        say(f"reuse_prefix: {sum(st[0] for st in reuse.stages)} of {len(reuse.stages)} stages reused the parent's prefix "
+              f"({runner.captures} captures on this rank)")
     out = os.path.join(args.quant_weights_path, configuration_name(args.fitness_fn, args.target_bitwidth))
-    with open(out, "w") as f:
-        f.write(configuration_text(grouped, parent, available))
-    print("Final configuration:")
+    if main_rank:  # to a temporary name, then renamed: no reader sees half a file
+        with open(out + ".tmp", "w") as f:
+            f.write(configuration_text(grouped, parent, available))
+        os.replace(out + ".tmp", out)
+        if args.trace_out:
+            with open(args.trace_out + ".tmp", "w") as f:
+                json.dump(trace, f)
+            os.replace(args.trace_out + ".tmp", args.trace_out)
+    say("Final configuration:")
     for group in parent:
-        print(group)
+        say(group)
     store.switch(parent)
     evaluate_parent()
-    if args.log_wandb:
+    if args.log_wandb and main_rank:
         wandb.log(log_dict)
     return parent, out
 

@@ -67,14 +67,16 @@ def nll_rows(model, data, batch_size: int = 1) -> torch.Tensor:
 
 
 @torch.no_grad()
-def compute_perplexity(model, data, batch_size: int = 1) -> float:
-    """exp(mean NLL of the next token) over all sequences (metrics.py:10-37)."""
+def compute_perplexity(model, data, batch_size: int = 1, logits_fn=None) -> float:
+    """exp(mean NLL of the next token) over all sequences (metrics.py:10-37).  logits_fn(i, inputs) -> [1, L, V], when given,
+    stands for model(inputs).logits of sequence i (suffix_forward: a forward from a cached block boundary)."""
+    assert logits_fn is None or batch_size == 1
     device = _device(model)
     total, rows = torch.zeros((), dtype=torch.float64, device=device), 0
     for i in range(0, len(data), batch_size):
         j = min(i + batch_size, len(data))
         inputs = _batch(data, i, j, device)
-        logits = model(inputs).logits
+        logits = model(inputs).logits if logits_fn is None else logits_fn(i, inputs)
         labels = torch.full_like(inputs, IGNORE)
         labels[:, :-1] = inputs[:, 1:]
         total += ops.eval_nll(logits, labels, IGNORE).sum(dtype=torch.float64)  # ignored rows are exact zeros
@@ -83,16 +85,18 @@ def compute_perplexity(model, data, batch_size: int = 1) -> float:
 
 
 @torch.no_grad()
-def compute_kl_div(model, data, target_logits, batch_size: int = 1) -> float:
+def compute_kl_div(model, data, target_logits, batch_size: int = 1, logits_fn=None) -> float:
     """mean over rows of KL(softmax(target) || softmax(model)), the last position of a sequence left out
-    (metrics.py:41-86).  target_logits: a list of [1, L, V] tensors (collect_target_logits)."""
+    (metrics.py:41-86).  target_logits: a list of [1, L, V] tensors (collect_target_logits).  logits_fn: as
+    compute_perplexity's."""
+    assert logits_fn is None or batch_size == 1
     device = _device(model)
     total, rows = torch.zeros((), dtype=torch.float64, device=device), 0
     for i in range(0, len(data), batch_size):
         j = min(i + batch_size, len(data))
         inputs = _batch(data, i, j, device)
         targets = _batch(target_logits, i, j, device)
-        logits = model(inputs).logits
+        logits = model(inputs).logits if logits_fn is None else logits_fn(i, inputs)
         kl = ops.eval_kl(logits[:, :-1, :], targets[:, :-1, :])  # row views, read in place
         total += kl.sum(dtype=torch.float64)
         rows += kl.numel()
@@ -100,15 +104,15 @@ def compute_kl_div(model, data, target_logits, batch_size: int = 1) -> float:
 
 
 @torch.no_grad()
-def compute_sparse_kl_div(model, data, target_logits) -> float:
+def compute_sparse_kl_div(model, data, target_logits, logits_fn=None) -> float:
     """The same over the target's top-k columns only, both softmaxes over those k (metrics.py:89-119).
-    target_logits: a list of (topk_values [1, L, k], topk_indices [1, L, k]) pairs."""
+    target_logits: a list of (topk_values [1, L, k], topk_indices [1, L, k]) pairs.  logits_fn: as compute_perplexity's."""
     device = _device(model)
     total, rows = torch.zeros((), dtype=torch.float64, device=device), 0
     for i in range(len(data)):
         inputs = data[i].to(device)
         vals, ids = (t.to(device) for t in target_logits[i])
-        logits = model(inputs).logits
+        logits = model(inputs).logits if logits_fn is None else logits_fn(i, inputs)
         kl = ops.eval_kl_sparse(logits[:, :-1, :], vals[:, :-1, :], ids[:, :-1, :])
         total += kl.sum(dtype=torch.float64)
         rows += kl.numel()
