@@ -37,6 +37,9 @@ EXPORTS_Q8 = ("gq_quantize_q8_0",)
 Q8_0 = 8  # GQ_Q8_0: the ggml type id
 # include/gptq_gguf_qgemm.h: the packed-weight forward, a GEMM that reads block bytes as its weight operand (additive in the same way)
 EXPORTS_QGEMM = ("gq_linear_packed",)
+# include/gptq_gguf_qgemv.h: the same forward for the 1 .. 16 tokens of a decode step (additive in the same way)
+EXPORTS_QGEMV = ("gq_gemv_packed",)
+GEMV_MAX_T = 16  # GQ_GEMV_MAX_T: tokens of one gq_gemv_packed call
 
 
 class GQError(RuntimeError):
@@ -146,6 +149,7 @@ def lib():
     L.gq_pack_bands.argtypes = [vp, vp, vp, vp, vp, i64, i64, ctypes.POINTER(Band), ci, ctypes.POINTER(vp), ctypes.POINTER(vp), vp]
     L.gq_quantize_q8_0.argtypes = [vp, ci, i64, i64, vp, vp, vp]
     L.gq_linear_packed.argtypes = [ci, vp, vp, i64, i64, vp, i64, ci, vp, vp]
+    L.gq_gemv_packed.argtypes = [ci, vp, vp, i64, i64, vp, i64, ci, vp, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -153,7 +157,8 @@ def lib():
     L.gq_prof_collect.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
-    for name in EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_QGEMM:
+    for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_QGEMM +
+                 EXPORTS_QGEMV):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

@@ -46,23 +46,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int TR = 128, KC = 64;  // tile of rows; k of an x chunk (the token tile TT = 256 or 128 is a template parameter)
 constexpr int64_t WIDE_TILES = 512;  // two workgroups on each of the 256 CUs: from there on the 256-token tile is used
 
-// the staging of one row's share of a superblock: UPR units of AL bytes, unit o at LDS byte lds_off(o) of the row's slot
-template <int QT> struct QL {
-    using L = Lay<QT>;
-    static constexpr int AL = L::AL, UPR = L::TS / L::AL, ROWB = L::TS;
-    static constexpr int SLOT = ((L::TS + 15) / 16 | 1) * 16;
-    static __device__ __forceinline__ int lds_off(int o) { return o * AL; }
-};
-template <> struct QL<GQ_Q8_0> {  // 8 blocks of 34 bytes: the eight d at bytes 0 .. 15, block b's 32 codes at 16 + 32 b
-    static constexpr int AL = 2, UPR = 8 * Q8_UPB, ROWB = 8 * Q8_TS;
-    static constexpr int SLOT = 16 + 8 * 32 + 32;
-    static __device__ __forceinline__ int lds_off(int o) {
-        const int b = o / Q8_UPB, w = o - b * Q8_UPB;
-        return w == 0 ? 2 * b : 16 + 32 * b + 2 * (w - 1);
-    }
-};
-static_assert(QL<GQ_Q8_0>::SLOT / 16 % 2 == 1, "an odd number of 16-byte units");
-
 // Stage superblock j of the tile's nr rows: sbase[r] = byte offset of the row's first block.  The caller has a barrier before
 // (sb free) and after.
 template <int QT>
@@ -87,36 +70,6 @@ __device__ __forceinline__ void stage_rows(const uint8_t* __restrict__ blocks, c
             if (u < n) *reinterpret_cast<U*>(sb + r * Q::SLOT + Q::lds_off(o)) = v[g];
         }
     }
-}
-
-// The 16 values 64 c + 16 q .. + 15 of the superblock in slot B, as 8 words of two OutT bit patterns: decode_turn's text.
-template <int QT, typename OutT>
-__device__ __forceinline__ void decode16(const uint8_t* B, int c, int q, uint32_t w[8]) {
-    uint32_t cd[4];
-    uint16_t o[16];
-    if constexpr (QT == GQ_Q8_0) {
-        const int b = 2 * c + (q >> 1);
-        const float d = h2f(ld2(B + 2 * b));
-        ld16(B + 16 + 32 * b + 16 * (q & 1), cd);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) o[k] = cvt_out<OutT>(q8_0_dequantize1(d, (cd[k >> 2] >> (8 * (k & 3))) & 0xffu)).b;
-    } else {
-        using L = Lay<QT>;
-        const int g16 = 4 * c + q;
-        uint16_t d, dmin;
-        int sc, mn;
-        block_d<QT>(B, d, dmin);
-        group_scale<QT>(B, g16 * L::NG / 16, sc, mn);
-        const float ds = h2f(d) * (float)sc, dm = h2f(dmin) * (float)mn;
-        codes16<QT>(B, g16, cd);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const float code = (float)((cd[k >> 2] >> (8 * (k & 3))) & 0xffu) - (float)L::OFF;
-            o[k] = cvt_out<OutT>(dequantize1(code, ds, dm)).b;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) w[k] = (uint32_t)o[2 * k] | ((uint32_t)o[2 * k + 1] << 16);
 }
 
 template <bool BF16>

@@ -1,0 +1,211 @@
+// gq_qgemv.hip -- K22: y = x W^T for 1 <= T <= 16 tokens and a weight [R, C] that exists only as GGUF block bytes (K-quants,
+// Q8_0): the decode step of a packed model.  gq_gemv_packed has the contract of gq_linear_packed (K21) -- the same operand
+// bits, fp32 accumulation, one rounding -- at the shape where that kernel launches R / 128 workgroups and fills 127 of 128
+// tokens of its tile with zeros.  Here the call is one stream over the weight bytes, spread over the whole device.
+//
+// Form: v_mfma_f32_16x16x32_{f16,bf16} with A = 16 rows of W and B = the (at most 16) tokens, fragments as in K21: lane l
+// holds W[r = l & 15][8 (l >> 4) + j] and x[t = l & 15][8 (l >> 4) + j], D[r = 4 (l >> 4) + i][t = l & 15] in register i.  The
+// matrix pipe does the T-fold work, so one kernel serves every T and the cost per weight is the decode alone.
+//
+// A workgroup owns 16 rows and all of C; its NW = min(16, C / 256) waves take the superblocks j = w, w + NW, ... of those
+// rows (K split across the waves of ONE workgroup, never across workgroups).  A [4096, 4096] weight is 256 workgroups of 16
+// waves, one superblock of 16 rows each.  Per superblock a wave
+//   * loads its x fragment straight to registers: lane (t, q) reads x[t][256 j + 64 c + 16 q .. + 15] for c = 0 .. 3, two
+//     16-byte loads per chunk, chunk c + 1's in flight during chunk c's decode (lanes with t >= T load nothing and hold
+//     zeros); x is re-read by every workgroup and comes from the caches;
+//   * stages the 16 rows' packed bytes of the superblock in its own LDS slots with loads of the type's natural alignment that
+//     cover exactly the blocks' bytes (QL<QT>, the slot layout of K21), consecutive lanes on consecutive bytes of a row;
+//   * decodes per 64-k chunk the 16 consecutive values of its row with decode16 (block_d / group_scale / codes16 / dequantize1
+//     / cvt_out: the operand bits are gq_dequantize_blocks') and issues two MFMAs.
+// The LDS slots are wave-private: a wavefront-scope fence orders the staging writes and the decode reads, no workgroup barrier
+// sits in the K loop.  The staging goes through LDS for every type, Q4_K and Q5_K included: the A fragment of an MFMA is 16
+// different rows per instruction, so direct loads would be 16-byte pieces 16 rows apart; staged, a row's bytes are read once,
+// contiguously.
+// The partial sums of the NW waves meet in LDS (each wave's 1 KB at the start of its own slots) after the one barrier of the
+// kernel; wave 0 adds them in wave order 0, 1, .. NW - 1 and stores: deterministic, no atomics, no workspace.
+// Rows >= R of the last workgroup are not staged (their slots hold stale bytes; an MFMA row depends on its own A row only, and
+// those D rows are never stored).  y is stored 8 bytes wide where R % 4 == 0, else 2 bytes wide with a row check.
+#include "../../../include/gptq_gguf_qgemv.h"
+#include <type_traits>
+
+#include "../search/gq_block_decode.hpp"
+
+namespace gq {
+namespace {
+
+using namespace blockdec;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int VR = 16;      // rows of a workgroup (one MFMA tile)
+constexpr int MAX_NW = 16;  // waves of a workgroup: the K split
+
+template <bool BF16>
+__device__ __forceinline__ f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
+    if constexpr (BF16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
+// the LDS accesses of one wave to its own slots, in program order for every lane of it
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Stage superblock j of the workgroup's nr rows into the wave's slots sb: lane r (< 16) holds in `base` the byte offset of row
+// r's first block, the other lanes fetch it by shuffle.
+template <int QT>
+__device__ __forceinline__ void stage_wave(const uint8_t* __restrict__ blocks, int64_t base, int64_t j, int nr, int lane,
+                                           uint8_t* sb) {
+    using Q = QL<QT>;
+    using U = typename std::conditional<Q::AL == 16, u32x4, typename Unit<Q::AL>::T>::type;  // (a vector type stays in registers)
+    // 3 (Q4_K) .. 34 (Q8_0) loads per lane, in groups of at most 17 that are all in flight before the group's first LDS write
+    // (all 27 or 34 at once spill; measured, groups of 8 are no slower: the 2-byte types pay for the number of loads)
+    constexpr int NIT = (VR * Q::UPR + 63) / 64, GRP = NIT < 17 ? NIT : 17;
+    const int n = nr * Q::UPR;
+#pragma unroll 1
+    for (int it0 = 0; it0 < NIT; it0 += GRP) {
+        U v[GRP] = {};
+#pragma unroll
+        for (int g = 0; g < GRP; ++g) {
+            const int u = lane + 64 * (it0 + g), r = u / Q::UPR, o = u - r * Q::UPR;
+            const int64_t rb = __shfl(base, r & (VR - 1));  // (every lane takes part; r < 16 where u < n)
+            if (it0 + g < NIT && u < n) v[g] = *reinterpret_cast<const U*>(blocks + rb + j * Q::ROWB + o * Q::AL);
+        }
+#pragma unroll
+        for (int g = 0; g < GRP; ++g) {
+            const int u = lane + 64 * (it0 + g), r = u / Q::UPR, o = u - r * Q::UPR;
+            if (it0 + g < NIT && u < n) *reinterpret_cast<U*>(sb + r * Q::SLOT + Q::lds_off(o)) = v[g];
+        }
+    }
+}
+
+template <int QT, bool BF16>
+__global__ __launch_bounds__(64 * MAX_NW) void gemv_packed_kernel(const uint8_t* __restrict__ blocks,
+                                                                  const int32_t* __restrict__ row_src, int64_t R, int64_t C,
+                                                                  const uint8_t* __restrict__ x, int T, uint16_t* __restrict__ y) {
+    using Q = QL<QT>;
+    using OutT = typename std::conditional<BF16, bf16_bits, half_bits>::type;
+    static_assert(VR * Q::SLOT >= 64 * 16, "a wave's slots hold its partial sums");
+    __shared__ __attribute__((aligned(16))) uint8_t smem[MAX_NW * VR * Q::SLOT];  // a wave's VR slots at wave * VR * SLOT
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6, l15 = lane & 15, q = lane >> 4;
+    uint8_t* sb = smem + wave * VR * Q::SLOT;
+    const int64_t r0 = (int64_t)blockIdx.x * VR, nsb = C / 256;
+    const int nr = (int)((R - r0) < VR ? (R - r0) : VR);
+    const int64_t base = l15 < nr ? (row_src ? (int64_t)row_src[r0 + l15] : r0 + l15) * nsb * Q::ROWB : 0;  // row l15's first block
+
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const uint8_t* B = sb + l15 * Q::SLOT;
+    const uint8_t* xl = x + ((int64_t)l15 * C + 16 * q) * 2;  // token l15 (read only where l15 < T)
+#pragma unroll 1
+    for (int64_t j = wave; j < nsb; j += nw) {
+        u32x4 xr[2], xn[2] = {};  // piece s of chunk c: x[t][256 j + 64 c + 16 q + 8 s .. + 7]
+#pragma unroll
+        for (int s = 0; s < 2; ++s) xr[s] = l15 < T ? *reinterpret_cast<const u32x4*>(xl + (256 * j + 8 * s) * 2) : u32x4{0, 0, 0, 0};
+        stage_wave<QT>(blocks, base, j, nr, lane, sb);
+        wave_sync();
+#pragma unroll 1
+        for (int c = 0; c < 4; ++c) {
+            if (c < 3 && l15 < T) {  // the next chunk's x is in flight during this chunk's decode
+#pragma unroll
+                for (int s = 0; s < 2; ++s) xn[s] = *reinterpret_cast<const u32x4*>(xl + (256 * j + 64 * (c + 1) + 8 * s) * 2);
+            }
+            uint32_t w[8];
+            decode16<QT, OutT>(B, c, q, w);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                acc = mfma<BF16>(u32x4{w[4 * s], w[4 * s + 1], w[4 * s + 2], w[4 * s + 3]}, xr[s], acc);
+                xr[s] = xn[s];
+            }
+        }
+        wave_sync();  // the slots may be overwritten
+    }
+
+    *reinterpret_cast<f32x4*>(sb + lane * 16) = acc;
+    __syncthreads();
+    if (wave != 0) return;
+    acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int w = 0; w < nw; ++w) {  // wave order: the same bits every call
+        const f32x4 p = *reinterpret_cast<const f32x4*>(smem + w * VR * Q::SLOT + lane * 16);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] += p[i];
+    }
+    const int64_t r = r0 + 4 * q;
+    if (l15 >= T || r >= R) return;
+    uint16_t o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = cvt_out<OutT>(acc[i]).b;
+    uint16_t* py = y + (int64_t)l15 * R + r;
+    if ((R & 3) == 0) {  // then (t R + r) * 2 is 8-byte aligned for r % 4 == 0
+        *reinterpret_cast<uint2*>(py) = make_uint2((uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16));
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (r + i < R) py[i] = o[i];
+    }
+}
+
+bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+int block_align(int q) { return q == GQ_Q2_K ? 4 : (q == GQ_Q4_K || q == GQ_Q5_K) ? 16 : 2; }
+
+template <int QT>
+void launch(bool bf16, dim3 grid, int nw, hipStream_t st, const uint8_t* blocks, const int32_t* row_src, int64_t R, int64_t C,
+            const uint8_t* x, int T, uint16_t* y) {
+    if (bf16) hipLaunchKernelGGL((gemv_packed_kernel<QT, true>), grid, dim3(64 * nw), 0, st, blocks, row_src, R, C, x, T, y);
+    else hipLaunchKernelGGL((gemv_packed_kernel<QT, false>), grid, dim3(64 * nw), 0, st, blocks, row_src, R, C, x, T, y);
+}
+
+}  // namespace
+}  // namespace gq
+
+using namespace gq;
+
+extern "C" {
+
+int gq_gemv_packed(int q_type, const void* blocks, const int32_t* row_src, int64_t R, int64_t C, const void* x, int64_t T,
+                   int x_dtype, void* y, void* stream) {
+    if (int rc = options_ok()) return rc;
+    const bool kq = q_type >= GQ_Q2_K && q_type <= GQ_Q6_K;
+    if (!kq && q_type != GQ_Q8_0) GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed: unknown q_type %d (a K-quant or GQ_Q8_0)", q_type);
+    if (x_dtype != GQ_F16 && x_dtype != GQ_BF16)
+        GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed: x_dtype %d (GQ_F16 or GQ_BF16; there is no fp32 path)", x_dtype);
+    if (!blocks) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed: blocks is NULL");
+    if (!x) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed: x is NULL");
+    if (!y) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed: y is NULL");
+    if (R < 1 || R > 0x7fffffff) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: R=%ld (not in [1, 2^31))", (long)R);
+    if (T < 1 || T > GQ_GEMV_MAX_T)
+        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: T=%ld (not in [1, %d]; gq_linear_packed takes more tokens)", (long)T, GQ_GEMV_MAX_T);
+    if (C < 256 || C > 0x7fffffff || C % 256)
+        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 included)", (long)C);
+    const int al = kq ? block_align(q_type) : 2;
+    if (!aligned(blocks, al)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: blocks not %d-byte aligned", al);
+    if (!aligned(row_src, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: row_src not 4-byte aligned");
+    if (!aligned(x, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: x not 16-byte aligned");
+    if (!aligned(y, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: y not 16-byte aligned");
+    const int64_t nsb = C / 256;
+    const int nw = (int)(nsb < MAX_NW ? nsb : MAX_NW);
+    const dim3 grid((unsigned)((R + VR - 1) / VR));  // < 2^27
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* b = static_cast<const uint8_t*>(blocks);
+    const uint8_t* xp = static_cast<const uint8_t*>(x);
+    uint16_t* yp = static_cast<uint16_t*>(y);
+    const bool bf = x_dtype == GQ_BF16;
+    switch (q_type) {
+    case GQ_Q2_K: launch<GQ_Q2_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
+    case GQ_Q3_K: launch<GQ_Q3_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
+    case GQ_Q4_K: launch<GQ_Q4_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
+    case GQ_Q5_K: launch<GQ_Q5_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
+    case GQ_Q6_K: launch<GQ_Q6_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
+    default: launch<GQ_Q8_0>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
+    }
+    GQ_LAUNCH_CHECK();
+    return GQ_OK;
+}
+
+}  // extern "C"

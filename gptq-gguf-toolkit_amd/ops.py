@@ -873,7 +873,37 @@ def level_switch(jobs) -> None:
     return None
 
 
-# ---- the packed-weight forward (gq_linear_packed): y = x W^T with W given as GGUF block bytes ----
+# ---- the packed-weight forward (gq_linear_packed, gq_gemv_packed): y = x W^T with W given as GGUF block bytes ----
+GEMV_MAX_T = _cabi.GEMV_MAX_T
+
+
+def _packed_args(who: str, q_type, blocks, x, row_src):
+    """The argument checks the two packed forwards share -> (k, R, C, T)."""
+    _need_cuda(blocks, x, row_src)
+    k = int(q_type)
+    bs, ts = block_geometry(k)
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise _cabi.GQError(f"{who}: x must be fp16 or bf16 (there is no fp32 path); got {x.dtype}")
+    if x.dim() < 1 or not x.is_contiguous() or x.numel() == 0:
+        raise _cabi.GQError(f"{who}: x must be a non-empty contiguous [..., C] tensor; got {tuple(x.shape)} strides "
+                            f"{tuple(x.stride())}")
+    for t in (blocks, row_src):
+        if t is not None and t.device != x.device:
+            raise _cabi.GQError(f"{who}: every tensor must be on one device ({x.device}); got one on {t.device}")
+    C = x.shape[-1]
+    if C % 256:
+        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 included)")
+    row_bytes = C // bs * ts
+    if (blocks.dtype != torch.uint8 or blocks.dim() not in (1, 2) or not blocks.is_contiguous() or blocks.numel() == 0
+            or blocks.numel() % row_bytes or (blocks.dim() == 2 and blocks.shape[1] != row_bytes)):
+        raise _cabi.GQError(f"{who}: packed blocks of q_type {k} for C={C} must be contiguous uint8, R rows of "
+                            f"{row_bytes} bytes; got {blocks.dtype} {tuple(blocks.shape)}")
+    R, T = blocks.numel() // row_bytes, x.numel() // C
+    if row_src is not None and (row_src.dtype != torch.int32 or row_src.numel() != R or not row_src.is_contiguous()):
+        raise _cabi.GQError(f"{who}: row_src must be a contiguous int32 [{R}] tensor")
+    return k, R, C, T
+
+
 def linear_packed(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [..., C] fp16 / bf16, contiguous, times the weight [R, C] that `blocks` holds packed (a K-quant q_type 10..14 or
     Q8_0 8; uint8, any 1-D / 2-D contiguous view of exactly R rows of C / 256 blocks -- Q8_0: C / 32 blocks of 34 bytes)
@@ -881,29 +911,21 @@ def linear_packed(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src: O
     bit for bit dequantize_blocks(q_type, blocks, x.dtype, row_src); fp32 accumulation, one rounding.  row_src: None or
     int32 [R], row r of the weight is packed row row_src[r]; every index must lie in [0, R) -- the kernel does not check.
     No dense weight, no workspace, no host read."""
-    _need_cuda(blocks, x, row_src)
-    k = int(q_type)
-    bs, ts = block_geometry(k)
-    if x.dtype not in (torch.float16, torch.bfloat16):
-        raise _cabi.GQError(f"linear_packed: x must be fp16 or bf16 (there is no fp32 path); got {x.dtype}")
-    if x.dim() < 1 or not x.is_contiguous() or x.numel() == 0:
-        raise _cabi.GQError(f"linear_packed: x must be a non-empty contiguous [..., C] tensor; got {tuple(x.shape)} strides "
-                            f"{tuple(x.stride())}")
-    for t in (blocks, row_src):
-        if t is not None and t.device != x.device:
-            raise _cabi.GQError(f"linear_packed: every tensor must be on one device ({x.device}); got one on {t.device}")
-    C = x.shape[-1]
-    if C % 256:
-        raise _cabi.GQError(f"linear_packed: C={C} (C % 256 != 0; Q8_0 included)")
-    row_bytes = C // bs * ts
-    if (blocks.dtype != torch.uint8 or blocks.dim() not in (1, 2) or not blocks.is_contiguous() or blocks.numel() == 0
-            or blocks.numel() % row_bytes or (blocks.dim() == 2 and blocks.shape[1] != row_bytes)):
-        raise _cabi.GQError(f"linear_packed: packed blocks of q_type {k} for C={C} must be contiguous uint8, R rows of "
-                            f"{row_bytes} bytes; got {blocks.dtype} {tuple(blocks.shape)}")
-    R, T = blocks.numel() // row_bytes, x.numel() // C
-    if row_src is not None and (row_src.dtype != torch.int32 or row_src.numel() != R or not row_src.is_contiguous()):
-        raise _cabi.GQError(f"linear_packed: row_src must be a contiguous int32 [{R}] tensor")
+    k, R, C, T = _packed_args("linear_packed", q_type, blocks, x, row_src)
     y = torch.empty(*x.shape[:-1], R, dtype=x.dtype, device=x.device)
     check(lib().gq_linear_packed(k, _ptr(blocks), _ptr(row_src), R, C, _ptr(x), T, _DT[x.dtype], _ptr(y), _stream(x)),
           "gq_linear_packed")
+    return y
+
+
+def gemv_packed(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_packed for the few tokens of a decode step (gq_gemv_packed): the same arguments, the same weight operand bits,
+    fp32 accumulation and one rounding, for 1 <= T = x.numel() // C <= GEMV_MAX_T tokens; the two differ by fp32 summation
+    order only.  One stream over the weight bytes that fills the device at T = 1, where linear_packed's token tile is empty."""
+    k, R, C, T = _packed_args("gemv_packed", q_type, blocks, x, row_src)
+    if T > GEMV_MAX_T:
+        raise _cabi.GQError(f"gemv_packed: T={T} tokens, at most GEMV_MAX_T={GEMV_MAX_T} (linear_packed takes more tokens)")
+    y = torch.empty(*x.shape[:-1], R, dtype=x.dtype, device=x.device)
+    check(lib().gq_gemv_packed(k, _ptr(blocks), _ptr(row_src), R, C, _ptr(x), T, _DT[x.dtype], _ptr(y), _stream(x)),
+          "gq_gemv_packed")
     return y

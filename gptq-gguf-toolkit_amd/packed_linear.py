@@ -3,6 +3,7 @@
     mods = install(model, names)                       # the named nn.Linear modules become PackedLinear, their dense storage is dropped
     mods[name].set_level(blocks, q_type, row_src)      # references only: no copy, no launch
     model(ids)                                         # forward = ops.linear_packed (gq_linear_packed): a GEMM that reads the block bytes
+                                                       # (ops.gemv_packed for the 1 .. gemv_max_t tokens of a decode step)
 
 The weight operand of that GEMM is, bit for bit, what a dense level switch (ops.level_switch) writes for the same level, so
 a packed-resident model differs from a dense-resident one only by the fp32 summation order of its Linears.  A level that
@@ -19,6 +20,10 @@ from ._cabi import GQError
 
 
 class PackedLinear(nn.Module):
+    # Inputs of 1 .. gemv_max_t tokens go through ops.gemv_packed, everything else through ops.linear_packed; 0 switches the
+    # routing off.  The default is the largest T at which profiles/qgemv_rate.txt has the GEMV no slower than the tile kernel
+    # for every type and shape measured (DESIGN K22); an instance may override it.
+    gemv_max_t = ops.GEMV_MAX_T
 
     def __init__(self, in_features: int, out_features: int, bias: Optional[nn.Parameter] = None,
                  dtype: torch.dtype = torch.float16):
@@ -60,7 +65,8 @@ class PackedLinear(nn.Module):
         self._need_level()
         if self.q_type is None:
             return F.linear(x, self.blocks, self.bias)
-        y = ops.linear_packed(self.q_type, self.blocks, x.contiguous(), self.row_src)
+        few = 1 <= x.numel() // self.in_features <= min(self.gemv_max_t, ops.GEMV_MAX_T)
+        y = (ops.gemv_packed if few else ops.linear_packed)(self.q_type, self.blocks, x.contiguous(), self.row_src)
         return y if self.bias is None else y + self.bias
 
     @torch.no_grad()
