@@ -40,6 +40,9 @@ EXPORTS_QGEMM = ("gq_linear_packed",)
 # include/gptq_gguf_qgemv.h: the same forward for the 1 .. 16 tokens of a decode step (additive in the same way)
 EXPORTS_QGEMV = ("gq_gemv_packed",)
 GEMV_MAX_T = 16  # GQ_GEMV_MAX_T: tokens of one gq_gemv_packed call
+# include/gptq_gguf_sample.h: logits -> token ids in one launch: temperature, top-k, top-p, the draw (additive in the same way)
+EXPORTS_SAMPLE = ("gq_sample_logits",)
+SAMPLE_MAX_K = 1024  # GQ_SAMPLE_MAX_K: the largest top_k
 
 
 class GQError(RuntimeError):
@@ -150,6 +153,7 @@ def lib():
     L.gq_quantize_q8_0.argtypes = [vp, ci, i64, i64, vp, vp, vp]
     L.gq_linear_packed.argtypes = [ci, vp, vp, i64, i64, vp, i64, ci, vp, vp]
     L.gq_gemv_packed.argtypes = [ci, vp, vp, i64, i64, vp, i64, ci, vp, vp]
+    L.gq_sample_logits.argtypes = [vp, ci, i64, i64, i64, ci, cf, cf, vp, vp, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -158,7 +162,7 @@ def lib():
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_QGEMM +
-                 EXPORTS_QGEMV):
+                 EXPORTS_QGEMV + EXPORTS_SAMPLE):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

@@ -153,19 +153,55 @@ def packed_linear_tensors(model: torch.nn.Module, path: str) -> Dict[str, tuple]
     return out
 
 
-def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor) -> Dict[str, torch.Tensor]:
+def packed_vocab_tensors(model: torch.nn.Module, path: str) -> Dict[str, tuple]:
+    """{HF module name: (GGUF tensor name, ggml type)} of the vocabulary ends that load_into_model(packed="all") keeps packed
+    beside packed_linear_tensors: `model.embed_tokens` (token_embd.weight) when it is an nn.Embedding and `lm_head`
+    (output.weight) when it is an nn.Linear, each if its tensor is a K-quant / Q8_0 of the module's shape with hidden % 256
+    == 0.  A file without output.weight ties the two: lm_head then names token_embd.weight as well, and both are kept or
+    neither.  A tensor stored as F16 / F32 is not among them (it loads dense)."""
+    _, tensors, _ = parse_gguf(str(path), mmap=True)
+    by_name = {name: (shape, gt) for name, shape, gt, _, _ in tensors}
+
+    def fits(gguf_name, mod, kind):
+        if gguf_name not in by_name:
+            return False
+        shape, gt = by_name[gguf_name]
+        try:
+            layer = model.get_submodule(mod)
+        except AttributeError:
+            return False
+        return ((gt in K_QUANTS or gt == GGMLType.Q8_0) and len(shape) == 2 and isinstance(layer, kind)
+                and tuple(layer.weight.shape) == tuple(shape) and shape[1] % 256 == 0)
+
+    out = {}
+    emb = fits("token_embd.weight", "model.embed_tokens", torch.nn.Embedding)
+    if "output.weight" in by_name:
+        if emb:
+            out["model.embed_tokens"] = ("token_embd.weight", by_name["token_embd.weight"][1])
+        if fits("output.weight", "lm_head", torch.nn.Linear):
+            out["lm_head"] = ("output.weight", by_name["output.weight"][1])
+    elif emb and fits("token_embd.weight", "lm_head", torch.nn.Linear):
+        out["model.embed_tokens"] = out["lm_head"] = ("token_embd.weight", by_name["token_embd.weight"][1])
+    return out
+
+
+def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bool = False) -> Dict[str, torch.Tensor]:
     """The packed half of load_into_model: the Linears of packed_linear_tensors become PackedLinear holding the file's
-    block bytes (with the rotary row gather of attn_q / attn_k as row_src) -> the state dict of everything else."""
+    block bytes (with the rotary row gather of attn_q / attn_k as row_src); with `vocab` also the modules of
+    packed_vocab_tensors (one device copy per GGUF tensor: a tied pair shares it) -> the state dict of everything else."""
+    from .packed_embedding import replace_embedding
     from .packed_linear import replace_linear
     if ref.dtype not in (torch.float16, torch.bfloat16):
         raise TypeError(f"load_into_model(packed=True) computes in fp16 / bf16, the model is {ref.dtype}")
     keep = packed_linear_tensors(model, path)
+    ends = packed_vocab_tensors(model, path) if vocab else {}
     by_gguf = {g: m for m, (g, _) in keep.items()}
     kv, tensors, buf = parse_gguf(str(path), mmap=True)
     arch = kv["general.architecture"][0] if "general.architecture" in kv else None
     n_head, n_kv = (kv_int(kv[k][0] if k in kv else None, k)
                     for k in (f"{arch}.attention.head_count", f"{arch}.attention.head_count_kv"))
     rows: Dict[tuple, Optional[torch.Tensor]] = {}  # one gather per (q or k, R)
+    held: Dict[str, torch.Tensor] = {}              # the vocabulary tensors' block bytes on the device, by GGUF name
     for name, shape, gt, off, nbytes in tensors:
         if name in by_gguf:
             key = (name.rsplit(".", 2)[-2], shape[0])
@@ -173,18 +209,31 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor) -> Dict[s
                 rows[key] = rotary_row_src(name, shape[0], arch, n_head, n_kv, ref.device)
             packed = replace_linear(model, by_gguf[name])
             packed.set_level(_host(buf, off, nbytes).to(ref.device), int(gt), rows[key])
-    skip = {m + ".weight" for m in keep}
-    return {k: t for k, t in iter_gguf_tensors(path, ref.device, ref.dtype, hf_layout=True, skip=by_gguf) if k not in skip}
+        elif any(g == name for g, _ in ends.values()):
+            held[name] = _host(buf, off, nbytes).to(ref.device)
+    for mod, (g, gt) in ends.items():
+        if mod == "lm_head":
+            replace_linear(model, mod).set_level(held[g], int(gt))
+        else:
+            replace_embedding(model, mod).set_level(held[g], int(gt))
+    skip = {m + ".weight" for m in list(keep) + list(ends)}
+    gone = set(by_gguf) | set(held)
+    return {k: t for k, t in iter_gguf_tensors(path, ref.device, ref.dtype, hf_layout=True, skip=gone) if k not in skip}
 
 
-def load_into_model(model: torch.nn.Module, path: str, packed: bool = False) -> torch.nn.Module:
+def load_into_model(model: torch.nn.Module, path: str, packed=False) -> torch.nn.Module:
     """Load the file's weights into `model` (parameters on a GPU), strict on names and shapes.  A tied lm_head (no
     `output.weight` in the file) follows token_embd.
     packed=True: the K-quant and Q8_0 tensors of the blocks' nn.Linear modules stay packed on the device -- each such Linear
     becomes a packed_linear.PackedLinear whose forward reads the block bytes (the q / k rotary permutation undone by its
-    row_src), about 4.5 bits per parameter for a Q4_K file instead of 16; embeddings, norms and lm_head load as without it."""
+    row_src), about 4.5 bits per parameter for a Q4_K file instead of 16; embeddings, norms and lm_head load as without it.
+    packed="all": that, and the vocabulary ends of packed_vocab_tensors: model.embed_tokens becomes a
+    packed_embedding.PackedEmbedding and lm_head a PackedLinear on the file's block bytes (a file without output.weight gives
+    both the same tensor: one device copy); an end stored as F16 / F32 loads dense as without it."""
+    if packed not in (False, True, "all"):
+        raise ValueError(f"load_into_model: packed must be False, True or 'all', got {packed!r}")
     ref = next(model.parameters())
-    sd = _load_packed(model, path, ref) if packed else load_state_dict(path, ref.device, ref.dtype)
+    sd = _load_packed(model, path, ref, vocab=packed == "all") if packed else load_state_dict(path, ref.device, ref.dtype)
     want = model.state_dict()
     if "lm_head.weight" in want and "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:
         sd["lm_head.weight"] = sd["model.embed_tokens.weight"]

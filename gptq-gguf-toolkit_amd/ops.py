@@ -929,3 +929,65 @@ def gemv_packed(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src: Opt
     check(lib().gq_gemv_packed(k, _ptr(blocks), _ptr(row_src), R, C, _ptr(x), T, _DT[x.dtype], _ptr(y), _stream(x)),
           "gq_gemv_packed")
     return y
+
+
+# ---- the vocabulary ends of a packed model: the embedding lookup from block bytes, the sampler on the logits ----
+def embed_packed(q_type: int, blocks: torch.Tensor, ids: torch.Tensor, out_dtype=torch.float16) -> torch.Tensor:
+    """The rows `ids` of the embedding table that `blocks` holds packed (uint8 [V, C/block*type_size], a K-quant or Q8_0)
+    -> [*ids.shape, C] in out_dtype: gq_dequantize_blocks with ids.numel() output rows and the ids as its row gather, so bit
+    for bit dequantize_blocks(q_type, blocks, out_dtype)[ids].  ids: int32 or int64 on the blocks' device, every id in
+    [0, V) -- the kernel does not check.  An empty ids gives an empty result without a launch."""
+    _need_cuda(blocks, ids)
+    bs, ts = block_geometry(q_type)
+    if blocks.dtype != torch.uint8 or blocks.dim() != 2 or blocks.shape[0] < 1 or blocks.shape[1] < ts or blocks.shape[1] % ts:
+        raise _cabi.GQError(f"embed_packed: packed blocks of q_type {int(q_type)} must be uint8 [V, C/{bs}*{ts}]; got "
+                            f"{blocks.dtype} {tuple(blocks.shape)}")
+    if ids.dtype not in (torch.int32, torch.int64):
+        raise _cabi.GQError(f"embed_packed: ids must be int32 or int64, got {ids.dtype}")
+    if ids.device != blocks.device:
+        raise _cabi.GQError(f"embed_packed: ids on {ids.device}, blocks on {blocks.device}")
+    if out_dtype not in _DT:
+        raise _cabi.GQError(f"embed_packed: out_dtype must be fp32, fp16 or bf16, got {out_dtype}")
+    blocks = blocks.contiguous()
+    C, n = blocks.shape[1] // ts * bs, ids.numel()
+    out = torch.empty(*ids.shape, C, dtype=out_dtype, device=blocks.device)
+    if n:
+        rows = ids.reshape(-1).to(torch.int32).contiguous()
+        check(lib().gq_dequantize_blocks(int(q_type), _ptr(blocks), n, C, _ptr(rows), _ptr(out), _DT[out_dtype],
+                                         _stream(blocks)), "gq_dequantize_blocks")
+    return out
+
+
+SAMPLE_MAX_K = _cabi.SAMPLE_MAX_K
+
+
+def sample_logits(logits: torch.Tensor, u: Optional[torch.Tensor], top_k: int, top_p: float = 1.0,
+                  temperature: float = 1.0) -> torch.Tensor:
+    """logits [B, V] fp32 / fp16 / bf16 (unit stride over V, any row stride >= V) -> int64 [B] token ids in one launch
+    (gq_sample_logits; include/gptq_gguf_sample.h is the contract): temperature, then the top_k tokens by (logit descending,
+    index ascending), then the top_p nucleus, then the inverse CDF at u[b].  u: fp32 [B] in [0, 1) on the device, the
+    caller's random numbers; may be None when temperature == 0 (the argmax, lowest index among equals).  A row with a NaN
+    or a non-finite maximum gives -1.  1 <= top_k <= SAMPLE_MAX_K: there is no unbounded nucleus, and no value is
+    substituted for top_k = 0.  No host synchronise."""
+    _need_cuda(logits, u)
+    if logits.dtype not in _DT or logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1:
+        raise _cabi.GQError(f"sample_logits: logits must be a non-empty fp32 / fp16 / bf16 [B, V] tensor with a unit stride "
+                            f"over V; got {logits.dtype} {tuple(logits.shape)} strides {tuple(logits.stride())}")
+    B, V = logits.shape
+    ld = logits.stride(0) if B > 1 else V
+    if ld < V:
+        raise _cabi.GQError(f"sample_logits: rows overlap (row stride {ld} < V={V})")
+    if not 1 <= int(top_k) <= SAMPLE_MAX_K:
+        raise _cabi.GQError(f"sample_logits: top_k={top_k} (not in [1, {SAMPLE_MAX_K}]; an unbounded nucleus is not built)")
+    if u is None:
+        if temperature != 0:
+            raise _cabi.GQError(f"sample_logits: u is None with temperature={temperature} (only the argmax needs no draw)")
+    elif u.dtype != torch.float32 or u.numel() != B or u.device != logits.device:
+        raise _cabi.GQError(f"sample_logits: u must be fp32 [{B}] on {logits.device}; got {u.dtype} {tuple(u.shape)} on "
+                            f"{u.device}")
+    else:
+        u = u.contiguous()
+    ids = torch.empty(B, dtype=torch.int64, device=logits.device)
+    check(lib().gq_sample_logits(_ptr(logits), _DT[logits.dtype], B, V, ld, int(top_k), float(top_p), float(temperature),
+                                 _ptr(u), _ptr(ids), _stream(logits)), "gq_sample_logits")
+    return ids

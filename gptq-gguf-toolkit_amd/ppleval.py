@@ -3,7 +3,7 @@
 eval/ppleval.py (:25-120 flags, :124-152 load_compressed_weights, :207-229 the result JSON) on the gq_eval_* kernels.
 
     python -m gptq_gguf_toolkit_amd.ppleval --model_name_or_path HF_DIR --eval_datasets ids.pt --output_file out.json \
-        [--quant_weights_path DB [--quant_config_path FILE] [--quant_default_level N] | --gguf FILE [--packed]] \
+        [--quant_weights_path DB [--quant_config_path FILE] [--quant_default_level N] | --gguf FILE [--packed [--packed_vocab]]] \
         [--kl_against none|model|gguf:FILE]
 
 Evaluation data are `.pt` files of [1, L] id tensors (no tokenizer, no download).  Left out: --memory_efficient, wandb,
@@ -56,9 +56,13 @@ def parse_args(argv=None):
     p.add_argument("--packed", default=False, action="store_true",
                    help="with --gguf: keep the K-quant / Q8_0 weights of the blocks' Linears packed on the device and compute "
                         "with the block bytes (no dense copy; fp16 / bf16)")
+    p.add_argument("--packed_vocab", default=False, action="store_true",
+                   help="with --packed: keep token_embd and output packed as well (a PackedEmbedding and a packed lm_head)")
     args = p.parse_args(argv)
     if args.packed and not args.gguf:
         p.error("--packed needs --gguf")
+    if args.packed_vocab and not args.packed:
+        p.error("--packed_vocab needs --packed")
     if args.gguf and args.quant_weights_path:
         p.error("--gguf and --quant_weights_path are mutually exclusive")
     if args.kl_against not in ("none", "model") and not (args.kl_against.startswith("gguf:") and args.kl_against[5:]):
@@ -117,7 +121,8 @@ def load_hf_model(args, device):
 def apply_weights(model, args):
     """The scored model: --gguf, the level database, or the HF weights as loaded."""
     if args.gguf:
-        gguf_loader.load_into_model(model, args.gguf, packed=getattr(args, "packed", False))
+        packed = getattr(args, "packed", False)
+        gguf_loader.load_into_model(model, args.gguf, packed="all" if packed and getattr(args, "packed_vocab", False) else packed)
     elif args.quant_weights_path:
         load_compressed_weights(model, args.quant_weights_path, args.quant_config_path, args.quant_default_level)
     return model
