@@ -43,6 +43,9 @@ GEMV_MAX_T = 16  # GQ_GEMV_MAX_T: tokens of one gq_gemv_packed call
 # include/gptq_gguf_sample.h: logits -> token ids in one launch: temperature, top-k, top-p, the draw (additive in the same way)
 EXPORTS_SAMPLE = ("gq_sample_logits",)
 SAMPLE_MAX_K = 1024  # GQ_SAMPLE_MAX_K: the largest top_k
+# include/gptq_gguf_moe.h: the grouped expert GEMV of a packed MoE layer's decode step (additive in the same way)
+EXPORTS_MOE = ("gq_gemv_packed_experts",)
+MOE_MAX_PAIRS = 64  # GQ_MOE_MAX_PAIRS: (token, expert) pairs of one gq_gemv_packed_experts call
 
 
 class GQError(RuntimeError):
@@ -154,6 +157,7 @@ def lib():
     L.gq_linear_packed.argtypes = [ci, vp, vp, i64, i64, vp, i64, ci, vp, vp]
     L.gq_gemv_packed.argtypes = [ci, vp, vp, i64, i64, vp, i64, ci, vp, vp]
     L.gq_sample_logits.argtypes = [vp, ci, i64, i64, i64, ci, cf, cf, vp, vp, vp]
+    L.gq_gemv_packed_experts.argtypes = [ci, vp, i64, i64, i64, vp, i64, vp, i64, i64, ci, vp, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -162,7 +166,7 @@ def lib():
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_QGEMM +
-                 EXPORTS_QGEMV + EXPORTS_SAMPLE):
+                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

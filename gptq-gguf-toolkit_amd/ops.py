@@ -931,6 +931,54 @@ def gemv_packed(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src: Opt
     return y
 
 
+# ---- the grouped expert GEMV of a packed MoE layer's decode step (gq_gemv_packed_experts) ----
+MOE_MAX_PAIRS = _cabi.MOE_MAX_PAIRS
+
+
+def gemv_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: torch.Tensor, pair_expert: torch.Tensor,
+                        pairs_per_row: int) -> torch.Tensor:
+    """y [P, R] with y[p] = W[pair_expert[p]] x[p // pairs_per_row] in ONE launch: `blocks` holds the stacked expert tensor
+    [E, R, C] packed (a K-quant q_type 10..14 or Q8_0 8; contiguous uint8 of exactly E * R rows of C / 256 blocks, any
+    shape), x is contiguous [x_rows, C] fp16 / bf16, pair_expert int32 [P] on the device with P = x_rows * pairs_per_row,
+    1 <= P <= MOE_MAX_PAIRS.  pairs_per_row = K: gate / up (x the hidden states, the pairs in the row-major order of the
+    router's [T, K] index); pairs_per_row = 1: down (x the [P, I] activation).  Row p is bit for bit
+    gemv_packed(q_type, expert pair_expert[p]'s slice, x[p // pairs_per_row]).  An id outside [0, E) is not checked: that
+    pair is skipped and its row of y stays as torch.empty left it.  The ids are never read by the host: no synchronisation."""
+    k, E, R, ppr = int(q_type), int(E), int(R), int(pairs_per_row)
+    bs, ts = block_geometry(k)
+    who = "gemv_packed_experts"
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise _cabi.GQError(f"{who}: x must be fp16 or bf16 (there is no fp32 path); got {x.dtype}")
+    if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
+        raise _cabi.GQError(f"{who}: x must be a non-empty contiguous [x_rows, C] tensor; got {tuple(x.shape)} strides "
+                            f"{tuple(x.stride())}")
+    for t in (blocks, pair_expert):
+        if t.device != x.device:
+            raise _cabi.GQError(f"{who}: every tensor must be on one device ({x.device}); got one on {t.device}")
+    x_rows, C = x.shape
+    if C % 256:
+        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 included)")
+    if pair_expert.dtype != torch.int32 or pair_expert.dim() != 1 or not pair_expert.is_contiguous():
+        raise _cabi.GQError(f"{who}: pair_expert must be a contiguous int32 [P] tensor; got {pair_expert.dtype} "
+                            f"{tuple(pair_expert.shape)}")
+    P = pair_expert.numel()
+    if P < 1 or P > MOE_MAX_PAIRS:
+        raise _cabi.GQError(f"{who}: P={P} pairs (not in [1, MOE_MAX_PAIRS={MOE_MAX_PAIRS}])")
+    if ppr < 1 or x_rows * ppr != P:
+        raise _cabi.GQError(f"{who}: x_rows={x_rows} * pairs_per_row={ppr} != P={P}")
+    if E < 1 or E > 65535 or R < 1:
+        raise _cabi.GQError(f"{who}: E={E}, R={R} (1 <= E <= 65535, R >= 1)")
+    need = E * R * (C // bs) * ts
+    if blocks.dtype != torch.uint8 or not blocks.is_contiguous() or blocks.numel() != need:
+        raise _cabi.GQError(f"{who}: packed blocks of q_type {k} for [E={E}, R={R}, C={C}] must be {need} contiguous uint8; "
+                            f"got {blocks.dtype} {tuple(blocks.shape)}")
+    _need_cuda(blocks, x, pair_expert)  # (last: the refusals above name their value for tensors on any device)
+    y = torch.empty(P, R, dtype=x.dtype, device=x.device)
+    check(lib().gq_gemv_packed_experts(k, _ptr(blocks), E, R, C, _ptr(x), x_rows, _ptr(pair_expert), P, ppr, _DT[x.dtype],
+                                       _ptr(y), _stream(x)), "gq_gemv_packed_experts")
+    return y
+
+
 # ---- the vocabulary ends of a packed model: the embedding lookup from block bytes, the sampler on the logits ----
 def embed_packed(q_type: int, blocks: torch.Tensor, ids: torch.Tensor, out_dtype=torch.float16) -> torch.Tensor:
     """The rows `ids` of the embedding table that `blocks` holds packed (uint8 [V, C/block*type_size], a K-quant or Q8_0)
