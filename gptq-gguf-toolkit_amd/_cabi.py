@@ -46,6 +46,10 @@ SAMPLE_MAX_K = 1024  # GQ_SAMPLE_MAX_K: the largest top_k
 # include/gptq_gguf_moe.h: the grouped expert GEMV of a packed MoE layer's decode step (additive in the same way)
 EXPORTS_MOE = ("gq_gemv_packed_experts",)
 MOE_MAX_PAIRS = 64  # GQ_MOE_MAX_PAIRS: (token, expert) pairs of one gq_gemv_packed_experts call
+# include/gptq_gguf_moe_gemm.h: the packed MoE prefill: device-side routing and the grouped expert GEMM (additive in the same way)
+EXPORTS_MOE_GEMM = ("gq_moe_route", "gq_linear_packed_experts")
+MOE_ROUTE_MAX_EXPERTS = 256  # GQ_MOE_ROUTE_MAX_EXPERTS: experts gq_moe_route sorts by
+MOE_ROUTE_MAX_PAIRS = 131072  # GQ_MOE_ROUTE_MAX_PAIRS: (token, expert) pairs of one gq_moe_route / gq_linear_packed_experts call
 
 
 class GQError(RuntimeError):
@@ -158,6 +162,8 @@ def lib():
     L.gq_gemv_packed.argtypes = [ci, vp, vp, i64, i64, vp, i64, ci, vp, vp]
     L.gq_sample_logits.argtypes = [vp, ci, i64, i64, i64, ci, cf, cf, vp, vp, vp]
     L.gq_gemv_packed_experts.argtypes = [ci, vp, i64, i64, i64, vp, i64, vp, i64, i64, ci, vp, vp]
+    L.gq_moe_route.argtypes = [vp, i64, i64, vp, vp, vp]
+    L.gq_linear_packed_experts.argtypes = [ci, vp, i64, i64, i64, vp, i64, i64, vp, vp, i64, ci, vp, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -166,7 +172,7 @@ def lib():
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_QGEMM +
-                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE):
+                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

@@ -29,153 +29,41 @@
 // that only reach output elements that are never stored), the tokens are staged as zeros; nothing is read or written
 // outside the arguments' extents.
 #include "../../../include/gptq_gguf_qgemm.h"
-#include <type_traits>
 
-#include "../search/gq_block_decode.hpp"
+#include "gq_qgemm_core.hpp"
 
 namespace gq {
 namespace {
 
-using namespace blockdec;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int TR = 128, KC = 64;  // tile of rows; k of an x chunk (the token tile TT = 256 or 128 is a template parameter)
-constexpr int64_t WIDE_TILES = 512;  // two workgroups on each of the 256 CUs: from there on the 256-token tile is used
-
-// Stage superblock j of the tile's nr rows: sbase[r] = byte offset of the row's first block.  The caller has a barrier before
-// (sb free) and after.
-template <int QT>
-__device__ __forceinline__ void stage_rows(const uint8_t* __restrict__ blocks, const int64_t* sbase, int64_t j, int nr,
-                                           uint8_t* sb) {
-    using Q = QL<QT>;
-    using U = typename Unit<Q::AL>::T;
-    constexpr int NIT = (TR * Q::UPR + 255) / 256, GRP = 8;
-    const int tid = threadIdx.x, n = nr * Q::UPR;
-#pragma unroll 1
-    for (int it0 = 0; it0 < NIT; it0 += GRP) {
-        if (tid + 256 * it0 >= n) break;
-        U v[GRP] = {};
-#pragma unroll
-        for (int g = 0; g < GRP; ++g) {
-            const int u = tid + 256 * (it0 + g), r = u / Q::UPR, o = u - r * Q::UPR;
-            if (u < n) v[g] = *reinterpret_cast<const U*>(blocks + sbase[r] + j * Q::ROWB + o * Q::AL);
-        }
-#pragma unroll
-        for (int g = 0; g < GRP; ++g) {
-            const int u = tid + 256 * (it0 + g), r = u / Q::UPR, o = u - r * Q::UPR;
-            if (u < n) *reinterpret_cast<U*>(sb + r * Q::SLOT + Q::lds_off(o)) = v[g];
-        }
-    }
-}
-
-template <bool BF16>
-__device__ __forceinline__ f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
-    if constexpr (BF16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-// the XP 16-byte pieces of a thread of x chunk (k0 .. k0 + 63) of tokens t0 .. t0 + TT - 1: piece p = tid + 256 i is
-// token p >> 3, 8-k piece p & 7 (a token's 128 bytes are read by 8 consecutive lanes)
-template <int XP>
-__device__ __forceinline__ void load_x(const uint8_t* __restrict__ x, int64_t C, int64_t T, int64_t t0, int64_t k0, u32x4 xr[XP]) {
-#pragma unroll
-    for (int i = 0; i < XP; ++i) {
-        const int p = threadIdx.x + 256 * i;
-        const int64_t t = t0 + (p >> 3);
-        xr[i] = t < T ? *reinterpret_cast<const u32x4*>(x + (t * C + k0 + 8 * (p & 7)) * 2) : u32x4{0, 0, 0, 0};
-    }
-}
+using namespace gemmcore;  // the tile's text: staging, K loop, epilogue (shared with gq_moe_gemm.hip)
 
 template <int QT, bool BF16, int TT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void linear_packed_kernel(const uint8_t* __restrict__ blocks, const int32_t* __restrict__ row_src,
                                                             int64_t R, int64_t C, const uint8_t* __restrict__ x, int64_t T,
                                                             uint16_t* __restrict__ y, uint32_t n_rt) {
     using Q = QL<QT>;
-    using OutT = typename std::conditional<BF16, bf16_bits, half_bits>::type;
-    constexpr int XP = TT * 8 / 256;
     __shared__ __attribute__((aligned(16))) uint8_t sb[TR * Q::SLOT];
     __shared__ __attribute__((aligned(16))) uint8_t sx[TT * KC * 2];
     __shared__ int64_t sbase[TR];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, q = lane >> 4;
+    const int tid = threadIdx.x;
     const int64_t r0 = (int64_t)(blockIdx.x % n_rt) * TR, t0 = (int64_t)(blockIdx.x / n_rt) * TT;  // row tiles fastest: they share x
     const int nr = (int)((R - r0) < TR ? (R - r0) : TR), nt = (int)((T - t0) < TT ? (T - t0) : TT), ntt = (nt + 15) >> 4;
     const int64_t nsb = C / 256;
     if (tid < nr) sbase[tid] = (row_src ? (int64_t)row_src[r0 + tid] : r0 + tid) * nsb * Q::ROWB;
-
-    f32x4 acc[2][TT / 16];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int tt = 0; tt < TT / 16; ++tt) acc[a][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    u32x4 xr[XP];
-    load_x<XP>(x, C, T, t0, 0, xr);
-    __syncthreads();  // sbase
-    const uint8_t* B0 = sb + (32 * wave + l15) * Q::SLOT;
-#pragma unroll 1
-    for (int64_t j = 0; j < nsb; ++j) {
-        stage_rows<QT>(blocks, sbase, j, nr, sb);  // (the barrier that ended the previous chunk freed sb)
-#pragma unroll 1
-        for (int c = 0; c < 256 / KC; ++c) {
-#pragma unroll
-            for (int i = 0; i < XP; ++i) {
-                const int p = tid + 256 * i;
-                *reinterpret_cast<u32x4*>(sx + ((p & 7) * TT + (p >> 3)) * 16) = xr[i];
-            }
-            __syncthreads();
-            const int64_t kn = 256 * j + KC * (c + 1);
-            if (kn < C) load_x<XP>(x, C, T, t0, kn, xr);
-            uint32_t w[2][8];
-            decode16<QT, OutT>(B0, c, q, w[0]);
-            decode16<QT, OutT>(B0 + 16 * Q::SLOT, c, q, w[1]);
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const u32x4 wa = {w[0][4 * s], w[0][4 * s + 1], w[0][4 * s + 2], w[0][4 * s + 3]};
-                const u32x4 wb = {w[1][4 * s], w[1][4 * s + 1], w[1][4 * s + 2], w[1][4 * s + 3]};
-                const uint8_t* px = sx + ((2 * q + s) * TT + l15) * 16;
-#pragma unroll
-                for (int tt = 0; tt < TT / 16; ++tt)
-                    if (tt < ntt) {
-                        const u32x4 xa = *reinterpret_cast<const u32x4*>(px + tt * 256);
-                        acc[0][tt] = mfma<BF16>(wa, xa, acc[0][tt]);
-                        acc[1][tt] = mfma<BF16>(wb, xa, acc[1][tt]);
-                    }
-            }
-            __syncthreads();  // sx (and after the last chunk sb) may be overwritten
-        }
-    }
-
-    const bool vec = (R & 3) == 0;  // then (t R + r) * 2 is 8-byte aligned for r % 4 == 0
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        const int64_t r = r0 + 32 * wave + 16 * a + 4 * q;
-#pragma unroll
-        for (int tt = 0; tt < TT / 16; ++tt) {
-            const int64_t t = t0 + 16 * tt + l15;
-            if (t >= T || r >= R) continue;
-            uint16_t o[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] = cvt_out<OutT>(acc[a][tt][i]).b;
-            uint16_t* py = y + t * R + r;
-            if (vec) {
-                *reinterpret_cast<uint2*>(py) = make_uint2((uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16));
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (r + i < R) py[i] = o[i];
-            }
-        }
-    }
+    tile_pass<QT, BF16, TT>(
+        blocks, sbase, nr, ntt, r0, R, C, x,
+        [=](int i) {
+            const int p = threadIdx.x + 256 * i;
+            const int64_t t = t0 + (p >> 3);
+            return Row{t < T, t};
+        },
+        y,
+        [=](int tt) {
+            const int64_t t = t0 + 16 * tt + (tid & 15);
+            return Row{t < T, t};
+        },
+        sb, sx);
 }
-
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-int block_align(int q) { return q == GQ_Q2_K ? 4 : (q == GQ_Q4_K || q == GQ_Q5_K) ? 16 : 2; }
 
 // the grid of token tile tt; 0 when it is more than one launch takes
 int64_t tiles(int64_t R, int64_t T, int tt) {

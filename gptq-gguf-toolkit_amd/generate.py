@@ -6,7 +6,7 @@ through gq_gemv_packed (PackedLinear routes inputs of a few tokens there), the p
 launch on the last row of logits (temperature, top-k, top-p, the draw) and a row stops at `--eos_token_id`.
 
     python -m gptq_gguf_toolkit_amd.generate --model_name_or_path HF_DIR --prompt_ids ids.pt --max_new_tokens N \
-        --output_file out.json [--gguf FILE [--packed] | --quant_weights_path DB --quant_config_path CFG] \
+        --output_file out.json [--gguf FILE [--packed [--moe_prefill grouped]] | --quant_weights_path DB --quant_config_path CFG] \
         [--dtype float16] [--attn_implementation eager] [--tokenizer_name NAME]
 
 Prompts are the `.pt` list of [1, L] id tensors that ppleval reads (no tokenizer is needed; with --tokenizer_name the new
@@ -136,6 +136,9 @@ def parse_args(argv=None):
                    help="with --gguf: keep the K-quant / Q8_0 weights of the blocks' Linears packed on the device")
     p.add_argument("--packed_vocab", default=False, action="store_true",
                    help="with --packed: keep token_embd and output packed as well (a PackedEmbedding and a packed lm_head)")
+    p.add_argument("--moe_prefill", type=str, default="loop", choices=["loop", "grouped"],
+                   help="with --packed: the prompt of a MoE model through the per-expert loop, or through device-side routing "
+                        "and one grouped GEMM per projection")
     p.add_argument("--do_sample", default=False, action="store_true", help="sample (gq_sample_logits) instead of the argmax")
     p.add_argument("--temperature", type=float, default=1.0, help="with --do_sample: 0 is the argmax")
     p.add_argument("--top_k", type=int, default=40, help=f"with --do_sample: 1 .. {ops.SAMPLE_MAX_K} (there is no 'off')")
@@ -155,6 +158,8 @@ def parse_args(argv=None):
         p.error("--packed needs --gguf")
     if args.packed_vocab and not args.packed:
         p.error("--packed_vocab needs --packed")
+    if args.moe_prefill != "loop" and not args.packed:
+        p.error("--moe_prefill needs --packed")
     if not 1 <= args.top_k <= ops.SAMPLE_MAX_K:
         p.error(f"--top_k must be in [1, {ops.SAMPLE_MAX_K}] (an unbounded nucleus is not built)")
     if not 0 < args.top_p <= 1 or not args.temperature >= 0:

@@ -289,7 +289,8 @@ def packed_expert_tensors(model: torch.nn.Module, path: str) -> Dict[str, dict]:
     return out
 
 
-def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bool = False) -> Dict[str, torch.Tensor]:
+def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bool = False,
+                 moe_prefill: str = "loop") -> Dict[str, torch.Tensor]:
     """The packed half of load_into_model: the Linears of packed_linear_tensors become PackedLinear holding the file's
     block bytes (with the rotary row gather of attn_q / attn_k as row_src); the modules of packed_expert_tensors become
     PackedExperts (or, per expert, PackedLinear on a slice view) on ONE device copy of each merged tensor; with `vocab` also
@@ -326,7 +327,7 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
             for mod, role, e in users[name]:
                 if e is None:
                     m = model.get_submodule(mod)
-                    (m if hasattr(m, "set_level") else replace_experts(model, mod)).set_level(role, dev, int(gt))
+                    (m if hasattr(m, "set_level") else replace_experts(model, mod, moe_prefill)).set_level(role, dev, int(gt))
                 else:
                     replace_linear(model, mod).set_level(dev.view(shape[0], -1)[e], int(gt))
         elif any(g == name for g, _ in ends.values()):
@@ -342,7 +343,7 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
                                                expert_layout=expert_layout_of(model)) if k not in skip}
 
 
-def load_into_model(model: torch.nn.Module, path: str, packed=False) -> torch.nn.Module:
+def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill: str = "loop") -> torch.nn.Module:
     """Load the file's weights into `model` (parameters on a GPU), strict on names and shapes.  A tied lm_head (no
     `output.weight` in the file) follows token_embd.
     packed=True: the K-quant and Q8_0 tensors of the blocks' nn.Linear modules stay packed on the device -- each such Linear
@@ -353,11 +354,15 @@ def load_into_model(model: torch.nn.Module, path: str, packed=False) -> torch.nn
     PackedLinear on its slice; the router loads dense.
     packed="all": that, and the vocabulary ends of packed_vocab_tensors: model.embed_tokens becomes a
     packed_embedding.PackedEmbedding and lm_head a PackedLinear on the file's block bytes (a file without output.weight gives
-    both the same tensor: one device copy); an end stored as F16 / F32 loads dense as without it."""
+    both the same tensor: one device copy); an end stored as F16 / F32 loads dense as without it.
+    moe_prefill (with packed): "loop" or "grouped", the prefill path of the PackedExperts modules (PackedExperts.prefill)."""
     if packed not in (False, True, "all"):
         raise ValueError(f"load_into_model: packed must be False, True or 'all', got {packed!r}")
+    if moe_prefill not in ("loop", "grouped") or (moe_prefill != "loop" and not packed):
+        raise ValueError(f"load_into_model: moe_prefill must be 'loop' or 'grouped' (with packed), got {moe_prefill!r} with "
+                         f"packed={packed!r}")
     ref = next(model.parameters())
-    sd = (_load_packed(model, path, ref, vocab=packed == "all") if packed
+    sd = (_load_packed(model, path, ref, vocab=packed == "all", moe_prefill=moe_prefill) if packed
           else load_state_dict(path, ref.device, ref.dtype, expert_layout_of(model)))
     want = model.state_dict()
     if "lm_head.weight" in want and "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:

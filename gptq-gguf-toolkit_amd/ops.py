@@ -979,6 +979,79 @@ def gemv_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: to
     return y
 
 
+# ---- the packed MoE prefill: device-side routing (gq_moe_route) and the grouped expert GEMM (gq_linear_packed_experts) ----
+MOE_ROUTE_MAX_EXPERTS = _cabi.MOE_ROUTE_MAX_EXPERTS
+MOE_ROUTE_MAX_PAIRS = _cabi.MOE_ROUTE_MAX_PAIRS
+
+
+def moe_route(pair_expert: torch.Tensor, E: int):
+    """The router's pairs sorted by expert, on the device, in one launch: pair_expert int32 [P] (the [T, K] index in row-major
+    order), 1 <= P <= MOE_ROUTE_MAX_PAIRS, 1 <= E <= MOE_ROUTE_MAX_EXPERTS -> (expert_start int32 [E + 1], order int32 [P]).
+    order[expert_start[e] : expert_start[e + 1]] are the pairs that name expert e, ascending (a stable sort); an id outside
+    [0, E) -- E for a masked pair, negative ids -- is in no run, expert_start[E] counts the others and order holds -1 from
+    there on.  Both outputs are defined for every input.  The ids are never read by the host: no synchronisation."""
+    E = int(E)
+    who = "moe_route"
+    if pair_expert.dtype != torch.int32 or pair_expert.dim() != 1 or not pair_expert.is_contiguous():
+        raise _cabi.GQError(f"{who}: pair_expert must be a contiguous int32 [P] tensor; got {pair_expert.dtype} "
+                            f"{tuple(pair_expert.shape)}")
+    P = pair_expert.numel()
+    if P < 1 or P > MOE_ROUTE_MAX_PAIRS:
+        raise _cabi.GQError(f"{who}: P={P} pairs (not in [1, MOE_ROUTE_MAX_PAIRS={MOE_ROUTE_MAX_PAIRS}])")
+    if E < 1 or E > MOE_ROUTE_MAX_EXPERTS:
+        raise _cabi.GQError(f"{who}: E={E} experts (not in [1, MOE_ROUTE_MAX_EXPERTS={MOE_ROUTE_MAX_EXPERTS}])")
+    _need_cuda(pair_expert)
+    expert_start = torch.empty(E + 1, dtype=torch.int32, device=pair_expert.device)
+    order = torch.empty(P, dtype=torch.int32, device=pair_expert.device)
+    check(lib().gq_moe_route(_ptr(pair_expert), P, E, _ptr(expert_start), _ptr(order), _stream(pair_expert)), "gq_moe_route")
+    return expert_start, order
+
+
+def linear_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: torch.Tensor, route, pairs_per_row: int) -> torch.Tensor:
+    """y [P, R] with y[p] = W[expert of pair p] x[p // pairs_per_row] for every pair of `route` = moe_route(pair_expert, E) in
+    ONE launch of the tile GEMM: `blocks` holds the stacked expert tensor [E, R, C] packed (a K-quant q_type 10..14 or Q8_0 8;
+    contiguous uint8 of exactly E * R rows of C / 256 blocks, any shape), x is contiguous [x_rows, C] fp16 / bf16 with
+    x_rows * pairs_per_row = P = route[1].numel().  pairs_per_row = K: gate / up; pairs_per_row = 1: down.  The tokens of an
+    expert are gathered and the results scattered to pair order inside the kernel.  Row p is bit for bit
+    linear_packed(q_type, that expert's slice, x[p // pairs_per_row]).  A pair that is in no run of the route (a masked
+    pair) is skipped and its row of y stays as torch.empty left it.  Nothing is read by the host: no synchronisation."""
+    k, E, R, ppr = int(q_type), int(E), int(R), int(pairs_per_row)
+    bs, ts = block_geometry(k)
+    who = "linear_packed_experts"
+    expert_start, order = route
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise _cabi.GQError(f"{who}: x must be fp16 or bf16 (there is no fp32 path); got {x.dtype}")
+    if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
+        raise _cabi.GQError(f"{who}: x must be a non-empty contiguous [x_rows, C] tensor; got {tuple(x.shape)} strides "
+                            f"{tuple(x.stride())}")
+    for t in (blocks, expert_start, order):
+        if t.device != x.device:
+            raise _cabi.GQError(f"{who}: every tensor must be on one device ({x.device}); got one on {t.device}")
+    x_rows, C = x.shape
+    if C % 256:
+        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 included)")
+    if E < 1 or E > MOE_ROUTE_MAX_EXPERTS or R < 1:
+        raise _cabi.GQError(f"{who}: E={E}, R={R} (1 <= E <= MOE_ROUTE_MAX_EXPERTS={MOE_ROUTE_MAX_EXPERTS}, R >= 1)")
+    for name, t, n in (("expert_start", expert_start, E + 1), ("order", order, order.numel())):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != n:
+            raise _cabi.GQError(f"{who}: route: {name} must be a contiguous int32 [{n}] tensor (moe_route's output for E={E}); "
+                                f"got {t.dtype} {tuple(t.shape)}")
+    P = order.numel()
+    if P < 1 or P > MOE_ROUTE_MAX_PAIRS:
+        raise _cabi.GQError(f"{who}: P={P} pairs (not in [1, MOE_ROUTE_MAX_PAIRS={MOE_ROUTE_MAX_PAIRS}])")
+    if ppr < 1 or x_rows * ppr != P:
+        raise _cabi.GQError(f"{who}: x_rows={x_rows} * pairs_per_row={ppr} != P={P}")
+    need = E * R * (C // bs) * ts
+    if blocks.dtype != torch.uint8 or not blocks.is_contiguous() or blocks.numel() != need:
+        raise _cabi.GQError(f"{who}: packed blocks of q_type {k} for [E={E}, R={R}, C={C}] must be {need} contiguous uint8; "
+                            f"got {blocks.dtype} {tuple(blocks.shape)}")
+    _need_cuda(blocks, x, expert_start, order)  # (last: the refusals above name their value for tensors on any device)
+    y = torch.empty(P, R, dtype=x.dtype, device=x.device)
+    check(lib().gq_linear_packed_experts(k, _ptr(blocks), E, R, C, _ptr(x), x_rows, ppr, _ptr(expert_start), _ptr(order), P,
+                                         _DT[x.dtype], _ptr(y), _stream(x)), "gq_linear_packed_experts")
+    return y
+
+
 # ---- the vocabulary ends of a packed model: the embedding lookup from block bytes, the sampler on the logits ----
 def embed_packed(q_type: int, blocks: torch.Tensor, ids: torch.Tensor, out_dtype=torch.float16) -> torch.Tensor:
     """The rows `ids` of the embedding table that `blocks` holds packed (uint8 [V, C/block*type_size], a K-quant or Q8_0)

@@ -3,7 +3,7 @@
 eval/ppleval.py (:25-120 flags, :124-152 load_compressed_weights, :207-229 the result JSON) on the gq_eval_* kernels.
 
     python -m gptq_gguf_toolkit_amd.ppleval --model_name_or_path HF_DIR --eval_datasets ids.pt --output_file out.json \
-        [--quant_weights_path DB [--quant_config_path FILE] [--quant_default_level N] | --gguf FILE [--packed [--packed_vocab]]] \
+        [--quant_weights_path DB [--quant_config_path FILE] [--quant_default_level N] | --gguf FILE [--packed [--packed_vocab] [--moe_prefill grouped]]] \
         [--kl_against none|model|gguf:FILE]
 
 Evaluation data are `.pt` files of [1, L] id tensors (no tokenizer, no download).  Left out: --memory_efficient, wandb,
@@ -58,11 +58,16 @@ def parse_args(argv=None):
                         "with the block bytes (no dense copy; fp16 / bf16)")
     p.add_argument("--packed_vocab", default=False, action="store_true",
                    help="with --packed: keep token_embd and output packed as well (a PackedEmbedding and a packed lm_head)")
+    p.add_argument("--moe_prefill", type=str, default="loop", choices=["loop", "grouped"],
+                   help="with --packed: how the packed experts of a MoE model take more than a decode step's tokens -- the "
+                        "per-expert loop, or device-side routing and one grouped GEMM per projection")
     args = p.parse_args(argv)
     if args.packed and not args.gguf:
         p.error("--packed needs --gguf")
     if args.packed_vocab and not args.packed:
         p.error("--packed_vocab needs --packed")
+    if args.moe_prefill != "loop" and not args.packed:
+        p.error("--moe_prefill needs --packed")
     if args.gguf and args.quant_weights_path:
         p.error("--gguf and --quant_weights_path are mutually exclusive")
     if args.kl_against not in ("none", "model") and not (args.kl_against.startswith("gguf:") and args.kl_against[5:]):
@@ -122,7 +127,9 @@ def apply_weights(model, args):
     """The scored model: --gguf, the level database, or the HF weights as loaded."""
     if args.gguf:
         packed = getattr(args, "packed", False)
-        gguf_loader.load_into_model(model, args.gguf, packed="all" if packed and getattr(args, "packed_vocab", False) else packed)
+        prefill = getattr(args, "moe_prefill", "loop")  # (named only where it is not the loader's default)
+        gguf_loader.load_into_model(model, args.gguf, packed="all" if packed and getattr(args, "packed_vocab", False) else packed,
+                                    **({"moe_prefill": prefill} if prefill != "loop" else {}))
     elif args.quant_weights_path:
         load_compressed_weights(model, args.quant_weights_path, args.quant_config_path, args.quant_default_level)
     return model
