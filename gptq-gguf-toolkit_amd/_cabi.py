@@ -35,6 +35,8 @@ PACK_BANDS_ALIGN = 16  # GQ_PACK_BANDS_ALIGN: alignment of every band's output b
 # include/gptq_gguf_q8.h: the Q8_0 encoder; gq_dequantize_blocks / gq_level_switch take the type (additive in the same way)
 EXPORTS_Q8 = ("gq_quantize_q8_0",)
 Q8_0 = 8  # GQ_Q8_0: the ggml type id
+# include/gptq_gguf_iq4.h: IQ4_NL / IQ4_XS, read by the decode and packed-forward entry points (no new symbol)
+IQ4_NL, IQ4_XS = 20, 23  # GQ_IQ4_NL, GQ_IQ4_XS: the ggml type ids
 # include/gptq_gguf_qgemm.h: the packed-weight forward, a GEMM that reads block bytes as its weight operand (additive in the same way)
 EXPORTS_QGEMM = ("gq_linear_packed",)
 # include/gptq_gguf_qgemv.h: the same forward for the 1 .. 16 tokens of a decode step (additive in the same way)

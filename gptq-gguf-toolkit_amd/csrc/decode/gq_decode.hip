@@ -20,7 +20,14 @@
 //
 // Q8_0 (include/gptq_gguf_q8.h; dequantize_row_q8_0) takes the same route through gq_dequantize_blocks: a turn is 128 blocks of
 // 32 values, staged by 2-byte loads into 48-byte LDS slots, half a block per thread, w = f32(d) * f32(q) and one cast
-// (blockdec::decode_turn_q8_0).  gq_unpack has no Q8_0 form: the five data.pth tensors are a K-quant notion.
+// (blockdec::decode_turn_b32).  gq_unpack has no Q8_0 form: the five data.pth tensors are a K-quant notion.
+//
+// IQ4_NL and IQ4_XS (include/gptq_gguf_iq4.h; dequantize_row_iq4_nl / _iq4_xs): w = f32(d) * f32(ls - 32) * f32(kv[code]), both
+// products exact, one cast.  IQ4_XS is a 256-value type and takes the K-quants' route (decode_turn): 8-byte staging loads -- 136
+// = 17 x 8 -- into a 144-byte slot with the block at byte 8, so that the 16 code bytes of a thread are one aligned 16-byte LDS
+// read; ds = d * (ls - 32), dm = 0 and the code is kv[nibble], looked up in a register-resident table with byte permutes
+// (blockdec::iq4_code4).  IQ4_NL is a 32-value type and takes Q8_0's route: 2-byte staging loads, half a block per thread.
+// Neither has a gq_unpack form.
 #include "../search/gq_block_decode.hpp"  // Lay, stage_blocks, codes16, group_scale, decode_turn: shared with search/gq_switch.hip
 
 namespace gq {
@@ -47,16 +54,17 @@ __global__ __launch_bounds__(256) void dequantize_blocks_kernel(const uint8_t* _
     }
 }
 
-// Q8_0 (include/gptq_gguf_q8.h): the same loop over turns of 128 blocks of 32 values, w = f32(d) * f32(q) and one cast
-template <typename OutT>
-__global__ __launch_bounds__(256) void dequantize_q8_0_kernel(const uint8_t* __restrict__ blocks,
-                                                              const int32_t* __restrict__ row_src, int64_t nblocks,
-                                                              int64_t nbr, OutT* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) uint8_t sb[Q8_DB * Q8_SLOT];
-    __shared__ int64_t ssrc[Q8_DB];
-    for (int64_t b0 = (int64_t)blockIdx.x * Q8_DB; b0 < nblocks; b0 += (int64_t)gridDim.x * Q8_DB) {
-        const int nb = (int)((nblocks - b0) < Q8_DB ? (nblocks - b0) : Q8_DB);
-        decode_turn_q8_0<OutT>(blocks, row_src, b0, nb, nbr, out, sb, ssrc);
+// Q8_0 (include/gptq_gguf_q8.h), IQ4_NL (include/gptq_gguf_iq4.h): the same loop over turns of 128 blocks of 32 values,
+// w = f32(d) * f32(q) and one cast
+template <int QT, typename OutT>
+__global__ __launch_bounds__(256) void dequantize_b32_kernel(const uint8_t* __restrict__ blocks,
+                                                             const int32_t* __restrict__ row_src, int64_t nblocks,
+                                                             int64_t nbr, OutT* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) uint8_t sb[B32_DB * B32_SLOT];
+    __shared__ int64_t ssrc[B32_DB];
+    for (int64_t b0 = (int64_t)blockIdx.x * B32_DB; b0 < nblocks; b0 += (int64_t)gridDim.x * B32_DB) {
+        const int nb = (int)((nblocks - b0) < B32_DB ? (nblocks - b0) : B32_DB);
+        decode_turn_b32<QT, OutT>(blocks, row_src, b0, nb, nbr, out, sb, ssrc);
         __syncthreads();
     }
 }
@@ -136,18 +144,20 @@ int launch_dequantize_blocks_t(const uint8_t* blocks, const int32_t* row_src, in
     return GQ_OK;
 }
 
-int launch_dequantize_q8_0(const uint8_t* blocks, const int32_t* row_src, int64_t nblocks, int64_t nbr, void* out,
-                           int out_dtype, hipStream_t st) {
-    dim3 grid(turns_grid(nblocks, Q8_DB)), block(256);
+template <int QT>
+int launch_dequantize_b32(const uint8_t* blocks, const int32_t* row_src, int64_t nblocks, int64_t nbr, void* out,
+                          int out_dtype, hipStream_t st) {
+    if (!aligned(blocks, 2)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_dequantize_blocks: blocks not 2-byte aligned");
+    dim3 grid(turns_grid(nblocks, B32_DB)), block(256);
     switch (out_dtype) {
     case GQ_F32:
-        hipLaunchKernelGGL((dequantize_q8_0_kernel<float>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (float*)out);
+        hipLaunchKernelGGL((dequantize_b32_kernel<QT, float>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (float*)out);
         break;
     case GQ_F16:
-        hipLaunchKernelGGL((dequantize_q8_0_kernel<half_bits>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (half_bits*)out);
+        hipLaunchKernelGGL((dequantize_b32_kernel<QT, half_bits>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (half_bits*)out);
         break;
     default:
-        hipLaunchKernelGGL((dequantize_q8_0_kernel<bf16_bits>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (bf16_bits*)out);
+        hipLaunchKernelGGL((dequantize_b32_kernel<QT, bf16_bits>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (bf16_bits*)out);
         break;
     }
     GQ_LAUNCH_CHECK();
@@ -195,8 +205,9 @@ int gq_dequantize_blocks(int q_type, const uint8_t* blocks, int64_t R, int64_t C
                          int out_dtype, void* stream) {
     if (int rc = options_ok()) return rc;
     TypeInfo ti;
-    const int bs = q_type == GQ_Q8_0 ? 32 : 256;  // values per block
-    if (q_type != GQ_Q8_0 && !type_info(q_type, ti)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_dequantize_blocks: unknown q_type %d", q_type);
+    const bool b32 = q_type == GQ_Q8_0 || q_type == GQ_IQ4_NL;
+    const int bs = b32 ? 32 : 256;  // values per block
+    if (!b32 && q_type != GQ_IQ4_XS && !type_info(q_type, ti)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_dequantize_blocks: unknown q_type %d", q_type);
     if (out_dtype != GQ_F32 && out_dtype != GQ_F16 && out_dtype != GQ_BF16)
         GQ_FAIL(GQ_E_BAD_TYPE, "gq_dequantize_blocks: unknown out_dtype %d", out_dtype);
     if (R <= 0 || C <= 0 || C % bs)
@@ -206,9 +217,9 @@ int gq_dequantize_blocks(int q_type, const uint8_t* blocks, int64_t R, int64_t C
     const int64_t nbr = C / bs, nblocks = R * nbr;
     hipStream_t st = (hipStream_t)stream;
     switch (q_type) {
-    case GQ_Q8_0:
-        if (!aligned(blocks, 2)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_dequantize_blocks: blocks not 2-byte aligned");
-        return launch_dequantize_q8_0(blocks, row_src, nblocks, nbr, out, out_dtype, st);
+    case GQ_Q8_0: return launch_dequantize_b32<GQ_Q8_0>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
+    case GQ_IQ4_NL: return launch_dequantize_b32<GQ_IQ4_NL>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
+    case GQ_IQ4_XS: return launch_dequantize_blocks_t<GQ_IQ4_XS>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
     case GQ_Q2_K: return launch_dequantize_blocks_t<GQ_Q2_K>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
     case GQ_Q3_K: return launch_dequantize_blocks_t<GQ_Q3_K>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
     case GQ_Q4_K: return launch_dequantize_blocks_t<GQ_Q4_K>(blocks, row_src, nblocks, nbr, out, out_dtype, st);

@@ -134,7 +134,9 @@ __device__ __forceinline__ void gemv_pass(int tid, const uint8_t* __restrict__ b
 }
 
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-inline int block_align(int q) { return q == GQ_Q2_K ? 4 : (q == GQ_Q4_K || q == GQ_Q5_K) ? 16 : 2; }
+inline int block_align(int q) { return q == GQ_Q2_K ? 4 : (q == GQ_Q4_K || q == GQ_Q5_K) ? 16 : q == GQ_IQ4_XS ? 8 : 2; }
+// the types whose blocks the packed forward reads
+inline bool packed_type(int q) { return (q >= GQ_Q2_K && q <= GQ_Q6_K) || q == GQ_Q8_0 || q == GQ_IQ4_NL || q == GQ_IQ4_XS; }
 
 }  // namespace gemvcore
 }  // namespace gq

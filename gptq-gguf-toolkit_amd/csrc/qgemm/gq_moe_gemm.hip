@@ -164,9 +164,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         sb, sx);
 }
 
-// The 256-token tile of Q4_K / Q5_K does not fit 256 registers in this text (K21's own four instances spill 160-208 bytes per lane;
-// with the gathered row indices it is 16 more): the grouped kernel does not have it, so that no instance of it uses scratch.
-constexpr bool wide_ok(int q_type) { return q_type != GQ_Q4_K && q_type != GQ_Q5_K; }
+// The 256-token tile of Q4_K / Q5_K / IQ4_XS does not fit 256 registers in this text (K21's own four Q4_K / Q5_K instances spill
+// 160-208 bytes per lane and it builds none for IQ4_XS; with the gathered row indices it is 16 more): the grouped kernel does not
+// have it, so that no instance of it uses scratch.
+constexpr bool wide_ok(int q_type) { return q_type != GQ_Q4_K && q_type != GQ_Q5_K && q_type != GQ_IQ4_XS; }
 
 template <int QT, bool BF16>
 void launch_dt(bool wide, dim3 grid, hipStream_t st, const uint8_t* blocks, int E, int64_t R, int64_t C, const uint8_t* x, int ppr,
@@ -217,8 +218,8 @@ int gq_linear_packed_experts(int q_type, const void* blocks, int64_t E, int64_t 
                              int64_t pairs_per_row, const int32_t* expert_start, const int32_t* order, int64_t P, int x_dtype,
                              void* y, void* stream) {
     if (int rc = options_ok()) return rc;
-    const bool kq = q_type >= GQ_Q2_K && q_type <= GQ_Q6_K;
-    if (!kq && q_type != GQ_Q8_0) GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed_experts: unknown q_type %d (a K-quant or GQ_Q8_0)", q_type);
+    if (!packed_type(q_type))
+        GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed_experts: unknown q_type %d (a K-quant, GQ_Q8_0, GQ_IQ4_NL or GQ_IQ4_XS)", q_type);
     if (x_dtype != GQ_F16 && x_dtype != GQ_BF16)
         GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed_experts: x_dtype %d (GQ_F16 or GQ_BF16; there is no fp32 path)", x_dtype);
     if (!blocks) GQ_FAIL(GQ_E_NULL, "gq_linear_packed_experts: blocks is NULL");
@@ -235,8 +236,8 @@ int gq_linear_packed_experts(int q_type, const void* blocks, int64_t E, int64_t 
         GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: x_rows=%ld * pairs_per_row=%ld != P=%ld", (long)x_rows,
                 (long)pairs_per_row, (long)P);
     if (C < 256 || C > 0x7fffffff || C % 256)
-        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 included)", (long)C);
-    const int al = kq ? block_align(q_type) : 2;
+        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 and IQ4_NL included)", (long)C);
+    const int al = block_align(q_type);
     if (!aligned(blocks, al)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: blocks not %d-byte aligned", al);
     if (!aligned(expert_start, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: expert_start not 4-byte aligned");
     if (!aligned(order, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: order not 4-byte aligned");
@@ -265,6 +266,8 @@ int gq_linear_packed_experts(int q_type, const void* blocks, int64_t E, int64_t 
     case GQ_Q4_K: launch<GQ_Q4_K>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
     case GQ_Q5_K: launch<GQ_Q5_K>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
     case GQ_Q6_K: launch<GQ_Q6_K>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
+    case GQ_IQ4_NL: launch<GQ_IQ4_NL>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
+    case GQ_IQ4_XS: launch<GQ_IQ4_XS>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
     default: launch<GQ_Q8_0>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
     }
     GQ_LAUNCH_CHECK();

@@ -84,8 +84,8 @@ extern "C" {
 int gq_gemv_packed_experts(int q_type, const void* blocks, int64_t E, int64_t R, int64_t C, const void* x, int64_t x_rows,
                            const int32_t* pair_expert, int64_t P, int64_t pairs_per_row, int x_dtype, void* y, void* stream) {
     if (int rc = options_ok()) return rc;
-    const bool kq = q_type >= GQ_Q2_K && q_type <= GQ_Q6_K;
-    if (!kq && q_type != GQ_Q8_0) GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed_experts: unknown q_type %d (a K-quant or GQ_Q8_0)", q_type);
+    if (!packed_type(q_type))
+        GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed_experts: unknown q_type %d (a K-quant, GQ_Q8_0, GQ_IQ4_NL or GQ_IQ4_XS)", q_type);
     if (x_dtype != GQ_F16 && x_dtype != GQ_BF16)
         GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed_experts: x_dtype %d (GQ_F16 or GQ_BF16; there is no fp32 path)", x_dtype);
     if (!blocks) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed_experts: blocks is NULL");
@@ -100,8 +100,8 @@ int gq_gemv_packed_experts(int q_type, const void* blocks, int64_t E, int64_t R,
         GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: x_rows=%ld * pairs_per_row=%ld != P=%ld", (long)x_rows,
                 (long)pairs_per_row, (long)P);
     if (C < 256 || C > 0x7fffffff || C % 256)
-        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 included)", (long)C);
-    const int al = kq ? block_align(q_type) : 2;
+        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 and IQ4_NL included)", (long)C);
+    const int al = block_align(q_type);
     if (!aligned(blocks, al)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: blocks not %d-byte aligned", al);
     if (!aligned(pair_expert, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: pair_expert not 4-byte aligned");
     if (!aligned(x, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: x not 16-byte aligned");
@@ -121,6 +121,8 @@ int gq_gemv_packed_experts(int q_type, const void* blocks, int64_t E, int64_t R,
     case GQ_Q4_K: launch<GQ_Q4_K>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
     case GQ_Q5_K: launch<GQ_Q5_K>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
     case GQ_Q6_K: launch<GQ_Q6_K>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
+    case GQ_IQ4_NL: launch<GQ_IQ4_NL>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
+    case GQ_IQ4_XS: launch<GQ_IQ4_XS>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
     default: launch<GQ_Q8_0>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
     }
     GQ_LAUNCH_CHECK();

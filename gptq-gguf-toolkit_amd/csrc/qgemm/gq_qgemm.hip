@@ -1,4 +1,5 @@
-// gq_qgemm.hip -- K21: y = x W^T for a Linear whose weight [R, C] exists only as GGUF block bytes (K-quants, Q8_0).
+// gq_qgemm.hip -- K21: y = x W^T for a Linear whose weight [R, C] exists only as GGUF block bytes (K-quants, Q8_0,
+// IQ4_NL, IQ4_XS).
 // gq_linear_packed is the forward of packed residency: the search and ppleval keep every level packed and no dense copy.
 //
 // Regime: T >= 256 tokens per call (calibration batches of the search, perplexity windows); small T is correct, not fast.
@@ -22,7 +23,7 @@
 // LDS: x chunk as 8 planes (one per 8-k piece u = 2 (l >> 4) + s) of 256 slots of 16 bytes: the 16 lanes of a quarter wave
 // read 256 contiguous bytes, and the lane groups of ds_read_b128 ({0-3, 12-15, 20-27}, ...) take slots {0-3, 12-15} of one
 // plane and {4-11} of another, planes 4096 bytes apart: conflict-free.  Packed slots have an odd number of 16-byte units
-// (Q2_K / Q3_K 112, Q4_K 144, Q5_K 176, Q6_K 240, Q8_0 304 bytes) so that 16 rows' reads at the same offset fall on 16
+// (Q2_K / Q3_K 112, Q4_K / IQ4_NL / IQ4_XS 144, Q5_K 176, Q6_K 240, Q8_0 304 bytes) so that 16 rows' reads at the same offset fall on 16
 // different 16-byte bank groups.  Budget: 32 KB + 128 slots + 1 KB of row offsets = 47 KB (Q2_K) .. 63 KB (Q6_K), 71 KB (Q8_0): two workgroups
 // per CU, which is also what ~220 VGPRs allow; the staging latency of one is covered by the MFMAs of the other.
 // Rows >= R and tokens >= T of an edge tile: the rows are not staged (their LDS slots hold stale bytes, decoded to values
@@ -71,11 +72,20 @@ int64_t tiles(int64_t R, int64_t T, int tt) {
     return n_tt > 0x7fffffff / n_rt ? 0 : n_rt * n_tt;
 }
 
+// IQ4_XS has the 128-token tile only: its 256-token instance spills 190 bytes per lane inside the K loop and was measured at
+// 1.7-2.3x Q4_K's time where the grid takes the wide tile, against 0.85-0.98x at the narrow one (DESIGN K26).
+constexpr bool wide_ok(int q_type) { return q_type != GQ_IQ4_XS; }
+
 template <int QT, bool BF16>
 void launch_dt(bool wide, dim3 grid, hipStream_t st, const uint8_t* blocks, const int32_t* row_src, int64_t R, int64_t C,
                const uint8_t* x, int64_t T, uint16_t* y, uint32_t n_rt) {
-    if (wide) hipLaunchKernelGGL((linear_packed_kernel<QT, BF16, 256>), grid, dim3(256), 0, st, blocks, row_src, R, C, x, T, y, n_rt);
-    else hipLaunchKernelGGL((linear_packed_kernel<QT, BF16, 128>), grid, dim3(256), 0, st, blocks, row_src, R, C, x, T, y, n_rt);
+    if constexpr (wide_ok(QT)) {
+        if (wide) {
+            hipLaunchKernelGGL((linear_packed_kernel<QT, BF16, 256>), grid, dim3(256), 0, st, blocks, row_src, R, C, x, T, y, n_rt);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((linear_packed_kernel<QT, BF16, 128>), grid, dim3(256), 0, st, blocks, row_src, R, C, x, T, y, n_rt);
 }
 
 template <int QT>
@@ -95,8 +105,8 @@ extern "C" {
 int gq_linear_packed(int q_type, const void* blocks, const int32_t* row_src, int64_t R, int64_t C, const void* x, int64_t T,
                      int x_dtype, void* y, void* stream) {
     if (int rc = options_ok()) return rc;
-    const bool kq = q_type >= GQ_Q2_K && q_type <= GQ_Q6_K;
-    if (!kq && q_type != GQ_Q8_0) GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed: unknown q_type %d (a K-quant or GQ_Q8_0)", q_type);
+    if (!packed_type(q_type))
+        GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed: unknown q_type %d (a K-quant, GQ_Q8_0, GQ_IQ4_NL or GQ_IQ4_XS)", q_type);
     if (x_dtype != GQ_F16 && x_dtype != GQ_BF16)
         GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed: x_dtype %d (GQ_F16 or GQ_BF16; there is no fp32 path)", x_dtype);
     if (!blocks) GQ_FAIL(GQ_E_NULL, "gq_linear_packed: blocks is NULL");
@@ -105,14 +115,14 @@ int gq_linear_packed(int q_type, const void* blocks, const int32_t* row_src, int
     if (R < 1 || R > 0x7fffffff) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: R=%ld (not in [1, 2^31))", (long)R);
     if (T < 1 || T > 0x7fffffff) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: T=%ld (not in [1, 2^31))", (long)T);
     if (C < 256 || C > 0x7fffffff || C % 256)
-        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 included)", (long)C);
-    const int al = kq ? block_align(q_type) : 2;
+        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 and IQ4_NL included)", (long)C);
+    const int al = block_align(q_type);
     if (!aligned(blocks, al)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: blocks not %d-byte aligned", al);
     if (!aligned(row_src, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: row_src not 4-byte aligned");
     if (!aligned(x, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: x not 16-byte aligned");
     if (!aligned(y, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: y not 16-byte aligned");
     // the 256-token tile halves the decode work per output, the 128-token one fills the device at small shapes
-    const bool wide = tiles(R, T, 256) >= WIDE_TILES;
+    const bool wide = wide_ok(q_type) && tiles(R, T, 256) >= WIDE_TILES;
     const int64_t n_rt = (R + TR - 1) / TR, n_wg = tiles(R, T, wide ? 256 : 128);
     if (!n_wg) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: R=%ld T=%ld is more than one launch takes", (long)R, (long)T);
     const dim3 grid((unsigned)n_wg);
@@ -127,6 +137,8 @@ int gq_linear_packed(int q_type, const void* blocks, const int32_t* row_src, int
     case GQ_Q4_K: launch<GQ_Q4_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
     case GQ_Q5_K: launch<GQ_Q5_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
     case GQ_Q6_K: launch<GQ_Q6_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
+    case GQ_IQ4_NL: launch<GQ_IQ4_NL>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
+    case GQ_IQ4_XS: launch<GQ_IQ4_XS>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
     default: launch<GQ_Q8_0>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
     }
     GQ_LAUNCH_CHECK();

@@ -1,5 +1,5 @@
 // gq_qgemv.hip -- K22: y = x W^T for 1 <= T <= 16 tokens and a weight [R, C] that exists only as GGUF block bytes (K-quants,
-// Q8_0): the decode step of a packed model.  gq_gemv_packed has the contract of gq_linear_packed (K21) -- the same operand
+// Q8_0, IQ4_NL, IQ4_XS): the decode step of a packed model.  gq_gemv_packed has the contract of gq_linear_packed (K21) -- the same operand
 // bits, fp32 accumulation, one rounding -- at the shape where that kernel launches R / 128 workgroups and fills 127 of 128
 // tokens of its tile with zeros.  Here the call is one stream over the weight bytes, spread over the whole device.
 //
@@ -65,8 +65,8 @@ extern "C" {
 int gq_gemv_packed(int q_type, const void* blocks, const int32_t* row_src, int64_t R, int64_t C, const void* x, int64_t T,
                    int x_dtype, void* y, void* stream) {
     if (int rc = options_ok()) return rc;
-    const bool kq = q_type >= GQ_Q2_K && q_type <= GQ_Q6_K;
-    if (!kq && q_type != GQ_Q8_0) GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed: unknown q_type %d (a K-quant or GQ_Q8_0)", q_type);
+    if (!packed_type(q_type))
+        GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed: unknown q_type %d (a K-quant, GQ_Q8_0, GQ_IQ4_NL or GQ_IQ4_XS)", q_type);
     if (x_dtype != GQ_F16 && x_dtype != GQ_BF16)
         GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed: x_dtype %d (GQ_F16 or GQ_BF16; there is no fp32 path)", x_dtype);
     if (!blocks) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed: blocks is NULL");
@@ -76,8 +76,8 @@ int gq_gemv_packed(int q_type, const void* blocks, const int32_t* row_src, int64
     if (T < 1 || T > GQ_GEMV_MAX_T)
         GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: T=%ld (not in [1, %d]; gq_linear_packed takes more tokens)", (long)T, GQ_GEMV_MAX_T);
     if (C < 256 || C > 0x7fffffff || C % 256)
-        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 included)", (long)C);
-    const int al = kq ? block_align(q_type) : 2;
+        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 and IQ4_NL included)", (long)C);
+    const int al = block_align(q_type);
     if (!aligned(blocks, al)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: blocks not %d-byte aligned", al);
     if (!aligned(row_src, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: row_src not 4-byte aligned");
     if (!aligned(x, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: x not 16-byte aligned");
@@ -96,6 +96,8 @@ int gq_gemv_packed(int q_type, const void* blocks, const int32_t* row_src, int64
     case GQ_Q4_K: launch<GQ_Q4_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
     case GQ_Q5_K: launch<GQ_Q5_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
     case GQ_Q6_K: launch<GQ_Q6_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
+    case GQ_IQ4_NL: launch<GQ_IQ4_NL>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
+    case GQ_IQ4_XS: launch<GQ_IQ4_XS>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
     default: launch<GQ_Q8_0>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
     }
     GQ_LAUNCH_CHECK();

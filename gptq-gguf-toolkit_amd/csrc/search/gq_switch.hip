@@ -13,11 +13,12 @@
 //   dense : 512 chunks of 16 output bytes, two per thread, chunk k = (row k / cpr, 16 / elsize columns): one 8- / 16- /
 //           32-byte load of the (gathered) source row, exact widening to fp32, one RNE cast (f2h / f2bf: torch's
 //           .to(dtype)), one 16-byte store.
-//   Q8_0  : blockdec::decode_turn_q8_0<OutT>, gq_dequantize_blocks' turn for that type: 128 blocks of 32 values -- the same
+//   Q8_0  : blockdec::decode_turn_b32<QT, OutT>, gq_dequantize_blocks' turn for that type: 128 blocks of 32 values -- the same
 //           4096 values per unit --, 2-byte staging loads, half a block per thread.
+//   IQ4_XS takes the packed arm (a 256-value type with 8-byte staging loads), IQ4_NL Q8_0's (include/gptq_gguf_iq4.h).
 // The kind / out_dtype dispatch is a switch on block-uniform values: a workgroup executes one arm.  HBM-bound like K15:
 // 0.33-0.82 B/param in, 2 or 4 B/param out; the unit is K15's turn so that the per-byte rate is K15's.
-#include "../../../include/gptq_gguf_q8.h"  // (includes gptq_gguf_search.h)
+#include "../../../include/gptq_gguf_iq4.h"  // (includes gptq_gguf_q8.h and gptq_gguf_search.h)
 #include "gq_block_decode.hpp"
 
 namespace gq {
@@ -31,7 +32,7 @@ struct SwitchEntry {
     const uint8_t* src;
     uint8_t* dst;
     const int32_t* row_src;
-    int64_t n;          // packed: blocks of the job (R * C / 256; Q8_0: R * C / 32); dense: 16-byte output chunks (R * cpr)
+    int64_t n;          // packed: blocks of the job (R * C / 256; Q8_0 / IQ4_NL: R * C / 32); dense: 16-byte output chunks (R * cpr)
     int32_t per_row;    // packed: blocks per row; dense: chunks per row (cpr)
     uint32_t unit_end;  // work units of entries 0 .. this one
     int32_t kind, out_dtype;
@@ -53,12 +54,13 @@ __device__ __forceinline__ void packed_unit(const SwitchEntry& J, int64_t b0, ui
     }
 }
 
-__device__ __forceinline__ void q8_0_unit(const SwitchEntry& J, int64_t b0, uint8_t* sb, int64_t* ssrc) {
-    const int nb = (int)((J.n - b0) < Q8_DB ? (J.n - b0) : Q8_DB);
+template <int QT>
+__device__ __forceinline__ void b32_unit(const SwitchEntry& J, int64_t b0, uint8_t* sb, int64_t* ssrc) {
+    const int nb = (int)((J.n - b0) < B32_DB ? (J.n - b0) : B32_DB);
     switch (J.out_dtype) {
-    case GQ_F32: decode_turn_q8_0<float>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<float*>(J.dst), sb, ssrc); break;
-    case GQ_F16: decode_turn_q8_0<half_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<half_bits*>(J.dst), sb, ssrc); break;
-    default: decode_turn_q8_0<bf16_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<bf16_bits*>(J.dst), sb, ssrc); break;
+    case GQ_F32: decode_turn_b32<QT, float>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<float*>(J.dst), sb, ssrc); break;
+    case GQ_F16: decode_turn_b32<QT, half_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<half_bits*>(J.dst), sb, ssrc); break;
+    default: decode_turn_b32<QT, bf16_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<bf16_bits*>(J.dst), sb, ssrc); break;
     }
 }
 
@@ -131,7 +133,9 @@ __global__ __launch_bounds__(256) void level_switch_kernel(const SwitchTable t) 
     case GQ_Q4_K: packed_unit<GQ_Q4_K>(J, ul * DB, sb, ssrc); break;
     case GQ_Q5_K: packed_unit<GQ_Q5_K>(J, ul * DB, sb, ssrc); break;
     case GQ_Q6_K: packed_unit<GQ_Q6_K>(J, ul * DB, sb, ssrc); break;
-    case GQ_Q8_0: q8_0_unit(J, ul * Q8_DB, sb, ssrc); break;
+    case GQ_IQ4_XS: packed_unit<GQ_IQ4_XS>(J, ul * DB, sb, ssrc); break;
+    case GQ_Q8_0: b32_unit<GQ_Q8_0>(J, ul * B32_DB, sb, ssrc); break;
+    case GQ_IQ4_NL: b32_unit<GQ_IQ4_NL>(J, ul * B32_DB, sb, ssrc); break;
     case GQ_F32: dense_unit_from<GQ_F32>(J, ul * DENSE_CHUNKS); break;
     case GQ_F16: dense_unit_from<GQ_F16>(J, ul * DENSE_CHUNKS); break;
     default: dense_unit_from<GQ_BF16>(J, ul * DENSE_CHUNKS); break;
@@ -141,13 +145,13 @@ __global__ __launch_bounds__(256) void level_switch_kernel(const SwitchTable t) 
 bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 bool is_dtype(int d) { return d == GQ_F32 || d == GQ_F16 || d == GQ_BF16; }
 int elsize(int d) { return d == GQ_F32 ? 4 : 2; }
-int block_align(int q) { return q == GQ_Q2_K ? 4 : (q == GQ_Q4_K || q == GQ_Q5_K) ? 16 : 2; }
+int block_align(int q) { return q == GQ_Q2_K ? 4 : (q == GQ_Q4_K || q == GQ_Q5_K) ? 16 : q == GQ_IQ4_XS ? 8 : 2; }
 
 constexpr int64_t MAX_UNITS = 0x7fffffff;  // of one launch (the grid's x extent) and so of one job
 
 // every check of job i; fills the job's table entry except unit_end, and its unit count
 int check_job(const gq_switch_job_t& j, int i, SwitchEntry& e, int64_t& units) {
-    const bool packed = j.kind >= GQ_Q2_K && j.kind <= GQ_Q6_K, q8 = j.kind == GQ_Q8_0;
+    const bool packed = (j.kind >= GQ_Q2_K && j.kind <= GQ_Q6_K) || j.kind == GQ_IQ4_XS, q8 = j.kind == GQ_Q8_0 || j.kind == GQ_IQ4_NL;
     if (!packed && !q8 && !is_dtype(j.kind)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_level_switch: job %d: unknown kind %d", i, j.kind);
     if (!is_dtype(j.out_dtype)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_level_switch: job %d: unknown out_dtype %d", i, j.out_dtype);
     if (!j.src) GQ_FAIL(GQ_E_NULL, "gq_level_switch: job %d: src is NULL", i);
@@ -166,7 +170,7 @@ int check_job(const gq_switch_job_t& j, int i, SwitchEntry& e, int64_t& units) {
     } else if (q8) {
         if (j.C % 32) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: C=%ld (C %% 32 != 0)", i, (long)j.C);
         if (!aligned(j.src, 2)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: src not 2-byte aligned", i);
-        e.per_row = (int32_t)(j.C / 32), per_unit = Q8_DB;
+        e.per_row = (int32_t)(j.C / 32), per_unit = B32_DB;
     } else {
         const int ses = elsize(j.kind);
         if (j.C * ses % 16 || j.C * des % 16)

@@ -133,7 +133,7 @@ def parse_args(argv=None):
     p.add_argument("--output_file", type=str, required=True, help="Path to the output JSON file")
     p.add_argument("--gguf", type=str, default=None, help="take ALL weights from this .gguf (decoded on the GPU)")
     p.add_argument("--packed", default=False, action="store_true",
-                   help="with --gguf: keep the K-quant / Q8_0 weights of the blocks' Linears packed on the device")
+                   help="with --gguf: keep the K-quant / Q8_0 / IQ4_NL / IQ4_XS weights of the blocks' Linears packed on the device")
     p.add_argument("--packed_vocab", default=False, action="store_true",
                    help="with --packed: keep token_embd and output packed as well (a PackedEmbedding and a packed lm_head)")
     p.add_argument("--moe_prefill", type=str, default="loop", choices=["loop", "grouped"],

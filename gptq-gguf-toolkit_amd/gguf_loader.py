@@ -1,13 +1,15 @@
 """GGUF -> HF tensors on the GPU: the inverse of pack_gptq_into_gguf.py for the dense Llama family and for Mixtral.
 
 The reference reads a .gguf back through transformers' GGUF loader (mapper/gguf_splitter.py:469-474), which needs gguf-py;
-that package is not installable here, so the file is parsed by gguf_writer.parse_gguf (spec level) and the K-quant and Q8_0
-payloads are decoded by this package's own kernel: bytes are uploaded as they lie in the file and `ops.dequantize_blocks` writes the
+that package is not installable here, so the file is parsed by gguf_writer.parse_gguf (spec level) and the K-quant, Q8_0,
+IQ4_NL and IQ4_XS payloads are decoded by this package's own kernel: bytes are uploaded as they lie in the file and `ops.dequantize_blocks` writes the
 weights in one pass.  The q_proj / k_proj rotary row permutation the converter applied (reference
 pack_gptq_into_gguf.py:2177-2183) is undone inside that pass by a row gather (`row_src`), for architecture "llama" only.
 F32 / F16 / BF16 tensors pass through with a cast.  Q8_0 (`--outtype q8_0` writes it for the tensors GPTQ did not quantize, and
 it may be a level of the search) takes the same one call as the K-quants: d * q of ggml-quants.c dequantize_row_q8_0, the row
-gather folded in, one cast to `dtype`.  The file is mapped, never read whole.
+gather folded in, one cast to `dtype`.  IQ4_NL and IQ4_XS (include/gptq_gguf_iq4.h), which llama.cpp writes and this package
+does not encode, are read in the same way; a tensor of a 32-value type whose rows are no multiple of 256 loads dense and is
+never kept packed.  The file is mapped, never read whole.
 Merged 3-D expert tensors (`blk.N.ffn_{gate,up,down}_exps.weight`, [E, R, C]) are decoded in one call over [E * R, C] and
 come back under the names the target model has (EXPERT_LAYOUTS): "fused", transformers 5.x, where a layer keeps
 `mlp.experts.gate_up_proj` [E, 2I, H] (per expert the gate rows, then the up rows) and `mlp.experts.down_proj` [E, H, I] and the
@@ -22,7 +24,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .gguf_writer import K_QUANTS, PLAIN_TYPES, GGMLType, parse_gguf
+from .gguf_writer import K_QUANTS, PACKED_TYPES, PLAIN_TYPES, parse_gguf
 from .pack_gptq_into_gguf import _BLOCK_TABLE
 
 ROTARY_TENSORS = (".attn_q.weight", ".attn_k.weight")  # the tensors whose rows the converter permutes
@@ -154,7 +156,7 @@ def iter_gguf_tensors(path: str, device="cuda:0", dtype: Optional[torch.dtype] =
         flat = (int(np.prod(shape[:-1])), shape[-1])  # an expert tensor: E * R rows
         if gt in K_QUANTS:
             t = ops.dequantize_blocks(gt, raw.view(flat[0], -1), dtype or quant_dtype or torch.float32, rows)
-        elif gt == GGMLType.Q8_0:  # (quant_dtype is the K-quants' alone)
+        elif gt in PACKED_TYPES:  # Q8_0, IQ4_NL, IQ4_XS (quant_dtype is the K-quants' alone)
             t = ops.dequantize_blocks(gt, raw.view(flat[0], -1), dtype or torch.float32, rows)
         else:
             if gt not in PLAIN_TYPES:
@@ -197,13 +199,13 @@ def load_state_dict(path: str, device="cuda:0", dtype: Optional[torch.dtype] = N
 
 
 def packed_linear_tensors(model: torch.nn.Module, path: str) -> Dict[str, tuple]:
-    """{HF module name: (GGUF tensor name, ggml type)} of the file's K-quant / Q8_0 tensors that are the weight of an
+    """{HF module name: (GGUF tensor name, ggml type)} of the file's K-quant / Q8_0 / IQ4_NL / IQ4_XS tensors that are the weight of an
     nn.Linear of a block of `model` with in_features % 256 == 0 -- what load_into_model(packed=True) keeps packed.
     lm_head, embeddings and norms are not among them."""
     _, tensors, _ = parse_gguf(str(path), mmap=True)
     out = {}
     for name, shape, gt, _, _ in tensors:
-        if not (gt in K_QUANTS or gt == GGMLType.Q8_0) or len(shape) != 2 or not name.startswith("blk."):
+        if not gt in PACKED_TYPES or len(shape) != 2 or not name.startswith("blk."):
             continue
         hf = hf_tensor_name(name)
         mod = hf[:-len(".weight")] if hf.endswith(".weight") else None
@@ -233,7 +235,7 @@ def packed_vocab_tensors(model: torch.nn.Module, path: str) -> Dict[str, tuple]:
             layer = model.get_submodule(mod)
         except AttributeError:
             return False
-        return ((gt in K_QUANTS or gt == GGMLType.Q8_0) and len(shape) == 2 and isinstance(layer, kind)
+        return (gt in PACKED_TYPES and len(shape) == 2 and isinstance(layer, kind)
                 and tuple(layer.weight.shape) == tuple(shape) and shape[1] % 256 == 0)
 
     out = {}
@@ -261,7 +263,7 @@ def packed_expert_tensors(model: torch.nn.Module, path: str) -> Dict[str, dict]:
     by_layer: Dict[int, dict] = {}
     for name, shape, gt, _, _ in tensors:
         exp = expert_tensor(name)
-        if exp is not None and len(shape) == 3 and (gt in K_QUANTS or gt == GGMLType.Q8_0) and shape[2] % 256 == 0:
+        if exp is not None and len(shape) == 3 and gt in PACKED_TYPES and shape[2] % 256 == 0:
             by_layer.setdefault(exp[0], {})[exp[1]] = (name, tuple(shape), gt, exp[2])
 
     def module(mod):
@@ -346,7 +348,7 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
 def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill: str = "loop") -> torch.nn.Module:
     """Load the file's weights into `model` (parameters on a GPU), strict on names and shapes.  A tied lm_head (no
     `output.weight` in the file) follows token_embd.
-    packed=True: the K-quant and Q8_0 tensors of the blocks' nn.Linear modules stay packed on the device -- each such Linear
+    packed=True: the K-quant, Q8_0, IQ4_NL and IQ4_XS tensors of the blocks' nn.Linear modules stay packed on the device -- each such Linear
     becomes a packed_linear.PackedLinear whose forward reads the block bytes (the q / k rotary permutation undone by its
     row_src), about 4.5 bits per parameter for a Q4_K file instead of 16; embeddings, norms and lm_head load as without it.
     The merged expert tensors of a MoE file stay packed in the same way (packed_expert_tensors): a transformers-5.x expert

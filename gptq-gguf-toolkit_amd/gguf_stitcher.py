@@ -18,7 +18,7 @@ the reports of validate_config / list_available_tensors / inspect_metadata.
 the dominant width (4.5 -> 4) and, when that width has more than half of the tensors, looks it up in a table of ggml TYPE
 ids (12 for Q4_K, 14 for Q6_K), otherwise writes 12; ties go to the width seen first.  llama.cpp reads the key as a
 LLAMA_FTYPE id, where 12 means Q3_K_M.  `--llama-ftype` / `llama_ftype=True` writes that enumeration instead (F32 0, F16 1,
-Q8_0 7, Q2_K 10, Q3_K_M 12, Q4_K_M 15, Q5_K_M 17, Q6_K 18, BF16 32; mixed or no majority 15).
+Q8_0 7, Q2_K 10, Q3_K_M 12, Q4_K_M 15, Q5_K_M 17, Q6_K 18, IQ4_NL 25, IQ4_XS 30, BF16 32; mixed or no majority 15).
 
 Deliberately different from the reference:
   * streaming: the reference loads every tensor into a list before it writes; here each tensor is a
@@ -34,8 +34,9 @@ Deliberately different from the reference:
   * a source without key/value data (a --both database, whose manifest.json is the HF side's, with no original model to be
     found) and a source whose general.alignment is not the writer's 32 are refused like a tensor that cannot be written: the
     reference would write a file without keys, or one whose alignment key contradicts its layout.
-Only F32 / F16 / BF16 / Q8_0 / Q2_K..Q6_K payloads can be written by gguf_writer.py; a tensor that resolves to any other
-type (the IQ family, Q4_0, Q8_K, ...: known by name for the reports) is refused by name, never written under another type.
+Only F32 / F16 / BF16 / Q8_0 / Q2_K..Q6_K / IQ4_NL / IQ4_XS payloads can be written by gguf_writer.py; a tensor that resolves
+to any other type (the other IQ types, Q4_0, Q8_K, ...: known by name for the reports) is refused by name, never written under
+another type.
 
 `verify` (a keyword here, `--verify` on the command line) is the guarantee the reference does not give -- the file written is
 the model the search scored: the renamed file is read back through gguf_loader (mapped, decoded on the GPU by
@@ -75,7 +76,8 @@ WIDTH_CLASSES = ((2.0, 2.7, {2.0625: "IQ2_XXS", 2.3125: "IQ2_XS", 2.5: "IQ2_S", 
                  (8.0, 9.0, {}, ("Q8_0", "Q8_1"), "Q8_K"),
                  (1.0, 1.6, {}, (), "IQ1_S"))
 FILE_TYPE_BY_WIDTH = {32: 0, 16: 1, 8: 7, 6: 14, 5: 13, 4: 12, 3: 11, 2: 10}  # the reference's table (:660-669): ggml TYPE ids
-LLAMA_FTYPE = {"F32": 0, "F16": 1, "Q8_0": 7, "Q2_K": 10, "Q3_K": 12, "Q4_K": 15, "Q5_K": 17, "Q6_K": 18, "BF16": 32}
+LLAMA_FTYPE = {"F32": 0, "F16": 1, "Q8_0": 7, "Q2_K": 10, "Q3_K": 12, "Q4_K": 15, "Q5_K": 17, "Q6_K": 18, "IQ4_NL": 25, "IQ4_XS": 30,
+               "BF16": 32}
 LLAMA_FTYPE_MIXED = 15  # LLAMA_FTYPE_MOSTLY_Q4_K_M
 SKIP_KEYS = ("general.file_type", "general.quantization_version")  # re-added last (:679-682, :766-774)
 VALUE_TYPE_NAMES = {v: k for k, v in vars(GGUFValueType).items() if k.isupper()}
@@ -501,8 +503,8 @@ class GGUFStitcher:
     def verify(self, device="cuda") -> int:
         """The file at output_path against the level files the configuration chose: read back through gguf_loader (mapped,
         decoded on the GPU) and compared bit for bit with level_db.load_level, tensor by tensor in file order.
-        Raises StitchError naming the first tensor that differs; returns the number of tensors compared (Q8_0 tensors are
-        compared as stored bytes: the loader decodes them to fp32 and load_level to fp16, and equal bytes are the stricter
+        Raises StitchError naming the first tensor that differs; returns the number of tensors compared (Q8_0, IQ4_NL and
+        IQ4_XS tensors are compared as stored bytes: the loader decodes them to fp32 and load_level to fp16, and equal bytes are the stricter
         check of the two)."""
         import torch
         from .gguf_loader import iter_gguf_tensors
@@ -521,7 +523,7 @@ class GGUFStitcher:
             if ggml_type != p.ggml_type or tuple(shape) != p.shape:
                 raise StitchError(f"verify: tensor {name!r} is type {ggml_type} of shape {tuple(shape)} in {self.output_path}, "
                                   f"level {p.path.name} is {p.type_name} of shape {p.shape}")
-            if p.type_name == "Q8_0":
+            if p.type_name in ("Q8_0", "IQ4_NL", "IQ4_XS"):
                 same = bool(np.array_equal(np.asarray(buf[off:off + nbytes]), level_db.read_level_raw(p)))
             else:
                 want = level_db.load_level(str(p.path), got.device).reshape(got.shape)

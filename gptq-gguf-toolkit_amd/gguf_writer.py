@@ -49,6 +49,7 @@ class GGMLType:
     F32, F16 = 0, 1
     Q8_0 = 8
     Q2_K, Q3_K, Q4_K, Q5_K, Q6_K = 10, 11, 12, 13, 14
+    IQ4_NL, IQ4_XS = 20, 23  # payload bytes pass through: there is no encoder for them (include/gptq_gguf_iq4.h)
     BF16 = 30
 
 
@@ -56,8 +57,10 @@ class GGMLType:
 GGML_QUANT_SIZES = {GGMLType.F32: (1, 4), GGMLType.F16: (1, 2), GGMLType.BF16: (1, 2), GGMLType.Q8_0: (32, 34),
                     GGMLType.Q2_K: (256, 84),
                     GGMLType.Q3_K: (256, 110), GGMLType.Q4_K: (256, 144), GGMLType.Q5_K: (256, 176),
-                    GGMLType.Q6_K: (256, 210)}
+                    GGMLType.Q6_K: (256, 210), GGMLType.IQ4_NL: (32, 18), GGMLType.IQ4_XS: (256, 136)}
 K_QUANTS = (GGMLType.Q2_K, GGMLType.Q3_K, GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q6_K)
+# the block types whose bytes the GPU reads (ops.dequantize_blocks, ops.level_switch, the packed forward)
+PACKED_TYPES = K_QUANTS + (GGMLType.Q8_0, GGMLType.IQ4_NL, GGMLType.IQ4_XS)
 # types stored as plain matrices: (torch dtype name, numpy dtype name -- numpy has no bf16 --, item size)
 PLAIN_TYPES = {GGMLType.F32: ("float32", "float32", 4), GGMLType.F16: ("float16", "float16", 2),
                GGMLType.BF16: ("bfloat16", "uint16", 2)}
@@ -320,7 +323,8 @@ def parse_gguf(path: str, mmap: bool = False):
     tensors = []
     for name, shape, gt, off in infos:
         if gt not in GGML_QUANT_SIZES:
-            raise ValueError(f"tensor {name!r}: ggml type {gt} is not supported (F32, F16, BF16, Q8_0 and the K-quants are)")
+            raise ValueError(f"tensor {name!r}: ggml type {gt} is not supported (F32, F16, BF16, Q8_0, the K-quants, IQ4_NL "
+                             f"and IQ4_XS are)")
         bs, ts = GGML_QUANT_SIZES[gt]
         tensors.append((name, shape, gt, data0 + off, int(np.prod(shape)) // bs * ts))
     return kv, tensors, buf

@@ -200,8 +200,8 @@ def read_level_raw(rec) -> np.ndarray:
 
 def load_level(path: str, device, db: Optional[str] = None):
     """One level's weight on `device`: a torch-saved tensor (--hf-layers) as it is; raw GGUF bytes (--gguf-layers) as a view
-    for plain types, decoded to fp16 by ops.dequantize_blocks for K-quants and Q8_0, with the manifest's q / k row gather if
-    `db`."""
+    for plain types, decoded to fp16 by ops.dequantize_blocks for K-quants, Q8_0, IQ4_NL and IQ4_XS, with the manifest's q / k
+    row gather if `db`."""
     import torch
     rec = read_sidecar(path)
     if rec.ggml_type is None:
@@ -231,7 +231,10 @@ NP_ITEMSIZE = {"uint8": 1, "int8": 1, **{np_name: size for _, np_name, size in P
 
 # Views of the tables on the types the reference's splitter names (mapper/gguf_splitter.py:42-50, :56-96; + BF16), narrow on
 # purpose: any other name ("IQ2_XS") keeps the exact width 32.0 there (resolve_hf_bitwidth with --exact), not the full table's.
-SPLIT_TYPES = ("F32", "F16", "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1", "Q2_K", "Q3_K", "Q4_K", "Q5_K", "Q6_K", "Q8_K", "BF16")
+# IQ4_NL / IQ4_XS are the two IQ types whose bytes this package reads (include/gptq_gguf_iq4.h): their levels are named and
+# sized as the reference's splitter does, "4.56-IQ4_NL.pth" / "4.25-IQ4_XS.pth".
+SPLIT_TYPES = ("F32", "F16", "Q4_0", "Q4_1", "Q5_0", "Q5_1", "Q8_0", "Q8_1", "Q2_K", "Q3_K", "Q4_K", "Q5_K", "Q6_K", "Q8_K", "BF16",
+               "IQ4_NL", "IQ4_XS")
 TYPE_NAMES = {GGML_TYPE_IDS[name]: name for name in SPLIT_TYPES}
 EXACT_BITS = {name: BIT_WIDTHS[name] for name in SPLIT_TYPES}
 

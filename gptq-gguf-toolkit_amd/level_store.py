@@ -11,14 +11,14 @@ storage: no file, no host copy, no [R, C] temporary, no reallocation (weight.dat
 Both database layouts of gguf_splitter are read, through level_db:
   --hf-layers   <db>/<HF module name>/<bpw>-<Qn_K>.pth   torch-saved dense tensors: kept dense in their own dtype; a switch
                 is a cast copy with .to(dtype) rounding, so the weight equals torch.load(file).to(dtype) bit for bit;
-  --gguf-layers <db>/<GGUF tensor name>/<bpw>.pth + -metadata.json   raw block bytes (K-quants, Q8_0): kept packed; a switch decodes them
+  --gguf-layers <db>/<GGUF tensor name>/<bpw>.pth + -metadata.json   raw block bytes (K-quants, Q8_0, IQ4_NL, IQ4_XS): kept packed; a switch decodes them
                 (with the q / k rotary row gather of the manifest) straight to the weight dtype.  For fp16 weights that is
                 level_db.load_level(file).to(dtype) bit for bit; for bf16 / fp32 weights the value is rounded ONCE
                 from the fp32 decode, where load_level's fp16 tensor followed by .to(dtype) rounds twice.
 
 resident="packed" (default "dense") keeps NO dense live copy: every held Linear becomes a packed_linear.PackedLinear whose
 forward reads the current level's block bytes (ops.linear_packed), its dense storage is freed, and a switch is a change of
-references -- no launch, no device memory moves.  The levels must then be packed (K-quants, Q8_0) or dense in the model's
+references -- no launch, no device memory moves.  The levels must then be packed (K-quants, Q8_0, IQ4_NL, IQ4_XS) or dense in the model's
 dtype; fp16 / bf16 models only.
 One rank, nn.Linear only."""
 import os
@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import level_db, ops, packed_linear
-from .gguf_writer import K_QUANTS, PLAIN_TYPES, GGMLType
+from .gguf_writer import PACKED_TYPES, PLAIN_TYPES
 
 _DENSE = (torch.float32, torch.float16, torch.bfloat16)
 
@@ -133,10 +133,10 @@ class LevelStore:
             return lv
         if gt in PLAIN_TYPES:
             lv.dtype = getattr(torch, PLAIN_TYPES[gt][0])
-        elif gt in K_QUANTS or gt == GGMLType.Q8_0:
+        elif gt in PACKED_TYPES:
             lv.kind, lv.dtype = int(gt), torch.uint8
         else:
-            raise ValueError(f"{path}: ggml type {gt} is not a K-quant, Q8_0 or a plain fp32 / fp16 / bf16 matrix")
+            raise ValueError(f"{path}: ggml type {gt} is not a K-quant, Q8_0, IQ4_NL, IQ4_XS or a plain fp32 / fp16 / bf16 matrix")
         if lv.info.shape != want:
             raise ValueError(f"{name}: level {lv.file!r} has shape {lv.info.shape}, the Linear {want}")
         lv.nbytes = level_db.check_level_size(lv.info)

@@ -548,9 +548,14 @@ def unpack(q_type: int, blocks: torch.Tensor):
 
 def block_geometry(q_type: int) -> Tuple[int, int]:
     """(values per block, bytes per block) of a type gq_dequantize_blocks / gq_level_switch decode: the K-quants' 256-value
-    blocks, Q8_0's 32 values in 34 bytes.  Any other type is the library's refusal (gq_type_info)."""
+    blocks, Q8_0's 32 values in 34 bytes, IQ4_NL's 32 in 18 and IQ4_XS's 256 in 136.  Any other type is the library's refusal
+    (gq_type_info)."""
     if int(q_type) == _cabi.Q8_0:
         return 32, 34
+    if int(q_type) == _cabi.IQ4_NL:
+        return 32, 18
+    if int(q_type) == _cabi.IQ4_XS:
+        return 256, 136
     return 256, type_info(q_type)["type_size"]
 
 
@@ -833,7 +838,7 @@ def quad_form(A: torch.Tensor, H: torch.Tensor, B: Optional[torch.Tensor] = None
 # ---- level switch of the bit-width search (gq_level_switch): stored levels -> live weights, one call ----
 def level_switch(jobs) -> None:
     """Apply a list of jobs (src, dst, kind, row_src) in ONE gq_level_switch call on the current stream of their device.
-    dst: contiguous [R, C] fp32 / fp16 / bf16, written in place.  kind a K-quant q_type (10..14) or Q8_0 (8): src uint8, R rows
+    dst: contiguous [R, C] fp32 / fp16 / bf16, written in place.  kind a K-quant q_type (10..14), Q8_0 (8), IQ4_NL (20) or IQ4_XS (23): src uint8, R rows
     of C / 256 packed blocks (Q8_0: C / 32 blocks of 34 bytes; any 1-D / 2-D contiguous view of exactly those bytes); kind None: src a dense
     contiguous [R, C] tensor, cast as .to(dst.dtype).  row_src: None or int32 [R], dst[r] = f(src[row_src[r]]); every index
     must lie in [0, R) -- the kernel does not check.  Returns None; no host read, no allocation on the device."""
@@ -892,7 +897,7 @@ def _packed_args(who: str, q_type, blocks, x, row_src):
             raise _cabi.GQError(f"{who}: every tensor must be on one device ({x.device}); got one on {t.device}")
     C = x.shape[-1]
     if C % 256:
-        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 included)")
+        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 and IQ4_NL included)")
     row_bytes = C // bs * ts
     if (blocks.dtype != torch.uint8 or blocks.dim() not in (1, 2) or not blocks.is_contiguous() or blocks.numel() == 0
             or blocks.numel() % row_bytes or (blocks.dim() == 2 and blocks.shape[1] != row_bytes)):
@@ -906,7 +911,7 @@ def _packed_args(who: str, q_type, blocks, x, row_src):
 
 def linear_packed(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [..., C] fp16 / bf16, contiguous, times the weight [R, C] that `blocks` holds packed (a K-quant q_type 10..14 or
-    Q8_0 8; uint8, any 1-D / 2-D contiguous view of exactly R rows of C / 256 blocks -- Q8_0: C / 32 blocks of 34 bytes)
+    Q8_0 8, IQ4_NL 20 or IQ4_XS 23; uint8, any 1-D / 2-D contiguous view of exactly R rows of block_geometry's blocks)
     -> y [..., R] in x's dtype, on the current stream of x's device.  C % 256 == 0 for every type.  The weight operand is
     bit for bit dequantize_blocks(q_type, blocks, x.dtype, row_src); fp32 accumulation, one rounding.  row_src: None or
     int32 [R], row r of the weight is packed row row_src[r]; every index must lie in [0, R) -- the kernel does not check.
@@ -938,7 +943,7 @@ MOE_MAX_PAIRS = _cabi.MOE_MAX_PAIRS
 def gemv_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: torch.Tensor, pair_expert: torch.Tensor,
                         pairs_per_row: int) -> torch.Tensor:
     """y [P, R] with y[p] = W[pair_expert[p]] x[p // pairs_per_row] in ONE launch: `blocks` holds the stacked expert tensor
-    [E, R, C] packed (a K-quant q_type 10..14 or Q8_0 8; contiguous uint8 of exactly E * R rows of C / 256 blocks, any
+    [E, R, C] packed (a K-quant q_type 10..14, Q8_0 8, IQ4_NL 20 or IQ4_XS 23; contiguous uint8 of exactly E * R rows of blocks, any
     shape), x is contiguous [x_rows, C] fp16 / bf16, pair_expert int32 [P] on the device with P = x_rows * pairs_per_row,
     1 <= P <= MOE_MAX_PAIRS.  pairs_per_row = K: gate / up (x the hidden states, the pairs in the row-major order of the
     router's [T, K] index); pairs_per_row = 1: down (x the [P, I] activation).  Row p is bit for bit
@@ -957,7 +962,7 @@ def gemv_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: to
             raise _cabi.GQError(f"{who}: every tensor must be on one device ({x.device}); got one on {t.device}")
     x_rows, C = x.shape
     if C % 256:
-        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 included)")
+        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 and IQ4_NL included)")
     if pair_expert.dtype != torch.int32 or pair_expert.dim() != 1 or not pair_expert.is_contiguous():
         raise _cabi.GQError(f"{who}: pair_expert must be a contiguous int32 [P] tensor; got {pair_expert.dtype} "
                             f"{tuple(pair_expert.shape)}")
@@ -1009,7 +1014,7 @@ def moe_route(pair_expert: torch.Tensor, E: int):
 
 def linear_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: torch.Tensor, route, pairs_per_row: int) -> torch.Tensor:
     """y [P, R] with y[p] = W[expert of pair p] x[p // pairs_per_row] for every pair of `route` = moe_route(pair_expert, E) in
-    ONE launch of the tile GEMM: `blocks` holds the stacked expert tensor [E, R, C] packed (a K-quant q_type 10..14 or Q8_0 8;
+    ONE launch of the tile GEMM: `blocks` holds the stacked expert tensor [E, R, C] packed (a K-quant q_type 10..14, Q8_0 8, IQ4_NL 20 or IQ4_XS 23;
     contiguous uint8 of exactly E * R rows of C / 256 blocks, any shape), x is contiguous [x_rows, C] fp16 / bf16 with
     x_rows * pairs_per_row = P = route[1].numel().  pairs_per_row = K: gate / up; pairs_per_row = 1: down.  The tokens of an
     expert are gathered and the results scattered to pair order inside the kernel.  Row p is bit for bit
@@ -1029,7 +1034,7 @@ def linear_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: 
             raise _cabi.GQError(f"{who}: every tensor must be on one device ({x.device}); got one on {t.device}")
     x_rows, C = x.shape
     if C % 256:
-        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 included)")
+        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 and IQ4_NL included)")
     if E < 1 or E > MOE_ROUTE_MAX_EXPERTS or R < 1:
         raise _cabi.GQError(f"{who}: E={E}, R={R} (1 <= E <= MOE_ROUTE_MAX_EXPERTS={MOE_ROUTE_MAX_EXPERTS}, R >= 1)")
     for name, t, n in (("expert_start", expert_start, E + 1), ("order", order, order.numel())):

@@ -1,4 +1,4 @@
-"""An Embedding whose table exists only in the form it is stored in: GGUF block bytes (K-quants, Q8_0) on the device.
+"""An Embedding whose table exists only in the form it is stored in: GGUF block bytes (K-quants, Q8_0, IQ4_NL, IQ4_XS) on the device.
 
     emb = replace_embedding(model, "model.embed_tokens")   # the nn.Embedding becomes a PackedEmbedding, its dense table is dropped
     emb.set_level(blocks, q_type)                          # a reference only: no copy, no launch

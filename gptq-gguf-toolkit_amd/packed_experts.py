@@ -1,5 +1,5 @@
 """The experts of a sparse-MoE layer whose weights exist only in the form they are stored in: the stacked GGUF tensors
-`blk.N.ffn_{gate,up,down}_exps.weight` as block bytes (K-quants, Q8_0) on the device.
+`blk.N.ffn_{gate,up,down}_exps.weight` as block bytes (K-quants, Q8_0, IQ4_NL, IQ4_XS) on the device.
 
     mods = install_experts(model, names)        # the named MixtralExperts-shaped modules become PackedExperts, their dense
                                                 # [E, 2I, H] / [E, H, I] parameters are dropped (prefill="grouped": see below)

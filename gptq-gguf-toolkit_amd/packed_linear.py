@@ -1,4 +1,4 @@
-"""A Linear whose weight exists only in the form it is stored in: GGUF block bytes (K-quants, Q8_0) on the device.
+"""A Linear whose weight exists only in the form it is stored in: GGUF block bytes (K-quants, Q8_0, IQ4_NL, IQ4_XS) on the device.
 
     mods = install(model, names)                       # the named nn.Linear modules become PackedLinear, their dense storage is dropped
     mods[name].set_level(blocks, q_type, row_src)      # references only: no copy, no launch
@@ -41,7 +41,7 @@ class PackedLinear(nn.Module):
         return self.weight.dtype
 
     def set_level(self, blocks: torch.Tensor, q_type: Optional[int], row_src: Optional[torch.Tensor] = None) -> None:
-        """Make a stored level current: `blocks` packed uint8 with its q_type (10..14 or 8) and optional row gather, or
+        """Make a stored level current: `blocks` packed uint8 with its q_type (10..14, 8, 20 or 23) and optional row gather, or
         q_type None and a dense [out_features, in_features] tensor of the module's dtype.  Keeps references only."""
         if q_type is None:
             if blocks.dtype != self.dtype or tuple(blocks.shape) != (self.out_features, self.in_features) or row_src is not None:

@@ -54,7 +54,7 @@ def parse_args(argv=None):
                    help="none | model | gguf:FILE -- also report the dense KL of the scored model against the unmodified "
                         "HF model or against another .gguf")
     p.add_argument("--packed", default=False, action="store_true",
-                   help="with --gguf: keep the K-quant / Q8_0 weights of the blocks' Linears packed on the device and compute "
+                   help="with --gguf: keep the K-quant / Q8_0 / IQ4_NL / IQ4_XS weights of the blocks' Linears packed on the device and compute "
                         "with the block bytes (no dense copy; fp16 / bf16)")
     p.add_argument("--packed_vocab", default=False, action="store_true",
                    help="with --packed: keep token_embd and output packed as well (a PackedEmbedding and a packed lm_head)")

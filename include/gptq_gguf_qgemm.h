@@ -14,7 +14,8 @@ extern "C" {
 /* ---- y[t, r] = sum_c x[t, c] * w[r, c],   t = 0 .. T - 1,   r = 0 .. R - 1,   for a weight [R, C] given as packed blocks:
    w[r, :] = decode(blocks row (row_src ? row_src[r] : r)).  No dense [R, C] weight exists before, during or after the call.
 
-     q_type  GQ_Q2_K .. GQ_Q6_K or GQ_Q8_0; anything else is GQ_E_BAD_TYPE.
+     q_type  GQ_Q2_K .. GQ_Q6_K or GQ_Q8_0 (with gptq_gguf_iq4.h also GQ_IQ4_NL and GQ_IQ4_XS, under the rules stated there);
+             anything else is GQ_E_BAD_TYPE.
      blocks  R rows of C / 256 blocks (Q8_0: C / 32 blocks of 34 bytes), as gq_level_switch takes them for the same kind:
              aligned to the block's natural alignment (Q2_K 4 bytes, Q3_K / Q6_K / Q8_0 2, Q4_K / Q5_K 16).  Staging loads
              are that wide and cover exactly the blocks' bytes: nothing outside [blocks, blocks + R * C / 256 * type_size)

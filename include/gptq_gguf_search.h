@@ -27,6 +27,9 @@ extern "C" {
                                (C * element size) must be multiples of 16 bytes.
      kind GQ_Q8_0 (gptq_gguf_q8.h) : src holds R rows of C / 32 blocks of 34 bytes, 2-byte aligned, C % 32 == 0; the unit is 128
                                such blocks.  That header states the contract.
+     kind GQ_IQ4_NL / GQ_IQ4_XS (gptq_gguf_iq4.h) : R rows of C / 32 blocks of 18 bytes, 2-byte aligned, C % 32 == 0 / of
+                               C / 256 blocks of 136 bytes, 8-byte aligned, C % 256 == 0; the unit is 4096 values.  That
+                               header states the contract.
    row_src: NULL (identity) or R int32 row indices on the device, each in [0, R) -- the kernel does not check.
    R >= 1.  Anything else is GQ_E_BAD_SHAPE (GQ_E_NULL / GQ_E_BAD_TYPE for pointers / kind / out_dtype); gq_last_error
    names the job index and the argument.  Every check is made before the first HIP call, for all jobs: a refused call has

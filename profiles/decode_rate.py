@@ -5,6 +5,8 @@ one process, HIP events around each launch, warm-up first, the candidates ALTERN
   (c) gq_pack alone, gq_dequantize alone                 (the neighbouring streaming kernels: the yardstick of this class)
 Rates are algorithmic bytes from the shapes (every input read once, every output written once) over the median time; the
 smaller shape's 117 MB of fp16 output fits the 256 MiB Infinity Cache, the larger one's 1 GB does not.
+A second part ("iq4") times (a) alone at 4096 x 14336 for Q4_K, IQ4_XS and IQ4_NL in the same alternating way: the two types
+that are only read (random blocks, profiles/iq4_blocks.py) beside the nearest K-quant.
 usage: python profiles/decode_rate.py [N=25]   (GPU box; needs only the built tree)"""
 import ctypes
 import json
@@ -15,6 +17,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from gptq_gguf_toolkit_amd import _cabi, ops  # noqa: E402
+from iq4_blocks import iq4_blocks  # noqa: E402
 
 HBM_PEAK = 8.0e12
 TS = {12: 144, 14: 210}
@@ -84,7 +87,39 @@ def main():
                       "of_hbm_peak": round(nbytes / med / HBM_PEAK, 3)}
         row["a_faster_than_b"] = row["a_dequantize_blocks"]["us"] < row["b_unpack_then_dequantize"]["us"]
         res["shapes"].append(row)
+    res["iq4"] = iq4_rows()
     print(json.dumps(res))
+
+
+def iq4_rows(R=4096, C=14336):
+    g = torch.Generator(device="cuda").manual_seed(0)
+    W = torch.randn(R, C, device="cuda", generator=g) * 0.02
+    src = {"Q4_K": (12, ops.pack(12, *ops.rtn_quantize(W, 12))), "IQ4_XS": (23, iq4_blocks(23, R, C, g)),
+           "IQ4_NL": (20, iq4_blocks(20, R, C, g))}
+    del W
+    for t, blocks in src.values():  # warm-up
+        for _ in range(3):
+            ops.dequantize_blocks(t, blocks, torch.float16)
+    torch.cuda.synchronize()
+    times, keys = {k: [] for k in src}, list(src)
+    for it in range(N):
+        evs = []
+        for k in keys[it % len(keys):] + keys[:it % len(keys)]:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ops.dequantize_blocks(src[k][0], src[k][1], torch.float16)
+            e1.record()
+            evs.append((k, e0, e1))
+        torch.cuda.synchronize()
+        for k, e0, e1 in evs:
+            times[k].append(e0.elapsed_time(e1) * 1e-3)
+    rows = {"R": R, "C": C, "out": "fp16 (each call allocates its output)"}
+    for k, (t, blocks) in src.items():
+        med, nbytes = statistics.median(times[k]), blocks.numel() + 2 * R * C
+        rows[k] = {"us": round(med * 1e6, 1), "bytes_per_param": round(nbytes / (R * C), 3), "TBps": round(nbytes / med / 1e12, 3)}
+    for k in ("IQ4_XS", "IQ4_NL"):
+        rows[k]["over_Q4_K"] = round(rows[k]["us"] / rows["Q4_K"]["us"], 3)
+    return rows
 
 
 if __name__ == "__main__":

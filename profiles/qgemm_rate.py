@@ -4,10 +4,11 @@ order), median of N with min-max, clocks as found.
   packed   ops.linear_packed(q_type, blocks, x)                 -- the forward of a packed-resident Linear
   dense    F.linear(x, W), W the decoded dense weight           -- the forward of a dense-resident Linear (the vendor GEMM)
   switch   ops.level_switch of that Linear (blocks -> W)        -- what a dense-resident search pays once per changed Linear
-for each of Q2_K .. Q6_K and Q8_0 at [R, C] in {4096 x 4096, 14336 x 4096, 4096 x 14336} and T in {2048, 8192}, bf16.
-Weights are RTN-quantized 0.02 N(0, 1) matrices (finite decodes); x is N(0, 1).
-usage: python profiles/qgemm_rate.py [N=9] [--out FILE]   (GPU box; needs only the built tree).  Writes FILE (default
-profiles/qgemm_rate.txt) and prints the same lines."""
+for each of Q2_K .. Q6_K, Q8_0, IQ4_NL and IQ4_XS at [R, C] in {4096 x 4096, 14336 x 4096, 4096 x 14336} and T in {2048, 8192},
+bf16.  Weights are RTN-quantized 0.02 N(0, 1) matrices (finite decodes), for the two IQ4 types, which have no encoder here,
+random blocks with a small d (profiles/iq4_blocks.py); x is N(0, 1).
+usage: python profiles/qgemm_rate.py [N=9] [--out FILE] [--types Q4_K,IQ4_XS] [--append]   (GPU box; needs only the built tree).
+Writes FILE (default profiles/qgemm_rate.txt; --append adds the run's lines to it) and prints the same lines."""
 import json
 import os
 import statistics
@@ -18,12 +19,13 @@ sys.path.insert(0, os.path.dirname(HERE))
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 from gptq_gguf_toolkit_amd import ops  # noqa: E402
+from iq4_blocks import iq4_blocks  # noqa: E402
 
-argv = [a for a in sys.argv[1:] if not a.startswith("--")]
-N = int(argv[0]) if argv and argv[0].isdecimal() else 9
+N = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdecimal() else 9
 OUT = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(HERE, "qgemm_rate.txt")
 DT = torch.bfloat16
-NAMES = {10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 8: "Q8_0"}
+NAMES = {10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 8: "Q8_0", 20: "IQ4_NL", 23: "IQ4_XS"}
+TYPES = sys.argv[sys.argv.index("--types") + 1].split(",") if "--types" in sys.argv else list(NAMES.values())
 
 
 def measure(cands):
@@ -55,8 +57,11 @@ def main():
     g = torch.Generator(device="cuda").manual_seed(0)
     for R, C in ((4096, 4096), (14336, 4096), (4096, 14336)):
         W = torch.randn(R, C, device="cuda", generator=g) * 0.02
-        for t in (10, 11, 12, 13, 14, 8):
-            blocks = ops.quantize_q8_0(W) if t == 8 else ops.pack(t, *ops.rtn_quantize(W, t))
+        for t in NAMES:
+            if NAMES[t] not in TYPES:
+                continue
+            blocks = (iq4_blocks(t, R, C, g) if t in (20, 23) else ops.quantize_q8_0(W) if t == 8
+                      else ops.pack(t, *ops.rtn_quantize(W, t)))
             Wd = ops.dequantize_blocks(t, blocks, DT)
             live = torch.empty_like(Wd)
             for T in (2048, 8192):
@@ -73,7 +78,7 @@ def main():
                 del x
             del blocks, Wd, live
         del W
-    with open(OUT, "w") as f:
+    with open(OUT, "a" if "--append" in sys.argv else "w") as f:
         f.write("\n".join(lines) + "\n")
 
 

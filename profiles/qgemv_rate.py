@@ -2,7 +2,7 @@
   gemv     ops.gemv_packed(q_type, blocks, x)                   -- K22
   tile     ops.linear_packed(q_type, blocks, x) at the same T   -- K21, the only packed forward before K22: the yardstick
   dense    F.linear(x, W), W the decoded dense weight           -- the forward of a dense-resident Linear (the vendor GEMM)
-for each of Q2_K .. Q6_K and Q8_0 at [R, C] in {4096 x 4096, 1024 x 4096, 14336 x 4096, 4096 x 14336} and T in {1, 2, 4, 8, 16},
+for each of Q2_K .. Q6_K, Q8_0, IQ4_NL and IQ4_XS at [R, C] in {4096 x 4096, 1024 x 4096, 14336 x 4096, 4096 x 14336} and T in {1, 2, 4, 8, 16},
 bf16.  One process, HIP events, warm-up first, the candidates ALTERNATING (every candidate takes every place in the order),
 median of N with min-max, clocks as found.  A measurement is M = 8 back-to-back calls of one candidate between two events,
 divided by M: a pair of events around ONE launch of ten microseconds reads several microseconds too long, and back to back
@@ -14,10 +14,11 @@ that walks a whole model does.  x (at most 458 KB) is the same buffer every call
 Short kernels: launches of a few microseconds would be timed as the host's enqueue, so each round is enqueued behind a
 matrix product of a few milliseconds that keeps the device busy meanwhile; the events then bracket device time alone.
 GB/s is algorithmic: the weight's bytes plus x plus y over the median time.
-Weights are RTN-quantized 0.02 N(0, 1) matrices (finite decodes); x is N(0, 1).
-usage: python profiles/qgemv_rate.py [N=15] [--out FILE] [--types Q4_K,Q6_K] [--tokens 1,16]   (GPU box; needs only the built
-tree; the two filters are for kernel A/B runs with GQ_SO_PATH).  Writes FILE (default
-profiles/qgemv_rate.txt) and prints the same lines; the last line names the largest T at which the GEMV was no slower than the
+Weights are RTN-quantized 0.02 N(0, 1) matrices (finite decodes), for the two IQ4 types, which have no encoder here, random
+blocks with a small d (profiles/iq4_blocks.py); x is N(0, 1).
+usage: python profiles/qgemv_rate.py [N=15] [--out FILE] [--types Q4_K,Q6_K] [--tokens 1,16] [--append]   (GPU box; needs only
+the built tree; the two filters are for kernel A/B runs with GQ_SO_PATH and for adding types).  Writes FILE (default
+profiles/qgemv_rate.txt; --append adds the run's lines to it) and prints the same lines; the last line names the largest T at which the GEMV was no slower than the
 tile kernel in every row."""
 import json
 import os
@@ -29,11 +30,12 @@ sys.path.insert(0, os.path.dirname(HERE))
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 from gptq_gguf_toolkit_amd import ops  # noqa: E402
+from iq4_blocks import iq4_blocks  # noqa: E402
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdecimal() else 15
 OUT = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(HERE, "qgemv_rate.txt")
 DT = torch.bfloat16
-NAMES = {10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 8: "Q8_0"}
+NAMES = {10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 8: "Q8_0", 20: "IQ4_NL", 23: "IQ4_XS"}
 RING_BYTES = 512 << 20
 M = 8
 TS = tuple(int(v) for v in sys.argv[sys.argv.index("--tokens") + 1].split(",")) if "--tokens" in sys.argv else (1, 2, 4, 8, 16)
@@ -83,10 +85,11 @@ def main():
     blocker = lambda: torch.mm(big, big[:8192])  # noqa: E731
     for R, C in ((4096, 4096), (1024, 4096), (14336, 4096), (4096, 14336)):
         W = torch.randn(R, C, device="cuda", generator=g) * 0.02
-        for t in (10, 11, 12, 13, 14, 8):
+        for t in NAMES:
             if NAMES[t] not in TYPES:
                 continue
-            blocks = ops.quantize_q8_0(W) if t == 8 else ops.pack(t, *ops.rtn_quantize(W, t))
+            blocks = (iq4_blocks(t, R, C, g) if t in (20, 23) else ops.quantize_q8_0(W) if t == 8
+                      else ops.pack(t, *ops.rtn_quantize(W, t)))
             packed, dense = ring(blocks), ring(ops.dequantize_blocks(t, blocks, DT))
             for T in TS:
                 x = torch.randn(T, C, device="cuda", generator=g).to(DT)
@@ -109,7 +112,7 @@ def main():
     lines.append(json.dumps({"worst_gemv_over_tile_by_T": {str(T): round(v, 3) for T, v in worst.items()},
                              "largest_T_gemv_no_slower_in_every_row": max(ok) if ok else 0}))
     print(lines[-1], flush=True)
-    with open(OUT, "w") as f:
+    with open(OUT, "a" if "--append" in sys.argv else "w") as f:
         f.write("\n".join(lines) + "\n")
 
 
