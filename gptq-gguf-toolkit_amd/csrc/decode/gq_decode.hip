@@ -28,7 +28,8 @@
 // read; ds = d * (ls - 32), dm = 0 and the code is kv[nibble], looked up in a register-resident table with byte permutes
 // (blockdec::iq4_code4).  IQ4_NL is a 32-value type and takes Q8_0's route: 2-byte staging loads, half a block per thread.
 // Neither has a gq_unpack form.
-#include "../search/gq_block_decode.hpp"  // Lay, stage_blocks, codes16, group_scale, decode_turn: shared with search/gq_switch.hip
+#include "../search/gq_block_host.hpp"  // gq_block_decode.hpp (Lay, stage_blocks, codes16, group_scale, decode_turn: shared with
+                                        // search/gq_switch.hip) and the host side: the type list and its geometry
 
 namespace gq {
 namespace {
@@ -120,45 +121,21 @@ unsigned turns_grid(int64_t nblocks, int per_turn = DB) {
     return (unsigned)(g < 16384 ? g : 16384);
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 template <int QT>
-int launch_dequantize_blocks_t(const uint8_t* blocks, const int32_t* row_src, int64_t nblocks, int64_t nbr, void* out,
-                               int out_dtype, hipStream_t st) {
-    if (!aligned(blocks, Lay<QT>::AL)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_dequantize_blocks: blocks not %d-byte aligned", Lay<QT>::AL);
-    dim3 grid(turns_grid(nblocks)), block(256);
+int launch_dequantize(const uint8_t* blocks, const int32_t* row_src, int64_t nblocks, int64_t nbr, void* out, int out_dtype,
+                      hipStream_t st) {
+    constexpr bool B32 = Geo<QT>::BS == 32;  // Q8_0, IQ4_NL: turns of 128 blocks of 32 values
+    if (!aligned(blocks, QL<QT>::AL)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_dequantize_blocks: blocks not %d-byte aligned", QL<QT>::AL);
+    const dim3 grid(turns_grid(nblocks, B32 ? B32_DB : DB)), block(256);
+    auto go = [&](auto* o) {
+        using OutT = std::remove_pointer_t<decltype(o)>;
+        if constexpr (B32) hipLaunchKernelGGL((dequantize_b32_kernel<QT, OutT>), grid, block, 0, st, blocks, row_src, nblocks, nbr, o);
+        else hipLaunchKernelGGL((dequantize_blocks_kernel<QT, OutT>), grid, block, 0, st, blocks, row_src, nblocks, nbr, o);
+    };
     switch (out_dtype) {
-    case GQ_F32:
-        hipLaunchKernelGGL((dequantize_blocks_kernel<QT, float>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (float*)out);
-        break;
-    case GQ_F16:
-        hipLaunchKernelGGL((dequantize_blocks_kernel<QT, half_bits>), grid, block, 0, st, blocks, row_src, nblocks, nbr,
-                           (half_bits*)out);
-        break;
-    default:
-        hipLaunchKernelGGL((dequantize_blocks_kernel<QT, bf16_bits>), grid, block, 0, st, blocks, row_src, nblocks, nbr,
-                           (bf16_bits*)out);
-        break;
-    }
-    GQ_LAUNCH_CHECK();
-    return GQ_OK;
-}
-
-template <int QT>
-int launch_dequantize_b32(const uint8_t* blocks, const int32_t* row_src, int64_t nblocks, int64_t nbr, void* out,
-                          int out_dtype, hipStream_t st) {
-    if (!aligned(blocks, 2)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_dequantize_blocks: blocks not 2-byte aligned");
-    dim3 grid(turns_grid(nblocks, B32_DB)), block(256);
-    switch (out_dtype) {
-    case GQ_F32:
-        hipLaunchKernelGGL((dequantize_b32_kernel<QT, float>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (float*)out);
-        break;
-    case GQ_F16:
-        hipLaunchKernelGGL((dequantize_b32_kernel<QT, half_bits>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (half_bits*)out);
-        break;
-    default:
-        hipLaunchKernelGGL((dequantize_b32_kernel<QT, bf16_bits>), grid, block, 0, st, blocks, row_src, nblocks, nbr, (bf16_bits*)out);
-        break;
+    case GQ_F32: go((float*)out); break;
+    case GQ_F16: go((half_bits*)out); break;
+    default: go((bf16_bits*)out); break;
     }
     GQ_LAUNCH_CHECK();
     return GQ_OK;
@@ -204,10 +181,8 @@ int gq_unpack(int q_type, const uint8_t* blocks, int64_t R, int64_t C, uint8_t* 
 int gq_dequantize_blocks(int q_type, const uint8_t* blocks, int64_t R, int64_t C, const int32_t* row_src, void* out,
                          int out_dtype, void* stream) {
     if (int rc = options_ok()) return rc;
-    TypeInfo ti;
-    const bool b32 = q_type == GQ_Q8_0 || q_type == GQ_IQ4_NL;
-    const int bs = b32 ? 32 : 256;  // values per block
-    if (!b32 && q_type != GQ_IQ4_XS && !type_info(q_type, ti)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_dequantize_blocks: unknown q_type %d", q_type);
+    if (!packed_type(q_type)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_dequantize_blocks: unknown q_type %d", q_type);
+    const int bs = block_geometry(q_type).bs;  // values per block
     if (out_dtype != GQ_F32 && out_dtype != GQ_F16 && out_dtype != GQ_BF16)
         GQ_FAIL(GQ_E_BAD_TYPE, "gq_dequantize_blocks: unknown out_dtype %d", out_dtype);
     if (R <= 0 || C <= 0 || C % bs)
@@ -216,16 +191,9 @@ int gq_dequantize_blocks(int q_type, const uint8_t* blocks, int64_t R, int64_t C
     if (!aligned(out, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_dequantize_blocks: out must be 16-byte aligned");
     const int64_t nbr = C / bs, nblocks = R * nbr;
     hipStream_t st = (hipStream_t)stream;
-    switch (q_type) {
-    case GQ_Q8_0: return launch_dequantize_b32<GQ_Q8_0>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
-    case GQ_IQ4_NL: return launch_dequantize_b32<GQ_IQ4_NL>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
-    case GQ_IQ4_XS: return launch_dequantize_blocks_t<GQ_IQ4_XS>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
-    case GQ_Q2_K: return launch_dequantize_blocks_t<GQ_Q2_K>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
-    case GQ_Q3_K: return launch_dequantize_blocks_t<GQ_Q3_K>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
-    case GQ_Q4_K: return launch_dequantize_blocks_t<GQ_Q4_K>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
-    case GQ_Q5_K: return launch_dequantize_blocks_t<GQ_Q5_K>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
-    default: return launch_dequantize_blocks_t<GQ_Q6_K>(blocks, row_src, nblocks, nbr, out, out_dtype, st);
-    }
+    int rc = GQ_OK;
+    dispatch_packed(q_type, [&](auto qt) { rc = launch_dequantize<decltype(qt)::value>(blocks, row_src, nblocks, nbr, out, out_dtype, st); });
+    return rc;
 }
 
 }  // extern "C"

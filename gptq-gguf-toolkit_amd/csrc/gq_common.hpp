@@ -80,6 +80,9 @@ enum Opt {
 int64_t opt(Opt o);
 int options_ok();  // GQ_OK, or GQ_E_UNSUPPORTED + gq_last_error when GQ_OPTIONS did not parse (checked by every entry point)
 
+// p is a multiple of a (a power of two); NULL is aligned
+inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
 constexpr int GQ_MAX_STACK = 8;  // row-stacked matrices of one gq_gptq_quantize_stacked call
 // The panel block of a scale-search call chain (256 bytes): words [2k], [2k + 1] = "some group valid" / "some group took the
 // candidate" bits per search iteration of stacked matrix k (left at zero by every launch); word GQ_PANEL_RESEARCH counts the

@@ -99,8 +99,6 @@ __global__ __launch_bounds__(256) void pack_bands_kernel(const PackTable t) {
     }
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace gq
 

@@ -93,8 +93,6 @@ __global__ __launch_bounds__(256) void q8_0_encode_kernel(const uint8_t* __restr
     }
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace gq
 

@@ -2,6 +2,7 @@
 // of a packed weight and all of C.  gq_qgemv.hip (K22, MFMA column t = token t) and gq_moe_gemv.hip (K24, MFMA column i = the
 // i-th pair that names the workgroup's expert) include it, so for one weight row and one input row the two kernels run the
 // same instructions in the same order: the same bits.  The form is described at the head of gq_qgemv.hip.
+// Device code only: the entry points' type dispatch and operand checks are search/gq_block_host.hpp's.
 #pragma once
 #include <type_traits>
 
@@ -132,11 +133,6 @@ __device__ __forceinline__ void gemv_pass(int tid, const uint8_t* __restrict__ b
             if (r + i < R) py[i] = o[i];
     }
 }
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-inline int block_align(int q) { return q == GQ_Q2_K ? 4 : (q == GQ_Q4_K || q == GQ_Q5_K) ? 16 : q == GQ_IQ4_XS ? 8 : 2; }
-// the types whose blocks the packed forward reads
-inline bool packed_type(int q) { return (q >= GQ_Q2_K && q <= GQ_Q6_K) || q == GQ_Q8_0 || q == GQ_IQ4_NL || q == GQ_IQ4_XS; }
 
 }  // namespace gemvcore
 }  // namespace gq

@@ -21,6 +21,7 @@
 // The K loop, the staging and the epilogue are gq_qgemm_core.hpp's tile_pass, the text gq_linear_packed runs.
 #include "../../../include/gptq_gguf_moe_gemm.h"
 
+#include "../search/gq_block_host.hpp"
 #include "gq_qgemm_core.hpp"
 
 namespace gq {
@@ -169,27 +170,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // have it, so that no instance of it uses scratch.
 constexpr bool wide_ok(int q_type) { return q_type != GQ_Q4_K && q_type != GQ_Q5_K && q_type != GQ_IQ4_XS; }
 
-template <int QT, bool BF16>
-void launch_dt(bool wide, dim3 grid, hipStream_t st, const uint8_t* blocks, int E, int64_t R, int64_t C, const uint8_t* x, int ppr,
-               const int32_t* es, const int32_t* order, int P, uint16_t* y, uint32_t n_rt) {
-    if constexpr (wide_ok(QT)) {
-        if (wide) {
-            hipLaunchKernelGGL((linear_packed_experts_kernel<QT, BF16, 256>), grid, dim3(256), 0, st, blocks, E, R, C, x, ppr, es, order,
-                               P, y, n_rt);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((linear_packed_experts_kernel<QT, BF16, 128>), grid, dim3(256), 0, st, blocks, E, R, C, x, ppr, es, order, P, y,
-                       n_rt);
-}
-
-template <int QT>
-void launch(bool bf16, bool wide, dim3 grid, hipStream_t st, const uint8_t* blocks, int E, int64_t R, int64_t C, const uint8_t* x,
-            int ppr, const int32_t* es, const int32_t* order, int P, uint16_t* y, uint32_t n_rt) {
-    if (bf16) launch_dt<QT, true>(wide, grid, st, blocks, E, R, C, x, ppr, es, order, P, y, n_rt);
-    else launch_dt<QT, false>(wide, grid, st, blocks, E, R, C, x, ppr, es, order, P, y, n_rt);
-}
-
 }  // namespace
 }  // namespace gq
 
@@ -218,31 +198,25 @@ int gq_linear_packed_experts(int q_type, const void* blocks, int64_t E, int64_t 
                              int64_t pairs_per_row, const int32_t* expert_start, const int32_t* order, int64_t P, int x_dtype,
                              void* y, void* stream) {
     if (int rc = options_ok()) return rc;
-    if (!packed_type(q_type))
-        GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed_experts: unknown q_type %d (a K-quant, GQ_Q8_0, GQ_IQ4_NL or GQ_IQ4_XS)", q_type);
-    if (x_dtype != GQ_F16 && x_dtype != GQ_BF16)
-        GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed_experts: x_dtype %d (GQ_F16 or GQ_BF16; there is no fp32 path)", x_dtype);
-    if (!blocks) GQ_FAIL(GQ_E_NULL, "gq_linear_packed_experts: blocks is NULL");
-    if (!x) GQ_FAIL(GQ_E_NULL, "gq_linear_packed_experts: x is NULL");
-    if (!expert_start) GQ_FAIL(GQ_E_NULL, "gq_linear_packed_experts: expert_start is NULL");
-    if (!order) GQ_FAIL(GQ_E_NULL, "gq_linear_packed_experts: order is NULL");
-    if (!y) GQ_FAIL(GQ_E_NULL, "gq_linear_packed_experts: y is NULL");
+    const char* who = "gq_linear_packed_experts";
+    if (int rc = check_types(who, q_type, x_dtype)) return rc;
+    if (int rc = need(who, "blocks", blocks)) return rc;
+    if (int rc = need(who, "x", x)) return rc;
+    if (int rc = need(who, "expert_start", expert_start)) return rc;
+    if (int rc = need(who, "order", order)) return rc;
+    if (int rc = need(who, "y", y)) return rc;
     if (E < 1 || E > GQ_MOE_ROUTE_MAX_EXPERTS)
         GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: E=%ld (not in [1, %d] experts)", (long)E, GQ_MOE_ROUTE_MAX_EXPERTS);
-    if (R < 1 || R > 0x7fffffff) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: R=%ld (not in [1, 2^31))", (long)R);
+    if (int rc = check_R(who, R)) return rc;
     if (P < 1 || P > GQ_MOE_ROUTE_MAX_PAIRS)
         GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: P=%ld (not in [1, %d] pairs)", (long)P, GQ_MOE_ROUTE_MAX_PAIRS);
-    if (pairs_per_row < 1 || x_rows < 1 || pairs_per_row > P || x_rows > P || x_rows * pairs_per_row != P)
-        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: x_rows=%ld * pairs_per_row=%ld != P=%ld", (long)x_rows,
-                (long)pairs_per_row, (long)P);
-    if (C < 256 || C > 0x7fffffff || C % 256)
-        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 and IQ4_NL included)", (long)C);
-    const int al = block_align(q_type);
-    if (!aligned(blocks, al)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: blocks not %d-byte aligned", al);
-    if (!aligned(expert_start, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: expert_start not 4-byte aligned");
-    if (!aligned(order, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: order not 4-byte aligned");
-    if (!aligned(x, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: x not 16-byte aligned");
-    if (!aligned(y, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed_experts: y not 16-byte aligned");
+    if (int rc = check_pairs(who, x_rows, pairs_per_row, P)) return rc;
+    if (int rc = check_C256(who, C)) return rc;
+    if (int rc = check_blocks_aligned(who, q_type, blocks)) return rc;
+    if (int rc = check_aligned(who, "expert_start", expert_start, 4)) return rc;
+    if (int rc = check_aligned(who, "order", order, 4)) return rc;
+    if (int rc = check_aligned(who, "x", x, 16)) return rc;
+    if (int rc = check_aligned(who, "y", y, 16)) return rc;
     // The host does not know the counts, it knows their mean: the 256-token tile is taken when a run is on average at least one
     // 128-token tile long.  About half of the runs or more then overflow a 128-token tile, which decodes the expert's rows once
     // more for the rest, while a 256-token tile that is half empty skips the matrix instructions of its empty half (K25 has both
@@ -258,18 +232,18 @@ int gq_linear_packed_experts(int q_type, const void* blocks, int64_t E, int64_t 
     const uint8_t* b = static_cast<const uint8_t*>(blocks);
     const uint8_t* xp = static_cast<const uint8_t*>(x);
     uint16_t* yp = static_cast<uint16_t*>(y);
-    const bool bf = x_dtype == GQ_BF16;
-    const int ne = (int)E, np = (int)P, ppr = (int)pairs_per_row;
-    switch (q_type) {
-    case GQ_Q2_K: launch<GQ_Q2_K>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
-    case GQ_Q3_K: launch<GQ_Q3_K>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
-    case GQ_Q4_K: launch<GQ_Q4_K>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
-    case GQ_Q5_K: launch<GQ_Q5_K>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
-    case GQ_Q6_K: launch<GQ_Q6_K>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
-    case GQ_IQ4_NL: launch<GQ_IQ4_NL>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
-    case GQ_IQ4_XS: launch<GQ_IQ4_XS>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
-    default: launch<GQ_Q8_0>(bf, wide, grid, st, b, ne, R, C, xp, ppr, expert_start, order, np, yp, (uint32_t)n_rt); break;
-    }
+    dispatch_packed(q_type, [&](auto qt) {
+        constexpr int QT = decltype(qt)::value;
+        dispatch_bool(x_dtype == GQ_BF16, [&](auto bf16) {
+            auto go = [&](auto w) {  // w: the 256-token tile
+                hipLaunchKernelGGL((linear_packed_experts_kernel<QT, decltype(bf16)::value, decltype(w)::value ? 256 : 128>), grid,
+                                   dim3(256), 0, st, b, (int)E, R, C, xp, (int)pairs_per_row, expert_start, order, (int)P, yp,
+                                   (uint32_t)n_rt);
+            };
+            if constexpr (wide_ok(QT)) dispatch_bool(wide, go);  // (no 256-token instance is built for the other types)
+            else go(std::false_type{});
+        });
+    });
     GQ_LAUNCH_CHECK();
     return GQ_OK;
 }

@@ -15,6 +15,7 @@
 // that input row at T = 1.  No atomics, no workspace, no scratch, no host synchronisation.
 #include "../../../include/gptq_gguf_moe.h"
 
+#include "../search/gq_block_host.hpp"
 #include "gq_gemv_core.hpp"
 
 namespace gq {
@@ -67,13 +68,6 @@ __global__ __launch_bounds__(64 * MAX_NW) void gemv_packed_experts_kernel(const 
     }
 }
 
-template <int QT>
-void launch(bool bf16, dim3 grid, int nw, hipStream_t st, const uint8_t* blocks, int64_t R, int64_t C, const uint8_t* x,
-            const int32_t* pe, int P, int ppr, uint16_t* y) {
-    if (bf16) hipLaunchKernelGGL((gemv_packed_experts_kernel<QT, true>), grid, dim3(64 * nw), 0, st, blocks, R, C, x, pe, P, ppr, y);
-    else hipLaunchKernelGGL((gemv_packed_experts_kernel<QT, false>), grid, dim3(64 * nw), 0, st, blocks, R, C, x, pe, P, ppr, y);
-}
-
 }  // namespace
 }  // namespace gq
 
@@ -84,28 +78,22 @@ extern "C" {
 int gq_gemv_packed_experts(int q_type, const void* blocks, int64_t E, int64_t R, int64_t C, const void* x, int64_t x_rows,
                            const int32_t* pair_expert, int64_t P, int64_t pairs_per_row, int x_dtype, void* y, void* stream) {
     if (int rc = options_ok()) return rc;
-    if (!packed_type(q_type))
-        GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed_experts: unknown q_type %d (a K-quant, GQ_Q8_0, GQ_IQ4_NL or GQ_IQ4_XS)", q_type);
-    if (x_dtype != GQ_F16 && x_dtype != GQ_BF16)
-        GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed_experts: x_dtype %d (GQ_F16 or GQ_BF16; there is no fp32 path)", x_dtype);
-    if (!blocks) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed_experts: blocks is NULL");
-    if (!x) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed_experts: x is NULL");
-    if (!pair_expert) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed_experts: pair_expert is NULL");
-    if (!y) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed_experts: y is NULL");
+    const char* who = "gq_gemv_packed_experts";
+    if (int rc = check_types(who, q_type, x_dtype)) return rc;
+    if (int rc = need(who, "blocks", blocks)) return rc;
+    if (int rc = need(who, "x", x)) return rc;
+    if (int rc = need(who, "pair_expert", pair_expert)) return rc;
+    if (int rc = need(who, "y", y)) return rc;
     if (E < 1 || E > 65535) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: E=%ld (not in [1, 65535])", (long)E);
-    if (R < 1 || R > 0x7fffffff) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: R=%ld (not in [1, 2^31))", (long)R);
+    if (int rc = check_R(who, R)) return rc;
     if (P < 1 || P > GQ_MOE_MAX_PAIRS)
         GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: P=%ld (not in [1, %d] pairs)", (long)P, GQ_MOE_MAX_PAIRS);
-    if (pairs_per_row < 1 || x_rows < 1 || pairs_per_row > P || x_rows > P || x_rows * pairs_per_row != P)
-        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: x_rows=%ld * pairs_per_row=%ld != P=%ld", (long)x_rows,
-                (long)pairs_per_row, (long)P);
-    if (C < 256 || C > 0x7fffffff || C % 256)
-        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 and IQ4_NL included)", (long)C);
-    const int al = block_align(q_type);
-    if (!aligned(blocks, al)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: blocks not %d-byte aligned", al);
-    if (!aligned(pair_expert, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: pair_expert not 4-byte aligned");
-    if (!aligned(x, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: x not 16-byte aligned");
-    if (!aligned(y, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed_experts: y not 16-byte aligned");
+    if (int rc = check_pairs(who, x_rows, pairs_per_row, P)) return rc;
+    if (int rc = check_C256(who, C)) return rc;
+    if (int rc = check_blocks_aligned(who, q_type, blocks)) return rc;
+    if (int rc = check_aligned(who, "pair_expert", pair_expert, 4)) return rc;
+    if (int rc = check_aligned(who, "x", x, 16)) return rc;
+    if (int rc = check_aligned(who, "y", y, 16)) return rc;
     const int64_t nsb = C / 256;
     const int nw = (int)(nsb < MAX_NW ? nsb : MAX_NW);
     const dim3 grid((unsigned)((R + VR - 1) / VR), (unsigned)E);  // x < 2^27, y <= 65535
@@ -113,18 +101,12 @@ int gq_gemv_packed_experts(int q_type, const void* blocks, int64_t E, int64_t R,
     const uint8_t* b = static_cast<const uint8_t*>(blocks);
     const uint8_t* xp = static_cast<const uint8_t*>(x);
     uint16_t* yp = static_cast<uint16_t*>(y);
-    const bool bf = x_dtype == GQ_BF16;
-    const int np = (int)P, ppr = (int)pairs_per_row;
-    switch (q_type) {
-    case GQ_Q2_K: launch<GQ_Q2_K>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
-    case GQ_Q3_K: launch<GQ_Q3_K>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
-    case GQ_Q4_K: launch<GQ_Q4_K>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
-    case GQ_Q5_K: launch<GQ_Q5_K>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
-    case GQ_Q6_K: launch<GQ_Q6_K>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
-    case GQ_IQ4_NL: launch<GQ_IQ4_NL>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
-    case GQ_IQ4_XS: launch<GQ_IQ4_XS>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
-    default: launch<GQ_Q8_0>(bf, grid, nw, st, b, R, C, xp, pair_expert, np, ppr, yp); break;
-    }
+    dispatch_packed(q_type, [&](auto qt) {
+        dispatch_bool(x_dtype == GQ_BF16, [&](auto bf16) {
+            hipLaunchKernelGGL((gemv_packed_experts_kernel<decltype(qt)::value, decltype(bf16)::value>), grid, dim3(64 * nw), 0, st, b, R,
+                               C, xp, pair_expert, (int)P, (int)pairs_per_row, yp);
+        });
+    });
     GQ_LAUNCH_CHECK();
     return GQ_OK;
 }

@@ -31,6 +31,7 @@
 // outside the arguments' extents.
 #include "../../../include/gptq_gguf_qgemm.h"
 
+#include "../search/gq_block_host.hpp"
 #include "gq_qgemm_core.hpp"
 
 namespace gq {
@@ -76,25 +77,6 @@ int64_t tiles(int64_t R, int64_t T, int tt) {
 // 1.7-2.3x Q4_K's time where the grid takes the wide tile, against 0.85-0.98x at the narrow one (DESIGN K26).
 constexpr bool wide_ok(int q_type) { return q_type != GQ_IQ4_XS; }
 
-template <int QT, bool BF16>
-void launch_dt(bool wide, dim3 grid, hipStream_t st, const uint8_t* blocks, const int32_t* row_src, int64_t R, int64_t C,
-               const uint8_t* x, int64_t T, uint16_t* y, uint32_t n_rt) {
-    if constexpr (wide_ok(QT)) {
-        if (wide) {
-            hipLaunchKernelGGL((linear_packed_kernel<QT, BF16, 256>), grid, dim3(256), 0, st, blocks, row_src, R, C, x, T, y, n_rt);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((linear_packed_kernel<QT, BF16, 128>), grid, dim3(256), 0, st, blocks, row_src, R, C, x, T, y, n_rt);
-}
-
-template <int QT>
-void launch(bool bf16, bool wide, dim3 grid, hipStream_t st, const uint8_t* blocks, const int32_t* row_src, int64_t R, int64_t C,
-            const uint8_t* x, int64_t T, uint16_t* y, uint32_t n_rt) {
-    if (bf16) launch_dt<QT, true>(wide, grid, st, blocks, row_src, R, C, x, T, y, n_rt);
-    else launch_dt<QT, false>(wide, grid, st, blocks, row_src, R, C, x, T, y, n_rt);
-}
-
 }  // namespace
 }  // namespace gq
 
@@ -105,22 +87,18 @@ extern "C" {
 int gq_linear_packed(int q_type, const void* blocks, const int32_t* row_src, int64_t R, int64_t C, const void* x, int64_t T,
                      int x_dtype, void* y, void* stream) {
     if (int rc = options_ok()) return rc;
-    if (!packed_type(q_type))
-        GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed: unknown q_type %d (a K-quant, GQ_Q8_0, GQ_IQ4_NL or GQ_IQ4_XS)", q_type);
-    if (x_dtype != GQ_F16 && x_dtype != GQ_BF16)
-        GQ_FAIL(GQ_E_BAD_TYPE, "gq_linear_packed: x_dtype %d (GQ_F16 or GQ_BF16; there is no fp32 path)", x_dtype);
-    if (!blocks) GQ_FAIL(GQ_E_NULL, "gq_linear_packed: blocks is NULL");
-    if (!x) GQ_FAIL(GQ_E_NULL, "gq_linear_packed: x is NULL");
-    if (!y) GQ_FAIL(GQ_E_NULL, "gq_linear_packed: y is NULL");
-    if (R < 1 || R > 0x7fffffff) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: R=%ld (not in [1, 2^31))", (long)R);
+    const char* who = "gq_linear_packed";
+    if (int rc = check_types(who, q_type, x_dtype)) return rc;
+    if (int rc = need(who, "blocks", blocks)) return rc;
+    if (int rc = need(who, "x", x)) return rc;
+    if (int rc = need(who, "y", y)) return rc;
+    if (int rc = check_R(who, R)) return rc;
     if (T < 1 || T > 0x7fffffff) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: T=%ld (not in [1, 2^31))", (long)T);
-    if (C < 256 || C > 0x7fffffff || C % 256)
-        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 and IQ4_NL included)", (long)C);
-    const int al = block_align(q_type);
-    if (!aligned(blocks, al)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: blocks not %d-byte aligned", al);
-    if (!aligned(row_src, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: row_src not 4-byte aligned");
-    if (!aligned(x, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: x not 16-byte aligned");
-    if (!aligned(y, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_linear_packed: y not 16-byte aligned");
+    if (int rc = check_C256(who, C)) return rc;
+    if (int rc = check_blocks_aligned(who, q_type, blocks)) return rc;
+    if (int rc = check_aligned(who, "row_src", row_src, 4)) return rc;
+    if (int rc = check_aligned(who, "x", x, 16)) return rc;
+    if (int rc = check_aligned(who, "y", y, 16)) return rc;
     // the 256-token tile halves the decode work per output, the 128-token one fills the device at small shapes
     const bool wide = wide_ok(q_type) && tiles(R, T, 256) >= WIDE_TILES;
     const int64_t n_rt = (R + TR - 1) / TR, n_wg = tiles(R, T, wide ? 256 : 128);
@@ -130,17 +108,17 @@ int gq_linear_packed(int q_type, const void* blocks, const int32_t* row_src, int
     const uint8_t* b = static_cast<const uint8_t*>(blocks);
     const uint8_t* xp = static_cast<const uint8_t*>(x);
     uint16_t* yp = static_cast<uint16_t*>(y);
-    const bool bf = x_dtype == GQ_BF16;
-    switch (q_type) {
-    case GQ_Q2_K: launch<GQ_Q2_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
-    case GQ_Q3_K: launch<GQ_Q3_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
-    case GQ_Q4_K: launch<GQ_Q4_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
-    case GQ_Q5_K: launch<GQ_Q5_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
-    case GQ_Q6_K: launch<GQ_Q6_K>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
-    case GQ_IQ4_NL: launch<GQ_IQ4_NL>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
-    case GQ_IQ4_XS: launch<GQ_IQ4_XS>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
-    default: launch<GQ_Q8_0>(bf, wide, grid, st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt); break;
-    }
+    dispatch_packed(q_type, [&](auto qt) {
+        constexpr int QT = decltype(qt)::value;
+        dispatch_bool(x_dtype == GQ_BF16, [&](auto bf16) {
+            auto go = [&](auto w) {  // w: the 256-token tile
+                hipLaunchKernelGGL((linear_packed_kernel<QT, decltype(bf16)::value, decltype(w)::value ? 256 : 128>), grid, dim3(256), 0,
+                                   st, b, row_src, R, C, xp, T, yp, (uint32_t)n_rt);
+            };
+            if constexpr (wide_ok(QT)) dispatch_bool(wide, go);  // (no 256-token instance is built for the other types)
+            else go(std::false_type{});
+        });
+    });
     GQ_LAUNCH_CHECK();
     return GQ_OK;
 }

@@ -4,6 +4,7 @@
 // `order`) include it, so for one weight row and one input row the two kernels run the same instructions in the same order:
 // superblock j, chunk c, step s, 32 k per MFMA, into an accumulator no other token touches -- the same bits.  The form is
 // described at the head of gq_qgemm.hip.
+// Device code only: the entry points' type dispatch and operand checks are search/gq_block_host.hpp's.
 #pragma once
 #include <type_traits>
 
@@ -153,11 +154,6 @@ __device__ __forceinline__ void tile_pass(const uint8_t* blocks, const int64_t* 
         }
     }
 }
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-inline int block_align(int q) { return q == GQ_Q2_K ? 4 : (q == GQ_Q4_K || q == GQ_Q5_K) ? 16 : q == GQ_IQ4_XS ? 8 : 2; }
-// the types whose blocks the packed forward reads
-inline bool packed_type(int q) { return (q >= GQ_Q2_K && q <= GQ_Q6_K) || q == GQ_Q8_0 || q == GQ_IQ4_NL || q == GQ_IQ4_XS; }
 
 }  // namespace gemmcore
 }  // namespace gq

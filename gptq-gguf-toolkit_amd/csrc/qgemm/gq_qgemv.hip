@@ -27,6 +27,7 @@
 // those D rows are never stored).  y is stored 8 bytes wide where R % 4 == 0, else 2 bytes wide with a row check.
 #include "../../../include/gptq_gguf_qgemv.h"
 
+#include "../search/gq_block_host.hpp"
 #include "gq_gemv_core.hpp"  // the K loop, the reduction and the store: one text with gq_moe_gemv.hip (K24)
 
 namespace gq {
@@ -48,13 +49,6 @@ __global__ __launch_bounds__(64 * MAX_NW) void gemv_packed_kernel(const uint8_t*
     gemv_pass<QT, BF16>(threadIdx.x, blocks, base, nr, r0, R, C, l15 < T, x, l15, y, [=] { return l15; }, smem);
 }
 
-template <int QT>
-void launch(bool bf16, dim3 grid, int nw, hipStream_t st, const uint8_t* blocks, const int32_t* row_src, int64_t R, int64_t C,
-            const uint8_t* x, int T, uint16_t* y) {
-    if (bf16) hipLaunchKernelGGL((gemv_packed_kernel<QT, true>), grid, dim3(64 * nw), 0, st, blocks, row_src, R, C, x, T, y);
-    else hipLaunchKernelGGL((gemv_packed_kernel<QT, false>), grid, dim3(64 * nw), 0, st, blocks, row_src, R, C, x, T, y);
-}
-
 }  // namespace
 }  // namespace gq
 
@@ -65,23 +59,19 @@ extern "C" {
 int gq_gemv_packed(int q_type, const void* blocks, const int32_t* row_src, int64_t R, int64_t C, const void* x, int64_t T,
                    int x_dtype, void* y, void* stream) {
     if (int rc = options_ok()) return rc;
-    if (!packed_type(q_type))
-        GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed: unknown q_type %d (a K-quant, GQ_Q8_0, GQ_IQ4_NL or GQ_IQ4_XS)", q_type);
-    if (x_dtype != GQ_F16 && x_dtype != GQ_BF16)
-        GQ_FAIL(GQ_E_BAD_TYPE, "gq_gemv_packed: x_dtype %d (GQ_F16 or GQ_BF16; there is no fp32 path)", x_dtype);
-    if (!blocks) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed: blocks is NULL");
-    if (!x) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed: x is NULL");
-    if (!y) GQ_FAIL(GQ_E_NULL, "gq_gemv_packed: y is NULL");
-    if (R < 1 || R > 0x7fffffff) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: R=%ld (not in [1, 2^31))", (long)R);
+    const char* who = "gq_gemv_packed";
+    if (int rc = check_types(who, q_type, x_dtype)) return rc;
+    if (int rc = need(who, "blocks", blocks)) return rc;
+    if (int rc = need(who, "x", x)) return rc;
+    if (int rc = need(who, "y", y)) return rc;
+    if (int rc = check_R(who, R)) return rc;
     if (T < 1 || T > GQ_GEMV_MAX_T)
         GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: T=%ld (not in [1, %d]; gq_linear_packed takes more tokens)", (long)T, GQ_GEMV_MAX_T);
-    if (C < 256 || C > 0x7fffffff || C % 256)
-        GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: C=%ld (C %% 256 != 0 or not in [256, 2^31); Q8_0 and IQ4_NL included)", (long)C);
-    const int al = block_align(q_type);
-    if (!aligned(blocks, al)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: blocks not %d-byte aligned", al);
-    if (!aligned(row_src, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: row_src not 4-byte aligned");
-    if (!aligned(x, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: x not 16-byte aligned");
-    if (!aligned(y, 16)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_gemv_packed: y not 16-byte aligned");
+    if (int rc = check_C256(who, C)) return rc;
+    if (int rc = check_blocks_aligned(who, q_type, blocks)) return rc;
+    if (int rc = check_aligned(who, "row_src", row_src, 4)) return rc;
+    if (int rc = check_aligned(who, "x", x, 16)) return rc;
+    if (int rc = check_aligned(who, "y", y, 16)) return rc;
     const int64_t nsb = C / 256;
     const int nw = (int)(nsb < MAX_NW ? nsb : MAX_NW);
     const dim3 grid((unsigned)((R + VR - 1) / VR));  // < 2^27
@@ -89,17 +79,12 @@ int gq_gemv_packed(int q_type, const void* blocks, const int32_t* row_src, int64
     const uint8_t* b = static_cast<const uint8_t*>(blocks);
     const uint8_t* xp = static_cast<const uint8_t*>(x);
     uint16_t* yp = static_cast<uint16_t*>(y);
-    const bool bf = x_dtype == GQ_BF16;
-    switch (q_type) {
-    case GQ_Q2_K: launch<GQ_Q2_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
-    case GQ_Q3_K: launch<GQ_Q3_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
-    case GQ_Q4_K: launch<GQ_Q4_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
-    case GQ_Q5_K: launch<GQ_Q5_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
-    case GQ_Q6_K: launch<GQ_Q6_K>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
-    case GQ_IQ4_NL: launch<GQ_IQ4_NL>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
-    case GQ_IQ4_XS: launch<GQ_IQ4_XS>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
-    default: launch<GQ_Q8_0>(bf, grid, nw, st, b, row_src, R, C, xp, (int)T, yp); break;
-    }
+    dispatch_packed(q_type, [&](auto qt) {
+        dispatch_bool(x_dtype == GQ_BF16, [&](auto bf16) {
+            hipLaunchKernelGGL((gemv_packed_kernel<decltype(qt)::value, decltype(bf16)::value>), grid, dim3(64 * nw), 0, st, b, row_src, R,
+                               C, xp, (int)T, yp);
+        });
+    });
     GQ_LAUNCH_CHECK();
     return GQ_OK;
 }

@@ -308,8 +308,6 @@ __global__ __launch_bounds__(NT) void sample_kernel(const typename Ld<DT>::E* __
     }
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace gq
 

@@ -1,7 +1,9 @@
 // gq_block_decode.hpp -- the device side of the block decoder (K-quants, Q8_0, IQ4_NL and IQ4_XS), shared by decode/gq_decode.hip (K15: one
-// matrix per launch), search/gq_switch.hip (K18: a table of matrices per launch), qgemm/gq_qgemm.hip and qgemm/gq_qgemv.hip
-// (K21, K22: decode16 at the end, the weight operand of a GEMM / GEMV).  One text, so the entry points
+// matrix per launch), search/gq_switch.hip (K18: a table of matrices per launch) and, through qgemm/gq_qgemm_core.hpp and
+// qgemm/gq_gemv_core.hpp, the four packed matmul files qgemm/gq_qgemm.hip, gq_qgemv.hip, gq_moe_gemv.hip and gq_moe_gemm.hip
+// (K21, K22, K24, K25: decode16 at the end, the weight operand of a GEMM / GEMV).  One text, so the entry points
 // cannot drift apart: a turn of either kernel is decode_turn() (K-quants, IQ4_XS) or decode_turn_b32() (Q8_0, IQ4_NL) below.
+// The host side of the same types -- the list of them, alignment, geometry, operand checks -- is gq_block_host.hpp.
 // Layouts, staging widths and the numerical contract are described at the top of decode/gq_decode.hip.
 #pragma once
 

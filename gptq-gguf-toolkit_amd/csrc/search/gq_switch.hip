@@ -19,7 +19,7 @@
 // The kind / out_dtype dispatch is a switch on block-uniform values: a workgroup executes one arm.  HBM-bound like K15:
 // 0.33-0.82 B/param in, 2 or 4 B/param out; the unit is K15's turn so that the per-byte rate is K15's.
 #include "../../../include/gptq_gguf_iq4.h"  // (includes gptq_gguf_q8.h and gptq_gguf_search.h)
-#include "gq_block_decode.hpp"
+#include "gq_block_host.hpp"
 
 namespace gq {
 namespace {
@@ -142,17 +142,15 @@ __global__ __launch_bounds__(256) void level_switch_kernel(const SwitchTable t) 
     }
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 bool is_dtype(int d) { return d == GQ_F32 || d == GQ_F16 || d == GQ_BF16; }
 int elsize(int d) { return d == GQ_F32 ? 4 : 2; }
-int block_align(int q) { return q == GQ_Q2_K ? 4 : (q == GQ_Q4_K || q == GQ_Q5_K) ? 16 : q == GQ_IQ4_XS ? 8 : 2; }
 
 constexpr int64_t MAX_UNITS = 0x7fffffff;  // of one launch (the grid's x extent) and so of one job
 
 // every check of job i; fills the job's table entry except unit_end, and its unit count
 int check_job(const gq_switch_job_t& j, int i, SwitchEntry& e, int64_t& units) {
-    const bool packed = (j.kind >= GQ_Q2_K && j.kind <= GQ_Q6_K) || j.kind == GQ_IQ4_XS, q8 = j.kind == GQ_Q8_0 || j.kind == GQ_IQ4_NL;
-    if (!packed && !q8 && !is_dtype(j.kind)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_level_switch: job %d: unknown kind %d", i, j.kind);
+    const int bs = block_geometry(j.kind).bs;  // values per block; 0: not a packed type
+    if (!bs && !is_dtype(j.kind)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_level_switch: job %d: unknown kind %d", i, j.kind);
     if (!is_dtype(j.out_dtype)) GQ_FAIL(GQ_E_BAD_TYPE, "gq_level_switch: job %d: unknown out_dtype %d", i, j.out_dtype);
     if (!j.src) GQ_FAIL(GQ_E_NULL, "gq_level_switch: job %d: src is NULL", i);
     if (!j.dst) GQ_FAIL(GQ_E_NULL, "gq_level_switch: job %d: dst is NULL", i);
@@ -162,15 +160,11 @@ int check_job(const gq_switch_job_t& j, int i, SwitchEntry& e, int64_t& units) {
     if (!aligned(j.row_src, 4)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: row_src not 4-byte aligned", i);
     const int des = elsize(j.out_dtype);
     int64_t per_unit;
-    if (packed) {
-        if (j.C % 256) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: C=%ld (C %% 256 != 0)", i, (long)j.C);
+    if (bs) {
+        if (j.C % bs) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: C=%ld (C %% %d != 0)", i, (long)j.C, bs);
         if (!aligned(j.src, block_align(j.kind)))
             GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: src not %d-byte aligned", i, block_align(j.kind));
-        e.per_row = (int32_t)(j.C / 256), per_unit = DB;
-    } else if (q8) {
-        if (j.C % 32) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: C=%ld (C %% 32 != 0)", i, (long)j.C);
-        if (!aligned(j.src, 2)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_level_switch: job %d: src not 2-byte aligned", i);
-        e.per_row = (int32_t)(j.C / 32), per_unit = B32_DB;
+        e.per_row = (int32_t)(j.C / bs), per_unit = bs == 32 ? B32_DB : DB;
     } else {
         const int ses = elsize(j.kind);
         if (j.C * ses % 16 || j.C * des % 16)

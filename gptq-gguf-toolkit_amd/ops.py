@@ -12,6 +12,7 @@ import torch
 from . import _cabi
 from ._cabi import F16, F32, BF16, Search, check, lib, type_info
 from ._cabi import option_get, option_set, options  # noqa: F401  (library tuning / test switches)
+from .gguf_writer import GGML_QUANT_SIZES, PACKED_TYPES  # (numpy-level host code: it imports neither this module nor the library)
 
 _DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
@@ -362,9 +363,6 @@ def gptq_quantize_bands(W: torch.Tensor, U: torch.Tensor, bands: Sequence[Tuple[
 
 
 # ---- the bands of a walk as GGUF block bytes (gq_pack_bands) ----
-_K_TYPE_SIZE = {10: 84, 11: 110, 12: 144, 13: 176, 14: 210}  # bytes of a 256-value block of Q2_K .. Q6_K
-
-
 def pack_bands_plan(bands: Sequence[Tuple[int, int]], C: int):
     """Pure: what a gq_pack_bands call over `bands` (the table of band_layout) writes.  -> [(row0, row1, q_type, row_bytes,
     nbytes, off)] per band and the total: band k packs to [rows_k, row_bytes] = nbytes bytes, and `off` is where it lies when
@@ -376,7 +374,7 @@ def pack_bands_plan(bands: Sequence[Tuple[int, int]], C: int):
     lay, _ = band_layout(bands, C)
     out, off = [], 0
     for r0, r1, t, _, _ in lay:
-        row_bytes = C // 256 * _K_TYPE_SIZE[t]
+        row_bytes = C // 256 * GGML_QUANT_SIZES[t][1]
         out.append((r0, r1, t, row_bytes, (r1 - r0) * row_bytes, off))
         off += (r1 - r0) * row_bytes
     return out, off
@@ -547,16 +545,12 @@ def unpack(q_type: int, blocks: torch.Tensor):
 
 
 def block_geometry(q_type: int) -> Tuple[int, int]:
-    """(values per block, bytes per block) of a type gq_dequantize_blocks / gq_level_switch decode: the K-quants' 256-value
-    blocks, Q8_0's 32 values in 34 bytes, IQ4_NL's 32 in 18 and IQ4_XS's 256 in 136.  Any other type is the library's refusal
-    (gq_type_info)."""
-    if int(q_type) == _cabi.Q8_0:
-        return 32, 34
-    if int(q_type) == _cabi.IQ4_NL:
-        return 32, 18
-    if int(q_type) == _cabi.IQ4_XS:
-        return 256, 136
-    return 256, type_info(q_type)["type_size"]
+    """(values per block, bytes per block) of a type gq_dequantize_blocks / gq_level_switch decode, from the one table
+    gguf_writer.GGML_QUANT_SIZES: the K-quants' 256-value blocks, Q8_0's 32 values in 34 bytes, IQ4_NL's 32 in 18 and IQ4_XS's
+    256 in 136.  Any other type is refused as the library refuses it."""
+    if int(q_type) not in PACKED_TYPES:
+        raise _cabi.GQError(f"block_geometry: unknown q_type {int(q_type)} (a K-quant, Q8_0, IQ4_NL or IQ4_XS)")
+    return GGML_QUANT_SIZES[int(q_type)]
 
 
 def dequantize_blocks(q_type: int, blocks: torch.Tensor, out_dtype=torch.float32,
@@ -940,6 +934,47 @@ def gemv_packed(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src: Opt
 MOE_MAX_PAIRS = _cabi.MOE_MAX_PAIRS
 
 
+def _packed_experts_args(who: str, q_type, blocks, E, R, x, idx, idx_check, pairs_per_row, max_E, max_E_name, max_P, max_P_name,
+                         E_first: bool):
+    """The argument checks the two grouped expert ops share -> (k, E, R, C, x_rows, P, ppr).  idx: the op's index tensors;
+    idx_check() refuses them in the op's own words and returns P.  E_first: the op names a bad E / R before its index tensors
+    (linear_packed_experts), else after the pairs (gemv_packed_experts).  _need_cuda comes last: the refusals before it name
+    their value for tensors on any device."""
+    k, E, R, ppr = int(q_type), int(E), int(R), int(pairs_per_row)
+    bs, ts = block_geometry(k)
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise _cabi.GQError(f"{who}: x must be fp16 or bf16 (there is no fp32 path); got {x.dtype}")
+    if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
+        raise _cabi.GQError(f"{who}: x must be a non-empty contiguous [x_rows, C] tensor; got {tuple(x.shape)} strides "
+                            f"{tuple(x.stride())}")
+    for t in (blocks, *idx):
+        if t.device != x.device:
+            raise _cabi.GQError(f"{who}: every tensor must be on one device ({x.device}); got one on {t.device}")
+    x_rows, C = x.shape
+    if C % 256:
+        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 and IQ4_NL included)")
+
+    def check_E():
+        if E < 1 or E > max_E or R < 1:
+            raise _cabi.GQError(f"{who}: E={E}, R={R} (1 <= E <= {max_E_name}, R >= 1)")
+
+    if E_first:
+        check_E()
+    P = idx_check()
+    if P < 1 or P > max_P:
+        raise _cabi.GQError(f"{who}: P={P} pairs (not in [1, {max_P_name}={max_P}])")
+    if ppr < 1 or x_rows * ppr != P:
+        raise _cabi.GQError(f"{who}: x_rows={x_rows} * pairs_per_row={ppr} != P={P}")
+    if not E_first:
+        check_E()
+    need = E * R * (C // bs) * ts
+    if blocks.dtype != torch.uint8 or not blocks.is_contiguous() or blocks.numel() != need:
+        raise _cabi.GQError(f"{who}: packed blocks of q_type {k} for [E={E}, R={R}, C={C}] must be {need} contiguous uint8; "
+                            f"got {blocks.dtype} {tuple(blocks.shape)}")
+    _need_cuda(blocks, x, *idx)
+    return k, E, R, C, x_rows, P, ppr
+
+
 def gemv_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: torch.Tensor, pair_expert: torch.Tensor,
                         pairs_per_row: int) -> torch.Tensor:
     """y [P, R] with y[p] = W[pair_expert[p]] x[p // pairs_per_row] in ONE launch: `blocks` holds the stacked expert tensor
@@ -949,35 +984,14 @@ def gemv_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: to
     router's [T, K] index); pairs_per_row = 1: down (x the [P, I] activation).  Row p is bit for bit
     gemv_packed(q_type, expert pair_expert[p]'s slice, x[p // pairs_per_row]).  An id outside [0, E) is not checked: that
     pair is skipped and its row of y stays as torch.empty left it.  The ids are never read by the host: no synchronisation."""
-    k, E, R, ppr = int(q_type), int(E), int(R), int(pairs_per_row)
-    bs, ts = block_geometry(k)
-    who = "gemv_packed_experts"
-    if x.dtype not in (torch.float16, torch.bfloat16):
-        raise _cabi.GQError(f"{who}: x must be fp16 or bf16 (there is no fp32 path); got {x.dtype}")
-    if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
-        raise _cabi.GQError(f"{who}: x must be a non-empty contiguous [x_rows, C] tensor; got {tuple(x.shape)} strides "
-                            f"{tuple(x.stride())}")
-    for t in (blocks, pair_expert):
-        if t.device != x.device:
-            raise _cabi.GQError(f"{who}: every tensor must be on one device ({x.device}); got one on {t.device}")
-    x_rows, C = x.shape
-    if C % 256:
-        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 and IQ4_NL included)")
-    if pair_expert.dtype != torch.int32 or pair_expert.dim() != 1 or not pair_expert.is_contiguous():
-        raise _cabi.GQError(f"{who}: pair_expert must be a contiguous int32 [P] tensor; got {pair_expert.dtype} "
-                            f"{tuple(pair_expert.shape)}")
-    P = pair_expert.numel()
-    if P < 1 or P > MOE_MAX_PAIRS:
-        raise _cabi.GQError(f"{who}: P={P} pairs (not in [1, MOE_MAX_PAIRS={MOE_MAX_PAIRS}])")
-    if ppr < 1 or x_rows * ppr != P:
-        raise _cabi.GQError(f"{who}: x_rows={x_rows} * pairs_per_row={ppr} != P={P}")
-    if E < 1 or E > 65535 or R < 1:
-        raise _cabi.GQError(f"{who}: E={E}, R={R} (1 <= E <= 65535, R >= 1)")
-    need = E * R * (C // bs) * ts
-    if blocks.dtype != torch.uint8 or not blocks.is_contiguous() or blocks.numel() != need:
-        raise _cabi.GQError(f"{who}: packed blocks of q_type {k} for [E={E}, R={R}, C={C}] must be {need} contiguous uint8; "
-                            f"got {blocks.dtype} {tuple(blocks.shape)}")
-    _need_cuda(blocks, x, pair_expert)  # (last: the refusals above name their value for tensors on any device)
+    def pairs():
+        if pair_expert.dtype != torch.int32 or pair_expert.dim() != 1 or not pair_expert.is_contiguous():
+            raise _cabi.GQError(f"gemv_packed_experts: pair_expert must be a contiguous int32 [P] tensor; got {pair_expert.dtype} "
+                                f"{tuple(pair_expert.shape)}")
+        return pair_expert.numel()
+
+    k, E, R, C, x_rows, P, ppr = _packed_experts_args("gemv_packed_experts", q_type, blocks, E, R, x, (pair_expert,), pairs,
+                                                      pairs_per_row, 65535, "65535", MOE_MAX_PAIRS, "MOE_MAX_PAIRS", E_first=False)
     y = torch.empty(P, R, dtype=x.dtype, device=x.device)
     check(lib().gq_gemv_packed_experts(k, _ptr(blocks), E, R, C, _ptr(x), x_rows, _ptr(pair_expert), P, ppr, _DT[x.dtype],
                                        _ptr(y), _stream(x)), "gq_gemv_packed_experts")
@@ -1020,37 +1034,18 @@ def linear_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: 
     expert are gathered and the results scattered to pair order inside the kernel.  Row p is bit for bit
     linear_packed(q_type, that expert's slice, x[p // pairs_per_row]).  A pair that is in no run of the route (a masked
     pair) is skipped and its row of y stays as torch.empty left it.  Nothing is read by the host: no synchronisation."""
-    k, E, R, ppr = int(q_type), int(E), int(R), int(pairs_per_row)
-    bs, ts = block_geometry(k)
-    who = "linear_packed_experts"
     expert_start, order = route
-    if x.dtype not in (torch.float16, torch.bfloat16):
-        raise _cabi.GQError(f"{who}: x must be fp16 or bf16 (there is no fp32 path); got {x.dtype}")
-    if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
-        raise _cabi.GQError(f"{who}: x must be a non-empty contiguous [x_rows, C] tensor; got {tuple(x.shape)} strides "
-                            f"{tuple(x.stride())}")
-    for t in (blocks, expert_start, order):
-        if t.device != x.device:
-            raise _cabi.GQError(f"{who}: every tensor must be on one device ({x.device}); got one on {t.device}")
-    x_rows, C = x.shape
-    if C % 256:
-        raise _cabi.GQError(f"{who}: C={C} (C % 256 != 0; Q8_0 and IQ4_NL included)")
-    if E < 1 or E > MOE_ROUTE_MAX_EXPERTS or R < 1:
-        raise _cabi.GQError(f"{who}: E={E}, R={R} (1 <= E <= MOE_ROUTE_MAX_EXPERTS={MOE_ROUTE_MAX_EXPERTS}, R >= 1)")
-    for name, t, n in (("expert_start", expert_start, E + 1), ("order", order, order.numel())):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != n:
-            raise _cabi.GQError(f"{who}: route: {name} must be a contiguous int32 [{n}] tensor (moe_route's output for E={E}); "
-                                f"got {t.dtype} {tuple(t.shape)}")
-    P = order.numel()
-    if P < 1 or P > MOE_ROUTE_MAX_PAIRS:
-        raise _cabi.GQError(f"{who}: P={P} pairs (not in [1, MOE_ROUTE_MAX_PAIRS={MOE_ROUTE_MAX_PAIRS}])")
-    if ppr < 1 or x_rows * ppr != P:
-        raise _cabi.GQError(f"{who}: x_rows={x_rows} * pairs_per_row={ppr} != P={P}")
-    need = E * R * (C // bs) * ts
-    if blocks.dtype != torch.uint8 or not blocks.is_contiguous() or blocks.numel() != need:
-        raise _cabi.GQError(f"{who}: packed blocks of q_type {k} for [E={E}, R={R}, C={C}] must be {need} contiguous uint8; "
-                            f"got {blocks.dtype} {tuple(blocks.shape)}")
-    _need_cuda(blocks, x, expert_start, order)  # (last: the refusals above name their value for tensors on any device)
+
+    def pairs():
+        for name, t, n in (("expert_start", expert_start, int(E) + 1), ("order", order, order.numel())):
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != n:
+                raise _cabi.GQError(f"linear_packed_experts: route: {name} must be a contiguous int32 [{n}] tensor (moe_route's "
+                                    f"output for E={int(E)}); got {t.dtype} {tuple(t.shape)}")
+        return order.numel()
+
+    k, E, R, C, x_rows, P, ppr = _packed_experts_args(
+        "linear_packed_experts", q_type, blocks, E, R, x, route, pairs, pairs_per_row, MOE_ROUTE_MAX_EXPERTS,
+        f"MOE_ROUTE_MAX_EXPERTS={MOE_ROUTE_MAX_EXPERTS}", MOE_ROUTE_MAX_PAIRS, "MOE_ROUTE_MAX_PAIRS", E_first=True)
     y = torch.empty(P, R, dtype=x.dtype, device=x.device)
     check(lib().gq_linear_packed_experts(k, _ptr(blocks), E, R, C, _ptr(x), x_rows, ppr, _ptr(expert_start), _ptr(order), P,
                                          _DT[x.dtype], _ptr(y), _stream(x)), "gq_linear_packed_experts")

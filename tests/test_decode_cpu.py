@@ -27,6 +27,9 @@ def test_cabi_declares_exports_and_checks_the_decode_entry_points():
     assert lib.gq_unpack(3, n, 16, 256, n, n, n, n, n, n) == -1
     assert lib.gq_dequantize_blocks(3, n, 16, 256, n, n, _cabi.F16, n) == -1
     assert lib.gq_dequantize_blocks(12, n, 16, 256, n, n, 7, n) == -1 and b"out_dtype" in lib.gq_last_error()
+    # two faults: the type's refusal comes before the out_dtype's
+    assert lib.gq_dequantize_blocks(9, n, 16, 256, n, n, 7, n) == -1
+    assert lib.gq_last_error() == b"gq_dequantize_blocks: unknown q_type 9"
     null = lib.gq_unpack(12, n, 16, 256, n, n, n, n, n, n)
     assert null == lib.gq_dequantize_blocks(12, n, 16, 256, n, n, _cabi.F32, n) == lib.gq_pack(12, n, n, n, n, n, 16, 256, n, n)
     assert null < 0 and b"null" in lib.gq_last_error()

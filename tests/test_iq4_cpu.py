@@ -120,6 +120,12 @@ def test_header_defines_equal_the_bindings_and_declare_no_symbol():
     assert ops.block_geometry(20) == (32, 18) and ops.block_geometry(23) == (256, 136)
     assert ops.block_geometry(8) == (32, 34) and ops.block_geometry(12) == (256, 144)
     assert {20, 23} <= set(PACKED_TYPES)
+    assert sorted(PACKED_TYPES) == [8, 10, 11, 12, 13, 14, 20, 23]
+    for t in PACKED_TYPES:
+        assert ops.block_geometry(t) == GGML_QUANT_SIZES[t]
+    for t in (9, 15):
+        with pytest.raises(_cabi.GQError, match=f"q_type {t}"):
+            ops.block_geometry(t)
     assert "gptq_gguf_iq4.h" in open(os.path.join(ROOT, "README.md")).read()
     assert "gptq_gguf_iq4.h" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
 

@@ -74,6 +74,23 @@ def test_gemv_packed_experts_refusals_need_no_device():
     refused(BAD_SHAPE, "y not 16-byte aligned", E=65535, y=P + 2)
 
 
+def test_gemv_packed_experts_names_the_earlier_of_two_faults():
+    from gptq_gguf_toolkit_amd import _cabi
+    L = _cabi.lib()
+    for status, word, kw in ((BAD_TYPE, "q_type 9", dict(q_type=9, x=None)),
+                             (BAD_TYPE, "x_dtype 0", dict(x_dtype=0, blocks=None)),
+                             (NULL, "x is NULL", dict(x=None, C=128)),
+                             (BAD_SHAPE, "R=0 (not in [1, 2^31))", dict(R=0, C=128)),
+                             (BAD_SHAPE, "C=128 (C % 256 != 0 or not in [256, 2^31); Q8_0 and IQ4_NL included)", dict(C=128, y=P + 2)),
+                             (BAD_SHAPE, "blocks not 16-byte aligned", dict(blocks=P + 8, x=P + 8))):
+        args = dict(q_type=12, blocks=P, E=3, R=4, C=256, x=P, x_rows=2, pe=P, n=4, ppr=2, x_dtype=F16, y=P)
+        args.update(kw)
+        rc = L.gq_gemv_packed_experts(args["q_type"], args["blocks"], args["E"], args["R"], args["C"], args["x"], args["x_rows"],
+                                      args["pe"], args["n"], args["ppr"], args["x_dtype"], args["y"], None)
+        msg = L.gq_last_error().decode()
+        assert rc == status and msg.startswith("gq_gemv_packed_experts: ") and word in msg, (kw, rc, msg)
+
+
 def test_ops_gemv_packed_experts_refusals_name_the_value():
     from gptq_gguf_toolkit_amd import _cabi, ops
     E, R, C = 3, 4, 256

@@ -69,6 +69,22 @@ def test_linear_packed_refusals_need_no_device():
     refused(BAD_SHAPE, "more than one launch", R=(1 << 31) - 1, T=(1 << 31) - 1)
 
 
+def test_linear_packed_names_the_earlier_of_two_faults():
+    from gptq_gguf_toolkit_amd import _cabi
+    L = _cabi.lib()
+    for status, word, kw in ((BAD_TYPE, "q_type 9", dict(q_type=9, x=None)),
+                             (BAD_TYPE, "x_dtype 0", dict(x_dtype=0, blocks=None)),
+                             (NULL, "x is NULL", dict(x=None, C=128)),
+                             (BAD_SHAPE, "R=0 (not in [1, 2^31))", dict(R=0, C=128)),
+                             (BAD_SHAPE, "C=128 (C % 256 != 0 or not in [256, 2^31); Q8_0 and IQ4_NL included)", dict(C=128, y=P + 2)),
+                             (BAD_SHAPE, "blocks not 16-byte aligned", dict(blocks=P + 8, x=P + 8))):
+        args = dict(q_type=12, blocks=P, row_src=None, R=4, C=256, x=P, T=3, x_dtype=F16, y=P)
+        args.update(kw)
+        rc = L.gq_linear_packed(args["q_type"], args["blocks"], args["row_src"], args["R"], args["C"], args["x"], args["T"],
+                                args["x_dtype"], args["y"], None)
+        assert rc == status and _msg(L).startswith("gq_linear_packed: ") and word in _msg(L), (kw, rc, _msg(L))
+
+
 def test_ops_linear_packed_refuses_cpu_tensors():
     from gptq_gguf_toolkit_amd import _cabi, ops
     with pytest.raises(_cabi.GQError, match="CPU"):
