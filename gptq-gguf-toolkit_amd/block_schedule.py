@@ -462,7 +462,8 @@ class BlockSchedule:
     @torch.no_grad()
     def quantize_levels(self, levels, propagate: Optional[GGMLQuantizationType],
                         extra: Optional[Callable[[str, GPTQ, dict], Any]] = None,
-                        pack: Optional[Callable[[tuple, list, list], Any]] = None) -> Dict[str, Dict[Any, Tuple[torch.Tensor, ...]]]:
+                        pack: Optional[Callable[[tuple, list, list], Any]] = None,
+                        before: Optional[Callable[[str, GPTQ], Any]] = None) -> Dict[str, Dict[Any, Tuple[torch.Tensor, ...]]]:
         """Every Linear of the block at every level of `levels` -> {name: {q_type: 5-tuple}}: the database the bit-width
         search starts from, without a run per level.  The phases are quantize()'s -- the Hessians are folded once, one chain
         per distinct Hessian on the same lanes, one factorisation per distinct (H, zero-column set) -- and a chain walks the
@@ -472,7 +473,11 @@ class BlockSchedule:
         level feeds it -- or None: the weights stay as they are.  `extra(name, handle, {q_type: result})` runs on the
         chain's stream; so does `pack(stacked, bands, members)`, once per walk (GPTQ.compute_levels' `walks`, members as
         (Linear name, q_type) or None): the place for work on a whole walk's device buffers, the level database's one
-        gq_pack_bands launch.  Tensors either returns are kept valid for the caller's stream.  Single rank only."""
+        gq_pack_bands launch.  `before(name, handle)` runs on the chain's stream ahead of the chain's first
+        GPTQ.compute_levels, for every Linear of the chain: the accumulated Hessian -- handle.H, or the leader's
+        (handle.shared_H_with.H) for a Linear that shares its input -- is still undamped there (_prepare damps it in place), and
+        handle.layer.weight is the block's unmodified weight.  None changes nothing.  Tensors any of the three returns are
+        kept valid for the caller's stream.  Single rank only."""
         handles = self.handles
         levels = [GGMLQuantizationType(t) for t in levels]
         if not levels or len(set(levels)) != len(levels):
@@ -503,7 +508,8 @@ class BlockSchedule:
             for k in enq:
                 lane = _Lane(streams[lane_of[k]], main)
                 lane.wait(start)
-                lanes.append((lane, self._run_level_chain(order[k], levels, propagate, own, extra, results, deq, lane, pack)))
+                lanes.append((lane, self._run_level_chain(order[k], levels, propagate, own, extra, results, deq, lane, pack,
+                                                          before)))
             for lane, born in lanes:
                 lane.join(born)
         self.stats["own_U"] = len(results) - self.stats["reused_U"]
@@ -514,7 +520,7 @@ class BlockSchedule:
         return {n: results[n] for n in handles}
 
     def _run_level_chain(self, names: List[str], levels, propagate, own: Dict[str, bool], extra, results, deq,
-                         lane: _Lane, pack=None) -> List[torch.Tensor]:
+                         lane: _Lane, pack=None, before=None) -> List[torch.Tensor]:
         """Enqueue one chain of a level build on its lane -> the tensors born there.  The leader and the followers KNOWN to
         share its factorisation build their levels in one walk; a follower with a column set of its own, or one whose
         sharing became known too late to be checked (MoE experts), factorises for itself and walks alone -- the same
@@ -527,6 +533,9 @@ class BlockSchedule:
         walks = [] if pack is not None else None
         name_of = {handles[n]: n for n in names}
         with lane.run():
+            for n in names if before is not None else ():  # ahead of every factorisation of the chain: H is still undamped
+                out = before(n, handles[n])
+                born.extend(t for t in (out if isinstance(out, (tuple, list)) else (out,)) if torch.is_tensor(t))
             for grp in ([together] if self.stack else [[n] for n in together]):
                 if not grp:
                     continue

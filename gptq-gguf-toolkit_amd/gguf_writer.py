@@ -32,7 +32,7 @@ behaviour, cited per rule as class.method; DESIGN.md section 0d lists them with 
       (`add_tensor`); fp16 / fp32 numpy arrays name their own type.
 """
 import struct
-from typing import Any, List, Sequence, Tuple
+from typing import Any, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -49,7 +49,7 @@ class GGMLType:
     F32, F16 = 0, 1
     Q8_0 = 8
     Q2_K, Q3_K, Q4_K, Q5_K, Q6_K = 10, 11, 12, 13, 14
-    IQ4_NL, IQ4_XS = 20, 23  # payload bytes pass through: there is no encoder for them (include/gptq_gguf_iq4.h)
+    IQ4_NL, IQ4_XS = 20, 23  # read as include/gptq_gguf_iq4.h states them; encoded by quantize_iq4 (gptq_gguf_iq4_encode.h)
     BF16 = 30
 
 
@@ -132,6 +132,93 @@ def quantize_q8_0(data: np.ndarray) -> np.ndarray:
     qs = (np.sign(v) * (fl + np.floor(2 * (a - fl)))).astype(np.int8).view(np.uint8)
     out = np.concatenate([d.astype(np.float16).view(np.uint8), qs], axis=1)
     return out.reshape(*data.shape[:-1], data.shape[-1] // 32 * 34)
+
+
+KVALUES_IQ4NL = np.array([-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113], np.float32)
+
+
+def _iq4_best(a: np.ndarray) -> np.ndarray:
+    """best(a) of include/gptq_gguf_iq4_encode.h, elementwise on fp32: the two rounded differences compared, a tie goes up."""
+    kv = KVALUES_IQ4NL
+    u = np.clip(np.searchsorted(kv, a, side="right"), 1, 15)  # the smallest index with kv[u] > a, inside the table
+    idx = np.where((a - kv[u - 1]) < (kv[u] - a), u - 1, u)
+    return np.where(a <= kv[0], 0, np.where(a >= kv[15], 15, idx))
+
+
+def _iq4_sums(x: np.ndarray, w: np.ndarray, inv: np.ndarray):
+    q = KVALUES_IQ4NL[_iq4_best(x * inv[:, None])]
+    sumqx, sumq2 = np.zeros(len(x), np.float32), np.zeros(len(x), np.float32)
+    for j in range(32):  # ascending j: the summation order is part of the contract
+        wq = w[:, j] * q[:, j]
+        sumqx = sumqx + wq * x[:, j]
+        sumq2 = sumq2 + wq * q[:, j]
+    return sumqx, sumq2
+
+
+def quantize_iq4(data: np.ndarray, q_type: int, importance: Optional[np.ndarray] = None) -> np.ndarray:
+    """The IQ4_NL / IQ4_XS encoder of include/gptq_gguf_iq4_encode.h (the header's own contract, after the ntry = 7 path of
+    ggml's quantize_row_iq4_nl_impl), in numpy over all blocks at once: every operation fp32 and rounded on its own, the sums
+    in ascending j (a Python loop over j keeps the order).  This is the host form for a box without a GPU and what
+    ops.quantize_iq4 (gq_quantize_iq4) equals byte for byte.  `importance`: None or C values >= 0, one per column (llama.cpp's
+    importance matrix; the diagonal of the calibration Hessian).  -> uint8 [..., C / block * bytes]."""
+    q_type = int(q_type)
+    if q_type not in (GGMLType.IQ4_NL, GGMLType.IQ4_XS):
+        raise ValueError(f"quantize_iq4: q_type {q_type} is neither IQ4_NL ({GGMLType.IQ4_NL}) nor IQ4_XS ({GGMLType.IQ4_XS})")
+    size, ts = GGML_QUANT_SIZES[q_type]
+    data = np.asarray(data)
+    C = data.shape[-1]
+    if C % size != 0:
+        raise QuantError(f"Can't quantize tensor with shape {data.shape} to {'IQ4_NL' if size == 32 else 'IQ4_XS'}")
+    xs = np.ascontiguousarray(data, dtype=np.float32).reshape(-1, size)
+    nsb, per = xs.shape[0], size // 32
+    x = xs.reshape(-1, 32)
+    kv = KVALUES_IQ4NL
+    with np.errstate(all="ignore"):
+        x2 = x * x
+        w = x2
+        if importance is not None:
+            imp = np.ascontiguousarray(importance, dtype=np.float32).reshape(-1)
+            if imp.size != C:
+                raise ValueError(f"quantize_iq4: importance has {imp.size} values for rows of {C}")
+            s = np.zeros(nsb, np.float32)
+            for j in range(size):
+                s = s + xs[:, j] * xs[:, j]
+            sigma2 = np.repeat(s * (np.float32(2) / np.float32(size)), per)
+            qw = np.broadcast_to(imp.reshape(1, C // 32, 32), (xs.size // C, C // 32, 32)).reshape(-1, 32)
+            w = np.where((qw != 0).any(axis=1, keepdims=True), qw * np.sqrt(sigma2[:, None] + x2), x2)
+        first = np.abs(x).argmax(axis=1)  # the first j that reaches amax
+        mx = x[np.arange(len(x)), first]
+        live = np.abs(mx) >= np.float32(1e-15)
+        d0 = -mx / kv[0]
+        sumqx, sumq2 = _iq4_sums(x, w, np.float32(1) / d0)
+        d = sumqx / sumq2
+        bst = d * sumqx
+        for itry in range(-7, 8):
+            sumqx, sumq2 = _iq4_sums(x, w, (np.float32(itry) + kv[0]) / mx)
+            take = (sumq2 > 0) & (sumqx * sumqx > bst * sumq2)
+            nd = sumqx / sumq2
+            d = np.where(take, nd, d)
+            bst = np.where(take, nd * sumqx, bst)
+        d = np.where(live, d, np.float32(0)).astype(np.float32)
+        if size == 32:
+            head = d.astype(np.float16).reshape(-1, 1).view(np.uint8)
+            inv = np.where(d != 0, np.float32(1) / d, np.float32(0)).astype(np.float32)
+        else:
+            db = d.reshape(nsb, 8)
+            ms = db[np.arange(nsb), np.abs(db).argmax(axis=1)]  # largest |d|, the first one on a tie
+            D = (-ms / np.float32(32)).astype(np.float32)
+            iD = np.where(D != 0, np.float32(1) / D, np.float32(0)).astype(np.float32)
+            l = np.clip(np.rint(iD[:, None] * db), -32, 31).astype(np.float32)
+            dl = (D[:, None] * l).reshape(-1)
+            inv = np.where(dl != 0, np.float32(1) / dl, np.float32(0)).astype(np.float32)
+            ls = l.astype(np.int64) + 32
+            scales_h = sum((ls[:, ib] >> 4) << (2 * ib) for ib in range(8)).astype("<u2").reshape(-1, 1).view(np.uint8)
+            scales_l = ((ls[:, 0::2] & 15) | ((ls[:, 1::2] & 15) << 4)).astype(np.uint8)
+            head = np.concatenate([D.astype(np.float16).reshape(-1, 1).view(np.uint8), scales_h, scales_l], axis=1)
+        L = _iq4_best(x * inv[:, None]).astype(np.uint8)
+    qs = (L[:, :16] | (L[:, 16:] << 4)).reshape(nsb, per * 16)
+    out = np.concatenate([head, qs], axis=1)
+    return out.reshape(*data.shape[:-1], C // size * ts)
 
 
 class GGUFWriter:

@@ -594,6 +594,42 @@ def quantize_q8_0(x: torch.Tensor, row_src: Optional[torch.Tensor] = None) -> to
     return out
 
 
+def quantize_iq4(x: torch.Tensor, q_type: int, importance: Optional[torch.Tensor] = None,
+                 row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[R, C] fp32 / fp16 / bf16 on the device -> IQ4_NL (q_type 20, C % 32 == 0) blocks uint8 [R, C/32*18] or IQ4_XS (23,
+    C % 256 == 0) blocks uint8 [R, C/256*136] (gq_quantize_iq4, include/gptq_gguf_iq4_encode.h): byte for byte
+    gguf_writer.quantize_iq4 of x widened to fp32.  importance: None, or fp32 [C] on x's device, finite and >= 0, one weight
+    per column (the diagonal of the calibration Hessian is one).  row_src (int32 [R] on the device): out[r] =
+    encode(x[row_src[r]]); every index must lie in [0, R) -- the kernel does not check."""
+    _need_cuda(x, row_src)
+    if int(q_type) not in (_cabi.IQ4_NL, _cabi.IQ4_XS):
+        raise _cabi.GQError(f"quantize_iq4: q_type {int(q_type)} is neither IQ4_NL ({_cabi.IQ4_NL}) nor IQ4_XS ({_cabi.IQ4_XS})")
+    bs, ts = GGML_QUANT_SIZES[int(q_type)]
+    if x.dim() != 2 or x.dtype not in _DT or x.shape[1] % bs or x.shape[0] < 1 or x.shape[1] < bs:
+        raise _cabi.GQError(f"quantize_iq4: x must be a [R, C] fp32 / fp16 / bf16 tensor with C % {bs} == 0; got {x.dtype} "
+                            f"{tuple(x.shape)}")
+    R, C = x.shape
+    if importance is not None:
+        if importance.dtype != torch.float32 or importance.dim() != 1 or importance.numel() != C or importance.device != x.device:
+            raise _cabi.GQError(f"quantize_iq4: importance must be an fp32 [{C}] tensor on {x.device}; got {importance.dtype} "
+                                f"{tuple(importance.shape)} on {importance.device}")
+    if row_src is not None:
+        if row_src.dtype != torch.int32 or row_src.numel() != R or row_src.device != x.device:
+            raise _cabi.GQError(f"quantize_iq4: row_src must be an int32 [{R}] tensor on {x.device}")
+        row_src = row_src.contiguous()
+    if x.is_contiguous() and x.data_ptr() % 16:
+        raise _cabi.GQError("quantize_iq4: x must be 16-byte aligned")
+    x = x.contiguous()
+    if importance is not None:
+        importance = importance.contiguous()
+        if importance.data_ptr() % 16:  # (a view into a larger buffer)
+            importance = importance.clone()
+    out = torch.empty(R, C // bs * ts, dtype=torch.uint8, device=x.device)
+    check(lib().gq_quantize_iq4(_ptr(x), _DT[x.dtype], R, C, int(q_type), _ptr(importance), _ptr(row_src), _ptr(out), _stream(x)),
+          "gq_quantize_iq4")
+    return out
+
+
 def trailing_update(Cm: torch.Tensor, A: torch.Tensor, B: torch.Tensor):
     """Cm -= A @ B (fp32; k-ordered fma chain then one subtraction per element)."""
     _need_cuda(Cm, A, B)

@@ -105,6 +105,14 @@ def parse_args(argv=None):
                    help="with --level_db: every tensor that has K-quant levels also gets the 8.5-bit level 8.5-Q8_0.pth, encoded "
                         "on the GPU.  This is round-to-nearest of the UNMODIFIED weights -- what llama-quantize Q8_0 followed by "
                         "the splitter would leave --, not a GPTQ result")
+    p.add_argument("--level_db_iq4", nargs="+", default=[], choices=["IQ4_XS", "IQ4_NL"], metavar="TYPE",
+                   help="with --level_db: every tensor that has K-quant levels also gets the level 4.25-IQ4_XS.pth and / or "
+                        "4.56-IQ4_NL.pth, encoded on the GPU from the UNMODIFIED weights (include/gptq_gguf_iq4_encode.h), weighted "
+                        "by the diagonal of the calibration Hessian -- llama.cpp's importance matrix.  No GPTQ error feedback. "
+                        "A tensor whose rows are no multiple of 256 gets no IQ4_XS level")
+    p.add_argument("--level_db_iq4_importance", choices=["hessian", "none"], default="hessian",
+                   help="with --level_db_iq4: the importance of a column is the diagonal of the Linear's calibration Hessian "
+                        "(default), or none: every level is encoded unweighted")
     args = p.parse_args(argv)
     problem = levels_problem(args)
     if problem:
@@ -119,6 +127,8 @@ def levels_problem(args, world_size=None):
         return "--level_db_only needs --level_db"
     if getattr(args, "level_db_q8_0", False) and level_db is None:
         return "--level_db_q8_0 needs --level_db: the Q8_0 level is a level of the database"
+    if getattr(args, "level_db_iq4", None) and level_db is None:
+        return "--level_db_iq4 needs --level_db: the IQ4 levels are levels of the database"
     if args.levels is None:
         if level_db is not None:
             return "--level_db needs --levels: the level database is written by the one-pass level build"
@@ -240,7 +250,8 @@ def _run(args):
         quantizer.quantize_levels([GGMLQuantizationType[n] for n in args.levels],
                                   None if args.propagate_level == "none" else GGMLQuantizationType[args.propagate_level],
                                   level_db=args.level_db, trees=not args.level_db_only, level_db_model=args.model_name_or_path,
-                                  level_db_q8_0=args.level_db_q8_0)
+                                  level_db_q8_0=args.level_db_q8_0, level_db_iq4=tuple(args.level_db_iq4),
+                                  level_db_iq4_importance=args.level_db_iq4_importance)
     else:
         quantizer.quantize(quant_config)
     torch.cuda.synchronize()

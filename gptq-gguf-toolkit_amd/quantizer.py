@@ -23,7 +23,7 @@ import queue
 import sys
 import threading
 import time
-from typing import Any, Dict, Iterable, List, Optional
+from typing import Any, Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -574,6 +574,22 @@ def check_levels(levels, propagate):
     return levels, propagate
 
 
+IQ4_LEVEL_TYPES = {"IQ4_XS": 23, "IQ4_NL": 20}  # the ggml type ids (include/gptq_gguf_iq4.h)
+
+
+def check_iq4_levels(iq4, importance: str = "hessian") -> Tuple[int, ...]:
+    """-> the ggml type ids of `iq4` (names out of IQ4_XS / IQ4_NL, or their ids), in its order; ValueError for anything else."""
+    ids = []
+    for t in iq4 or ():
+        t = IQ4_LEVEL_TYPES.get(str(t).upper(), t)
+        if t not in IQ4_LEVEL_TYPES.values() or t in ids:
+            raise ValueError(f"level_db_iq4: {list(iq4)} (distinct types out of {list(IQ4_LEVEL_TYPES)})")
+        ids.append(int(t))
+    if importance not in ("hessian", "none"):
+        raise ValueError(f"level_db_iq4_importance: {importance!r} (hessian or none)")
+    return tuple(ids)
+
+
 class _LevelDbSink:
     """The level-database side of a level build (quant.py --level_db): packs every walk's bands into GGUF block bytes with
     ONE gq_pack_bands launch on the walk's stream -- q / k rows gathered into GGUF's rotary order on the way -- and books the
@@ -583,9 +599,16 @@ class _LevelDbSink:
     level's tree and splitting the files with --exact leaves.  Dense Llama family only; the HF side is not written.
     `q8_0`: every tensor whose K-quant levels were packed also gets the 8.5-bit level 8.5-Q8_0.pth -- round-to-nearest of
     the checkpoint's unmodified weights (gq_quantize_q8_0, q / k rows gathered on the way), what `llama-quantize Q8_0` and
-    the splitter would leave; GPTQ has no part in it."""
+    the splitter would leave; GPTQ has no part in it.
+    `iq4`: type names out of ("IQ4_XS", "IQ4_NL") -- every such tensor also gets the levels 4.25-IQ4_XS.pth / 4.56-IQ4_NL.pth,
+    encoded from the block's unmodified weight by gq_quantize_iq4 (include/gptq_gguf_iq4_encode.h; q / k rows gathered on the
+    way) ahead of its walk (`before_levels`, BlockSchedule.quantize_levels' `before`), registered BEFORE its K-quant levels so
+    that the tensor's gguf_layer_database.json record stays its last K-quant level.  `iq4_importance` "hessian": a column's
+    importance is the diagonal of the Linear's accumulated calibration Hessian, what llama.cpp calls the importance matrix;
+    "none", and the tensors that have no Hessian (embed / lm_head): unweighted.  No GPTQ error feedback either way.  A tensor
+    whose rows are no multiple of 256 gets no IQ4_XS level."""
 
-    def __init__(self, db: str, dir_model: str, vocab: bool = True, q8_0: bool = False):
+    def __init__(self, db: str, dir_model: str, vocab: bool = True, q8_0: bool = False, iq4=(), iq4_importance: str = "hessian"):
         import json
         from pathlib import Path
         from . import level_db
@@ -594,6 +617,8 @@ class _LevelDbSink:
             raise ValueError(f"level_db needs the model as a local directory with config.json and *.safetensors (got "
                              f"{dir_model!r}): the key/value data and the plain tensors are read from it")
         self.dir_model, self.vocab, self.q8_0 = Path(dir_model), vocab, bool(q8_0)
+        self.iq4 = check_iq4_levels(iq4, iq4_importance)
+        self.iq4_importance = iq4_importance
         self.hp = json.load(open(self.dir_model / "config.json"))
         arch = self.hp.get("architectures", ["LlamaForCausalLM"])[0]
         if arch not in ("LlamaForCausalLM", "LLaMAForCausalLM", "MistralForCausalLM") or self.hp.get("num_local_experts"):
@@ -647,6 +672,36 @@ class _LevelDbSink:
                 self.packed.add(mem[0])
             r0 = r1
         return outs
+
+    def encode_iq4(self, name: str, weight: torch.Tensor, importance: Optional[torch.Tensor]) -> List[torch.Tensor]:
+        """The IQ4 levels of HF module `name` from its unmodified `weight` [R, C] on the current stream: one gq_quantize_iq4
+        launch per type, the bytes booked and queued like a walk's.  Nothing for a module the database does not hold."""
+        from .gguf_writer import GGML_QUANT_SIZES
+        tensor = self.tensor_of.get(name)
+        if tensor is None or not self.iq4:
+            return []
+        w = weight.detach()
+        if w.dim() != 2 or w.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise NotImplementedError(f"level_db_iq4: {name} has a {w.dtype} weight of shape {tuple(w.shape)}")
+        w = w.contiguous()
+        rows = self._row_src(tensor, w.shape[0], w.device)
+        outs = []
+        for t in self.iq4:
+            if w.shape[1] % GGML_QUANT_SIZES[t][0]:
+                continue  # (rows that are no multiple of the type's block: the tensor has no such level)
+            blocks = _ops.quantize_iq4(w, t, importance, rows)
+            path = self.writer.register(tensor, tuple(w.shape), t)
+            self.items.append((path, RAW_BYTES, (blocks.view(-1),)))
+            outs.append(blocks)
+        return outs
+
+    def before_levels(self, name: str, handle) -> List[torch.Tensor]:
+        """BlockSchedule.quantize_levels' `before`: handle.H is the accumulated Hessian (undamped), handle.layer.weight the
+        block's unmodified weight."""
+        imp = None
+        if self.iq4_importance == "hessian":
+            imp = handle.H.diagonal().contiguous()  # (a copy: _prepare damps H in place later on this stream)
+        return self.encode_iq4(name, handle.layer.weight, imp) + ([imp] if imp is not None else [])
 
     def take(self) -> List[tuple]:
         items, self.items = self.items, []
@@ -730,7 +785,8 @@ class Quantizer:
     # ------------------------------------------------------------------ walk
     @torch.no_grad()
     def quantize_levels(self, levels, propagate, level_db: Optional[str] = None, trees: bool = True,
-                        level_db_model: Optional[str] = None, level_db_vocab: bool = True, level_db_q8_0: bool = False) -> None:
+                        level_db_model: Optional[str] = None, level_db_vocab: bool = True, level_db_q8_0: bool = False,
+                        level_db_iq4=(), level_db_iq4_importance: str = "hessian") -> None:
         """The level database in one pass: every quantizable module at every level of `levels`, one ordinary tree per level
         under <save_dir>/<LEVEL>/ (level_tree_name; same schema, same writer as quantize()).  The calibration forwards, the
         Hessians, the factorisations and the column walk are those of ONE run (BlockSchedule.quantize_levels).
@@ -745,7 +801,10 @@ class Quantizer:
         model's own name_or_path, which must be a local directory), `level_db_vocab`: write the tokenizer keys, as
         convert(vocab=...).  `trees=False` (with level_db): the per-level trees are not written.  `level_db_q8_0` (with
         level_db): every tensor that has K-quant levels also gets the 8.5-bit level 8.5-Q8_0.pth, round-to-nearest of its
-        unmodified weights.  Everything is refused before any work; a failed run leaves no database."""
+        unmodified weights.  `level_db_iq4` (with level_db; names out of "IQ4_XS", "IQ4_NL"): it also gets the levels
+        4.25-IQ4_XS.pth / 4.56-IQ4_NL.pth, encoded from its unmodified weights with the diagonal of its calibration Hessian as
+        the importance of a column (`level_db_iq4_importance` "hessian"; "none": unweighted) -- _LevelDbSink.  Everything is
+        refused before any work; a failed run leaves no database."""
         levels, propagate = check_levels(levels, propagate)
         if dist_utils.get_world_size() > 1:
             raise NotImplementedError("quantize_levels runs on one rank (multi-rank level builds are not built)")
@@ -755,12 +814,15 @@ class Quantizer:
             raise ValueError("quantize_levels: trees=False needs level_db (nothing would be written)")
         if level_db is None and level_db_q8_0:
             raise ValueError("quantize_levels: level_db_q8_0 needs level_db (the Q8_0 level is a level of the database)")
+        if level_db is None and level_db_iq4:
+            raise ValueError("quantize_levels: level_db_iq4 needs level_db (the IQ4 levels are levels of the database)")
+        check_iq4_levels(level_db_iq4, level_db_iq4_importance)
         sink = None
         if level_db is not None:
             if os.environ.get("GQ_SAVE_SKIP") == "1":
                 raise ValueError("quantize_levels: GQ_SAVE_SKIP=1 writes no files, a level database cannot be completed")
             sink = _LevelDbSink(level_db, level_db_model or getattr(self.model.config, "_name_or_path", None), level_db_vocab,
-                                q8_0=level_db_q8_0)
+                                q8_0=level_db_q8_0, iq4=level_db_iq4, iq4_importance=level_db_iq4_importance)
         self._levels, self._level_src, self._level_sink, self._level_trees = (levels, propagate), {}, sink, bool(trees)
         try:
             self.quantize({})
@@ -978,7 +1040,9 @@ class Quantizer:
         if getattr(self, "_levels", None) is not None:
             levels, propagate = self._levels
             sink = getattr(self, "_level_sink", None)
-            for n, per_level in sched.quantize_levels(levels, propagate, pack=sink.pack_walk if sink else None).items():
+            before = sink.before_levels if sink is not None and sink.iq4 else None
+            for n, per_level in sched.quantize_levels(levels, propagate, pack=sink.pack_walk if sink else None,
+                                                      before=before).items():
                 for t in levels if getattr(self, "_level_trees", True) else ():
                     item = self._save(level_tree_name(t, n), t, *per_level[t], defer=True)
                     if item is not None:
@@ -1037,6 +1101,10 @@ class Quantizer:
         tied = key in self._level_src
         src = self._level_src.setdefault(key, module.weight.data)  # the weight before any write-back (kept alive here)
         back = None
+        sink = getattr(self, "_level_sink", None)
+        if sink is not None and sink.iq4:  # no Hessian here: the IQ4 levels are unweighted, and come before the K-quant levels
+            sink.encode_iq4(name, src, None)
+            self._saver.put_many(sink.take())
         for t in levels:
             w = src
             if tied:

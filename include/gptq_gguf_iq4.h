@@ -2,7 +2,8 @@
    of gptq_gguf.h in the way of gptq_gguf_q8.h (same library, same conventions: status codes, gq_last_error, GQ_F32 / GQ_F16 /
    GQ_BF16, device pointers, `stream` a hipStream_t).  There is NO new symbol and GQ_ABI_VERSION does not change: the header
    carries two type ids, their layouts and the rules under which the existing decode and packed-forward entry points take
-   them.  There is no encoder for either type: levels of these types come from files that llama.cpp quantized. */
+   them.  The encoder of both types is gq_quantize_iq4 of gptq_gguf_iq4_encode.h; levels of these types also come from files that
+   llama.cpp quantized. */
 #ifndef GPTQ_GGUF_IQ4_H
 #define GPTQ_GGUF_IQ4_H
 
