@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "gq_common.hpp"
+#include "gq_syrk_plan.hpp"
 #include <utility>
 #include <vector>
 
@@ -85,10 +86,9 @@ __global__ __launch_bounds__(256) void transpose16_kernel(const uint16_t* __rest
 // 16-B slots (conflict-free; (row & 7) measured 2-way).  global_load_lds writes lane-linear,
 // so the swizzle is applied to the per-lane SOURCE address (8 consecutive lanes still
 // fetch one full 128-B line) and again on the ds_read_b128 fragment address.
-constexpr int HT = 128;  // output tile
+// HT = 128, the output tile, and H_MAX_GROUP: gq_syrk_plan.hpp
 constexpr int HK = 64;   // k per stage (16-bit elements) = 128 B per row
 constexpr int H_STAGE_BYTES = 2 * HT * HK * 2;  // A + B = 32 KiB
-constexpr int H_MAX_GROUP = 8;
 
 struct SyrkProblem {
     float* H;
@@ -111,7 +111,7 @@ __device__ __forceinline__ uint64_t sload64_now(const uint64_t* p) {
 struct SyrkGroup {
     int n, total_tiles;
     SyrkProblem p[H_MAX_GROUP];
-    // syrk16_256e_kernel only: balanced tile table, entry = problem << 24 | ti << 12 | tj (0xffffffff: none),
+    // syrk16_256e_kernel and syrk16_256w_kernel: balanced tile table, entry = problem << 24 | ti << 12 | tj (0xffffffff: none),
     // row x holds the tiles workgroups with blockIdx % 8 == x (= XCD x) process, in order
     const uint32_t* table;
     int per_xcd;
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256, 2) void syrk16_kernel(const SyrkGroup grp) {
 }
 
 // ------------------------------------------ 16-bit SYRK, 256x256 tiles, direct-to-LDS operand ring
-constexpr int BT = 256;                         // tile
+// BT = 256, the tile: gq_syrk_plan.hpp
 constexpr int SK = 32;                          // k per half-stage
 constexpr int S_BUF_BYTES = 2 * BT * SK * 2;    // one ring slot: A 16 KiB | B 16 KiB
 constexpr int S_NBUF = 4;
@@ -1002,212 +1002,80 @@ __global__ __launch_bounds__(256) void syrk32_kernel(float* __restrict__ H, int6
         }
 }
 
-// 16-bit inputs with C % 256 == 0 and T % 128 == 0 are read in place (syrk16_256w_kernel): only the tile table
-// needs scratch.  Everything else goes through the re-laid-out operand image.
-static inline bool syrk_in_place(int64_t T, int64_t C) {
-    return (C % BT == 0) && (T % (2 * HK) == 0) && !opt(OPT_syrk_image);
+// options are read per call, and once per call (SyrkOptions, gq_syrk_plan.hpp): tests and A/B runs flip them inside one process
+static SyrkOptions syrk_options() {
+    return SyrkOptions{opt(OPT_syrk_image) != 0, opt(OPT_syrk_nosplit) != 0, (int)opt(OPT_syrk_gw), opt(OPT_syrk_ck),
+                       opt(OPT_syrk_wgs)};
 }
 
-// K-split of the last (partial) round of tiles (syrk16_256w_kernel): partial-sum slots a problem may need.
-// Only long token ranges are split (every part is at least 8 turns of the ring); option syrk_nosplit disables it.
-static inline size_t syrk_partial_slots(int64_t T, size_t ntile) {
-    if (T < 8192 || opt(OPT_syrk_nosplit)) return 0;
-    return 4 * ntile < 512 ? 4 * ntile : 512;
-}
-
-size_t h_accumulate_workspace_bytes(int64_t T, int64_t C) {
-    const size_t nt = (size_t)(C / BT);
-    const size_t ntile = nt * (nt + 1) / 2;
-    // tile table + unit attributes + reduce list of the 256x256 kernels (K-split adds up to 512 units)
-    const size_t table = (ntile + 512 + 320) * 4 * 2 + 512 * 8 + 256 + (size_t)(T / 128 + 2) * 8 + 64;  // + block addresses, counters
-    if (syrk_in_place(T, C)) return table + syrk_partial_slots(T, ntile) * (size_t)BT * BT * 4 + 256;
-    const int64_t Tp = (T + 2 * HK - 1) / (2 * HK) * (2 * HK);
-    return (size_t)C * (size_t)Tp * 2 + 256 + table;
-}
+size_t h_accumulate_workspace_bytes(int64_t T, int64_t C) { return syrk_workspace_bytes(T, C, syrk_options()); }
 
 // one launch over the problems idx[0..m): kind 0 = 128x128 kernel, 1 = 256x256 ring kernel on the re-laid-out
-// image, 2 = 256x256 ring kernel reading X in place
+// image, 2 = 256x256 ring kernel reading X in place.  What is launched, and where everything lies in the workspace, is
+// the plan's (make_syrk_plan); here are the checks against the workspace's end, the addresses and the HIP calls.
 static int syrk16_launch(int kind, const int* idx, int m, float* const* H, const void* const* X, const int64_t* T,
                          const int64_t* C, const float* beta, const float* alpha, int x_dtype, unsigned char*& wp,
-                         unsigned char* ws_end, hipStream_t st, const void* const* const* segs = nullptr,
-                         const int64_t* nseg = nullptr) {
+                         unsigned char* ws_end, hipStream_t st, const SyrkOptions& o,
+                         const void* const* const* segs = nullptr, const int64_t* nseg = nullptr) {
+    SyrkShape shape[H_MAX_GROUP];
+    for (int k = 0; k < m; ++k) shape[k] = SyrkShape{T[idx[k]], C[idx[k]], segs && segs[idx[k]] ? nseg[idx[k]] : 1};
+    SyrkPlan pl = make_syrk_plan(kind, shape, m, o);
+    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)wp + 255) & ~(uintptr_t)255);
+    const size_t room = base < ws_end ? (size_t)(ws_end - base) : 0, table_bytes = pl.words.size() * 4;
+    if (pl.img_end > room) GQ_FAIL(GQ_E_WORKSPACE, "gq_h_accumulate: workspace too small for the operand image");
+    if (pl.table_off + table_bytes > room) GQ_FAIL(GQ_E_WORKSPACE, "gq_h_accumulate: workspace too small for the tile table");
+    if (pl.total > room) GQ_FAIL(GQ_E_WORKSPACE, "gq_h_accumulate: workspace too small for the K-split partial sums");
+    wp = base + pl.total;
     const dim3 block(256);
     SyrkGroup grp;
     grp.n = m;
-    int tiles = 0;
+    grp.total_tiles = pl.total_tiles;
     for (int k = 0; k < m; ++k) {
         const int i = idx[k];
-        const int64_t Tp = (T[i] + 2 * HK - 1) / (2 * HK) * (2 * HK);  // whole turns of the 4-slot ring
+        const SyrkPlan::Problem& p = pl.p[k];
         const uint16_t* Xt = reinterpret_cast<const uint16_t*>(X[i]);
-        if (kind != 2) {
-            uint16_t* img = reinterpret_cast<uint16_t*>(wp);
-            wp += ((size_t)C[i] * Tp * 2 + 255) & ~(size_t)255;
-            if (wp > ws_end) GQ_FAIL(GQ_E_WORKSPACE, "gq_h_accumulate: workspace too small for the operand image");
+        if (p.img_bytes) {
+            uint16_t* img = reinterpret_cast<uint16_t*>(base + p.img_off);
             ProfScope ps(PT_TRANSPOSE, st);
-            dim3 tg((unsigned)(Tp / HK), (unsigned)(C[i] / HT));
-            hipLaunchKernelGGL(transpose16_kernel, tg, block, 0, st, (const uint16_t*)X[i], T[i], C[i], img, Tp / HK,
-                               kind == 1 ? 1 : 0);
+            dim3 tg((unsigned)(p.Tp / HK), (unsigned)(C[i] / HT));
+            hipLaunchKernelGGL(transpose16_kernel, tg, block, 0, st, Xt, T[i], C[i], img, p.Tp / HK, kind == 1 ? 1 : 0);
             GQ_LAUNCH_CHECK();
             Xt = img;
         }
-        const int nt = (int)(C[i] / (kind ? BT : HT));
-        grp.p[k] = SyrkProblem{H[i], Xt, C[i], Tp, beta[i], alpha[i], tiles, nt, nullptr, 0};
-        if (!kind) {
-            const int ns = (nt + 7) / 8;  // 8x8 super-tiles per dimension
-            tiles += ns * (ns + 1) / 2;
+        grp.p[k] = SyrkProblem{H[i], Xt, C[i], p.Tp, beta[i], alpha[i], p.tile_begin, p.nt, nullptr, p.hs_per_seg};
+        if (p.seg_word == SYRK_NO_WORD) continue;
+        grp.p[k].segs = reinterpret_cast<const uint64_t*>(base + pl.table_off) + p.seg_word / 2;
+        for (int64_t b = 0; b < nseg[i]; ++b) {
+            const uint64_t a = (uint64_t)(uintptr_t)segs[i][b];
+            pl.words[p.seg_word + 2 * b] = (uint32_t)a;
+            pl.words[p.seg_word + 2 * b + 1] = (uint32_t)(a >> 32);
         }
     }
-    grp.total_tiles = tiles;
-    grp.table = nullptr;
-    grp.per_xcd = 0;
-    grp.aux = nullptr;
-    grp.partial = nullptr;
-    grp.bar = nullptr;
-    grp.ck = 0;
-    grp.nck = 0;
-    int n_reduce = 0;
-    const uint32_t* reduce_list = nullptr;
-    std::vector<uint32_t> table;
-    if (kind) {
-        // Balanced schedule: the valid (ti <= tj) tiles of all problems, enumerated super-tile by super-tile
-        // (8 x 4 tiles share 12 operand panels), are cut into groups of 32 CONSECUTIVE tiles -- one group =
-        // what the 32 CUs of an XCD run at the same time out of one L2 -- and the groups are dealt
-        // round-robin to the 8 XCDs, so every XCD gets the same number of tiles (+-32) and no workgroup
-        // exits early.  (An arithmetic id -> super-tile map leaves XCDs up to 30 % apart: diagonal
-        // super-tiles are half empty.)
-        std::vector<uint32_t> all;
-        // (option syrk_gw: the super-tile's width in tiles, 32 / gw rows.  r06 A/B of the fabric traffic on random operands at
-        // C = 14336, profiles/r06_syrk_traffic_ab.txt: 4 x 8 (r02-r05) 29.7 GB of L2-miss reads per launch, 1312 TFLOP/s; 2 x 16
-        // 41.5 GB, 1283; 1 x 32 51.3 GB, 1269; 8 x 4 (default since r06) 26.5 GB, 1332 -- and 89.3 against 90.2 ms per bench
-        // step in four alternating pairs.  Which tiles fall into the K-split round depends on the shape, so H moves within
-        // K1's tolerance class.)
-        const int gw = (int)opt(OPT_syrk_gw), gh = 32 / gw;
-        for (int k = 0; k < m; ++k) {
-            const int nt = grp.p[k].nt, nsc = (nt + gw - 1) / gw, nsr = (nt + gh - 1) / gh;
-            for (int sI = 0; sI < nsr; ++sI)
-                for (int sJ = (sI * gh) / gw; sJ < nsc; ++sJ)
-                    for (int slot = 0; slot < 32; ++slot) {
-                        const int ti = sI * gh + slot / gw, tj = sJ * gw + slot % gw;
-                        if (ti < nt && tj < nt && ti <= tj) all.push_back((uint32_t)k << 24 | (uint32_t)ti << 12 | (uint32_t)tj);
-                    }
-        }
-        // K-split of the last, partial round (in-place kernel): 1596 tiles of a 14336-wide Hessian are 6.23 rounds
-        // of 256 CUs, and the 7th round would run 60 tiles on 256 CUs for a whole tile time.  The R = N mod 256
-        // tiles left after the full rounds are cut into s token ranges each, s minimising ceil(R s / 256) / s
-        // (14336: s = 4, +0.25 instead of +1 round; 3 x 4096: R = 152, s = 3, +0.67 instead of +1); every unit
-        // stores raw fp32 sums and syrk_reduce_kernel adds them in fixed order (deterministic).
-        const size_t N = all.size(), full = (N / 256) * 256, R = N - full;
-        int sp = 1;
-        size_t cap_units = 0;
-        bool can_split = kind == 2 && R > 0;
-        for (int k = 0; k < m && can_split; ++k) {
-            const size_t slots = syrk_partial_slots(grp.p[k].Tp, (size_t)grp.p[k].nt * (grp.p[k].nt + 1) / 2);
-            if (slots == 0) can_split = false;
-            cap_units += slots;
-        }
-        if (cap_units > 512) cap_units = 512;  // (measured, r04: 1024 -- s = 5 instead of 3 for the three 4096-wide inputs of a dense block, 1.6 rounds instead of 1.667 -- is 1-2 % SLOWER: partial-sum traffic and a longer reduce)
-        if (can_split) {
-            double best = 1.0;
-            for (int c = 2; c <= 8 && R * c <= cap_units; ++c) {
-                const double cost = (double)((R * c + 255) / 256) / c;
-                if (cost < best - 1e-9) { best = cost; sp = c; }
-            }
-        }
-        std::vector<uint32_t> unit, uaux, rlist;
-        for (size_t t = 0; t < N; ++t) {
-            if (t < full || sp == 1) {
-                unit.push_back(all[t]);
-                uaux.push_back(0xffffffffu);
-            } else {
-                const uint32_t first = (uint32_t)((t - full) * sp);
-                rlist.push_back(all[t]);
-                rlist.push_back(first << 8 | (uint32_t)sp);
-                for (int k = 0; k < sp; ++k) {
-                    unit.push_back(all[t]);
-                    uaux.push_back((first + k) << 12 | (uint32_t)k << 6 | (uint32_t)sp);
-                }
-            }
-        }
-        const size_t ngroups = (unit.size() + 31) / 32;
-        const int per_xcd = (int)((ngroups + 7) / 8) * 32;
-        const size_t tl = (size_t)8 * per_xcd;
-        table.assign(2 * tl + rlist.size(), 0xffffffffu);  // [table | aux | reduce list]
-        for (size_t t = 0; t < unit.size(); ++t) {
-            const size_t gi = t >> 5, pos = (gi & 7) * per_xcd + (gi >> 3) * 32 + (t & 31);
-            table[pos] = unit[t];
-            table[tl + pos] = uaux[t];
-        }
-        for (size_t t = 0; t < rlist.size(); ++t) table[2 * tl + t] = rlist[t];
-        wp = reinterpret_cast<unsigned char*>(((uintptr_t)wp + 255) & ~(uintptr_t)255);
-        // rendezvous counters of the persistent launch (zeroed by this upload), then the block address lists of the
-        // problems whose X arrives in separate blocks, behind the tile table
-        // (more than one round per XCD; measured in r02, L2-miss reads of a 14336-wide launch 37.5 against 49.6 GB with one tile
-        // per workgroup, rocprofv3 FETCH_SIZE, +0.8 % speed: the switch to the one-tile form for every shape removed)
-        size_t bar_at = 0;
-        if (kind == 2 && per_xcd > 32) {
-            bar_at = table.size();
-            for (int x = 0; x < 16; ++x) table.push_back(0u);  // [0..7] rounds, [8..15] checkpoints inside a tile
-            // checkpoints: only when every problem of the launch walks the same number of half-stages (a dense block's inputs do;
-            // MoE experts with their own token counts do not)
-            int64_t ck = opt(OPT_syrk_ck);
-            bool same = (ck & (ck - 1)) == 0 && ck >= 16;
-            for (int k = 1; k < m && same; ++k) same = grp.p[k].Tp == grp.p[0].Tp;
-            if (same && grp.p[0].Tp / 32 > ck) {
-                grp.ck = (int)ck;
-                grp.nck = (int)((grp.p[0].Tp / 32 - 1) / ck);
-            }
-        }
-        if (table.size() & 1) table.push_back(0xffffffffu);
-        for (int k = 0; k < m && segs; ++k) {
-            const int i = idx[k];
-            if (!segs[i] || nseg[i] <= 1) continue;
-            grp.p[k].segs = reinterpret_cast<const uint64_t*>(wp + table.size() * 4);
-            grp.p[k].hs_per_seg = (int)(T[i] / nseg[i] / 32);
-            for (int64_t b = 0; b < nseg[i]; ++b) {
-                const uint64_t a = (uint64_t)(uintptr_t)segs[i][b];
-                table.push_back((uint32_t)a);
-                table.push_back((uint32_t)(a >> 32));
-            }
-        }
-        if (wp + table.size() * 4 > ws_end) GQ_FAIL(GQ_E_WORKSPACE, "gq_h_accumulate: workspace too small for the tile table");
-        GQ_HIP(hipMemcpyAsync(wp, table.data(), table.size() * 4, hipMemcpyHostToDevice, st));  // pageable: staged before return
-        grp.table = reinterpret_cast<const uint32_t*>(wp);
-        if (bar_at) grp.bar = reinterpret_cast<unsigned*>(wp) + bar_at;
-        grp.per_xcd = per_xcd;
-        grp.aux = sp > 1 ? grp.table + tl : nullptr;
-        wp += table.size() * 4;
-        if (sp > 1) {
-            wp = reinterpret_cast<unsigned char*>(((uintptr_t)wp + 255) & ~(uintptr_t)255);
-            grp.partial = reinterpret_cast<float*>(wp);
-            wp += R * sp * (size_t)BT * BT * 4;
-            if (wp > ws_end) GQ_FAIL(GQ_E_WORKSPACE, "gq_h_accumulate: workspace too small for the K-split partial sums");
-            n_reduce = (int)R;
-            reduce_list = grp.table + 2 * tl;
-        }
-    }
+    const uint32_t* up = reinterpret_cast<const uint32_t*>(base + pl.table_off);  // the upload, on the device
+    if (table_bytes) GQ_HIP(hipMemcpyAsync(base + pl.table_off, pl.words.data(), table_bytes, hipMemcpyHostToDevice, st));  // pageable: staged before return
+    grp.table = table_bytes ? up : nullptr;
+    grp.per_xcd = pl.per_xcd;
+    grp.aux = pl.aux_word != SYRK_NO_WORD ? up + pl.aux_word : nullptr;
+    grp.partial = pl.sp > 1 ? reinterpret_cast<float*>(base + pl.partial_off) : nullptr;
+    grp.bar = pl.bar_word != SYRK_NO_WORD ? const_cast<unsigned*>(up) + pl.bar_word : nullptr;
+    grp.ck = pl.ck;
+    grp.nck = pl.nck;
     ProfScope ps(PT_SYRK, st);
     const bool bf = x_dtype == GQ_BF16;
+    const dim3 grid(pl.grid), blk(pl.block);
     if (kind == 2) {
-        // one tile per workgroup, or (grp.bar) one workgroup per CU walking its XCD's list in rounds
-        // (option syrk_wgs, read per call: fewer resident workgroups for a fold that runs NEXT TO a latency-bound chain --
-        // the block schedule's postponed folds -- so that the chain's kernels always find free CUs)
-        int wgs = 256;
-        if (const int64_t e = opt(OPT_syrk_wgs)) wgs = (e >= 8 && e <= 256) ? (int)(e & ~7) : 256;
-        const dim3 grid((unsigned)(grp.bar ? wgs : 8 * grp.per_xcd));
-        if (bf) hipLaunchKernelGGL(syrk16_256w_kernel<true>, grid, block, S_LDS_BYTES, st, grp);
-        else hipLaunchKernelGGL(syrk16_256w_kernel<false>, grid, block, S_LDS_BYTES, st, grp);
-        if (n_reduce > 0) {
+        if (bf) hipLaunchKernelGGL(syrk16_256w_kernel<true>, grid, blk, S_LDS_BYTES, st, grp);
+        else hipLaunchKernelGGL(syrk16_256w_kernel<false>, grid, blk, S_LDS_BYTES, st, grp);
+        if (pl.n_reduce > 0) {
             GQ_LAUNCH_CHECK();
-            hipLaunchKernelGGL(syrk_reduce_kernel, dim3((unsigned)n_reduce, 16), dim3(256), 0, st, grp, reduce_list);
+            hipLaunchKernelGGL(syrk_reduce_kernel, dim3((unsigned)pl.n_reduce, 16), dim3(256), 0, st, grp, up + pl.reduce_word);
         }
     } else if (kind == 1) {
-        const dim3 grid((unsigned)(8 * grp.per_xcd)), blk(512);
         if (bf) hipLaunchKernelGGL(syrk16_256e_kernel<true>, grid, blk, S_LDS_BYTES, st, grp);
         else hipLaunchKernelGGL(syrk16_256e_kernel<false>, grid, blk, S_LDS_BYTES, st, grp);
     } else {
-        const dim3 grid((unsigned)((tiles + 7) / 8 * 8 * 64));
-        if (bf) hipLaunchKernelGGL(syrk16_kernel<true>, grid, block, 2 * H_STAGE_BYTES, st, grp);
-        else hipLaunchKernelGGL(syrk16_kernel<false>, grid, block, 2 * H_STAGE_BYTES, st, grp);
+        if (bf) hipLaunchKernelGGL(syrk16_kernel<true>, grid, blk, 2 * H_STAGE_BYTES, st, grp);
+        else hipLaunchKernelGGL(syrk16_kernel<false>, grid, blk, 2 * H_STAGE_BYTES, st, grp);
     }
     GQ_LAUNCH_CHECK();
     return GQ_OK;
@@ -1379,14 +1247,15 @@ int h_accumulate_grouped(int n, float* const* H, const void* const* X, const int
         return GQ_OK;
     }
     if (x_dtype != GQ_F16 && x_dtype != GQ_BF16) GQ_FAIL(GQ_E_BAD_TYPE, "gq_h_accumulate: unknown x_dtype %d", x_dtype);
+    const SyrkOptions o = syrk_options();
     size_t need = 0;
     for (int i = 0; i < n; ++i) {
         if (!H[i] || !X[i]) GQ_FAIL(GQ_E_NULL, "gq_h_accumulate: null pointer");
         if (T[i] <= 0 || C[i] <= 0 || (C[i] % HT)) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_h_accumulate: T=%ld C=%ld (C %% 128 != 0)", (long)T[i], (long)C[i]);
-        need += h_accumulate_workspace_bytes(T[i], C[i]);
+        need += syrk_workspace_bytes(T[i], C[i], o);
         if (segs && segs[i] && nseg[i] > 1) {
             // separate blocks are only read in place: whole ring turns per block, 16-byte aligned rows
-            if (T[i] % nseg[i] || (T[i] / nseg[i]) % (2 * HK) || !syrk_in_place(T[i], C[i]))
+            if (T[i] % nseg[i] || (T[i] / nseg[i]) % SYRK_TURN || syrk_kind(T[i], C[i], o) != 2)
                 GQ_FAIL(GQ_E_UNSUPPORTED, "gq_h_accumulate_segments: %ld blocks of %ld tokens, C=%ld: blocks must hold a "
                         "multiple of 128 tokens and C %% 256 == 0 (stage the rows into one buffer instead)",
                         (long)nseg[i], (long)(T[i] / nseg[i]), (long)C[i]);
@@ -1409,14 +1278,14 @@ int h_accumulate_grouped(int n, float* const* H, const void* const* X, const int
     // in place (kind 2), 256x256 on the image (kind 1: T not a multiple of 128), 128x128 (kind 0: C % 256 != 0).
     int idx[3][H_MAX_GROUP], cnt[3] = {0, 0, 0};
     for (int i = 0; i < n; ++i) {
-        const int kind = (C[i] % BT) ? 0 : (syrk_in_place(T[i], C[i]) ? 2 : 1);
+        const int kind = syrk_kind(T[i], C[i], o);
         idx[kind][cnt[kind]++] = i;
     }
     unsigned char* wp = reinterpret_cast<unsigned char*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
     unsigned char* ws_end = reinterpret_cast<unsigned char*>(ws) + ws_bytes;
     for (int kind = 2; kind >= 0; --kind)
         if (cnt[kind]) {
-            const int rc = syrk16_launch(kind, idx[kind], cnt[kind], H, X, T, C, beta, alpha, x_dtype, wp, ws_end, st,
+            const int rc = syrk16_launch(kind, idx[kind], cnt[kind], H, X, T, C, beta, alpha, x_dtype, wp, ws_end, st, o,
                                          kind == 2 ? segs : nullptr, nseg);
             if (rc) return rc;
         }

@@ -451,6 +451,29 @@ def test_h_accumulate_k_split_of_the_last_round(ops, Cs):
         assert not torch.equal(outs[0][0], outs[2][0])  # the split schedule really ran (different rounding)
 
 
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
+def test_h_accumulate_grouped_mixed_kinds_equal_single_calls(ops, dt):
+    """One grouped call that is sorted into all three launches -- (256, 512) in place, (200, 512) on the image, (200, 384)
+    on the 128-tile kernel, and (256, 5888), in place with 276 tiles: the smallest width whose launch is persistent --
+    equals four single calls BIT FOR BIT: no T reaches the K-split, and a tile's sum does not depend on where the table
+    puts it.  The default workspace is exactly what gq_workspace_bytes reports, so the three launches carve it at the bound."""
+    torch.manual_seed(41)
+    shapes = ((256, 512), (200, 512), (200, 384), (256, 5888))
+    Xs = [(torch.randn(T, C, device="cuda") * torch.exp(torch.randn(C, device="cuda") * 0.5)).to(dt) for T, C in shapes]
+    H0s = [torch.randn(C, C, device="cuda") for _, C in shapes]
+    H0s = [h + h.T for h in H0s]
+    alphas = [2.0 / 3, 0.125, 1.5, 0.75]
+    grouped = [h.clone() for h in H0s]
+    ops.h_accumulate_grouped(grouped, Xs, [0.5] * 4, alphas)
+    for g, H0, X, alpha in zip(grouped, H0s, Xs, alphas):
+        single = H0.clone()
+        ops.h_accumulate(single, X, 0.5, alpha)
+        assert torch.equal(g, single), tuple(X.shape)
+        assert torch.equal(g, g.T)
+        ref = 0.5 * H0.double() + alpha * (X.double().T @ X.double())
+        assert (g.double() - ref).abs().max().item() <= 3e-6 * ref.abs().max().item(), tuple(X.shape)
+
+
 @pytest.mark.parametrize("C", [128, 1280, 4096])
 def test_h_pack_unpack_upper(ops, C):
     """The all-reduce payload: pack(H) holds every 128x128 tile on or above the diagonal exactly once; unpack
