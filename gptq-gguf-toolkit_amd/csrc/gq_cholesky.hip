@@ -599,7 +599,7 @@ struct P3Run {  // per gq_h_prepare call
     size_t next = 0;
     unsigned char* img[2] = {nullptr, nullptr};
     float* partial = nullptr;
-    unsigned* rmax = nullptr;     // NP == 2: [2][n/2] row maxima (bits) ...
+    unsigned* rmax = nullptr;     // NP == 2: [2][n/2] row maxima (bits) of the transposed operands (the others: image_rows_kernel) ...
     float* inv_scale = nullptr;   // ... and [2][n/2] epilogue scales
 };
 static size_t p3_image_bytes(int64_t C) { return (size_t)(C / 2) * (size_t)(C / 2) * 2 * (size_t)p3_planes(); }

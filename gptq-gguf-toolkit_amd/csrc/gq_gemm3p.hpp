@@ -55,6 +55,7 @@ __host__ __device__ __forceinline__ unsigned swz(int r) { return (0x78u >> (2 * 
 // tri: 1 = Op is zero where (k >> 7) > (r >> 7) (those source blocks are never read: they may hold garbage),
 //      2 = zero where (k >> 7) < (r >> 7).
 // NP == 2: rmax[r] = bits of max_k |Op[r][k]| (row_absmax_kernel); inv_scale[r] = 2^-e is written for the epilogue.
+// Operands that are not transposed, K <= IMAGE_ROWS_MAX_K, take image_rows_kernel instead: one pass, rmax unused.
 __device__ __forceinline__ void split3(const float (&x)[8], uint4& p1, uint4& p2, uint4& p3) {
     unsigned a[8], b[8], c[8];
 #pragma unroll
@@ -194,6 +195,80 @@ __global__ __launch_bounds__(256) void row_absmax_kernel(const float* __restrict
     }
     __syncthreads();
     if (tid < 128 && part[tid]) atomicMax(&rmax[128 * pn + tid], part[tid]);
+}
+
+// NP == 2, not transposed: row maxima and both planes in ONE pass over the source.  A workgroup owns four whole rows
+// (r0 = 4 * blockIdx.x, all in one 128-row panel and one swz class): wave w reads row r0 + w once into LDS with 16-byte
+// loads (skipped `tri` blocks are never read and stand as zeros, as for row_absmax_kernel / split_kernel) and reduces its
+// maximum -- exact and order-free, so scale, images and inv_scale are bit-equal to the two-pass form; then all four
+// waves split from LDS to the image addresses of split_kernel.  No rmax array, no memset, no atomics.
+// Read-back: thread = (q = p & 3, chunk c, row), 8 floats at row * Kp + 32 c + 8 (q ^ swz).  A ds_read_b128 is served in
+// 16-lane groups {lane >> 2 of even parity in its low three bits | odd parity} x {lane >> 5}: inside a group the low TWO
+// bits of lane >> 2 take every value.  Bit 0 is the parity of the chunk (+128 B) and bit 1 picks which 16-byte half
+// of the 32 bytes is read first (+16 B); with q (+32 B) the 16 lanes of a group land on 16 distinct 16-byte slots of the
+// 256-byte bank row: conflict-free without padding (rows are Kp * 4 = 0 mod 256 bytes apart and share their slots, but
+// the row index sits in the bits that are fixed or parity-bound inside a group).
+constexpr int IMAGE_ROWS_MAX_K = 8192;  // 4 rows x K fp32 <= 128 KiB of LDS
+// LDS row stride in floats: whole wave steps of 64 float4 (K = 7168: no padding)
+__host__ __device__ __forceinline__ int image_rows_stride(int K) { return (K + 255) & ~255; }
+inline size_t image_rows_lds(int K) { return (size_t)image_rows_stride(K) * 16 + 16; }
+__global__ __launch_bounds__(256) void image_rows_kernel(const float* __restrict__ S, int64_t ld, int K, int tri, int rev,
+                                                         unsigned char* __restrict__ img, float* __restrict__ inv_scale) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rows_smem[];
+    const int Kp = image_rows_stride(K);
+    float* rows = reinterpret_cast<float*>(rows_smem);            // [4][Kp]
+    unsigned* smax = reinterpret_cast<unsigned*>(rows + 4 * Kp);  // [4]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r0 = 4 * (int)blockIdx.x, pn = r0 >> 7, rp = r0 & 127;  // rp: first row inside the panel
+    const int KC = K >> 5;
+    // valid k range of this panel's rows in float4 units (whole 128-blocks), and the wave steps of 64 that touch it
+    const int j_lo = tri == 2 ? 32 * pn : 0, j_hi = tri == 1 ? (32 * (pn + 1) < K / 4 ? 32 * (pn + 1) : K / 4) : K / 4;
+    const int t_end = Kp >> 8, t_lo = j_lo < j_hi ? j_lo >> 6 : t_end, t_hi = j_lo < j_hi ? (j_hi + 63) >> 6 : t_end;
+    {
+        const float* src = S + (int64_t)(r0 + w) * ld;
+        float4* dst = reinterpret_cast<float4*>(rows + (size_t)w * Kp);
+        const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int t = 0; t < t_lo; ++t) dst[lane + 64 * t] = zero4;
+        for (int t = t_hi; t < t_end; ++t) dst[lane + 64 * t] = zero4;
+        float m = 0.f;
+        // batches of eight unconditional loads, all in flight before the first use: a lane (or a whole step of a ragged
+        // last batch) outside the range re-reads the nearest valid float4 and drops it
+        for (int tb = t_lo; tb < t_hi; tb += 8) {
+            float4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int j = lane + 64 * (tb + u), jc = j < j_lo ? j_lo : (j >= j_hi ? j_hi - 1 : j);
+                v[u] = *reinterpret_cast<const float4*>(src + 4 * jc);
+                if (j != jc) v[u] = zero4;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                m = fmaxf(m, fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
+                if (tb + u < t_hi) dst[lane + 64 * (tb + u)] = v[u];
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        if (lane == 0) smax[w] = __builtin_bit_cast(unsigned, m);
+    }
+    __syncthreads();
+    const int q = lane & 3, hi = lane >> 2, row = hi >> 2, half = (hi >> 1) & 1;
+    const int r = rp + row, kc = q ^ (int)swz(r);
+    float inv;
+    const float mult = scale_from_max(smax[row], inv);
+    if (w == 0 && (hi & 3) == 0 && q == 0) inv_scale[r0 + row] = inv;
+    const float* lrow = rows + (size_t)row * Kp + 8 * kc;
+    for (int c = 4 * w + (hi & 3); c < KC; c += 16) {
+        const float4 va = *reinterpret_cast<const float4*>(lrow + 32 * c + 4 * half);
+        const float4 vb = *reinterpret_cast<const float4*>(lrow + 32 * c + 4 * (half ^ 1));
+        const float4 v0 = half ? vb : va, v1 = half ? va : vb;
+        const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+        uint4 p1, p2;
+        split2h(x, mult, p1, p2);
+        unsigned char* out = img + ((size_t)pn * KC + (rev ? KC - 1 - c : c)) * (size_t)(2 * BLK) + (r * 4 + q) * 16;
+        *reinterpret_cast<uint4*>(out) = p1;
+        *reinterpret_cast<uint4*>(out + BLK) = p2;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ the GEMM
@@ -695,6 +770,18 @@ inline int launch_split(bool trans, const float* S, int64_t ld, int64_t R, int64
     const dim3 grid((unsigned)(K / 32), (unsigned)(R / 128)), block(256);
     ProfScope ps(PT_CHOL_SPLIT, st);
     if constexpr (NP == 2) {
+        if (!trans && K <= IMAGE_ROWS_MAX_K) {  // whole rows fit in LDS: one pass, rmax is not used
+            static std::atomic<bool> attr_set{false};
+            if (!attr_set) {
+                GQ_HIP(hipFuncSetAttribute((const void*)image_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)image_rows_lds(IMAGE_ROWS_MAX_K)));
+                attr_set = true;
+            }
+            hipLaunchKernelGGL(image_rows_kernel, dim3((unsigned)(R / 4)), block, image_rows_lds((int)K), st, S, ld, (int)K, tri, rev,
+                               img, inv_scale);
+            GQ_LAUNCH_CHECK();
+            return GQ_OK;
+        }
         GQ_HIP(hipMemsetAsync(rmax, 0, (size_t)R * 4, st));
         const dim3 g2((unsigned)(K / 128), (unsigned)(R / 128));
         if (trans) hipLaunchKernelGGL(row_absmax_kernel<true>, g2, block, 0, st, S, ld, tri, rmax);

@@ -751,8 +751,11 @@ static int far_event(int i, hipEvent_t* out) {
 // The far update of super-block s (everything beyond it) is one MFMA-bound GEMM; the walk of super-block s+1 is a string
 // of small latency-bound launches that needs the far update on ITS OWN G = la * 128 columns only.  So the far update is
 // cut by column groups (g = index of a group of G columns; F_s[g] = super-block s's update of group g):
-//   caller's stream:  walk(s) | F_s[s+1] | walk(s+1) | F_{s+1}[s+2] | ...
-//   helper stream:             F_s[s+2] , F_s[s+3..] | F_{s+1}[s+3] , F_{s+1}[s+4..] | ...
+//   caller's stream:  walk(s) | F_s[s+1] | walk(s+1)            | F_{s+1}[s+2] | walk(s+2) ...
+//   helper stream:                       | F_s[s+2] , F_s[s+3..] |              | F_{s+1}[s+3] , F_{s+1}[s+4..] ...
+// The helper's launches of super-block s are released BEHIND F_s[s+1] (the event `ready`), not next to it: the walk
+// waits for F_s[s+1], so that launch gets every CU; the helper stream is in order, so while it is still busy with
+// F_{s-1}[..] the later release costs it nothing, and once it is idle it has the whole walk(s+1) to catch up.
 // F_s[s+1] waits for F_{s-1}[s+1] (an event after that small launch); the helper launches are PERSISTENT with a
 // bounded number of workgroups, so the walk's kernels always find free CUs instead of queueing behind 56-us GEMM
 // tiles.  Every element of W still sees ((w - E_0 U_0) - E_1 U_1) - ... in the same order: results are unchanged.
@@ -787,10 +790,6 @@ struct FarPipeline {
         const float* Us = c.U + S0 * C;
         hipEvent_t ready = nullptr, ev = nullptr;
         int rc;
-        if (g1 < C) {  // the helper may start on this super-block's errors
-            if ((rc = far_event(ev_i++, &ready))) return rc;
-            GQ_HIP(hipEventRecord(ready, c.st));
-        }
         if (ev_small_prev) GQ_HIP(hipStreamWaitEvent(c.st, ev_small_prev, 0));  // F_{s-1}[s+1] is in
         ev_small_prev = nullptr;
         {
@@ -798,6 +797,10 @@ struct FarPipeline {
             if ((rc = launch_gemm32_chain_full<LA_B>(c.W + S1, C, b.Err, ldE, Us + S1, C, c.R, g1 - S1, K, c.st))) return rc;
         }
         if (g1 >= C) return GQ_OK;
+        // the helper's two launches of this super-block queue behind F_s[s+1]: the walk waits for that one, so it
+        // gets the whole chip instead of the CUs the helper's persistent workgroups leave over
+        if ((rc = far_event(ev_i++, &ready))) return rc;
+        GQ_HIP(hipEventRecord(ready, c.st));
         GQ_HIP(hipStreamWaitEvent(helper, ready, 0));
         ProfScope ps(PT_TRAILING_FAR, helper);
         if ((rc = launch_gemm32_chain_full<LA_B>(c.W + g1, C, b.Err, ldE, Us + g1, C, c.R, g2 - g1, K, helper, w.p.far_wgs)))
