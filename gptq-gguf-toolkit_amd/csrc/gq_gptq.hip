@@ -28,7 +28,9 @@ namespace gq {
 constexpr int SEG = 128;
 constexpr int SB = 16;  // register sub-block
 constexpr int SEG_WAVES = 8;  // wave 0 walks the dependent chain, all waves share the rank-1 tile updates
-constexpr int SEG_LDS_BYTES = (SEG * 64 + SEG * SEG + 2 * SB * 64) * 4 + SEG * 8;
+constexpr int SEG_NT = SEG / SB;
+// working copy, U's diagonal block, two error tiles, the reciprocal diagonal and the group parameters of every tile
+constexpr int SEG_LDS_BYTES = (SEG * 64 + SEG * SEG + 2 * SB * 64) * 4 + SEG * 8 + SEG_NT * 64 * 16;
 
 // Correctly rounded fp32 division through an fp64 reciprocal: fl32(fl64(n * fl64(1 / d))) == fl32(n / d) for all
 // finite fp32 n, d != 0.  The exact quotient of two 24-bit significands is either representable or at least 2^-49
@@ -85,10 +87,11 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void gptq_segment_kernel(
                                             // with wave-uniform (broadcast) 16-byte LDS loads
     float* ne = Us + SEG * SEG;             // ne[(t & 1)*SB*64 + k*64 + lane]: -err of tile t, double-buffered (8 KiB)
     double* rdiag = reinterpret_cast<double*>(ne + 2 * SB * 64);  // rdiag[i] = 1 / U[a+i, a+i] in fp64 (1 KiB)
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int64_t row = (int64_t)blockIdx.x * 64 + lane;
-    const bool live = row < R;
-    const int64_t r = live ? row : 0;
+    // the group parameters of tile t for the row of `lane` (8 KiB): in registers they stayed live across all eight
+    // tiles and, with U's rows hoisted over an unrolled tile loop, pushed wave 0's chain into scratch
+    double* rdg = rdiag + SEG;                                    // rdg[t*64 + lane] = 1 / max(ds, 1e-9) in fp64
+    float* dsg = reinterpret_cast<float*>(rdg + SEG_NT * 64);     // dsg[t*64 + lane] = f32(d) * s
+    float* dmg = dsg + SEG_NT * 64;                               // dmg[t*64 + lane] = f32(dmin) * m
     int64_t band_row0 = 0;  // BANDS: s / m are indexed by the row inside the band
     if constexpr (BANDS) {
         static_assert(!PERM && !UNI, "bands are K-quants in natural column order");
@@ -104,6 +107,16 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void gptq_segment_kernel(
         s += bt.sm_off[k];
         m += bt.sm_off[k];
     }
+    // The row's parameter arrays as per-lane pointers, formed once: the seven scalar arguments behind them need not stay
+    // in SGPRs over both halves (VGPRs are plentiful here, SGPRs are not).
+    const int64_t nsg = C / 256, ng = C / G;
+    const int64_t prow = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63), pr = prow < R ? prow : 0;
+    const uint16_t* const drow = UNI ? nullptr : d + pr * nsg;
+    const uint16_t* const dminrow = UNI ? nullptr : dmin + pr * nsg;
+    const uint8_t* const srow = UNI ? nullptr : s + (pr - band_row0) * ng;  // BANDS: the row inside the band
+    const uint8_t* const mrow = UNI ? nullptr : m + (pr - band_row0) * ng;
+    const float* const uscrow = UNI ? uscale + pr * ng : nullptr;
+    const float* const uzrow = UNI ? uzero + pr * ng : nullptr;
     for (int half = 0; half < npair; ++half) {
     if (half) {  // the partner block: same rows, next 128 columns; the epilogue's stores of this workgroup are complete
         __syncthreads();
@@ -112,6 +125,16 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void gptq_segment_kernel(
         err_col0 += SEG;
         Unext = nullptr;
     }
+    // The thread's index is opaque per half: every predicate on it (row < R, tid < first, the epilogue's sixteen row
+    // tests, ...) is invariant over this loop, and hoisted out of it the exec masks alone overflow the SGPR file.
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    int lenq = len;  // the prologue's copy of len, opaque likewise (still wave-uniform): loop bounds and clamped offsets
+    asm volatile("" : "+s"(lenq));
+    const int lane = tid & 63, wid = tid >> 6;
+    const int64_t row = (int64_t)blockIdx.x * 64 + lane;
+    const bool live = row < R;
+    const int64_t r = live ? row : 0;
     // Two-step prologue: everything the FIRST tile's chain needs (U rows 0..15, the tile's 16 columns of W, its
     // reciprocal diagonal) is brought in by all waves, then the chain starts while waves 1..7 -- idle in
     // iteration 0 -- bring in the other 7/8 (gptq.py:225 w_blk = w[:, c1:c2].clone()).
@@ -119,7 +142,7 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void gptq_segment_kernel(
         for (int idx = t0; idx < (i_hi - i_lo) * (SEG / 4); idx += nthr) {
             const int i = i_lo + idx / (SEG / 4), j4 = (idx % (SEG / 4)) * 4;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (j4 < len) v = *reinterpret_cast<const float4*>(U + (a + i) * C + a + j4);
+            if (j4 < lenq) v = *reinterpret_cast<const float4*>(U + (a + i) * C + a + j4);
             *reinterpret_cast<float4*>(Us + i * SEG + j4) = v;
         }
     };
@@ -133,48 +156,60 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void gptq_segment_kernel(
             wl[(j + 3) * 64 + lane] = v.w;
         }
     };
-    const int first = len < SB ? len : SB;
+    const int first = lenq < SB ? lenq : SB;
     if (tid < first) rdiag[tid] = 1.0 / (double)U[(a + tid) * C + a + tid];
     load_u_rows(0, first, tid, SEG_WAVES * 64);
     load_w_cols(0, first, wid, SEG_WAVES);
-    const int64_t nsg = C / 256, ng = C / G;
     // group parameters of every tile of the segment, fetched before the chain starts (they do not depend on it): a
-    // tile lies inside one group (16 | G), ds = f32(d) * s, dm = f32(dmin) * m, and 1 / max(ds, 1e-9) in fp64
-    constexpr int NT = SEG / SB;
-    float dst[PERM ? 1 : NT], dmt[PERM ? 1 : NT];
-    double rdt[PERM ? 1 : NT];
+    // tile lies inside one group (16 | G), ds = f32(d) * s, dm = f32(dmin) * m, and 1 / max(ds, 1e-9) in fp64.  A lane
+    // of wave 0 writes them and is the only one to read them back.
+    // The segment lies inside one 256-column super-group (walk_block cuts it there), so d and dmin are read once; the
+    // group of tile t is a / G + (a % G + 16 t) / G: one 64-bit division per segment, the eight others in 32 bits.
+    // All loads are issued before the first value is used.
+    constexpr int NT = SEG_NT;
     if constexpr (!PERM) {
         if (wid == 0) {
+            const int64_t ga = a / G;
+            const int ra = (int)(a - ga * G);
+            float st[NT], mt[NT], dsup = 0.f, dminsup = 0.f;
+            if constexpr (!UNI) {
+                dsup = h2f(drow[a / 256]);
+                dminsup = h2f(dminrow[a / 256]);
+            }
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-                const int64_t col0 = a + t * SB < a + len ? a + t * SB : a;
+                const int64_t gi = ga + (ra + (t * SB < lenq ? t * SB : 0)) / G;
                 if constexpr (UNI) {
-                    dst[t] = uscale[r * ng + col0 / G];
-                    dmt[t] = uzero[r * ng + col0 / G];
-                } else if constexpr (BANDS) {
-                    const int64_t rb = r - band_row0;
-                    dst[t] = h2f(d[r * nsg + col0 / 256]) * ival(s[rb * ng + col0 / G], is_signed);
-                    dmt[t] = h2f(dmin[r * nsg + col0 / 256]) * ival(m[rb * ng + col0 / G], is_signed);
+                    st[t] = uscrow[gi];
+                    mt[t] = uzrow[gi];
                 } else {
-                    dst[t] = h2f(d[r * nsg + col0 / 256]) * ival(s[r * ng + col0 / G], is_signed);
-                    dmt[t] = h2f(dmin[r * nsg + col0 / 256]) * ival(m[r * ng + col0 / G], is_signed);
+                    st[t] = ival(srow[gi], is_signed);
+                    mt[t] = ival(mrow[gi], is_signed);
                 }
-                rdt[t] = 1.0 / (double)(dst[t] < 1e-9f ? 1e-9f : dst[t]);  // quant_utils.py:37 clamp_min(eps)
+            }
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const float dst = UNI ? st[t] : dsup * st[t], dmt = UNI ? mt[t] : dminsup * mt[t];
+                dsg[t * 64 + lane] = dst;
+                dmg[t * 64 + lane] = dmt;
+                rdg[t * 64 + lane] = 1.0 / (double)(dst < 1e-9f ? 1e-9f : dst);  // quant_utils.py:37 clamp_min(eps)
             }
         }
     }
     __syncthreads();
     if (wid != 0) {  // under the first chain
         const int ht = tid - 64;
-        if (ht >= first && ht < len) rdiag[ht] = 1.0 / (double)U[(a + ht) * C + a + ht];
-        load_u_rows(first, len, ht, (SEG_WAVES - 1) * 64);
-        load_w_cols(first, len, wid - 1, SEG_WAVES - 1);
+        if (ht >= first && ht < lenq) rdiag[ht] = 1.0 / (double)U[(a + ht) * C + a + ht];
+        load_u_rows(first, lenq, ht, (SEG_WAVES - 1) * 64);
+        load_w_cols(first, lenq, wid - 1, SEG_WAVES - 1);
     }
 
+    // The tile loop stays rolled: unrolled, the compiler hoisted the wave-uniform reads of U's rows across tiles into
+    // SGPRs and spilled both register files.  ntile is wave-uniform (a kernel argument), so all eight waves reach
+    // every barrier of the loop and leave it together.
     const int ntile = len / SB;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        if (t >= ntile) break;
+#pragma unroll 1
+    for (int t = 0; t < ntile; ++t) {
         const int i0 = t * SB;
         float* net = ne + (t & 1) * (SB * 64);
         if (wid == 0) {
@@ -182,17 +217,20 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void gptq_segment_kernel(
             float ds = 0.f, dm = 0.f, dsv[PERM ? SB : 1], dmv[PERM ? SB : 1];
             double rden = 0.0, rdenv[PERM ? SB : 1];
             if constexpr (PERM) {
+                // lane k & 15 looks up column k: one vector division by G for the tile, handed round by lane shuffles
+                // (sixteen wave-uniform lookups are 32 scalar quotients alive at once -- they spilled the SGPR file)
+                const int pcl = perm[col0 + (lane & (SB - 1))], sgl = pcl / 256, gl = pcl / G;
 #pragma unroll
                 for (int k = 0; k < SB; ++k) {
-                    const int64_t pc = perm[col0 + k];
-                    dsv[k] = h2f(d[r * nsg + pc / 256]) * ival(s[r * ng + pc / G], is_signed);
-                    dmv[k] = h2f(dmin[r * nsg + pc / 256]) * ival(m[r * ng + pc / G], is_signed);
+                    const int sg = __shfl(sgl, k), g = __shfl(gl, k);
+                    dsv[k] = h2f(drow[sg]) * ival(srow[g], is_signed);
+                    dmv[k] = h2f(dminrow[sg]) * ival(mrow[g], is_signed);
                     rdenv[k] = 1.0 / (double)(dsv[k] < 1e-9f ? 1e-9f : dsv[k]);
                 }
             } else {
-                ds = dst[t];
-                dm = dmt[t];
-                rden = rdt[t];
+                ds = dsg[t * 64 + lane];
+                dm = dmg[t * 64 + lane];
+                rden = rdg[t * 64 + lane];
             }
             float wr[SB], nerr[SB], wq[SB];
             uint32_t qpack[4] = {0, 0, 0, 0};
@@ -310,17 +348,23 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void gptq_segment_kernel(
         // all 16 loads in flight before the first store (written as `*p += acc` the compiler must keep every load behind
         // the previous store: 16 dependent HBM round trips, 12 us per block)
         const int64_t r0 = (int64_t)blockIdx.x * 64 + rb + 4 * lk;
-        float* wp = W + r0 * C + a + SEG + cb + li;
+        int64_t Cq = C;  // opaque like tid above: the row offsets ro * C are formed here, not kept in SGPRs all along
+        asm volatile("" : "+s"(Cq));
+        float* wp = W + r0 * Cq + a + SEG + cb + li;
         float wv[16];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int ro = (e & 3) + 8 * (e >> 2);
-            wv[e] = (r0 + ro < R) ? wp[(int64_t)ro * C] : 0.0f;
+            wv[e] = (r0 + ro < R) ? wp[(int64_t)ro * Cq] : 0.0f;
         }
+        // s_waitcnt vmcnt(0), on every path: the loads above sit under row predicates, and on the path that skips the
+        // matching store nothing waits for them -- the compiler then pays that wait at the top of the partner block's
+        // chains, where it also covers the previous tile's global stores.  The first store needs the loads anyway.
+        __builtin_amdgcn_s_waitcnt(0x0f70);
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int ro = (e & 3) + 8 * (e >> 2);
-            if (r0 + ro < R) wp[(int64_t)ro * C] = wv[e] + acc[e];
+            if (r0 + ro < R) wp[(int64_t)ro * Cq] = wv[e] + acc[e];
         }
     }
     }  // half
