@@ -39,6 +39,8 @@ Q8_0 = 8  # GQ_Q8_0: the ggml type id
 IQ4_NL, IQ4_XS = 20, 23  # GQ_IQ4_NL, GQ_IQ4_XS: the ggml type ids
 # include/gptq_gguf_iq4_encode.h: the IQ4_NL / IQ4_XS encoder, with an optional importance value per column (additive in the same way)
 EXPORTS_IQ4_ENCODE = ("gq_quantize_iq4",)
+# include/gptq_gguf_iq4_gptq.h: GPTQ's column walk on the IQ4_XS / IQ4_NL grid and the packer of its outputs (additive in the same way)
+EXPORTS_IQ4_GPTQ = ("gq_gptq_quantize_iq4", "gq_pack_iq4")
 # include/gptq_gguf_qgemm.h: the packed-weight forward, a GEMM that reads block bytes as its weight operand (additive in the same way)
 EXPORTS_QGEMM = ("gq_linear_packed",)
 # include/gptq_gguf_qgemv.h: the same forward for the 1 .. 16 tokens of a decode step (additive in the same way)
@@ -163,6 +165,8 @@ def lib():
     L.gq_pack_bands.argtypes = [vp, vp, vp, vp, vp, i64, i64, ctypes.POINTER(Band), ci, ctypes.POINTER(vp), ctypes.POINTER(vp), vp]
     L.gq_quantize_q8_0.argtypes = [vp, ci, i64, i64, vp, vp, vp]
     L.gq_quantize_iq4.argtypes = [vp, ci, i64, i64, ci, vp, vp, vp, vp]
+    L.gq_gptq_quantize_iq4.argtypes = [vp, vp, i64, i64, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.gq_pack_iq4.argtypes = [ci, i64, i64, vp, vp, vp, vp, vp, vp]
     L.gq_linear_packed.argtypes = [ci, vp, vp, i64, i64, vp, i64, ci, vp, vp]
     L.gq_gemv_packed.argtypes = [ci, vp, vp, i64, i64, vp, i64, ci, vp, vp]
     L.gq_sample_logits.argtypes = [vp, ci, i64, i64, i64, ci, cf, cf, vp, vp, vp]
@@ -176,7 +180,7 @@ def lib():
     L.gq_prof_collect.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
-    for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_QGEMM +
+    for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_IQ4_GPTQ + EXPORTS_QGEMM +
                  EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L

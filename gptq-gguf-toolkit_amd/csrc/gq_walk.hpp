@@ -24,11 +24,18 @@ enum class WalkKind {
                // from W as it is when the block holding the group's first column starts (fast_obq.py:168-171)
     Bands,     // row bands of different K-quant types: only the lazy scale search is per band, and the segment kernel
                // reads the band table
+    Iq4,       // the non-linear grids IQ4_XS / IQ4_NL (include/gptq_gguf_iq4_gptq.h): the scales of a 256-column group are found
+               // lazily like a K-quant's, by the encoder's scale search; the segment kernel gets step / istep per 32-column block
 };
 
 struct UniformSpec {
     int bits, group, sym;  // group == 0: one grid per row, from the original W (fast_obq.py:153-154)
     float *scale, *zero;   // [R, C / group]
+};
+struct Iq4Spec {
+    const float* importance;  // nullptr or [C]
+    uint8_t* ls;              // IQ4_XS: [R, C / 32] (d of the call record is [R, C / 256]); IQ4_NL: unused (d is [R, C / 32])
+    float *step, *istep;      // [R, C / 32]
 };
 struct BandPlan;  // the checked band table of gq_gptq_quantize_bands (gq_gptq.hip, next to the kernel that reads it)
 
@@ -57,6 +64,8 @@ struct WalkCall {
     UniformSpec uni = {};
     // Bands
     const BandPlan* bands = nullptr;
+    // Iq4 (reads q_type, writes d)
+    Iq4Spec iq4 = {};
 };
 
 // The options the walk reads, taken ONCE per call (walk_options): a gq_option_set from another thread in the middle of
@@ -102,5 +111,13 @@ int gptq_quantize_bands(float* W, const float* U, int64_t R, int64_t C, const gq
                         uint8_t* m, void* ws, size_t ws_bytes, hipStream_t st);
 int obq_quantize(float* W, const float* U, int64_t R, int64_t C, int bits, int group_size, int sym, int block_size,
                  uint8_t* qweight, float* scale, float* zero, void* ws, size_t ws_bytes, hipStream_t st);
+
+// include/gptq_gguf_iq4_gptq.h
+int gptq_quantize_iq4(float* W, const float* U, int64_t R, int64_t C, int q_type, int block_size, const float* importance,
+                      uint8_t* qweight, uint16_t* d, uint8_t* ls, float* step, float* istep, void* ws, size_t ws_bytes,
+                      hipStream_t st);
+// iq4/gq_iq4_gptq.hip: the scale search of gptq_gguf_iq4_encode.h on W[:, a : a + 256] as it is now -> d, ls, step, istep
+int launch_iq4_scale_step(const float* W, int64_t R, int64_t C, int64_t a, bool xs, const float* importance, uint16_t* d,
+                          uint8_t* ls, float* step, float* istep, hipStream_t st);
 
 }  // namespace gq

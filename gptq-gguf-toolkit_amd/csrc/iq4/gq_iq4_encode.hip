@@ -24,6 +24,7 @@
 // Numerical contract (exact class; -ffp-contract=off, no fast-math, hipcc's correctly rounded fp32 division and sqrtf).
 #include "../gq_common.hpp"
 #include "../../../include/gptq_gguf_iq4_encode.h"
+#include "gq_iq4_search.hpp"
 
 namespace gq {
 namespace {
@@ -36,23 +37,7 @@ template <> struct Src<GQ_F32> { static constexpr int ES = 4; };
 template <> struct Src<GQ_F16> { static constexpr int ES = 2; };
 template <> struct Src<GQ_BF16> { static constexpr int ES = 2; };
 
-// kv and a sentinel above every finite product: best() reads kvs[u + 1] with u up to 15
-__device__ const float KV17[17] = {-127.f, -104.f, -83.f, -65.f, -49.f, -35.f, -22.f, -10.f, 1.f,
-                                   13.f,   25.f,   38.f,  53.f,  69.f,  89.f,  113.f, 3.0e38f};
-
-// best(a) of the header -> (index, kv[index]).  u counts the entries <= a by binary search, so kv[u] <= a < kv[u + 1] inside the
-// table; below it u = 0 and (a - kv[0]) < 0 picks 0, above it u = 15 and the sentinel picks 15.  The two rounded differences are
-// compared, a tie goes up.
-__device__ __forceinline__ void best(const float* __restrict__ kvs, float a, int& idx, float& q) {
-    int u = a >= 1.0f ? 8 : 0;  // kv[8]
-    u += a >= kvs[u + 4] ? 4 : 0;
-    u += a >= kvs[u + 2] ? 2 : 0;
-    u += a >= kvs[u + 1] ? 1 : 0;
-    const float lo = kvs[u], hi = kvs[u + 1];
-    const bool down = (a - lo) < (hi - a);
-    idx = down ? u : u + 1;
-    q = down ? lo : hi;
-}
+using namespace iq4;  // KV17, best and the candidate sums: gq_iq4_search.hpp, shared with the column walk on this grid
 
 // 32 values of one block from its staged bytes at p (16-byte aligned), widened exactly to fp32
 template <int SD>
@@ -138,7 +123,7 @@ __global__ __launch_bounds__(256) void iq4_encode_kernel(const uint8_t* __restri
 #pragma unroll
                     for (int j = 0; j < 32; ++j) s += xv[j] * xv[j];
                 }
-                sigma2 = s * (2.0f / (XS ? 256.0f : 32.0f));
+                sigma2 = sigma2_of(s, XS ? 256.0f : 32.0f);
                 const uint32_t jl = j0 + (uint32_t)tid, j = jl % nbr;
                 const float4* ip = reinterpret_cast<const float4*>(importance + (size_t)j * 32);
 #pragma unroll
@@ -148,47 +133,27 @@ __global__ __launch_bounds__(256) void iq4_encode_kernel(const uint8_t* __restri
                 }
 #pragma unroll
                 for (int j2 = 0; j2 < 32; ++j2) weighted = weighted || w[j2] != 0.0f;
-            }
-            if (weighted) {
+            } else {
 #pragma unroll
-                for (int j = 0; j < 32; ++j) w[j] = w[j] * sqrtf(sigma2 + xv[j] * xv[j]);
-            } else {  // no importance, or all of it zero over this block
-#pragma unroll
-                for (int j = 0; j < 32; ++j) w[j] = xv[j] * xv[j];
+                for (int j = 0; j < 32; ++j) w[j] = 0.0f;
             }
-            float amax = 0.0f, mx = 0.0f;
 #pragma unroll
-            for (int j = 0; j < 32; ++j) {
-                const float ax = fabsf(xv[j]);
-                if (ax > amax) amax = ax, mx = xv[j];
-            }
+            for (int j = 0; j < 32; ++j) w[j] = weight_of(xv[j], w[j], sigma2, weighted);  // (not weighted: none, or all zero here)
+            float amax, mx;
+            block_max(xv, amax, mx);
             float d = 0.0f;
             if (!(amax < 1e-15f)) {
                 float bst = 0.0f;
-                const float d0 = -mx / -127.0f;
 #pragma unroll 1
-                for (int itry = -8; itry <= 7; ++itry) {  // -8: the first candidate 1 / d0, always taken
-                    const float id = itry == -8 ? 1.0f / d0 : ((float)itry + -127.0f) / mx;
-                    float sumqx = 0.0f, sumq2 = 0.0f;
-#pragma unroll
-                    for (int j = 0; j < 32; ++j) {
-                        int idx;
-                        float q;
-                        best(kvs, id * xv[j], idx, q);
-                        const float wq = w[j] * q;
-                        sumqx += wq * xv[j];
-                        sumq2 += wq * q;
-                    }
-                    if (itry == -8 || (sumq2 > 0.0f && sumqx * sumqx > bst * sumq2)) {
-                        d = sumqx / sumq2;
-                        bst = d * sumqx;
-                    }
+                for (int itry = -8; itry <= 7; ++itry) {
+                    float sumqx, sumq2;
+                    cand_sums(kvs, xv, w, cand_id(itry, mx), sumqx, sumq2);
+                    cand_take(itry, sumqx, sumq2, d, bst);
                 }
             }
             uint32_t qs[4];
             if constexpr (!XS) {
-                const float id = d != 0.0f ? 1.0f / d : 0.0f;
-                codes(kvs, xv, id, qs);
+                codes(kvs, xv, nl_inverse(d), qs);
                 uint16_t* ob = reinterpret_cast<uint16_t*>(img + tid * 18);
                 ob[0] = f2h(d);
 #pragma unroll
@@ -199,11 +164,9 @@ __global__ __launch_bounds__(256) void iq4_encode_kernel(const uint8_t* __restri
                     const float v = __shfl(d, ib, 8);
                     if (fabsf(v) > dmax) dmax = fabsf(v), ms = v;
                 }
-                const float D = -ms / 32.0f;
-                const float iD = D != 0.0f ? 1.0f / D : 0.0f;
-                const float lf = fminf(fmaxf(rintf(iD * d), -32.0f), 31.0f);
-                const float dl = D * lf;
-                const float idl = dl != 0.0f ? 1.0f / dl : 0.0f;
+                const float D = xs_super_scale(ms);
+                float lf, dl, idl;
+                xs_block_scale(D, d, lf, dl, idl);
                 codes(kvs, xv, idl, qs);
                 const uint32_t ls = (uint32_t)((int)lf + 32);
                 uint32_t scales_h = 0, scales_l = 0;

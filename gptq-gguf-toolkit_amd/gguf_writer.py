@@ -161,6 +161,22 @@ def quantize_iq4(data: np.ndarray, q_type: int, importance: Optional[np.ndarray]
     in ascending j (a Python loop over j keeps the order).  This is the host form for a box without a GPU and what
     ops.quantize_iq4 (gq_quantize_iq4) equals byte for byte.  `importance`: None or C values >= 0, one per column (llama.cpp's
     importance matrix; the diagonal of the calibration Hessian).  -> uint8 [..., C / block * bytes]."""
+    data = np.asarray(data)
+    head, inv = iq4_scales(data, q_type, importance)
+    size, ts = GGML_QUANT_SIZES[int(q_type)]
+    x = np.ascontiguousarray(data, dtype=np.float32).reshape(-1, 32)
+    with np.errstate(all="ignore"):
+        L = _iq4_best(x * inv[:, None]).astype(np.uint8)
+    qs = (L[:, :16] | (L[:, 16:] << 4)).reshape(len(head), size // 2)
+    out = np.concatenate([head, qs], axis=1)
+    return out.reshape(*data.shape[:-1], data.shape[-1] // size * ts)
+
+
+def iq4_scales(data: np.ndarray, q_type: int, importance: Optional[np.ndarray] = None):
+    """The scale search of quantize_iq4 alone -> (head, inv): head uint8 [super-blocks, 2 or 8], the bytes in front of a
+    super-block's codes (fp16 d for IQ4_NL; fp16 D, scales_h, scales_l for IQ4_XS), and inv fp32 [32-value blocks], the inverse
+    scale the codes of a block are taken under (id / idl of the header, 0 where it says 0).  The column walk on this grid
+    (include/gptq_gguf_iq4_gptq.h) keeps both per block."""
     q_type = int(q_type)
     if q_type not in (GGMLType.IQ4_NL, GGMLType.IQ4_XS):
         raise ValueError(f"quantize_iq4: q_type {q_type} is neither IQ4_NL ({GGMLType.IQ4_NL}) nor IQ4_XS ({GGMLType.IQ4_XS})")
@@ -215,10 +231,7 @@ def quantize_iq4(data: np.ndarray, q_type: int, importance: Optional[np.ndarray]
             scales_h = sum((ls[:, ib] >> 4) << (2 * ib) for ib in range(8)).astype("<u2").reshape(-1, 1).view(np.uint8)
             scales_l = ((ls[:, 0::2] & 15) | ((ls[:, 1::2] & 15) << 4)).astype(np.uint8)
             head = np.concatenate([D.astype(np.float16).reshape(-1, 1).view(np.uint8), scales_h, scales_l], axis=1)
-        L = _iq4_best(x * inv[:, None]).astype(np.uint8)
-    qs = (L[:, :16] | (L[:, 16:] << 4)).reshape(nsb, per * 16)
-    out = np.concatenate([head, qs], axis=1)
-    return out.reshape(*data.shape[:-1], C // size * ts)
+    return head, inv
 
 
 class GGUFWriter:

@@ -630,6 +630,70 @@ def quantize_iq4(x: torch.Tensor, q_type: int, importance: Optional[torch.Tensor
     return out
 
 
+def _iq4_type(what: str, q_type: int) -> bool:
+    if int(q_type) not in (_cabi.IQ4_NL, _cabi.IQ4_XS):
+        raise _cabi.GQError(f"{what}: q_type {int(q_type)} is neither IQ4_NL ({_cabi.IQ4_NL}) nor IQ4_XS ({_cabi.IQ4_XS})")
+    return int(q_type) == _cabi.IQ4_XS
+
+
+def gptq_quantize_iq4(W: torch.Tensor, U: torch.Tensor, q_type: int, block_size=128, importance: Optional[torch.Tensor] = None,
+                      ws: Optional[torch.Tensor] = None):
+    """GPTQ's column walk on the IQ4_XS / IQ4_NL grid (gq_gptq_quantize_iq4, include/gptq_gguf_iq4_gptq.h): the scales of a
+    256-column group come from the encoder's scale search on the error-compensated weights when the walk reaches the group,
+    every rounding error goes into later columns through U.  W (fp32 [R, C], C % 256 == 0, contiguous) becomes exactly what
+    dequantize_blocks makes of pack_iq4 of the outputs.  importance: None or fp32 [C] as for quantize_iq4.
+    Returns (qweight u8 [R, C] codes 0..15, d f16 [R, C/256] (IQ4_XS) / [R, C/32] (IQ4_NL), ls u8 [R, C/32] (IQ4_XS) / None,
+    step f32 [R, C/32])."""
+    _need_cuda(W, U, importance)
+    xs = _iq4_type("gptq_quantize_iq4", q_type)
+    assert W.dtype == torch.float32 and U.dtype == torch.float32 and W.is_contiguous() and U.is_contiguous() and W.dim() == 2
+    R, C = W.shape
+    if importance is not None:
+        if importance.dtype != torch.float32 or importance.dim() != 1 or importance.numel() != C or importance.device != W.device:
+            raise _cabi.GQError(f"gptq_quantize_iq4: importance must be an fp32 [{C}] tensor on {W.device}; got {importance.dtype} "
+                                f"{tuple(importance.shape)} on {importance.device}")
+        importance = importance.contiguous()
+        if importance.data_ptr() % 16:  # (a view into a larger buffer)
+            importance = importance.clone()
+    nb = max(C // 32, 1)
+    q = torch.empty(R, C, dtype=torch.uint8, device=W.device)
+    d = torch.empty(R, max(C // 256, 1) if xs else nb, dtype=torch.float16, device=W.device)
+    ls = torch.empty(R, nb, dtype=torch.uint8, device=W.device) if xs else None
+    step = torch.empty(R, nb, dtype=torch.float32, device=W.device)
+    istep = torch.empty(R, nb, dtype=torch.float32, device=W.device)
+    bs = int(block_size or 0)
+    ws = _walk_ws(ws, R, C, bs, W.device)
+    check(lib().gq_gptq_quantize_iq4(_ptr(W), _ptr(U), R, C, int(q_type), bs, _ptr(importance), _ptr(q), _ptr(d), _ptr(ls),
+                                     _ptr(step), _ptr(istep), _ptr(ws), ws.numel(), _stream(W)), "gq_gptq_quantize_iq4")
+    return q, d, ls, step
+
+
+def pack_iq4(q_type: int, qweight: torch.Tensor, d: torch.Tensor, ls: Optional[torch.Tensor],
+             row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The outputs of gptq_quantize_iq4 as block bytes (gq_pack_iq4): uint8 [R, C/256*136] (IQ4_XS) or [R, C/32*18] (IQ4_NL).
+    row_src (int32 [R] on the device): out[r] = the blocks of row row_src[r]; every index must lie in [0, R)."""
+    _need_cuda(qweight, d, ls, row_src)
+    xs = _iq4_type("pack_iq4", q_type)
+    bs, ts = GGML_QUANT_SIZES[int(q_type)]
+    if qweight.dtype != torch.uint8 or qweight.dim() != 2 or qweight.shape[1] % bs or qweight.shape[1] < bs:
+        raise _cabi.GQError(f"pack_iq4: qweight must be uint8 [R, C] with C % {bs} == 0; got {qweight.dtype} {tuple(qweight.shape)}")
+    R, C = qweight.shape
+    if d.dtype != torch.float16 or tuple(d.shape) != (R, C // bs):
+        raise _cabi.GQError(f"pack_iq4: d must be fp16 [{R}, {C // bs}]; got {d.dtype} {tuple(d.shape)}")
+    if xs and (ls is None or ls.dtype != torch.uint8 or tuple(ls.shape) != (R, C // 32)):
+        raise _cabi.GQError(f"pack_iq4: ls must be uint8 [{R}, {C // 32}] for IQ4_XS")
+    if row_src is not None:
+        if row_src.dtype != torch.int32 or row_src.numel() != R or row_src.device != qweight.device:
+            raise _cabi.GQError(f"pack_iq4: row_src must be an int32 [{R}] tensor on {qweight.device}")
+        row_src = row_src.contiguous()
+    qweight, d = qweight.contiguous(), d.contiguous()
+    ls = ls.contiguous() if xs else None
+    out = torch.empty(R, C // bs * ts, dtype=torch.uint8, device=qweight.device)
+    check(lib().gq_pack_iq4(int(q_type), R, C, _ptr(qweight), _ptr(d), _ptr(ls), _ptr(row_src), _ptr(out), _stream(qweight)),
+          "gq_pack_iq4")
+    return out
+
+
 def trailing_update(Cm: torch.Tensor, A: torch.Tensor, B: torch.Tensor):
     """Cm -= A @ B (fp32; k-ordered fma chain then one subtraction per element)."""
     _need_cuda(Cm, A, B)

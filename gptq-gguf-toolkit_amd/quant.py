@@ -108,8 +108,14 @@ def parse_args(argv=None):
     p.add_argument("--level_db_iq4", nargs="+", default=[], choices=["IQ4_XS", "IQ4_NL"], metavar="TYPE",
                    help="with --level_db: every tensor that has K-quant levels also gets the level 4.25-IQ4_XS.pth and / or "
                         "4.56-IQ4_NL.pth, encoded on the GPU from the UNMODIFIED weights (include/gptq_gguf_iq4_encode.h), weighted "
-                        "by the diagonal of the calibration Hessian -- llama.cpp's importance matrix.  No GPTQ error feedback. "
-                        "A tensor whose rows are no multiple of 256 gets no IQ4_XS level")
+                        "by the diagonal of the calibration Hessian -- llama.cpp's importance matrix.  No GPTQ error feedback "
+                        "unless --level_db_iq4_method gptq.  A tensor whose rows are no multiple of 256 gets no IQ4_XS level")
+    p.add_argument("--level_db_iq4_method", choices=["rtn", "gptq"], default="rtn",
+                   help="with --level_db_iq4: rtn (default) encodes the unmodified weights by round-to-nearest; gptq builds the IQ4 "
+                        "levels of every Linear with GPTQ's column walk on the IQ4 grid (include/gptq_gguf_iq4_gptq.h): scales "
+                        "found lazily from the error-compensated weights, every rounding error pushed into later columns "
+                        "through the Linear's own factorisation, the same importance.  embed / lm_head have no Hessian and stay "
+                        "rtn.  One extra walk per Linear and type")
     p.add_argument("--level_db_iq4_importance", choices=["hessian", "none"], default="hessian",
                    help="with --level_db_iq4: the importance of a column is the diagonal of the Linear's calibration Hessian "
                         "(default), or none: every level is encoded unweighted")
@@ -129,6 +135,8 @@ def levels_problem(args, world_size=None):
         return "--level_db_q8_0 needs --level_db: the Q8_0 level is a level of the database"
     if getattr(args, "level_db_iq4", None) and level_db is None:
         return "--level_db_iq4 needs --level_db: the IQ4 levels are levels of the database"
+    if getattr(args, "level_db_iq4_method", "rtn") != "rtn" and not getattr(args, "level_db_iq4", None):
+        return "--level_db_iq4_method needs --level_db_iq4: there is no IQ4 level to build"
     if args.levels is None:
         if level_db is not None:
             return "--level_db needs --levels: the level database is written by the one-pass level build"
@@ -251,7 +259,8 @@ def _run(args):
                                   None if args.propagate_level == "none" else GGMLQuantizationType[args.propagate_level],
                                   level_db=args.level_db, trees=not args.level_db_only, level_db_model=args.model_name_or_path,
                                   level_db_q8_0=args.level_db_q8_0, level_db_iq4=tuple(args.level_db_iq4),
-                                  level_db_iq4_importance=args.level_db_iq4_importance)
+                                  level_db_iq4_importance=args.level_db_iq4_importance,
+                                  level_db_iq4_method=args.level_db_iq4_method)
     else:
         quantizer.quantize(quant_config)
     torch.cuda.synchronize()

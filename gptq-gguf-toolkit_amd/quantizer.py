@@ -577,8 +577,12 @@ def check_levels(levels, propagate):
 IQ4_LEVEL_TYPES = {"IQ4_XS": 23, "IQ4_NL": 20}  # the ggml type ids (include/gptq_gguf_iq4.h)
 
 
-def check_iq4_levels(iq4, importance: str = "hessian") -> Tuple[int, ...]:
-    """-> the ggml type ids of `iq4` (names out of IQ4_XS / IQ4_NL, or their ids), in its order; ValueError for anything else."""
+IQ4_LEVEL_METHODS = ("rtn", "gptq")
+
+
+def check_iq4_levels(iq4, importance: str = "hessian", method: str = "rtn") -> Tuple[int, ...]:
+    """-> the ggml type ids of `iq4` (names out of IQ4_XS / IQ4_NL, or their ids), in its order; ValueError for anything else,
+    for an unknown importance or method, and for the method "gptq" without a type."""
     ids = []
     for t in iq4 or ():
         t = IQ4_LEVEL_TYPES.get(str(t).upper(), t)
@@ -587,6 +591,10 @@ def check_iq4_levels(iq4, importance: str = "hessian") -> Tuple[int, ...]:
         ids.append(int(t))
     if importance not in ("hessian", "none"):
         raise ValueError(f"level_db_iq4_importance: {importance!r} (hessian or none)")
+    if method not in IQ4_LEVEL_METHODS:
+        raise ValueError(f"level_db_iq4_method: {method!r} (rtn or gptq)")
+    if method != "rtn" and not ids:
+        raise ValueError(f"level_db_iq4_method: {method!r} needs level_db_iq4 (there is no IQ4 level to build)")
     return tuple(ids)
 
 
@@ -605,10 +613,16 @@ class _LevelDbSink:
     way) ahead of its walk (`before_levels`, BlockSchedule.quantize_levels' `before`), registered BEFORE its K-quant levels so
     that the tensor's gguf_layer_database.json record stays its last K-quant level.  `iq4_importance` "hessian": a column's
     importance is the diagonal of the Linear's accumulated calibration Hessian, what llama.cpp calls the importance matrix;
-    "none", and the tensors that have no Hessian (embed / lm_head): unweighted.  No GPTQ error feedback either way.  A tensor
-    whose rows are no multiple of 256 gets no IQ4_XS level."""
+    "none", and the tensors that have no Hessian (embed / lm_head): unweighted.  A tensor whose rows are no multiple of 256
+    gets no IQ4_XS level.
+    `iq4_method` "rtn" (the default): as above, no GPTQ error feedback.  "gptq": the IQ4 levels of a Linear come out of GPTQ's
+    column walk on the IQ4 grid (gq_gptq_quantize_iq4, include/gptq_gguf_iq4_gptq.h) with the Linear's own
+    factorisation: `before_levels` only keeps diag(H), `after_levels` (BlockSchedule.quantize_levels' `extra`, which runs ahead
+    of `pack`, so the files are still registered before the K-quant levels) walks a fresh working copy once per type and packs
+    it with gq_pack_iq4.  embed / lm_head have no Hessian and stay round-to-nearest, unweighted, under either method."""
 
-    def __init__(self, db: str, dir_model: str, vocab: bool = True, q8_0: bool = False, iq4=(), iq4_importance: str = "hessian"):
+    def __init__(self, db: str, dir_model: str, vocab: bool = True, q8_0: bool = False, iq4=(), iq4_importance: str = "hessian",
+                 iq4_method: str = "rtn"):
         import json
         from pathlib import Path
         from . import level_db
@@ -617,8 +631,9 @@ class _LevelDbSink:
             raise ValueError(f"level_db needs the model as a local directory with config.json and *.safetensors (got "
                              f"{dir_model!r}): the key/value data and the plain tensors are read from it")
         self.dir_model, self.vocab, self.q8_0 = Path(dir_model), vocab, bool(q8_0)
-        self.iq4 = check_iq4_levels(iq4, iq4_importance)
-        self.iq4_importance = iq4_importance
+        self.iq4 = check_iq4_levels(iq4, iq4_importance, iq4_method)
+        self.iq4_importance, self.iq4_method = iq4_importance, iq4_method
+        self._iq4_imp: Dict[str, Optional[torch.Tensor]] = {}  # "gptq": diag(H) of a Linear between its two hooks
         self.hp = json.load(open(self.dir_model / "config.json"))
         arch = self.hp.get("architectures", ["LlamaForCausalLM"])[0]
         if arch not in ("LlamaForCausalLM", "LLaMAForCausalLM", "MistralForCausalLM") or self.hp.get("num_local_experts"):
@@ -701,7 +716,32 @@ class _LevelDbSink:
         imp = None
         if self.iq4_importance == "hessian":
             imp = handle.H.diagonal().contiguous()  # (a copy: _prepare damps H in place later on this stream)
+        if self.iq4_method == "gptq":  # the levels are built behind the walk, from the factorisation: after_levels
+            self._iq4_imp[name] = imp
+            return [imp] if imp is not None else []
         return self.encode_iq4(name, handle.layer.weight, imp) + ([imp] if imp is not None else [])
+
+    def after_levels(self, name: str, handle, results) -> List[torch.Tensor]:
+        """BlockSchedule.quantize_levels' `extra` under iq4_method "gptq": handle._last_U / _last_cf are the Linear's
+        factorisation and column flags, handle.layer.weight still the block's unmodified weight.  Per type a fresh working
+        copy with the dead columns of the first one (as GPTQ.compute_levels makes its later levels'), one walk, one pack."""
+        imp = self._iq4_imp.pop(name, None)
+        tensor = self.tensor_of.get(name)
+        if tensor is None or not self.iq4:
+            return []
+        rows = self._row_src(tensor, handle.d_row, handle.W_device)
+        outs = []
+        for t in self.iq4:
+            if handle.d_col % 256:
+                continue  # (the walk's rule; such a tensor has no K-quant level either)
+            handle.make_working_copy()
+            _ops.w_prepare(handle._last_cf, handle.W)
+            q, d, ls, _ = _ops.gptq_quantize_iq4(handle.W, handle._last_U, t, handle.block_size, imp)
+            blocks = _ops.pack_iq4(t, q, d, ls, rows)
+            path = self.writer.register(tensor, (handle.d_row, handle.d_col), t)
+            self.items.append((path, RAW_BYTES, (blocks.view(-1),)))
+            outs += [blocks, handle.W]
+        return outs
 
     def take(self) -> List[tuple]:
         items, self.items = self.items, []
@@ -786,7 +826,7 @@ class Quantizer:
     @torch.no_grad()
     def quantize_levels(self, levels, propagate, level_db: Optional[str] = None, trees: bool = True,
                         level_db_model: Optional[str] = None, level_db_vocab: bool = True, level_db_q8_0: bool = False,
-                        level_db_iq4=(), level_db_iq4_importance: str = "hessian") -> None:
+                        level_db_iq4=(), level_db_iq4_importance: str = "hessian", level_db_iq4_method: str = "rtn") -> None:
         """The level database in one pass: every quantizable module at every level of `levels`, one ordinary tree per level
         under <save_dir>/<LEVEL>/ (level_tree_name; same schema, same writer as quantize()).  The calibration forwards, the
         Hessians, the factorisations and the column walk are those of ONE run (BlockSchedule.quantize_levels).
@@ -803,8 +843,10 @@ class Quantizer:
         level_db): every tensor that has K-quant levels also gets the 8.5-bit level 8.5-Q8_0.pth, round-to-nearest of its
         unmodified weights.  `level_db_iq4` (with level_db; names out of "IQ4_XS", "IQ4_NL"): it also gets the levels
         4.25-IQ4_XS.pth / 4.56-IQ4_NL.pth, encoded from its unmodified weights with the diagonal of its calibration Hessian as
-        the importance of a column (`level_db_iq4_importance` "hessian"; "none": unweighted) -- _LevelDbSink.  Everything is
-        refused before any work; a failed run leaves no database."""
+        the importance of a column (`level_db_iq4_importance` "hessian"; "none": unweighted) -- _LevelDbSink.
+        `level_db_iq4_method` "rtn" (default): round-to-nearest; "gptq": the IQ4 levels of every Linear come out of GPTQ's
+        column walk on the IQ4 grid with the same importance (gq_gptq_quantize_iq4; embed / lm_head stay round-to-nearest).
+        Everything is refused before any work; a failed run leaves no database."""
         levels, propagate = check_levels(levels, propagate)
         if dist_utils.get_world_size() > 1:
             raise NotImplementedError("quantize_levels runs on one rank (multi-rank level builds are not built)")
@@ -816,13 +858,14 @@ class Quantizer:
             raise ValueError("quantize_levels: level_db_q8_0 needs level_db (the Q8_0 level is a level of the database)")
         if level_db is None and level_db_iq4:
             raise ValueError("quantize_levels: level_db_iq4 needs level_db (the IQ4 levels are levels of the database)")
-        check_iq4_levels(level_db_iq4, level_db_iq4_importance)
+        check_iq4_levels(level_db_iq4, level_db_iq4_importance, level_db_iq4_method)
         sink = None
         if level_db is not None:
             if os.environ.get("GQ_SAVE_SKIP") == "1":
                 raise ValueError("quantize_levels: GQ_SAVE_SKIP=1 writes no files, a level database cannot be completed")
             sink = _LevelDbSink(level_db, level_db_model or getattr(self.model.config, "_name_or_path", None), level_db_vocab,
-                                q8_0=level_db_q8_0, iq4=level_db_iq4, iq4_importance=level_db_iq4_importance)
+                                q8_0=level_db_q8_0, iq4=level_db_iq4, iq4_importance=level_db_iq4_importance,
+                                iq4_method=level_db_iq4_method)
         self._levels, self._level_src, self._level_sink, self._level_trees = (levels, propagate), {}, sink, bool(trees)
         try:
             self.quantize({})
@@ -1041,7 +1084,8 @@ class Quantizer:
             levels, propagate = self._levels
             sink = getattr(self, "_level_sink", None)
             before = sink.before_levels if sink is not None and sink.iq4 else None
-            for n, per_level in sched.quantize_levels(levels, propagate, pack=sink.pack_walk if sink else None,
+            after = sink.after_levels if before is not None and sink.iq4_method == "gptq" else None
+            for n, per_level in sched.quantize_levels(levels, propagate, extra=after, pack=sink.pack_walk if sink else None,
                                                       before=before).items():
                 for t in levels if getattr(self, "_level_trees", True) else ():
                     item = self._save(level_tree_name(t, n), t, *per_level[t], defer=True)
