@@ -56,6 +56,9 @@ MOE_MAX_PAIRS = 64  # GQ_MOE_MAX_PAIRS: (token, expert) pairs of one gq_gemv_pac
 EXPORTS_MOE_GEMM = ("gq_moe_route", "gq_linear_packed_experts")
 MOE_ROUTE_MAX_EXPERTS = 256  # GQ_MOE_ROUTE_MAX_EXPERTS: experts gq_moe_route sorts by
 MOE_ROUTE_MAX_PAIRS = 131072  # GQ_MOE_ROUTE_MAX_PAIRS: (token, expert) pairs of one gq_moe_route / gq_linear_packed_experts call
+# include/gptq_gguf_moe_calib.h: the combine of the calibration forward of fused (dense) experts, transformers' roundings (additive in the same way)
+EXPORTS_MOE_CALIB = ("gq_fwd_moe_combine",)
+MOE_COMBINE_MAX_K = 8  # GQ_MOE_COMBINE_MAX_K: experts per token of one gq_fwd_moe_combine call
 
 
 class GQError(RuntimeError):
@@ -173,6 +176,7 @@ def lib():
     L.gq_gemv_packed_experts.argtypes = [ci, vp, i64, i64, i64, vp, i64, vp, i64, i64, ci, vp, vp]
     L.gq_moe_route.argtypes = [vp, i64, i64, vp, vp, vp]
     L.gq_linear_packed_experts.argtypes = [ci, vp, i64, i64, i64, vp, i64, i64, vp, vp, i64, ci, vp, vp]
+    L.gq_fwd_moe_combine.argtypes = [vp, vp, vp, vp, vp, ci, i64, i64, i64, i64, ci, vp, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -181,7 +185,7 @@ def lib():
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_IQ4_GPTQ + EXPORTS_QGEMM +
-                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM):
+                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

@@ -1152,6 +1152,45 @@ def linear_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: 
     return y
 
 
+# ---- the calibration forward of fused (dense) experts: the combine with transformers' roundings (gq_fwd_moe_combine) ----
+MOE_COMBINE_MAX_K = _cabi.MOE_COMBINE_MAX_K
+
+
+def fwd_moe_combine(y: torch.Tensor, pair_expert: torch.Tensor, route, w: torch.Tensor, E: int) -> torch.Tensor:
+    """out [T, H] = what transformers' MixtralExperts.forward leaves in final_hidden_states, in ONE launch: y [P, H] fp16 / bf16
+    contiguous holds the down-projection outputs in expert-sorted order (row s belongs to pair route[1][s]), pair_expert int32
+    [P] is the router's [T, K] index TRANSPOSED and flattened (pair p = k T + t) and route = moe_route(pair_expert, E); w [T, K]
+    contiguous, fp32 or y's dtype, 1 <= K <= MOE_COMBINE_MAX_K, H % 8 == 0.  Per token and element: the products
+    round(float(y) float(w)) are added in ascending expert id (ties by k) to an accumulator that starts at +0 and is rounded to
+    y's dtype after every add; a pair with an id outside [0, E) contributes nothing (include/gptq_gguf_moe_calib.h).  Nothing
+    is read by the host: no synchronisation."""
+    who = "fwd_moe_combine"
+    expert_start, order = route
+    E = int(E)
+    if y.dtype not in (torch.float16, torch.bfloat16) or y.dim() != 2 or not y.is_contiguous():
+        raise _cabi.GQError(f"{who}: y must be a contiguous fp16 or bf16 [P, H] tensor; got {y.dtype} {tuple(y.shape)}")
+    if w.dim() != 2 or not w.is_contiguous() or w.dtype not in (torch.float32, y.dtype):
+        raise _cabi.GQError(f"{who}: w must be a contiguous [T, K] tensor, fp32 or {y.dtype}; got {w.dtype} {tuple(w.shape)}")
+    T, K = w.shape
+    P, H = y.shape
+    if K < 1 or K > MOE_COMBINE_MAX_K:
+        raise _cabi.GQError(f"{who}: K={K} experts per token (not in [1, MOE_COMBINE_MAX_K={MOE_COMBINE_MAX_K}])")
+    if T < 1 or T * K != P or P > MOE_ROUTE_MAX_PAIRS:
+        raise _cabi.GQError(f"{who}: T={T} * K={K} != P={P} rows of y (or not in [1, MOE_ROUTE_MAX_PAIRS={MOE_ROUTE_MAX_PAIRS}])")
+    if H < 8 or H % 8:
+        raise _cabi.GQError(f"{who}: H={H} (H % 8 == 0)")
+    if E < 1 or E > MOE_ROUTE_MAX_EXPERTS:
+        raise _cabi.GQError(f"{who}: E={E} experts (not in [1, MOE_ROUTE_MAX_EXPERTS={MOE_ROUTE_MAX_EXPERTS}])")
+    for name, t, n in (("pair_expert", pair_expert, P), ("expert_start", expert_start, E + 1), ("order", order, P)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != n:
+            raise _cabi.GQError(f"{who}: {name} must be a contiguous int32 [{n}] tensor; got {t.dtype} {tuple(t.shape)}")
+    _need_cuda(y, pair_expert, expert_start, order, w)
+    out = torch.empty(T, H, dtype=y.dtype, device=y.device)
+    check(lib().gq_fwd_moe_combine(_ptr(y), _ptr(pair_expert), _ptr(expert_start), _ptr(order), _ptr(w), _DT[w.dtype], T, K, E, H,
+                                   _DT[y.dtype], _ptr(out), _stream(y)), "gq_fwd_moe_combine")
+    return out
+
+
 # ---- the vocabulary ends of a packed model: the embedding lookup from block bytes, the sampler on the logits ----
 def embed_packed(q_type: int, blocks: torch.Tensor, ids: torch.Tensor, out_dtype=torch.float16) -> torch.Tensor:
     """The rows `ids` of the embedding table that `blocks` holds packed (uint8 [V, C/block*type_size], a K-quant or Q8_0)

@@ -82,7 +82,9 @@ def parse_args(argv=None):
                    help="HIP kernels for the elementwise modules of the calibration forward (the reference runs the HF "
                         "eager modules): exact (default) = rotary embedding, SwiGLU and RMSNorm, bit-identical to HF eager "
                         "(RMSNorm checked at run time); all (or the bare flag) = also the free-order RMSNorm kernel, "
-                        "<= 2 ulp, where the exact one is not verified; off = none")
+                        "<= 2 ulp, where the exact one is not verified; off = none.  Fused experts (Mixtral) take the routed "
+                        "forward of moe_calibration.py at exact and all (bit-identical to HF's eager loop, checked at run time), "
+                        "the eager loop itself at off")
     p.add_argument("--eval_data", type=str, default=None,
                    help="a .pt file of [1, L] token-id tensors: what --eval_perplexity scores the quantized model on (the "
                         "reference downloads WikiText-2 there)")

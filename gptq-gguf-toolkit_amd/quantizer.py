@@ -14,6 +14,9 @@ schema (quantizer.py:268-275).  MI355X-first differences, none of which changes 
     file), by a writer thread behind a copy stream, so that the device-to-host copies and the file writes of
     block i overlap with the forwards of block i+1; `quantize()` returns after the last file of every rank is
     closed (final barrier).
+  * fused experts (transformers 5.x `MixtralExperts`: two 3-D parameters, nothing to hook) that the regex names as
+    `...experts.<e>.w{1,2,3}` are presented as nn.Linear views for the duration of their block (moe_calibration.py); their
+    trees are written under the checkpoint's names (`block_sparse_moe.experts.<e>.w{1,2,3}`).
 `Quantizer.timing` holds the split of the last `quantize()` call (host seconds per phase and, with
 GQ_TIMING=gpu, HIP-event seconds per phase on the main stream).
 """
@@ -29,7 +32,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import dist_utils
+from . import dist_utils, moe_calibration
 from . import ops as _ops
 from .block_schedule import BlockSchedule
 from .forward_fused import fused_forward, level_of, reset_verdicts
@@ -859,6 +862,10 @@ class Quantizer:
         if level_db is None and level_db_iq4:
             raise ValueError("quantize_levels: level_db_iq4 needs level_db (the IQ4 levels are levels of the database)")
         check_iq4_levels(level_db_iq4, level_db_iq4_importance, level_db_iq4_method)
+        fused = moe_calibration.named_fused_experts(self.model, self.block_modules + ".", self.quantizable_modules)
+        if fused:
+            raise NotImplementedError(f"quantize_levels: {fused[0][0]} ({type(fused[0][1]).__name__}) keeps fused experts that "
+                                      "quantizable_modules names; the level build for MoE is not built (quantize() takes them)")
         sink = None
         if level_db is not None:
             if os.environ.get("GQ_SAVE_SKIP") == "1":
@@ -886,12 +893,16 @@ class Quantizer:
         if os.environ.get("GQ_SAVE_SKIP") != "1":
             self._saver.warm_up(device)
         self._saved_names: List[str] = []
+        self._calib_experts: list = []          # moe_calibration.install()'s records of the block in work
+        self._tree_names: Dict[str, str] = {}   # synthesized expert Linear -> the checkpoint's name its tree is written under
         try:
             reset_verdicts()  # every run re-verifies the forward kernels on its own first inputs
+            moe_calibration.reset_verdicts()
             with fused_forward(self.fused_forward if torch.device(device).type == "cuda" else "off") as patched:
                 self._fused_modules = patched
                 self._quantize(quant_config, device)
         finally:
+            moe_calibration.restore(self._calib_experts)  # (a run that raised inside a block: the model gets its own modules back)
             BlockSchedule.discard_checks()  # nothing of this run may leak into the next Quantizer of the process
             t0 = time.perf_counter()
             self._saver.close()
@@ -965,6 +976,14 @@ class Quantizer:
                 dist_utils.print_on_main(f"Processing {self.block_modules} {block_id}/{len(blocks)}.")
             block = block.to(device)
             prefix = f"{self.block_modules}.{block_id}."
+            # fused experts (transformers 5.x MixtralExperts) that the regex names: a stand-in with one nn.Linear per expert
+            # matrix, views of the fused storage, for this block's two forwards and its column walks (moe_calibration.py)
+            routed = torch.device(device).type == "cuda" and self.fused_forward in moe_calibration.ROUTED_LEVELS
+            self._calib_experts += moe_calibration.install(self.model, prefix, self.quantizable_modules,
+                                                           "routed" if routed else "loop")
+            for _, _, original, name in self._calib_experts:
+                for n in moe_calibration.synthesized_names(name, original.down_proj.shape[0]):
+                    self._tree_names[n] = moe_calibration.checkpoint_name(n)
             layers = select_layers(self.model, prefix, self.quantizable_modules, LINEAR_LAYERS)
             handles, hooks = self._prepare_hooks_and_handles(layers, block)
             sched = self._schedule
@@ -992,6 +1011,7 @@ class Quantizer:
                     kw["hidden_states"] = out
                 else:
                     raise ValueError("Unsupported block input format.")
+            moe_calibration.restore(self._calib_experts)  # the block's own modules are back, holding the quantized weights
             if self.cpu_offload_modules:
                 block.cpu()
             del handles, hooks, sched
@@ -1096,8 +1116,9 @@ class Quantizer:
             self._saver.put_many(batch)
             self.schedule_stats = sched.stats
             return
+        tree = getattr(self, "_tree_names", {})
         for n, res in sched.quantize(qtypes, writeback=True).items():
-            item = self._save(n, qtypes[n], *res, defer=True)
+            item = self._save(tree.get(n, n), qtypes[n], *res, defer=True)
             if item is not None:
                 batch.append(item)
         self._saver.put_many(batch)  # the block's files travel in one staging slot

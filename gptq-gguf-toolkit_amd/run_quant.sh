@@ -1,6 +1,8 @@
 #!/usr/bin/env bash
 # run_quant.sh -- launcher with the reference's env-var surface (quant/gptq/run_quant.sh:1-40).
 # One process per GPU over RCCL/xGMI.  HIP_VISIBLE_DEVICES (or CUDA_VISIBLE_DEVICES) picks the GPUs.
+# Mixtral (fused experts): QUANTIZABLE_MODULES='.*layers.*((q|k|v|o)_proj|experts\.\d+\.w[123])$' names the expert matrices too
+# (moe_calibration.py); their types come from BIT_WIDTH_CONFIGURATION's keys w1 / w2 / w3, Q4_K without it.
 set -euo pipefail
 
 BITS=${1:-Q4_K}
@@ -17,7 +19,7 @@ python -m torch.distributed.run --nnodes=1 --nproc-per-node="$NUM_GPUS" --master
     --master-port "$MASTER_PORT" "$HERE/quant.py" \
     --model_name_or_path "${MODEL:-meta-llama/Llama-3.2-1B-Instruct}" \
     ${TOKENIZER_NAME:+--tokenizer_name "$TOKENIZER_NAME"} \
-    --quantizable_modules '.*layers.*((q|k|v|o|gate|up|down)_proj)$' \
+    --quantizable_modules "${QUANTIZABLE_MODULES:-.*layers.*((q|k|v|o|gate|up|down)_proj)\$}" \
     --pre_block_modules model.embed_tokens \
     --block_modules model.layers \
     --post_block_modules lm_head \
