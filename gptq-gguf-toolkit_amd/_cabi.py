@@ -59,6 +59,9 @@ MOE_ROUTE_MAX_PAIRS = 131072  # GQ_MOE_ROUTE_MAX_PAIRS: (token, expert) pairs of
 # include/gptq_gguf_moe_calib.h: the combine of the calibration forward of fused (dense) experts, transformers' roundings (additive in the same way)
 EXPORTS_MOE_CALIB = ("gq_fwd_moe_combine",)
 MOE_COMBINE_MAX_K = 8  # GQ_MOE_COMBINE_MAX_K: experts per token of one gq_fwd_moe_combine call
+# include/gptq_gguf_moe_search.h: the level switch of a stacked [E, R, C] expert tensor, one job per tensor (additive in the same way)
+EXPORTS_MOE_SEARCH = ("gq_level_switch_experts",)
+SWITCH_EXPERTS_MAX_JOBS = 71  # GQ_SWITCH_EXPERTS_MAX_JOBS: jobs of one launch (a longer list is cut by the library)
 
 
 class GQError(RuntimeError):
@@ -79,6 +82,13 @@ class SwitchJob(ctypes.Structure):
     """gq_switch_job_t"""
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("row_src", ctypes.c_void_p),
                 ("R", ctypes.c_int64), ("C", ctypes.c_int64), ("kind", ctypes.c_int32), ("out_dtype", ctypes.c_int32)]
+
+
+class SwitchExpertsJob(ctypes.Structure):
+    """gq_switch_experts_job_t"""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("E", ctypes.c_int64), ("R", ctypes.c_int64),
+                ("C", ctypes.c_int64), ("dst_expert_stride", ctypes.c_int64), ("kind", ctypes.c_int32),
+                ("out_dtype", ctypes.c_int32)]
 
 
 class Band(ctypes.Structure):
@@ -177,6 +187,7 @@ def lib():
     L.gq_moe_route.argtypes = [vp, i64, i64, vp, vp, vp]
     L.gq_linear_packed_experts.argtypes = [ci, vp, i64, i64, i64, vp, i64, i64, vp, vp, i64, ci, vp, vp]
     L.gq_fwd_moe_combine.argtypes = [vp, vp, vp, vp, vp, ci, i64, i64, i64, i64, ci, vp, vp]
+    L.gq_level_switch_experts.argtypes = [ctypes.POINTER(SwitchExpertsJob), ci, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -185,7 +196,7 @@ def lib():
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_IQ4_GPTQ + EXPORTS_QGEMM +
-                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB):
+                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

@@ -18,15 +18,16 @@
 //   IQ4_XS takes the packed arm (a 256-value type with 8-byte staging loads), IQ4_NL Q8_0's (include/gptq_gguf_iq4.h).
 // The kind / out_dtype dispatch is a switch on block-uniform values: a workgroup executes one arm.  HBM-bound like K15:
 // 0.33-0.82 B/param in, 2 or 4 B/param out; the unit is K15's turn so that the per-byte rate is K15's.
+// The three unit functions live in gq_switch_units.hpp, shared with gq_switch_experts.hip (K30: a job of E stacked matrices).
 #include "../../../include/gptq_gguf_iq4.h"  // (includes gptq_gguf_q8.h and gptq_gguf_search.h)
 #include "gq_block_host.hpp"
+#include "gq_switch_units.hpp"
 
 namespace gq {
 namespace {
 
 using namespace blockdec;
-
-constexpr int DENSE_CHUNKS = 512;  // 16-byte output chunks per dense unit (two per thread)
+using namespace switchunit;  // the units themselves: gq_switch_units.hpp, shared with gq_switch_experts.hip
 
 struct SwitchEntry {
     const uint8_t* src;
@@ -43,77 +44,6 @@ struct SwitchTable {
     SwitchEntry e[GQ_SWITCH_MAX_JOBS];
 };
 static_assert(sizeof(SwitchTable) <= 4096 - 64, "the job table must fit the kernel-argument segment");
-
-template <int QT>
-__device__ __forceinline__ void packed_unit(const SwitchEntry& J, int64_t b0, uint8_t* sb, int64_t* ssrc) {
-    const int nb = (int)((J.n - b0) < DB ? (J.n - b0) : DB);
-    switch (J.out_dtype) {
-    case GQ_F32: decode_turn<QT, float>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<float*>(J.dst), sb, ssrc); break;
-    case GQ_F16: decode_turn<QT, half_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<half_bits*>(J.dst), sb, ssrc); break;
-    default: decode_turn<QT, bf16_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<bf16_bits*>(J.dst), sb, ssrc); break;
-    }
-}
-
-template <int QT>
-__device__ __forceinline__ void b32_unit(const SwitchEntry& J, int64_t b0, uint8_t* sb, int64_t* ssrc) {
-    const int nb = (int)((J.n - b0) < B32_DB ? (J.n - b0) : B32_DB);
-    switch (J.out_dtype) {
-    case GQ_F32: decode_turn_b32<QT, float>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<float*>(J.dst), sb, ssrc); break;
-    case GQ_F16: decode_turn_b32<QT, half_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<half_bits*>(J.dst), sb, ssrc); break;
-    default: decode_turn_b32<QT, bf16_bits>(J.src, J.row_src, b0, nb, J.per_row, reinterpret_cast<bf16_bits*>(J.dst), sb, ssrc); break;
-    }
-}
-
-template <int DT> __device__ __forceinline__ float widen(uint32_t bits);
-template <> __device__ __forceinline__ float widen<GQ_F32>(uint32_t bits) { return __builtin_bit_cast(float, bits); }
-template <> __device__ __forceinline__ float widen<GQ_F16>(uint32_t bits) { return h2f((uint16_t)bits); }
-template <> __device__ __forceinline__ float widen<GQ_BF16>(uint32_t bits) { return bf2f((uint16_t)bits); }
-
-// chunk k of a dense job: CH = 16 / sizeof(dst element) consecutive elements of one row
-template <int SD, int OD>
-__device__ __forceinline__ void dense_unit(const SwitchEntry& J, int64_t k0) {
-    constexpr int SES = SD == GQ_F32 ? 4 : 2, DES = OD == GQ_F32 ? 4 : 2, CH = 16 / DES, NW = CH * SES / 4;
-#pragma unroll
-    for (int i = 0; i < DENSE_CHUNKS / 256; ++i) {
-        const int64_t k = k0 + i * 256 + threadIdx.x;
-        if (k < J.n) {
-            const int64_t r = k / J.per_row, cc = k - r * J.per_row;
-            const int64_t sr = J.row_src ? (int64_t)J.row_src[r] : r;
-            const uint8_t* sp = J.src + (sr * J.per_row + cc) * (CH * SES);
-            uint32_t w[NW];
-            if constexpr (NW == 2) {
-                const uint2 v = *reinterpret_cast<const uint2*>(sp);
-                w[0] = v.x, w[1] = v.y;
-            } else {
-#pragma unroll
-                for (int q = 0; q < NW / 4; ++q) {
-                    const uint4 v = reinterpret_cast<const uint4*>(sp)[q];
-                    w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
-                }
-            }
-            uint32_t o[4];
-#pragma unroll
-            for (int e = 0; e < CH; ++e) {
-                const float f = SES == 4 ? widen<SD>(w[e]) : widen<SD>((w[e >> 1] >> (16 * (e & 1))) & 0xffffu);
-                if constexpr (OD == GQ_F32) o[e] = __builtin_bit_cast(uint32_t, f);
-                else {
-                    const uint32_t h = OD == GQ_F16 ? f2h(f) : f2bf(f);
-                    o[e >> 1] = (e & 1) ? (o[e >> 1] | (h << 16)) : h;
-                }
-            }
-            *reinterpret_cast<uint4*>(J.dst + k * 16) = make_uint4(o[0], o[1], o[2], o[3]);
-        }
-    }
-}
-
-template <int SD>
-__device__ __forceinline__ void dense_unit_from(const SwitchEntry& J, int64_t k0) {
-    switch (J.out_dtype) {
-    case GQ_F32: dense_unit<SD, GQ_F32>(J, k0); break;
-    case GQ_F16: dense_unit<SD, GQ_F16>(J, k0); break;
-    default: dense_unit<SD, GQ_BF16>(J, k0); break;
-    }
-}
 
 __global__ __launch_bounds__(256) void level_switch_kernel(const SwitchTable t) {
     __shared__ __attribute__((aligned(16))) uint8_t sb[SB_BYTES];

@@ -28,8 +28,12 @@ What differs from the reference, on purpose:
   * --reuse_prefix on: the parent is run once per minibatch and a candidate from its first changed block on (suffix_forward);
     under `python -m torch.distributed.run --nproc-per-node N -m gptq_gguf_toolkit_amd.evo_quant_search ...` a selection's
     candidates are dealt to the N ranks and the fitnesses all-gathered.  Both keep the trajectory of a seed; [--backend],
-    [--reuse_prefix_bytes], [--trace_out FILE].
-nn.Linear only."""
+    [--reuse_prefix_bytes], [--trace_out FILE], [--report_out FILE].
+  * a model with fused experts (transformers' MixtralExperts: gate_up_proj [E, 2I, H], down_proj [E, H, I]) is searched too: the
+    three stacked tensors of an experts module are the units `<module>.gate_proj / .up_proj / .down_proj` (level_store), of
+    E * R * C elements each (layer_numel), named in the configuration the way config_converter reads them; [--moe_prefill]
+    is packed residency's PackedExperts.prefill.
+nn.Linear and expert units only."""
 import argparse
 import copy
 import math
@@ -46,7 +50,7 @@ if __package__ in (None, ""):  # run as a script: make the package importable un
     import gptq_gguf_toolkit_amd  # noqa: F401
     __package__ = "gptq_gguf_toolkit_amd"
 
-from .level_db import Levels, filename_of, has_layer, scan_available_bitwidths  # noqa: E402
+from .level_db import Levels, expert_unit, filename_of, scan_available_bitwidths  # noqa: E402
 
 State = List[List[float]]
 
@@ -58,6 +62,16 @@ def layer_order_fn(layer_name: str):
     return (int(split_key[2]), *split_key[3:])
 
 
+def layer_numel(model, layer_name: str) -> int:
+    """The elements of one searchable layer: a Linear's weight, or the E * R * C of the expert unit
+    `<experts module>.{gate,up,down}_proj` (gate and up are E * I * H each, half of gate_up_proj; down is down_proj)."""
+    unit = expert_unit(layer_name)
+    if unit is None:
+        return model.get_submodule(layer_name).weight.numel()
+    E, H, I = model.get_submodule(unit[0]).down_proj.shape
+    return E * H * I
+
+
 def group_layers(model, layer_names: Sequence[str], group_rule: str) -> Tuple[List[str], ...]:
     """evopress/src/model_utils.py:371-385: groups in order of first appearance."""
     assert group_rule in ("none", "name", "size")
@@ -66,7 +80,7 @@ def group_layers(model, layer_names: Sequence[str], group_rule: str) -> Tuple[Li
     elif group_rule == "name":
         key = lambda n: n.split(".")[-1]  # noqa: E731
     else:
-        key = lambda n: model.get_submodule(n).weight.numel()  # noqa: E731
+        key = lambda n: layer_numel(model, n)  # noqa: E731
     groups = defaultdict(list)
     for n in layer_names:
         groups[key(n)].append(n)
@@ -79,13 +93,13 @@ def calculate_total_bits(current_bitwidths: State, grouped_layer_names, model):
     total_bits = 0
     for g_id in range(len(grouped_layer_names)):
         for l_id, l_name in enumerate(grouped_layer_names[g_id]):
-            total_bits += model.get_submodule(l_name).weight.numel() * current_bitwidths[g_id][l_id]
+            total_bits += layer_numel(model, l_name) * current_bitwidths[g_id][l_id]
     return total_bits
 
 
 def target_bits_of(grouped_layer_names, model, target_bitwidth: float) -> int:
     """:394-399: the per-layer products are truncated before they are added."""
-    return sum(int(model.get_submodule(n).weight.numel() * target_bitwidth) for g in grouped_layer_names for n in g)
+    return sum(int(layer_numel(model, n) * target_bitwidth) for g in grouped_layer_names for n in g)
 
 
 def get_next_bitwidth(current_bitwidths: State, target_bits, grouped_layer_names, available_bitwidths: Levels, model,
@@ -100,10 +114,10 @@ def get_next_bitwidth(current_bitwidths: State, target_bits, grouped_layer_names
     candidates = [bw for bw, _ in available_bitwidths[layer_name] if bw > current_bw]
     if not candidates:
         return None
-    layer_numel = model.get_submodule(layer_name).weight.numel()
+    numel = layer_numel(model, layer_name)
     current_total_bits = calculate_total_bits(current_bitwidths, grouped_layer_names, model)
     for bw in candidates:
-        if current_total_bits + layer_numel * (bw - current_bw) <= target_bits:
+        if current_total_bits + numel * (bw - current_bw) <= target_bits:
             return bw
     return None
 
@@ -414,6 +428,9 @@ def parse_args(argv=None):
     p.add_argument("--resident", type=str, default="dense", choices=["dense", "packed"],
                    help="dense (default): the model keeps a dense live weight per Linear and a switch decodes into it; packed: "
                         "no dense copy, the forward reads the stored block bytes (fp16 / bf16 models, packed levels)")
+    p.add_argument("--moe_prefill", type=str, default="loop", choices=["loop", "grouped"],
+                   help="with --resident packed: how the packed experts of a MoE model take more than a decode step's tokens "
+                        "(PackedExperts.prefill)")
     p.add_argument("--reuse_prefix", type=str, default="off", choices=["off", "on"],
                    help="on: run the parent once per minibatch and evaluate every candidate from its first changed block "
                         "(suffix_forward); the trajectory is the one of `off`")
@@ -423,6 +440,9 @@ def parse_args(argv=None):
                    help="under torch.distributed.run: nccl (= RCCL; default with one GPU per rank) or gloo (default "
                         "otherwise: the ranks share the visible GPUs)")
     p.add_argument("--trace_out", type=str, default=None, help="write search()'s trace to this file as JSON (rank 0)")
+    p.add_argument("--report_out", type=str, default=None,
+                   help="write the report of the final configuration -- ppl_eval/<dataset>, ppl_train, train_fitness, in full "
+                        "precision -- to this file as JSON (rank 0)")
     args = p.parse_args(argv)
     # every refusal BEFORE any work
     for what, names in (("calibration_data", [args.calibration_data]), ("eval_datasets", args.eval_datasets)):
@@ -542,7 +562,7 @@ def _run(args, ranks, device):
     import torch
     from . import metrics
     from . import dist_utils
-    from .level_store import LevelStore
+    from .level_store import LevelStore, default_layer_names
     from .ppleval import load_hf_model
     main_rank = ranks is None or ranks.rank == 0
     say = dist_utils.print_on_main  # every line of the run's report is rank 0's
@@ -562,8 +582,7 @@ def _run(args, ranks, device):
     # the levels: HF-named directories as the reference scans them, else the model's Linears through layer_dir
     available = scan_available_bitwidths(args.quant_weights_path)
     if not available or not all(_is_module(model, n) for n in available):
-        names = [n for n, m in model.named_modules()
-                 if isinstance(m, torch.nn.Linear) and has_layer(args.quant_weights_path, n)]
+        names = default_layer_names(model, args.quant_weights_path)  # Linears, and the units of fused experts modules
         # a database cut from a whole model also holds output.weight: lm_head is no Linear of a block (layer_order_fn has
         # no place for it) and is not searched -- it keeps the model's own weights
         outside = [n for n in names if not _in_a_block(n)]
@@ -580,7 +599,8 @@ def _run(args, ranks, device):
     if args.resident == "packed":  # the targets need the unmodified dense model: first, before the store frees it
         target_logits, where = collect_targets(model, calibration_data, args.fitness_fn, args.kl_topk, args.targets_on)
     # refuses what does not fit before uploading
-    store = LevelStore(model, args.quant_weights_path, device, layer_names, resident=args.resident)
+    store = LevelStore(model, args.quant_weights_path, device, layer_names, resident=args.resident,
+                       moe_prefill=args.moe_prefill)
     store.grouped_layer_names = grouped
     say(f"level store: {store.bytes()} bytes on {device}" +
           (f", {store.freed_bytes} bytes of dense weights freed" if args.resident == "packed" else ""))
@@ -590,7 +610,7 @@ def _run(args, ranks, device):
         say(f"targets on: {where}")
 
     ctx = _Ctx(model, grouped, available, target_bits_of(grouped, model, args.target_bitwidth))
-    quantizable_weights = sum(model.get_submodule(n).weight.numel() for n in layer_names)
+    quantizable_weights = sum(layer_numel(model, n) for n in layer_names)
     log_dict = {}
 
     reuse = runner = None
@@ -656,6 +676,10 @@ def _run(args, ranks, device):
     evaluate_parent()
     if args.log_wandb and main_rank:
         wandb.log(log_dict)
+    if args.report_out and main_rank:
+        with open(args.report_out + ".tmp", "w") as f:
+            json.dump(log_dict, f)
+        os.replace(args.report_out + ".tmp", args.report_out)
     return parent, out
 
 

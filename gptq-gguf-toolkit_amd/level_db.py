@@ -111,14 +111,39 @@ def scan_available_bitwidths(quant_weights_path: str, layer_names: Optional[Sequ
 
 
 # ------------------------------------------------------------------------------------------------ directories
+EXPERT_UNIT_ROLES = ("gate_proj", "up_proj", "down_proj")  # the three searchable units of a fused experts module
+
+
+def expert_unit(layer_name: str) -> Optional[Tuple[str, str]]:
+    """("<experts module name>", "gate" | "up" | "down") of an expert unit `<experts module name>.{gate,up,down}_proj` -- the
+    names config_converter maps to `ffn_{gate,up,down}_exps.weight` --, None for any other name.  By name alone: the module
+    is `...mlp.experts` of a decoder block."""
+    mod, _, leaf = layer_name.rpartition(".")
+    if leaf in EXPERT_UNIT_ROLES and mod.endswith(".mlp.experts"):
+        return mod, leaf[:-len("_proj")]
+    return None
+
+
+def expert_unit_tensor(layer_name: str) -> Optional[str]:
+    """`blk.N.ffn_{gate,up,down}_exps.weight` of the expert unit `model.layers.N.mlp.experts.{gate,up,down}_proj`, else None."""
+    unit = expert_unit(layer_name)
+    parts = layer_name.split(".")
+    if parts[0] == "model":
+        parts = parts[1:]
+    if unit is None or len(parts) != 5 or parts[0] != "layers" or not parts[1].isdecimal():
+        return None
+    return f"blk.{parts[1]}.ffn_{unit[1]}_exps.weight"
+
+
 def layer_dir(db: str, layer_name: str) -> str:
-    """<db>/<HF module name> (gguf_splitter --hf-layers), else <db>/<GGUF tensor name> (--gguf-layers)."""
+    """<db>/<HF module name> (gguf_splitter --hf-layers), else <db>/<GGUF tensor name> (--gguf-layers; an expert unit
+    `<experts module>.{gate,up,down}_proj` is the stacked tensor `blk.N.ffn_{gate,up,down}_exps.weight`)."""
     d = os.path.join(db, layer_name)
     if os.path.isdir(d):
         return d
     from .pack_gptq_into_gguf import map_tensor_name
     try:
-        g = os.path.join(db, map_tensor_name(layer_name + ".weight"))
+        g = os.path.join(db, expert_unit_tensor(layer_name) or map_tensor_name(layer_name + ".weight"))
     except ValueError:
         g = d
     if not os.path.isdir(g):
@@ -138,7 +163,8 @@ def has_layer(db: str, layer_name: str) -> bool:
 class LevelInfo:
     """What `<stem>-metadata.json` says of a level file.  ggml_type None: a torch-saved tensor (no sidecar, or the HF side's,
     without np_dtype / np_shape); the fields after it are unset then.  np_shape: the stored array, [R, C] values for plain
-    types, [R, C / block * type_size] bytes for block types; nbytes: what np_shape of np_dtype describes; shape: logical."""
+    types, [R, C / block * type_size] bytes for block types ([E, R, ..] for a stacked expert tensor); nbytes: what np_shape of
+    np_dtype describes; shape: logical, outermost first ([R, C] or [E, R, C])."""
     __slots__ = ("path", "name", "quantization", "ggml_type", "np_dtype", "np_shape", "shape", "nbytes")
 
 
@@ -208,11 +234,13 @@ def load_level(path: str, device, db: Optional[str] = None):
         return torch.load(path, map_location=device)
     from . import ops
     raw = torch.from_numpy(read_level_raw(rec)).to(device)
-    rows = rotary_rows(db, rec.name, rec.np_shape[0], device) if db else None
+    lead = rec.np_shape[:-1]  # [R], or [E, R] of a stacked expert tensor (no row gather: not a rotary tensor)
+    rows = rotary_rows(db, rec.name, rec.np_shape[0], device) if db and len(lead) == 1 else None
     if rec.ggml_type in PLAIN_TYPES:
         w = raw.view(getattr(torch, PLAIN_TYPES[rec.ggml_type][0])).reshape(rec.np_shape)
         return w[rows.long()] if rows is not None else w
-    return ops.dequantize_blocks(rec.ggml_type, raw.view(rec.np_shape[0], -1), torch.float16, rows)
+    w = ops.dequantize_blocks(rec.ggml_type, raw.view(int(np.prod(lead, dtype=np.int64)), -1), torch.float16, rows)
+    return w if len(lead) == 1 else w.view(*rec.shape)
 
 
 # ------------------------------------------------------------------------------------------------ ggml type tables

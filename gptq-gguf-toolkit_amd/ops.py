@@ -972,6 +972,53 @@ def level_switch(jobs) -> None:
     return None
 
 
+# ---- level switch of stacked expert tensors (gq_level_switch_experts): one job per [E, R, C] tensor, one call ----
+SWITCH_EXPERTS_MAX_JOBS = _cabi.SWITCH_EXPERTS_MAX_JOBS
+
+
+def level_switch_experts(jobs) -> None:
+    """Apply a list of jobs (src, dst_view, kind) in ONE gq_level_switch_experts call on the current stream of their device.
+    dst_view: an [E, R, C] fp32 / fp16 / bf16 view whose last two dimensions are contiguous, written in place; its stride(0) is
+    the expert stride, so `gate_up_proj[:, :I]`, `gate_up_proj[:, I:]` and `down_proj` of a fused experts module are all
+    destinations (nothing outside the view is written).  kind a K-quant q_type (10..14), Q8_0 (8), IQ4_NL (20) or IQ4_XS (23):
+    src uint8, E * R rows of packed blocks as in the file (any contiguous view of exactly those bytes); kind None: src a dense
+    contiguous [E, R, C] tensor, cast as .to(dst.dtype).  The values are those of level_switch with the E per-expert jobs.
+    Returns None; no host read, no allocation on the device."""
+    jobs = list(jobs)
+    if not jobs:
+        return None
+    dev = jobs[0][1].device
+    table = (_cabi.SwitchExpertsJob * len(jobs))()
+    for i, (src, dst, kind) in enumerate(jobs):
+        _need_cuda(src, dst)
+        for t in (src, dst):
+            if t.device != dev:
+                raise _cabi.GQError(f"level_switch_experts: job {i}: every tensor must be on one device ({dev}); got one on "
+                                    f"{t.device}")
+        if dst.dim() != 3 or dst.dtype not in _DT or 0 in dst.shape or not dst[0].is_contiguous():
+            raise _cabi.GQError(f"level_switch_experts: job {i}: dst must be an [E, R, C] fp32 / fp16 / bf16 view with contiguous "
+                                f"[R, C] matrices; got {dst.dtype} {tuple(dst.shape)} strides {tuple(dst.stride())}")
+        E, R, C = dst.shape
+        stride = dst.stride(0) if E > 1 else R * C  # (torch reports any stride for an extent of 1)
+        if not src.is_contiguous():
+            raise _cabi.GQError(f"level_switch_experts: job {i}: src must be contiguous")
+        if kind is None:
+            if src.dtype not in _DT or tuple(src.shape) != (E, R, C):
+                raise _cabi.GQError(f"level_switch_experts: job {i}: a dense src must be fp32 / fp16 / bf16 {(E, R, C)}; got "
+                                    f"{src.dtype} {tuple(src.shape)}")
+            k = _DT[src.dtype]
+        else:
+            k = int(kind)
+            bs, ts = block_geometry(k)
+            need = E * R * (C // bs) * ts
+            if src.dtype != torch.uint8 or C % bs or src.numel() != need:
+                raise _cabi.GQError(f"level_switch_experts: job {i}: packed src of q_type {k} for {(E, R, C)} must be {need} uint8; "
+                                    f"got {src.dtype} {tuple(src.shape)}")
+        table[i] = _cabi.SwitchExpertsJob(src.data_ptr(), dst.data_ptr(), E, R, C, stride, k, _DT[dst.dtype])
+    check(lib().gq_level_switch_experts(table, len(jobs), _stream(jobs[0][1])), "gq_level_switch_experts")
+    return None
+
+
 # ---- the packed-weight forward (gq_linear_packed, gq_gemv_packed): y = x W^T with W given as GGUF block bytes ----
 GEMV_MAX_T = _cabi.GEMV_MAX_T
 
