@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "gq_common.hpp"
+#include "gq_chol_plan.hpp"
 #include "gq_gemm32.hpp"
 #include "gq_gemm3b.hpp"
 #include "gq_gemm3p.hpp"
@@ -27,7 +28,8 @@
 
 namespace gq {
 
-constexpr int NB = 128;
+constexpr int NB = CHOL_NB;
+static_assert(GEMM32_TK == TK, "gemm32_uses_64_full (gq_chol_plan.hpp) states launch_gemm32's rule");
 
 // ------------------------------------------------------------------ prelude
 // dead[j] = (H[j,j] == 0)                               gptq.py:134
@@ -535,92 +537,39 @@ __device__ __forceinline__ f32x16 mfma_nt_32(const float* Ap, int lda_, const fl
 #include "gq_diag5.hpp"
 namespace gq {
 
-// ---- the top recursion levels on pre-split operand images (gq_gemm3p.hpp) ----
-// A node (n1 | n2) goes there when both halves are multiples of 256 and at least p3_min() wide.  The schedules of all
-// its GEMMs depend on C only: they are planned once per C (cached), and uploaded with ONE copy per gq_h_prepare
-// call (the upload also zeroes the pop counters).
-// (The switches are read on every call -- a handful per transformer block -- so that tests can flip them.)
-static int64_t p3_min() { return opt(OPT_chol_3p_min); }  // 0: never
-static int p3_planes() { return opt(OPT_chol_planes) == 3 ? 3 : 2; }  // default: row-scaled fp16 x 2, equilibrated matrix
-static inline bool p3_node(int64_t n1, int64_t n2) {
-    return p3_min() > 0 && n1 >= p3_min() && n2 >= p3_min() && n1 % 256 == 0 && n2 % 256 == 0;
+// ---- the host side of the chain: the options once per call, the cached plan (gq_chol_plan.hpp), one launch body per step ----
+// (The switches are read on every call -- a handful per transformer block -- so that tests can flip them; once per call,
+// here and nowhere below.)
+static CholOptions chol_options() {
+    CholOptions o;
+    o.p3_min = opt(OPT_chol_3p_min);
+    o.b3_min = opt(OPT_chol_3b_min);
+    o.planes = opt(OPT_chol_planes) == 3 ? 3 : 2;
+    o.fp32 = opt(OPT_chol_fp32) != 0;
+    o.no_pair = opt(OPT_chol_no_pair) != 0;
+    o.no_equil = opt(OPT_chol_no_equil) != 0;
+    o.poison = opt(OPT_chol_poison) != 0;
+    o.diag_ref = opt(OPT_diag_ref) != 0;
+    o.gemm32_64_max = opt(OPT_gemm32_64_max);
+    return o;
 }
-constexpr int P3_MAX_SLOTS = 1024;  // 256 MiB of K-split partial sums
-struct P3Gemm {
-    size_t table_at, rlist_at;  // word offsets into the uploaded buffer
-    int n_reduce;
-};
-struct P3Plans {
-    std::vector<uint32_t> words;
-    std::vector<P3Gemm> gemms;  // three launches per node, in the order chol_inv_rec issues them
-};
-static void p3_collect(P3Plans& pl, int64_t lo, int64_t hi) {
-    if (hi - lo == 1) return;
-    const int64_t mid = (lo + hi) / 2;
-    const int64_t n1 = (mid - lo) * NB, n2 = (hi - mid) * NB;
-    p3_collect(pl, lo, mid);
-    const bool big = p3_node(n1, n2);
-    const int gran = p3_planes() == 3 ? 2 : 4;
-    auto add = [&](const std::vector<p3::GemmShape>& shs) {
-        p3::Plan p = p3::make_plan(shs, gran, P3_MAX_SLOTS);
-        P3Gemm g;
-        while (pl.words.size() % 4) pl.words.push_back(0u);
-        g.table_at = pl.words.size();
-        pl.words.insert(pl.words.end(), p.table.begin(), p.table.end());
-        g.rlist_at = pl.words.size();
-        pl.words.insert(pl.words.end(), p.rlist.begin(), p.rlist.end());
-        g.n_reduce = (int)(p.rlist.size() / 2);
-        if (p.nslots < 0) fprintf(stderr, "gq: image GEMM plan needs more than %d partial slots\n", P3_MAX_SLOTS), abort();
-        pl.gemms.push_back(g);
-    };
-    if (big) {
-        const int t1 = (int)(n1 / 256), t2 = (int)(n2 / 256), k1 = (int)(n1 / 32);
-        add({{t2, t1, k1, 1, false}});                          // L21 = A21 X11^T
-        add({{t2, t2, k1, 0, true}, {t2, t1, k1, 2, false}});   // A22 -= L21 L21^T  and  L21 X11, one launch
-    }
-    p3_collect(pl, mid, hi);
-    if (big) add({{(int)(n2 / 256), (int)(n1 / 256), (int)(n2 / 32), 3, false}});  // X21 = -X22 (L21 X11)
-}
-static std::shared_ptr<const P3Plans> p3_plans_for(int64_t nblk) {
+// The plan depends on C and the options only: it is made once per (C, options) and cached for the process; the words of its
+// image-GEMM schedules are uploaded with ONE copy per gq_h_prepare call (the upload also zeroes the pop counters).
+static std::shared_ptr<const CholPlan> chol_plan_for(int64_t C, const CholOptions& o) {
     static std::mutex mu;
-    static std::map<std::pair<int64_t, int64_t>, std::shared_ptr<const P3Plans>> cache;
+    static std::map<std::pair<int64_t, CholOptions>, std::shared_ptr<const CholPlan>> cache;
     std::lock_guard<std::mutex> lk(mu);
-    const std::pair<int64_t, int64_t> key{nblk, p3_min() * 4 + p3_planes()};
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    auto pl = std::make_shared<P3Plans>();
-    p3_collect(*pl, 0, nblk);
-    cache[key] = pl;
+    std::shared_ptr<const CholPlan>& pl = cache[{C, o}];
+    if (!pl) pl = std::make_shared<const CholPlan>(make_chol_plan(C, o));
     return pl;
-}
-struct P3Run {  // per gq_h_prepare call
-    const P3Plans* plans = nullptr;
-    const uint32_t* words_dev = nullptr;
-    size_t next = 0;
-    unsigned char* img[2] = {nullptr, nullptr};
-    float* partial = nullptr;
-    unsigned* rmax = nullptr;     // NP == 2: [2][n/2] row maxima (bits) of the transposed operands (the others: image_rows_kernel) ...
-    float* inv_scale = nullptr;   // ... and [2][n/2] epilogue scales
-};
-static size_t p3_image_bytes(int64_t C) { return (size_t)(C / 2) * (size_t)(C / 2) * 2 * (size_t)p3_planes(); }
-static bool p3_used(int64_t C) {
-    const int64_t nblk = C / NB, mid = nblk / 2;
-    return nblk >= 2 && p3_node(mid * NB, (nblk - mid) * NB);
 }
 
 size_t h_prepare_workspace_bytes(int64_t R, int64_t C) {
     (void)R;
-    const size_t n2 = (size_t)C * (size_t)C * sizeof(float);
-    size_t extra = 0;
-    if (p3_used(C)) {
-        auto pl = p3_plans_for(C / NB);
-        extra = 2 * (p3_image_bytes(C) + 256) + (size_t)P3_MAX_SLOTS * p3::TILE * p3::TILE * 4 + pl->words.size() * 4 +
-                4 * (size_t)C * 4 + 2048;
-    }
-    return 2 * n2 + 2 * (size_t)C + 4 * (size_t)C + 1024 + extra;
+    return chol_workspace_bytes(*chol_plan_for(C, chol_options()));
 }
 
-// Recursive blocked Cholesky WITH inverse, all level-3 work on the fp32 matrix cores:
+// Recursive blocked Cholesky WITH inverse, all level-3 work on the matrix cores:
 //   [A11 .  ]      L11 = chol(A11), X11 = L11^-1                     (recursion)
 //   [A21 A22]      L21 = A21 X11^T                                   (GEMM, X11 triangular: k-range skip)
 //                  A22 -= L21 L21^T                                  (SYRK, lower tiles only)
@@ -628,33 +577,57 @@ size_t h_prepare_workspace_bytes(int64_t R, int64_t C) {
 //                  X21 = -X22 (L21 X11)                              (two GEMMs, triangular k-range skips)
 // L21 lives in Tmp (the factor itself is not an output: only X = L^-1 is), the product L21 X11
 // reuses the dead A21 block.  Leaves are 128x128 (diag_potrf_inv_kernel, writes X_kk directly).
+// The plan flattens the recursion: LEAF(block), and per node NODE_FRONT (in front of the recursion into A22) and NODE_BACK.
 // (Measured and dropped, r02: L21 X11 of the large nodes on helper streams -- one per recursion depth -- under the
 // recursion into A22, which it does not depend on: h_prepare(14336) alone 24.3 -> 23.5 ms, but inside a block's
 // four-chain schedule the three extra hardware queues cost far more than that: 102 -> 113 ms per step.)
+struct CholRun {  // per gq_h_prepare call: the plan and the addresses its steps launch on
+    const CholPlan* plan;
+    float *A, *X, *Tmp;
+    int* flag;
+    int64_t n;
+    size_t diag_lds;
+    hipStream_t st;
+    const uint32_t* words_dev;
+    unsigned char* img[2];
+    float* partial;
+    unsigned* rmax;     // NP == 2: [2][n/2] row maxima (bits) of the transposed operands (the others: image_rows_kernel) ...
+    float* inv_scale;   // ... and [2][n/2] epilogue scales
+};
 template <int NP>
-static p3::Problem p3_problem(P3Run& run, const unsigned char* Aimg, int64_t Ka, const unsigned char* Bimg, int64_t Kb,
+static p3::Problem p3_problem(const CholRun& run, const unsigned char* Aimg, int64_t Ka, const unsigned char* Bimg, int64_t Kb,
                               float* Cm, int64_t ldc, int mode, const float* rs, const float* cs) {
     return p3::Problem{Aimg, Bimg, (uint32_t)(Ka / 32 * NP * p3::BLK), (uint32_t)(Kb / 32 * NP * p3::BLK), Cm, ldc, mode,
                        rs, cs, run.partial};
 }
 template <int NP>
-static int p3_gemm(P3Run& run, const p3::Problem& p0, const p3::Problem* p1, hipStream_t st) {
-    const P3Gemm& gm = run.plans->gemms[run.next++];
+static int p3_gemm(const CholRun& run, int gemm, const p3::Problem& p0, const p3::Problem* p1) {
+    const CholGemm& gm = run.plan->gemms[gemm];
     p3::Group g;
     g.p[0] = p0;
     g.p[1] = p1 ? *p1 : p0;
     g.table = run.words_dev + gm.table_at;
-    return p3::launch_gemm<NP>(g, gm.n_reduce, run.words_dev + gm.rlist_at, st);
+    return p3::launch_gemm<NP>(g, gm.n_reduce, run.words_dev + gm.rlist_at, run.st);
 }
 
-static int chol_inv_rec(float* A, float* X, float* Tmp, int* flag, int64_t n, int64_t lo, int64_t hi, size_t diag_lds,
-                        hipStream_t st, P3Run& run);
+static int chol_leaf(const CholRun& run, int64_t blk) {
+    ProfScope ps(PT_DIAG_POTRF, run.st);
+    const int64_t n = run.n, o = (blk * NB) * n + blk * NB;
+    if (run.diag_lds == DIAG5_LDS)
+        hipLaunchKernelGGL(diag_blk5_kernel, dim3(1), dim3(320), run.diag_lds, run.st, run.A + o, n, run.X + o, n, run.flag);
+    else
+        hipLaunchKernelGGL(diag_potrf_inv_kernel, dim3(1), dim3(256), run.diag_lds, run.st, run.A + o, n, run.X + o, n, run.flag);
+    GQ_LAUNCH_CHECK();
+    return GQ_OK;
+}
 
-// One node of the recursion on the image GEMMs.  Same products as the generic path below; L21 X11 moves in front of
+// One node of the recursion on the image GEMMs.  Same products as the generic node below; L21 X11 moves in front of
 // the recursion into A22 (it does not depend on it) and shares the launch -- and the image of L21 -- with the SYRK update.
 template <int NP>
-static int chol_node_p3(float* A, float* X, float* Tmp, int* flag, int64_t n, int64_t lo, int64_t mid, int64_t hi,
-                        size_t diag_lds, hipStream_t st, P3Run& run) {
+static int chol_node_p3(const CholRun& run, const CholNode& nd, bool back) {
+    float *const A = run.A, *const X = run.X, *const Tmp = run.Tmp;
+    const hipStream_t st = run.st;
+    const int64_t n = run.n, lo = nd.lo, mid = nd.mid, hi = nd.hi;
     const int64_t n1 = (mid - lo) * NB, n2 = (hi - mid) * NB;
     const int64_t o21 = (mid * NB) * n + lo * NB, o11 = (lo * NB) * n + lo * NB, o22 = (mid * NB) * n + mid * NB;
     unsigned* rm0 = run.rmax, *rm1 = run.rmax ? run.rmax + n / 2 : nullptr;
@@ -662,72 +635,72 @@ static int chol_node_p3(float* A, float* X, float* Tmp, int* flag, int64_t n, in
     const float* s0 = NP == 2 ? is0 : nullptr;
     const float* s1 = NP == 2 ? is1 : nullptr;
     int rc;
-    {
+    if (!back) {
         ProfScope ps(PT_CHOL_GEMM, st);
         // L21 = A21 X11^T  (X11 lower-triangular: k < 256 (tn + 1))
         if ((rc = p3::launch_split<NP>(false, A + o21, n, n2, n1, 0, 0, run.img[0], rm0, is0, st))) return rc;
         if ((rc = p3::launch_split<NP>(false, X + o11, n, n1, n1, 1, 0, run.img[1], rm1, is1, st))) return rc;
         const p3::Problem g1 = p3_problem<NP>(run, run.img[0], n1, run.img[1], n1, Tmp + o21, n, 1, s0, s1);
-        if ((rc = p3_gemm<NP>(run, g1, nullptr, st))) return rc;
+        if ((rc = p3_gemm<NP>(run, nd.gemm[0], g1, nullptr))) return rc;
         // A22 -= L21 L21^T (lower tiles) and A21 <- L21 X11 in ONE launch: both need only L21.  X11[k][j] = 0 for k < j,
         // so both images have their chunks in reverse order: every tile of the second product starts at chunk 0
         if ((rc = p3::launch_split<NP>(false, Tmp + o21, n, n2, n1, 0, 1, run.img[0], rm0, is0, st))) return rc;
         if ((rc = p3::launch_split<NP>(true, X + o11, n, n1, n1, 2, 1, run.img[1], rm1, is1, st))) return rc;
         const p3::Problem g2 = p3_problem<NP>(run, run.img[0], n1, run.img[0], n1, A + o22, n, 0, s0, s0);
         const p3::Problem g3 = p3_problem<NP>(run, run.img[0], n1, run.img[1], n1, A + o21, n, 1, s0, s1);
-        if ((rc = p3_gemm<NP>(run, g2, &g3, st))) return rc;
+        return p3_gemm<NP>(run, nd.gemm[1], g2, &g3);
     }
-    if ((rc = chol_inv_rec(A, X, Tmp, flag, n, mid, hi, diag_lds, st, run))) return rc;
     ProfScope ps(PT_TRTRI_GEMM, st);
     // X21 = -X22 (L21 X11)  (X22 lower-triangular: k < 256 (tm + 1))
     if ((rc = p3::launch_split<NP>(false, X + o22, n, n2, n2, 1, 0, run.img[0], rm0, is0, st))) return rc;
     if ((rc = p3::launch_split<NP>(true, A + o21, n, n1, n2, 0, 0, run.img[1], rm1, is1, st))) return rc;
     const p3::Problem g4 = p3_problem<NP>(run, run.img[0], n2, run.img[1], n2, X + o21, n, 2, s0, s1);
-    return p3_gemm<NP>(run, g4, nullptr, st);
+    return p3_gemm<NP>(run, nd.gemm[2], g4, nullptr);
 }
 
-static int chol_inv_rec(float* A, float* X, float* Tmp, int* flag, int64_t n, int64_t lo, int64_t hi, size_t diag_lds,
-                        hipStream_t st, P3Run& run) {
-    if (hi - lo == 1) {
-        ProfScope ps(PT_DIAG_POTRF, st);
-        const int64_t o = (lo * NB) * n + lo * NB;
-        if (diag_lds == DIAG5_LDS)
-            hipLaunchKernelGGL(diag_blk5_kernel, dim3(1), dim3(320), diag_lds, st, A + o, n, X + o, n, flag);
-        else
-            hipLaunchKernelGGL(diag_potrf_inv_kernel, dim3(1), dim3(256), diag_lds, st, A + o, n, X + o, n, flag);
-        GQ_LAUNCH_CHECK();
-        return GQ_OK;
-    }
-    const int64_t mid = (lo + hi) / 2;
-    int rc;
-    if ((rc = chol_inv_rec(A, X, Tmp, flag, n, lo, mid, diag_lds, st, run))) return rc;
+// One product of a generic node: CHOL_SPLIT_BF16 on the bf16 matrix cores (gq_gemm3b.hpp), the fp32 regimes on the fp32
+// instruction.
+template <bool TB, int MODE, bool LOW, int KRV>
+static int chol_node_gemm(CholRegime regime, float* Cm, int64_t ldc, const float* A, int64_t lda, const float* B, int64_t ldb,
+                          int64_t M, int64_t N, int64_t K, hipStream_t st) {
+    return regime == CHOL_SPLIT_BF16 ? launch_gemm3b<TB, MODE, LOW, KRV>(Cm, ldc, A, lda, B, ldb, M, N, K, st)
+                                     : launch_gemm32<TB, MODE, LOW, KRV>(Cm, ldc, A, lda, B, ldb, M, N, K, st);
+}
+static int chol_node(const CholRun& run, const CholNode& nd, bool back) {
+    float *const A = run.A, *const X = run.X, *const Tmp = run.Tmp;
+    const hipStream_t st = run.st;
+    const int64_t n = run.n, lo = nd.lo, mid = nd.mid, hi = nd.hi;
     const int64_t n1 = (mid - lo) * NB, n2 = (hi - mid) * NB;
-    if (run.plans && p3_node(n1, n2))
-        return p3_planes() == 3 ? chol_node_p3<3>(A, X, Tmp, flag, n, lo, mid, hi, diag_lds, st, run)
-                                : chol_node_p3<2>(A, X, Tmp, flag, n, lo, mid, hi, diag_lds, st, run);
     const int64_t o21 = (mid * NB) * n + lo * NB, o11 = (lo * NB) * n + lo * NB, o22 = (mid * NB) * n + mid * NB;
-    // large nodes: fp32-accurate products on the bf16 matrix cores (gq_gemm3b.hpp); small ones are
-    // latency-bound and stay on the fp32 instruction
-    const int64_t min3b = opt(OPT_chol_fp32) ? (int64_t)1 << 40 : opt(OPT_chol_3b_min);
-    const bool big = n1 >= min3b && n2 >= min3b;
-#define GQ_CHOL_GEMM(TB, MODE, LOW, KRV, ...) \
-    (big ? launch_gemm3b<TB, MODE, LOW, KRV>(__VA_ARGS__) : launch_gemm32<TB, MODE, LOW, KRV>(__VA_ARGS__))
-    // small nodes: the SYRK update and L21 X11 (both need only L21) share one launch of whole 64-tiles, in front of the
-    // recursion into A22 (bit-identical to separate launches: every output element is the same k-ordered chain)
-    const bool pair = !big && !opt(OPT_chol_no_pair) && n % 4 == 0 && gemm32_uses_64_full(n2, n2, n1, true) &&
-                      gemm32_uses_64_full(n2, n1, n1, false);
-    {
+    const CholRegime rg = nd.regime;
+    const bool pair = rg == CHOL_FP32_PAIR;  // the SYRK update and L21 X11 share one launch, in front of the recursion into A22
+    int rc;
+    if (!back) {
         ProfScope ps(PT_CHOL_GEMM, st);
-        if ((rc = GQ_CHOL_GEMM(true, 1, false, 1, Tmp + o21, n, A + o21, n, X + o11, n, n2, n1, n1, st))) return rc;
-        if (pair) {
-            if ((rc = launch_gemm32_pair(A + o22, Tmp + o21, n2, n1, A + o21, Tmp + o21, X + o11, n2, n1, n1, n, st))) return rc;
-        } else if ((rc = GQ_CHOL_GEMM(true, 0, true, 0, A + o22, n, Tmp + o21, n, Tmp + o21, n, n2, n2, n1, st))) return rc;
+        if ((rc = chol_node_gemm<true, 1, false, 1>(rg, Tmp + o21, n, A + o21, n, X + o11, n, n2, n1, n1, st))) return rc;
+        if (pair) return launch_gemm32_pair(A + o22, Tmp + o21, n2, n1, A + o21, Tmp + o21, X + o11, n2, n1, n1, n, st);
+        return chol_node_gemm<true, 0, true, 0>(rg, A + o22, n, Tmp + o21, n, Tmp + o21, n, n2, n2, n1, st);
     }
-    if ((rc = chol_inv_rec(A, X, Tmp, flag, n, mid, hi, diag_lds, st, run))) return rc;
     ProfScope ps(PT_TRTRI_GEMM, st);
-    if (!pair && (rc = GQ_CHOL_GEMM(false, 1, false, 2, A + o21, n, Tmp + o21, n, X + o11, n, n2, n1, n1, st))) return rc;
-    return GQ_CHOL_GEMM(false, 2, false, 3, X + o21, n, X + o22, n, A + o21, n, n2, n1, n2, st);
-#undef GQ_CHOL_GEMM
+    if (!pair && (rc = chol_node_gemm<false, 1, false, 2>(rg, A + o21, n, Tmp + o21, n, X + o11, n, n2, n1, n1, st))) return rc;
+    return chol_node_gemm<false, 2, false, 3>(rg, X + o21, n, X + o22, n, A + o21, n, n2, n1, n2, st);
+}
+
+static int chol_walk(const CholRun& run) {
+    const CholPlan& pl = *run.plan;
+    for (const CholStep& s : pl.steps) {
+        int rc;
+        if (s.kind == CholStep::LEAF) {
+            rc = chol_leaf(run, s.at);
+        } else {
+            const CholNode& nd = pl.nodes[s.at];
+            const bool back = s.kind == CholStep::NODE_BACK;
+            if (nd.regime != CHOL_IMAGE) rc = chol_node(run, nd, back);
+            else rc = pl.planes == 3 ? chol_node_p3<3>(run, nd, back) : chol_node_p3<2>(run, nd, back);
+        }
+        if (rc) return rc;
+    }
+    return GQ_OK;
 }
 
 int w_prepare(const uint8_t* flags, float* W, int64_t R, int64_t C, int* mismatch, hipStream_t st) {
@@ -751,37 +724,43 @@ int h_prepare(float* H, float* W, int64_t R, int64_t C, float rel_damp, float* U
               uint8_t* col_flags_out, void* ws, size_t ws_bytes, hipStream_t st, bool obq_order) {
     if (!H || !W || !U || !not_invertible) GQ_FAIL(GQ_E_NULL, "gq_h_prepare: null pointer");
     if (R <= 0 || C <= 0 || C % NB) GQ_FAIL(GQ_E_BAD_SHAPE, "gq_h_prepare: R=%ld C=%ld (C %% 128 != 0)", (long)R, (long)C);
-    const size_t need = h_prepare_workspace_bytes(R, C);
+    const CholOptions o = chol_options();
+    const std::shared_ptr<const CholPlan> plan = chol_plan_for(C, o);
+    if (plan->too_many_slots)
+        GQ_FAIL(GQ_E_UNSUPPORTED, "gq_h_prepare: an image GEMM schedule needs more than %d partial slots", P3_MAX_SLOTS);
+    const size_t need = chol_workspace_bytes(*plan);
     if (!ws || ws_bytes < need) GQ_FAIL(GQ_E_WORKSPACE, "gq_h_prepare: workspace %zu < %zu bytes", ws_bytes, need);
-    const int64_t n = C, nblk = C / NB;
-    float* A = reinterpret_cast<float*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    float* X = A + (size_t)n * n;
-    uint8_t* dead = reinterpret_cast<uint8_t*>(X + (size_t)n * n);
-    uint8_t* zc = dead + n;
-    int rc;
+    const int64_t n = C;
+    const CholLayout& at = plan->at;
+    unsigned char* const base = reinterpret_cast<unsigned char*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    const size_t room = ws_bytes - (size_t)(base - reinterpret_cast<unsigned char*>(ws));  // need > 255
+    if (at.scales + (size_t)n * 4 > room) GQ_FAIL(GQ_E_WORKSPACE, "gq_h_prepare: workspace too small for the matrices, flags and scales");
+    if (plan->images && at.words > room) GQ_FAIL(GQ_E_WORKSPACE, "gq_h_prepare: workspace too small for the operand images and partial sums");
+    if (at.total > room) GQ_FAIL(GQ_E_WORKSPACE, "gq_h_prepare: workspace too small for the image GEMM schedules");
+    float* A = reinterpret_cast<float*>(base + at.A);
+    float* X = reinterpret_cast<float*>(base + at.X);
+    uint8_t* dead = base + at.dead;
+    uint8_t* zc = base + at.zc;
 
-    P3Run run;
-    std::shared_ptr<const P3Plans> plans;
-    if (p3_used(C)) {
-        plans = p3_plans_for(nblk);
-        unsigned char* p = reinterpret_cast<unsigned char*>(zc + n);
-        p = reinterpret_cast<unsigned char*>(((uintptr_t)p + 255) & ~(uintptr_t)255) + (((size_t)n * 4 + 255) & ~(size_t)255);
-        run.img[0] = p; p += (p3_image_bytes(C) + 255) & ~(size_t)255;
-        run.img[1] = p; p += (p3_image_bytes(C) + 255) & ~(size_t)255;
-        run.partial = reinterpret_cast<float*>(p); p += (size_t)P3_MAX_SLOTS * p3::TILE * p3::TILE * 4;
-        if (p3_planes() == 2) {
-            run.rmax = reinterpret_cast<unsigned*>(p); p += (size_t)n * 4;
-            run.inv_scale = reinterpret_cast<float*>(p); p += (size_t)n * 4;
-        } else {
-            p += 2 * (size_t)n * 4;
+    CholRun run{};
+    run.plan = plan.get();
+    run.A = A;
+    run.X = X;
+    run.Tmp = U;
+    run.flag = not_invertible;
+    run.n = n;
+    run.st = st;
+    if (plan->images) {
+        run.img[0] = base + at.img[0];
+        run.img[1] = base + at.img[1];
+        run.partial = reinterpret_cast<float*>(base + at.partial);
+        if (at.rmax != CHOL_NO_REGION) {
+            run.rmax = reinterpret_cast<unsigned*>(base + at.rmax);
+            run.inv_scale = reinterpret_cast<float*>(base + at.inv_scale);
         }
-        p = reinterpret_cast<unsigned char*>(((uintptr_t)p + 255) & ~(uintptr_t)255);
-        if (p + plans->words.size() * 4 > reinterpret_cast<unsigned char*>(ws) + ws_bytes)
-            GQ_FAIL(GQ_E_WORKSPACE, "gq_h_prepare: workspace too small for the image GEMMs");
-        // pageable source: staged before the call returns; the plans object outlives it (cached for the process)
-        GQ_HIP(hipMemcpyAsync(p, plans->words.data(), plans->words.size() * 4, hipMemcpyHostToDevice, st));
-        run.words_dev = reinterpret_cast<const uint32_t*>(p);
-        run.plans = plans.get();
+        // pageable source: staged before the call returns; the plan outlives it (cached for the process)
+        GQ_HIP(hipMemcpyAsync(base + at.words, plan->words.data(), plan->words.size() * 4, hipMemcpyHostToDevice, st));
+        run.words_dev = reinterpret_cast<const uint32_t*>(base + at.words);
     }
     GQ_HIP(hipMemsetAsync(not_invertible, 0, sizeof(int), st));
     float* eq_s = nullptr;
@@ -804,21 +783,20 @@ int h_prepare(float* H, float* W, int64_t R, int64_t C, float rel_damp, float* U
         hipLaunchKernelGGL(damp_kernel, dim3(1), dim3(1024), 0, st, H, C, rel_damp);
     }
     GQ_LAUNCH_CHECK();
-    const bool equil = !opt(OPT_chol_no_equil);
-    if (equil) {
-        eq_s = reinterpret_cast<float*>(((uintptr_t)(zc + n) + 255) & ~(uintptr_t)255);
+    if (!o.no_equil) {
+        eq_s = reinterpret_cast<float*>(base + at.scales);
         hipLaunchKernelGGL(equil_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, H, n, eq_s);
     }
     // Neither A above its block diagonal nor X needs clearing: every block that is read is written first (diagonal
     // blocks whole, zeros included).  The test that pins this fills both with NaN patterns first (option chol_poison) and
     // expects the same U.
-    if (opt(OPT_chol_poison)) GQ_HIP(hipMemsetAsync(A, 0xff, 2 * (size_t)n * n * sizeof(float), st));
+    if (o.poison) GQ_HIP(hipMemsetAsync(A, 0xff, 2 * (size_t)n * n * sizeof(float), st));
     hipLaunchKernelGGL(reverse_copy_kernel, dim3((unsigned)n), dim3(256), 0, st, A, H, n, eq_s);
     GQ_LAUNCH_CHECK();
     }
     static std::atomic<bool> attr_set{false};  // guards an idempotent call: a race sets the same value twice
-    const bool use_ref = opt(OPT_diag_ref) != 0;  // the column-by-column kernel
-    const size_t diag_lds = use_ref ? (2 * NB * LDP + NB) * sizeof(float) : DIAG5_LDS;
+    // diag_ref: the column-by-column kernel
+    run.diag_lds = o.diag_ref ? (2 * NB * LDP + NB) * sizeof(float) : DIAG5_LDS;
     if (!attr_set) {
         GQ_HIP(hipFuncSetAttribute((const void*)diag_potrf_inv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)((2 * NB * LDP + NB) * sizeof(float))));
@@ -826,7 +804,8 @@ int h_prepare(float* H, float* W, int64_t R, int64_t C, float rel_damp, float* U
                                    (int)DIAG5_LDS));
         attr_set = true;
     }
-    if ((rc = chol_inv_rec(A, X, U, not_invertible, n, 0, nblk, diag_lds, st, run))) return rc;
+    int rc;
+    if ((rc = chol_walk(run))) return rc;
     ProfScope ps(PT_PREP_ELEM, st);
     hipLaunchKernelGGL(finish_u_kernel, dim3((unsigned)n), dim3(256), 0, st, U, X, n, not_invertible, eq_s);
     GQ_LAUNCH_CHECK();
@@ -834,36 +813,23 @@ int h_prepare(float* H, float* W, int64_t R, int64_t C, float rel_damp, float* U
 }
 
 // ---- gq_chol_gemm: one product of the chain through the image path, for tests and benchmarks ----
-size_t chol_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-    const size_t img = (size_t)3 * 2 * (size_t)K;
-    return img * (size_t)M + img * (size_t)N + (size_t)P3_MAX_SLOTS * p3::TILE * p3::TILE * 4 + 2 * (size_t)(M + N) * 4 +
-           ((size_t)(M / 256 + 1) * (size_t)(N / 256 + 1) * 6 * 4 + 64) * 4 + 4096;
-}
+// (It reads no option: the number of planes is an argument.)
+size_t chol_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) { return chol_gemm_workspace_bound(M, N, K); }
 template <int NP>
 static int chol_gemm_np(float* Cm, int64_t ldc, const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N,
-                        int64_t K, int trans_b, int mode, int kr, int lower, unsigned char* p, unsigned char* end,
-                        hipStream_t st) {
-    auto take = [&](size_t bytes) {
-        unsigned char* q = p;
-        p += (bytes + 255) & ~(size_t)255;
-        return q;
-    };
-    unsigned char* ia = take((size_t)NP * 2 * M * K);
-    unsigned char* ib = take((size_t)NP * 2 * N * K);
-    float* partial = reinterpret_cast<float*>(take((size_t)P3_MAX_SLOTS * p3::TILE * p3::TILE * 4));
-    unsigned* rma = reinterpret_cast<unsigned*>(take((size_t)M * 4));
-    unsigned* rmb = reinterpret_cast<unsigned*>(take((size_t)N * 4));
-    float* isa = reinterpret_cast<float*>(take((size_t)M * 4));
-    float* isb = reinterpret_cast<float*>(take((size_t)N * 4));
-    const p3::GemmShape sh{(int)(M / 256), (int)(N / 256), (int)(K / 32), kr, lower != 0};
-    const p3::Plan pl = p3::make_plan({sh}, NP == 3 ? 2 : 4, P3_MAX_SLOTS);
-    if (pl.nslots < 0) GQ_FAIL(GQ_E_UNSUPPORTED, "gq_chol_gemm: the schedule needs more than %d partial slots", P3_MAX_SLOTS);
-    std::vector<uint32_t> words(pl.table);
-    const size_t rl_at = words.size();
-    words.insert(words.end(), pl.rlist.begin(), pl.rlist.end());
-    uint32_t* wd = reinterpret_cast<uint32_t*>(take(words.size() * 4));
-    if (p > end) GQ_FAIL(GQ_E_WORKSPACE, "gq_chol_gemm: workspace too small");
-    GQ_HIP(hipMemcpyAsync(wd, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));  // pageable: staged before return
+                        int64_t K, int trans_b, int mode, int kr, int lower, unsigned char* base, size_t room, hipStream_t st) {
+    const CholGemmPlan pl = make_chol_gemm_plan(NP, M, N, K, kr, lower != 0);
+    if (pl.too_many_slots) GQ_FAIL(GQ_E_UNSUPPORTED, "gq_chol_gemm: the schedule needs more than %d partial slots", P3_MAX_SLOTS);
+    if (pl.total > room) GQ_FAIL(GQ_E_WORKSPACE, "gq_chol_gemm: workspace too small");
+    unsigned char* ia = base + pl.ia;
+    unsigned char* ib = base + pl.ib;
+    float* partial = reinterpret_cast<float*>(base + pl.partial);
+    unsigned* rma = reinterpret_cast<unsigned*>(base + pl.rma);
+    unsigned* rmb = reinterpret_cast<unsigned*>(base + pl.rmb);
+    float* isa = reinterpret_cast<float*>(base + pl.isa);
+    float* isb = reinterpret_cast<float*>(base + pl.isb);
+    uint32_t* wd = reinterpret_cast<uint32_t*>(base + pl.words_at);
+    GQ_HIP(hipMemcpyAsync(wd, pl.words.data(), pl.words.size() * 4, hipMemcpyHostToDevice, st));  // pageable: staged before return
     const int rev = kr == 2;
     int rc;
     if ((rc = p3::launch_split<NP>(false, A, lda, M, K, kr == 3 ? 1 : 0, rev, ia, rma, isa, st))) return rc;
@@ -878,7 +844,7 @@ static int chol_gemm_np(float* Cm, int64_t ldc, const float* A, int64_t lda, con
                          NP == 2 ? isa : nullptr, NP == 2 ? isb : nullptr, partial};
     g.p[1] = g.p[0];
     g.table = wd;
-    return p3::launch_gemm<NP>(g, (int)(pl.rlist.size() / 2), wd + rl_at, st);
+    return p3::launch_gemm<NP>(g, pl.n_reduce, wd + pl.rlist_at, st);
 }
 int chol_gemm(float* Cm, int64_t ldc, const float* A, int64_t lda, const float* B, int64_t ldb, int64_t M, int64_t N, int64_t K,
               int trans_b, int mode, int kr, int lower, int planes, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -887,10 +853,11 @@ int chol_gemm(float* Cm, int64_t ldc, const float* A, int64_t lda, const float* 
         GQ_FAIL(GQ_E_BAD_SHAPE, "gq_chol_gemm: M=%ld N=%ld (multiples of 256) K=%ld (of 128), ld %% 4 == 0", (long)M, (long)N, (long)K);
     if (mode < 0 || mode > 2 || kr < 0 || kr > 3 || (planes != 2 && planes != 3) || (kr == 1 && !trans_b) || (kr == 2 && trans_b))
         GQ_FAIL(GQ_E_UNSUPPORTED, "gq_chol_gemm: mode=%d kr=%d planes=%d trans_b=%d", mode, kr, planes, trans_b);
-    unsigned char* p = reinterpret_cast<unsigned char*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    unsigned char* base = reinterpret_cast<unsigned char*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
     unsigned char* end = reinterpret_cast<unsigned char*>(ws) + ws_bytes;
-    return planes == 3 ? chol_gemm_np<3>(Cm, ldc, A, lda, B, ldb, M, N, K, trans_b, mode, kr, lower, p, end, st)
-                       : chol_gemm_np<2>(Cm, ldc, A, lda, B, ldb, M, N, K, trans_b, mode, kr, lower, p, end, st);
+    const size_t room = base < end ? (size_t)(end - base) : 0;
+    return planes == 3 ? chol_gemm_np<3>(Cm, ldc, A, lda, B, ldb, M, N, K, trans_b, mode, kr, lower, base, room, st)
+                       : chol_gemm_np<2>(Cm, ldc, A, lda, B, ldb, M, N, K, trans_b, mode, kr, lower, base, room, st);
 }
 
 }  // namespace gq

@@ -322,12 +322,8 @@ inline int launch_gemm32_pair(float* Ca, const float* Aa, int64_t Ma, int64_t Ka
     GQ_LAUNCH_CHECK();
     return GQ_OK;
 }
-// does launch_gemm32 pick whole 64-tiles for a Cholesky-node product of this size?
-inline bool gemm32_uses_64_full(int64_t M, int64_t N, int64_t K, bool lower) {
-    const int64_t max64 = opt(OPT_gemm32_64_max);
-    const int64_t tiles128 = ((M + 127) / 128) * ((N + 127) / 128) / (lower ? 2 : 1);
-    return tiles128 < max64 && M % 64 == 0 && N % 64 == 0 && K % TK == 0;
-}
+// (gemm32_uses_64_full -- does launch_gemm32 pick whole 64-tiles for a Cholesky-node product of this size? -- is part of the
+// chain's plan: gq_chol_plan.hpp, with gemm32_64_max as an argument.)
 
 // ---- the GPTQ far trailing update on whole tiles: C = (..((C - A_0 B_0) - A_1 B_1)..), NN, 128x128 tiles ----
 // Same arithmetic as gemm32_kernel<false, 0, false, 0, CHAIN, 128, true, 8> (every output element is the same
