@@ -62,6 +62,9 @@ MOE_COMBINE_MAX_K = 8  # GQ_MOE_COMBINE_MAX_K: experts per token of one gq_fwd_m
 # include/gptq_gguf_moe_search.h: the level switch of a stacked [E, R, C] expert tensor, one job per tensor (additive in the same way)
 EXPORTS_MOE_SEARCH = ("gq_level_switch_experts",)
 SWITCH_EXPERTS_MAX_JOBS = 71  # GQ_SWITCH_EXPERTS_MAX_JOBS: jobs of one launch (a longer list is cut by the library)
+# include/gptq_gguf_moe_errest.h: gq_quad_form for the E experts of a stacked tensor, each with its own Hessian (additive in the same way)
+EXPORTS_MOE_ERREST = ("gq_quad_form_experts_workspace_bytes", "gq_quad_form_experts")
+QUAD_EXPERTS_MAX = 256  # GQ_QUAD_EXPERTS_MAX: experts of one gq_quad_form_experts call
 
 
 class GQError(RuntimeError):
@@ -173,6 +176,9 @@ def lib():
     L.gq_quad_form_workspace_bytes.argtypes = [i64, i64]
     L.gq_quad_form_workspace_bytes.restype = sz
     L.gq_quad_form.argtypes = [vp, ci, i64, vp, ci, i64, vp, i64, i64, vp, vp, sz, vp]
+    L.gq_quad_form_experts_workspace_bytes.argtypes = [i64, i64, i64]
+    L.gq_quad_form_experts_workspace_bytes.restype = sz
+    L.gq_quad_form_experts.argtypes = [vp, ci, i64, i64, vp, ci, i64, i64, vp, i64, i64, i64, vp, vp, sz, vp]
     L.gq_level_switch.argtypes = [ctypes.POINTER(SwitchJob), ci, vp]
     L.gq_gptq_quantize_bands.argtypes = [vp, vp, i64, i64, ctypes.POINTER(Band), ci, ci, sp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.gq_pack_bands.argtypes = [vp, vp, vp, vp, vp, i64, i64, ctypes.POINTER(Band), ci, ctypes.POINTER(vp), ctypes.POINTER(vp), vp]
@@ -196,7 +202,7 @@ def lib():
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_IQ4_GPTQ + EXPORTS_QGEMM +
-                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH):
+                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH + EXPORTS_MOE_ERREST):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

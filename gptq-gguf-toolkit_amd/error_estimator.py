@@ -14,10 +14,17 @@ and H is not modified: the dead-channel fix of pre_step (:88-89) happens where t
 
 The one deliberate difference: the levels of a Linear are ordered by the file name's numeric prefix parsed as a FLOAT
 ("4.5-Q4_K.pth" after "4-Q4_K.pth"; the reference's int(name.split(".")[0]) cannot tell them apart), and the file names
-are kept next to the values (`ErrorEstimator.levels`).  Left out: convolutions (nn.Linear only), more than one rank."""
+are kept next to the values (`ErrorEstimator.levels`).  Left out: convolutions (nn.Linear only), more than one rank.
+
+Fused experts (transformers 5.x's MixtralExperts: two 3-D parameters) are scored as the three units the search and LevelStore
+move, `<experts module>.{gate,up,down}_proj`: err(unit) = sum_e num_e / sum_e den_e over the E experts, each with its own
+Hessian on ONE common scale (`ExpertUnitsEstimator`), both sums one ops.quad_form_experts call on the fused parameter read in
+place.  A unit is scored when target_modules matches its name, the database has its directory and the module is adaptable
+(moe_calibration.why_not_adaptable); every nn.Linear, and a model without such modules, is treated as before."""
 import argparse
 import json
 import os
+import re
 import sys
 from collections import defaultdict
 from typing import Dict, Iterable, List, Optional
@@ -30,8 +37,18 @@ if __package__ in (None, ""):  # run as a script: make the package importable un
     import gptq_gguf_toolkit_amd  # noqa: F401
     __package__ = "gptq_gguf_toolkit_amd"
 
-from . import dist_utils, level_db, metrics, ops as _ops  # noqa: E402
+from . import dist_utils, level_db, metrics, moe_calibration, packed_experts, ops as _ops  # noqa: E402
 from .model_utils import LINEAR_LAYERS, ForwardInterrupt, InputCollector, _to, select_layers  # noqa: E402
+
+
+def _count_tokens(input_args, input_kwargs) -> int:
+    """The calibration tokens of the collected block inputs: rows of the hidden states, summed over the samples."""
+    n = 0
+    for args, kwargs in zip(input_args, input_kwargs):
+        x = args[0] if len(args) > 0 else kwargs.get("hidden_states")
+        if isinstance(x, torch.Tensor) and x.dim() >= 2:
+            n += x.numel() // x.shape[-1]
+    return max(n, 1)
 
 
 def _single_rank():
@@ -110,6 +127,90 @@ class LayerErrorEstimator:
         return _ops.quad_form(self.W.detach(), self.hessian(), W_c) / self.norm()
 
 
+class ExpertUnitsEstimator:
+    """The three units `<experts module>.{gate,up,down}_proj` of one fused experts module (gate_up_proj [E, 2I, H], down_proj
+    [E, H, I]) while a moe_calibration.CalibExperts stands in for it: per expert one Hessian for w1 and w3, which share an
+    input, and one for w2, each a view of a stacked [E, C, C] fp32 buffer, all with ONE scale:
+
+        H_e = (2/N) sum_{tokens routed to e} x^T x,    N = the number of calibration tokens, the same for every expert,
+
+    so that err(unit) = sum_e num_e / sum_e den_e is the unit's calibration-weighted output error: an expert that sees more
+    tokens weighs more (per-expert normalisation by n_e would weigh all experts alike, which is not what the search's
+    fitness sees).  An expert no token reaches keeps H_e = 0, which the kernel reads as the identity."""
+    ROLES = {"gate_proj": "in", "up_proj": "in", "down_proj": "mid"}
+
+    def __init__(self, name: str, original: nn.Module, roles: List[str], n_tokens: int, buffers: dict, ordinal: int = 0):
+        self.name, self.original, self.roles = name, original, list(roles)
+        self.E, self.hidden, self.inter = (int(n) for n in original.down_proj.shape)
+        self.alpha = 2.0 / n_tokens
+        dev = original.down_proj.device
+        self.H = {}
+        for kind, C in (("in", self.hidden), ("mid", self.inter)):
+            if any(self.ROLES[r] == kind for r in self.roles):
+                key = (kind, self.E, C, dev, ordinal)  # ordinal: the module's place in its block -- two experts modules of
+                if key not in buffers:                 # one shape under one block never share storage; once per role for the walk
+                    buffers[key] = torch.empty((self.E, C, C), device=dev, dtype=torch.float32)
+                self.H[kind] = buffers[key].zero_()
+        self._norm = {}
+
+    def hooks(self, stand_in) -> list:
+        """Forward pre-hooks on the synthesized children (CalibExperts fires pre-hooks only): w1 feeds the shared Hessian
+        of w1 / w3, w2 its own."""
+        def feed(H):
+            def _hook(_, inp):
+                x = inp[0].reshape(-1, inp[0].shape[-1])
+                if x.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                    x = x.float()
+                _ops.h_accumulate(H, x if x.is_contiguous() else x.contiguous(), 1.0, self.alpha)
+            return _hook
+
+        out = []
+        for e in range(self.E):
+            ex = stand_in.expert(e)
+            if "in" in self.H:
+                out.append(ex.w1.register_forward_pre_hook(feed(self.H["in"][e])))
+            if "mid" in self.H:
+                out.append(ex.w2.register_forward_pre_hook(feed(self.H["mid"][e])))
+        return out
+
+    def weight(self, role: str) -> torch.Tensor:
+        """The unit's [E, R, C] tensor: a view of the fused parameter, read in place."""
+        o, I = self.original, self.inter
+        return {"gate_proj": o.gate_up_proj.detach()[:, :I], "up_proj": o.gate_up_proj.detach()[:, I:],
+                "down_proj": o.down_proj.detach()}[role]
+
+    def numel(self, role: str) -> int:
+        return self.weight(role).numel()
+
+    def _quad(self, role: str, W_c: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """sum_e of the E quadratic forms, fp64 on the device."""
+        W, H = self.weight(role), self.H[self.ROLES[role]]
+        if -(-W.shape[1] // 128) * (W.shape[2] // 128) <= GROUPED_MAX_TILES_PER_EXPERT:
+            return _ops.quad_form_experts(W, H, W_c).sum()
+        return torch.stack([_ops.quad_form(W[e], H[e], None if W_c is None else W_c[e]) for e in range(self.E)]).sum()
+
+    @torch.no_grad()
+    def estimate(self, role: str, W_c: torch.Tensor) -> torch.Tensor:
+        """sum_e num_e / sum_e den_e as a 0-dim fp64 tensor on the device (no host read); the denominator once per unit."""
+        W = self.weight(role)
+        if tuple(W_c.shape) != tuple(W.shape):
+            raise ValueError(f"{self.name}.{role}: the compressed unit has shape {tuple(W_c.shape)}, the experts "
+                             f"{tuple(W.shape)}")
+        if role not in self._norm:
+            self._norm[role] = self._quad(role)
+        return self._quad(role, W_c) / self._norm[role]
+
+
+# The grouped call (ops.quad_form_experts: two launches) scores a unit whose experts have at most this many 128 x 128 tiles
+# each, the per-expert ops.quad_form loop (2 E launches) a unit of larger experts; the values are the same bit for bit.
+# profiles/quad_form_experts_rate.txt: at 96 tiles per expert (E = 128, 768 x 2048 and 2048 x 768) one expert leaves most of
+# the device idle and the grouped call takes 0.16 - 0.18x the loop's time; at 3584 tiles per expert (E = 8, 14336 x 4096 and
+# 4096 x 14336) every expert fills the device by itself and the grouped call takes 1.12 - 1.14x (presumably because the
+# loop's concurrent tiles share ONE panel of H where the grouped launch reads E; not profiled).  Nothing between was measured: the threshold is two rounds of the
+# 512 workgroups the device holds at once (256 CUs x 2), below which a single expert's launch ends in a partly filled round.
+GROUPED_MAX_TILES_PER_EXPERT = 1024
+
+
 class ErrorEstimator:
 
     def __init__(
@@ -171,6 +272,9 @@ class ErrorEstimator:
             for module in pre_blocks:
                 module.cpu()
 
+        n_tokens = _count_tokens(input_args, input_kwargs)  # the common scale of every expert Hessian
+        moe_calibration.reset_verdicts()  # every walk re-verifies the routed forward on its own first inputs
+        unit_buffers = {}
         all_errors = defaultdict(dict)
         for block_id, block in enumerate(blocks):
             if self.verbose:
@@ -179,34 +283,47 @@ class ErrorEstimator:
             layer_prefix = f"{self.block_modules}.{block_id}."
             layers = select_layers(self.model, layer_prefix, self.target_modules, LINEAR_LAYERS)  # a conv raises below
             handles, hooks, seen = self._prepare_hooks_and_handles(layers)
-            for i, (inp_args, inp_kwargs) in enumerate(zip(input_args, input_kwargs)):
-                inp_args, inp_kwargs = _to(inp_args, device=device), _to(inp_kwargs, device=device)
-                out = block(*inp_args, **inp_kwargs)
-                seen.clear()
-                out = out[0] if isinstance(out, (list, tuple)) else out
-                if self.cpu_offload_activations:
-                    out = out.cpu()
-                # only the first input argument changes from block to block
-                if len(inp_args) > 0:
-                    input_args[i] = (out, *inp_args[1:])
-                elif "hidden_states" in inp_kwargs:
-                    input_kwargs[i] = {**input_kwargs[i], "hidden_states": out}
-                else:
-                    raise ValueError("Unsupported block input format.")
+            installed, units, unit_hooks = [], [], []
+            try:  # the model gets its own experts modules back whatever happens in between
+                units, unit_hooks = self._install_expert_units(layer_prefix, device, n_tokens, unit_buffers, installed)
+                for i, (inp_args, inp_kwargs) in enumerate(zip(input_args, input_kwargs)):
+                    inp_args, inp_kwargs = _to(inp_args, device=device), _to(inp_kwargs, device=device)
+                    out = block(*inp_args, **inp_kwargs)
+                    seen.clear()
+                    out = out[0] if isinstance(out, (list, tuple)) else out
+                    if self.cpu_offload_activations:
+                        out = out.cpu()
+                    # only the first input argument changes from block to block
+                    if len(inp_args) > 0:
+                        input_args[i] = (out, *inp_args[1:])
+                    elif "hidden_states" in inp_kwargs:
+                        input_kwargs[i] = {**input_kwargs[i], "hidden_states": out}
+                    else:
+                        raise ValueError("Unsupported block input format.")
+            finally:
+                for h in unit_hooks:
+                    h.remove()
+                moe_calibration.restore(installed)
             for h in hooks.values():
                 h.remove()
             self.hessians_built += sum(h.shared_H_with is None for h in handles.values())
+            self.hessians_built += sum(u.E * len(u.H) for u in units)
             block_errors = self._estimate_errors_group(handles)
+            numel = {k: handles[k].W.numel() for k in block_errors}
+            for u in units:
+                unit_errors = self._estimate_unit_errors(u)
+                block_errors.update(unit_errors)
+                numel.update({k: u.numel(k.rpartition(".")[2]) for k in unit_errors})
             if group_by_numel:
                 for k, v in block_errors.items():
-                    all_errors[handles[k].W.numel()][k] = v
+                    all_errors[numel[k]][k] = v
             else:
                 all_errors[-1].update(block_errors)
             for h in handles.values():
                 h.reset()
             if self.cpu_offload_modules:
                 block = block.cpu()
-            del handles, hooks
+            del handles, hooks, units
         if has_cache:
             self.model.config.use_cache = use_cache
         return all_errors
@@ -237,6 +354,55 @@ class ErrorEstimator:
 
     def _create_handle(self, layer):
         return LayerErrorEstimator(layer)
+
+    def _has_unit(self, name: str) -> bool:
+        if self.level_store is not None and name not in self.level_store.units:
+            return False
+        return level_db.has_layer(self.compressed_weights_path, name)
+
+    def _install_expert_units(self, layer_prefix: str, device, n_tokens: int, buffers: dict, installed: list):
+        """Put a CalibExperts in place of every adaptable fused experts module under the prefix that has a unit
+        `<module>.{gate,up,down}_proj` which target_modules matches and the database holds; -> (their
+        ExpertUnitsEstimators, the hooks on the synthesized children).  `installed` collects moe_calibration.restore's
+        records as they are made.  "routed" on the GPU in 16-bit, else "loop": the Quantizer's rule, and CalibExperts
+        verifies routed against loop on the first input of every class as it does there."""
+        units, hooks = [], []
+        root = layer_prefix.rstrip(".")
+        for name, layer in list(self.model.get_submodule(root).named_modules(prefix=root)):
+            if not packed_experts.experts_shaped(layer) or moe_calibration.why_not_adaptable(layer):
+                continue
+            roles = [r for r in level_db.EXPERT_UNIT_ROLES
+                     if re.search(self.target_modules, f"{name}.{r}") and self._has_unit(f"{name}.{r}")]
+            if not roles:
+                continue
+            routed = torch.device(device).type == "cuda" and layer.down_proj.dtype in (torch.float16, torch.bfloat16)
+            parent_name, _, leaf = name.rpartition(".")
+            parent = self.model.get_submodule(parent_name)
+            stand_in = moe_calibration.CalibExperts(layer, "routed" if routed else "loop")
+            setattr(parent, leaf, stand_in)
+            installed.append((parent, leaf, layer, name))
+            unit = ExpertUnitsEstimator(name, layer, roles, n_tokens, buffers, ordinal=len(units))
+            hooks += unit.hooks(stand_in)
+            units.append(unit)
+        return units, hooks
+
+    def _estimate_unit_errors(self, unit: ExpertUnitsEstimator) -> Dict[str, List[float]]:
+        errors = {}
+        for role in unit.roles:
+            name = f"{unit.name}.{role}"
+            ldir = level_db.layer_dir(self.compressed_weights_path, name)
+            files = level_db.level_files(ldir)
+            if self.level_store is not None:
+                vals = [unit.estimate(role, self.level_store.level_tensor(name, f)) for f in files]
+            else:
+                vals = [unit.estimate(role, level_db.load_level(os.path.join(ldir, f), unit.original.down_proj.device,
+                                                                self.compressed_weights_path)) for f in files]
+            # the E-element sums and the division ran on the device in fp64: ONE host read per unit
+            errors[name] = torch.stack(vals).tolist() if vals else []
+            self.levels[name] = files
+            if self.verbose:
+                dist_utils.print_on_main(f"{name}: " + "  ".join(f"{f[:-4]} {e:.4e}" for f, e in zip(files, errors[name])))
+        return errors
 
     def _estimate_errors_group(self, handles: Dict[str, LayerErrorEstimator]) -> Dict[str, List[float]]:
         errors = {}

@@ -595,13 +595,15 @@ def quantize_q8_0(x: torch.Tensor, row_src: Optional[torch.Tensor] = None) -> to
 
 
 def quantize_iq4(x: torch.Tensor, q_type: int, importance: Optional[torch.Tensor] = None,
-                 row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 row_src: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[R, C] fp32 / fp16 / bf16 on the device -> IQ4_NL (q_type 20, C % 32 == 0) blocks uint8 [R, C/32*18] or IQ4_XS (23,
     C % 256 == 0) blocks uint8 [R, C/256*136] (gq_quantize_iq4, include/gptq_gguf_iq4_encode.h): byte for byte
     gguf_writer.quantize_iq4 of x widened to fp32.  importance: None, or fp32 [C] on x's device, finite and >= 0, one weight
     per column (the diagonal of the calibration Hessian is one).  row_src (int32 [R] on the device): out[r] =
-    encode(x[row_src[r]]); every index must lie in [0, R) -- the kernel does not check."""
-    _need_cuda(x, row_src)
+    encode(x[row_src[r]]); every index must lie in [0, R) -- the kernel does not check.  out: None, or a contiguous uint8
+    tensor of exactly the result's bytes on x's device, 16-byte aligned (a slot of a stacked buffer), written in place and
+    returned as the [R, row bytes] view."""
+    _need_cuda(x, row_src, out)
     if int(q_type) not in (_cabi.IQ4_NL, _cabi.IQ4_XS):
         raise _cabi.GQError(f"quantize_iq4: q_type {int(q_type)} is neither IQ4_NL ({_cabi.IQ4_NL}) nor IQ4_XS ({_cabi.IQ4_XS})")
     bs, ts = GGML_QUANT_SIZES[int(q_type)]
@@ -624,7 +626,14 @@ def quantize_iq4(x: torch.Tensor, q_type: int, importance: Optional[torch.Tensor
         importance = importance.contiguous()
         if importance.data_ptr() % 16:  # (a view into a larger buffer)
             importance = importance.clone()
-    out = torch.empty(R, C // bs * ts, dtype=torch.uint8, device=x.device)
+    if out is None:
+        out = torch.empty(R, C // bs * ts, dtype=torch.uint8, device=x.device)
+    else:
+        if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != R * (C // bs * ts) or out.device != x.device \
+                or out.data_ptr() % 16:
+            raise _cabi.GQError(f"quantize_iq4: out must be a contiguous, 16-byte aligned uint8 tensor of {R * (C // bs * ts)} "
+                                f"bytes on {x.device}; got {out.dtype} {tuple(out.shape)}")
+        out = out.view(R, C // bs * ts)
     check(lib().gq_quantize_iq4(_ptr(x), _DT[x.dtype], R, C, int(q_type), _ptr(importance), _ptr(row_src), _ptr(out), _stream(x)),
           "gq_quantize_iq4")
     return out
@@ -669,10 +678,12 @@ def gptq_quantize_iq4(W: torch.Tensor, U: torch.Tensor, q_type: int, block_size=
 
 
 def pack_iq4(q_type: int, qweight: torch.Tensor, d: torch.Tensor, ls: Optional[torch.Tensor],
-             row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+             row_src: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The outputs of gptq_quantize_iq4 as block bytes (gq_pack_iq4): uint8 [R, C/256*136] (IQ4_XS) or [R, C/32*18] (IQ4_NL).
-    row_src (int32 [R] on the device): out[r] = the blocks of row row_src[r]; every index must lie in [0, R)."""
-    _need_cuda(qweight, d, ls, row_src)
+    row_src (int32 [R] on the device): out[r] = the blocks of row row_src[r]; every index must lie in [0, R).  out: None, or
+    a contiguous, 16-byte aligned uint8 tensor of exactly the result's bytes on qweight's device (a slot of a stacked buffer),
+    written in place and returned as the [R, row bytes] view."""
+    _need_cuda(qweight, d, ls, row_src, out)
     xs = _iq4_type("pack_iq4", q_type)
     bs, ts = GGML_QUANT_SIZES[int(q_type)]
     if qweight.dtype != torch.uint8 or qweight.dim() != 2 or qweight.shape[1] % bs or qweight.shape[1] < bs:
@@ -688,7 +699,14 @@ def pack_iq4(q_type: int, qweight: torch.Tensor, d: torch.Tensor, ls: Optional[t
         row_src = row_src.contiguous()
     qweight, d = qweight.contiguous(), d.contiguous()
     ls = ls.contiguous() if xs else None
-    out = torch.empty(R, C // bs * ts, dtype=torch.uint8, device=qweight.device)
+    if out is None:
+        out = torch.empty(R, C // bs * ts, dtype=torch.uint8, device=qweight.device)
+    else:
+        if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != R * (C // bs * ts) \
+                or out.device != qweight.device or out.data_ptr() % 16:
+            raise _cabi.GQError(f"pack_iq4: out must be a contiguous, 16-byte aligned uint8 tensor of {R * (C // bs * ts)} bytes "
+                                f"on {qweight.device}; got {out.dtype} {tuple(out.shape)}")
+        out = out.view(R, C // bs * ts)
     check(lib().gq_pack_iq4(int(q_type), R, C, _ptr(qweight), _ptr(d), _ptr(ls), _ptr(row_src), _ptr(out), _stream(qweight)),
           "gq_pack_iq4")
     return out
@@ -926,6 +944,60 @@ def quad_form(A: torch.Tensor, H: torch.Tensor, B: Optional[torch.Tensor] = None
     ldb = 0 if B is None else (B.stride(0) if R > 1 else max(B.stride(0), C))
     check(lib().gq_quad_form(_ptr(A), _DT[A.dtype], lda, _ptr(B), _DT[B.dtype] if B is not None else 0, ldb, _ptr(H), R, C,
                              _ptr(out), _ptr(ws), ws.numel() * ws.element_size(), _stream(A)), "gq_quad_form")
+    return out
+
+
+# ---- layer error estimate of a stacked expert tensor (gq_quad_form_experts): quad_form per expert, two launches ----
+QUAD_EXPERTS_MAX = _cabi.QUAD_EXPERTS_MAX
+
+
+def _qf_experts(t: torch.Tensor) -> torch.Tensor:
+    """t [E, R, C] as the kernel can read it: every t[e] as _qf_rows wants it, the expert stride a multiple of 16 bytes and
+    no smaller than a matrix; a copy only when that fails (the halves of a fused gate_up_proj are read in place)."""
+    E, R, C = t.shape
+    es = t.element_size()
+    ld = t.stride(1) if R > 1 else max(t.stride(1), C)
+    rows = t.stride(2) == 1 and t.data_ptr() % 16 == 0 and (R == 1 or (t.stride(1) >= C and t.stride(1) * es % 16 == 0))
+    if rows and (E == 1 or (t.stride(0) >= (R - 1) * ld + C and t.stride(0) * es % 16 == 0)):
+        return t
+    return t.contiguous()
+
+
+def quad_form_experts(A: torch.Tensor, H: torch.Tensor, B: Optional[torch.Tensor] = None,
+                      ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[e] = quad_form(A[e], H[e], B[e]) for the E experts of a stacked tensor, bit for bit, as an fp64 [E] device tensor
+    in two launches whatever E (gq_quad_form_experts).  A, B [E, R, C] fp32 / fp16 / bf16 views, each in its own dtype and
+    with its own strides (`gate_up_proj[:, :I]` and `gate_up_proj[:, I:]` are read in place; a view is copied only when its
+    rows or its expert stride are not 16-byte aligned); H [E, C, C] fp32 contiguous, every H[e] symmetric, a zero on a
+    diagonal counts as 1 (an all-zero H[e] is the identity) and H is not written.  No host read."""
+    _need_cuda(A, H, B, ws)
+    if A.dim() != 3 or A.dtype not in _DT or 0 in A.shape or (B is not None and (B.shape != A.shape or B.dtype not in _DT)):
+        raise _cabi.GQError(f"quad_form_experts: A and B must be [E, R, C] fp32 / fp16 / bf16 tensors of one shape; got "
+                            f"{A.dtype} {tuple(A.shape)} and {None if B is None else (B.dtype, tuple(B.shape))}")
+    E, R, C = A.shape
+    for t in (H, B, ws):
+        if t is not None and t.device != A.device:
+            raise _cabi.GQError(f"quad_form_experts: every tensor must be on A's device {A.device}; got one on {t.device}")
+    if ws is not None and (not ws.is_contiguous() or ws.data_ptr() % 8):
+        raise _cabi.GQError("quad_form_experts: ws must be contiguous and 8-byte aligned")
+    if H.dtype != torch.float32 or tuple(H.shape) != (E, C, C) or not H.is_contiguous():
+        raise _cabi.GQError(f"quad_form_experts: H must be a contiguous fp32 [{E}, {C}, {C}] tensor; got {H.dtype} "
+                            f"{tuple(H.shape)}")
+    A = _qf_experts(A)
+    B = _qf_experts(B) if B is not None else None
+    need = int(lib().gq_quad_form_experts_workspace_bytes(E, R, C))
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = _ws(need, A.device)
+    out = torch.empty(E, dtype=torch.float64, device=A.device)
+
+    def geom(t):  # (ld, expert stride); torch reports any stride for an extent of 1
+        ld = t.stride(1) if R > 1 else max(t.stride(1), C)
+        return ld, (t.stride(0) if E > 1 else R * ld)
+
+    (lda, sa), (ldb, sb) = geom(A), (geom(B) if B is not None else (0, 0))
+    check(lib().gq_quad_form_experts(_ptr(A), _DT[A.dtype], lda, sa, _ptr(B), _DT[B.dtype] if B is not None else 0, ldb, sb,
+                                     _ptr(H), E, R, C, _ptr(out), _ptr(ws), ws.numel() * ws.element_size(), _stream(A)),
+          "gq_quad_form_experts")
     return out
 
 

@@ -121,6 +121,10 @@ def parse_args(argv=None):
     p.add_argument("--level_db_iq4_importance", choices=["hessian", "none"], default="hessian",
                    help="with --level_db_iq4: the importance of a column is the diagonal of the Linear's calibration Hessian "
                         "(default), or none: every level is encoded unweighted")
+    p.add_argument("--level_fused_experts", action="store_true",
+                   help="with --levels: also build the levels of fused experts (transformers 5.x MixtralExperts) that "
+                        "--quantizable_modules names, through the stand-in quantize() uses; trees under the checkpoint's names, "
+                        "stacked expert units in --level_db.  Without it such a model is refused")
     args = p.parse_args(argv)
     problem = levels_problem(args)
     if problem:
@@ -140,6 +144,8 @@ def levels_problem(args, world_size=None):
     if getattr(args, "level_db_iq4_method", "rtn") != "rtn" and not getattr(args, "level_db_iq4", None):
         return "--level_db_iq4_method needs --level_db_iq4: there is no IQ4 level to build"
     if args.levels is None:
+        if getattr(args, "level_fused_experts", False):
+            return "--level_fused_experts needs --levels: it is an option of the one-pass level build"
         if level_db is not None:
             return "--level_db needs --levels: the level database is written by the one-pass level build"
         return "--propagate_level needs --levels" if args.propagate_level is not None else None
@@ -262,7 +268,7 @@ def _run(args):
                                   level_db=args.level_db, trees=not args.level_db_only, level_db_model=args.model_name_or_path,
                                   level_db_q8_0=args.level_db_q8_0, level_db_iq4=tuple(args.level_db_iq4),
                                   level_db_iq4_importance=args.level_db_iq4_importance,
-                                  level_db_iq4_method=args.level_db_iq4_method)
+                                  level_db_iq4_method=args.level_db_iq4_method, fused_experts=args.level_fused_experts)
     else:
         quantizer.quantize(quant_config)
     torch.cuda.synchronize()

@@ -639,20 +639,46 @@ class _LevelDbSink:
         self._iq4_imp: Dict[str, Optional[torch.Tensor]] = {}  # "gptq": diag(H) of a Linear between its two hooks
         self.hp = json.load(open(self.dir_model / "config.json"))
         arch = self.hp.get("architectures", ["LlamaForCausalLM"])[0]
-        if arch not in ("LlamaForCausalLM", "LLaMAForCausalLM", "MistralForCausalLM") or self.hp.get("num_local_experts"):
-            raise NotImplementedError(f"level_db: {arch} (dense Llama family only; expert stacking in the database is not built)")
+        self.n_experts = int(self.hp.get("num_local_experts") or 0)
+        dense = ("LlamaForCausalLM", "LLaMAForCausalLM", "MistralForCausalLM")
+        if not ((arch in dense and not self.n_experts) or (arch == "MixtralForCausalLM" and self.n_experts)):
+            raise NotImplementedError(f"level_db: {arch} (the dense Llama family, and MixtralForCausalLM with num_local_experts)")
         self.n_head = self.hp["num_attention_heads"]
         self.n_kv = self.hp.get("num_key_value_heads", self.n_head)
         _, self.rope_type = rope_setup(self.hp)
         self.tensor_of: Dict[str, str] = {}  # HF module name -> GGUF tensor name, for what the checkpoint holds
+        # checkpoint name of an expert matrix (model.layers.N.block_sparse_moe.experts.<e>.w1) -> (unit tensor
+        # blk.N.ffn_gate_exps.weight, slot e): the packer stacks the E matrices of a block and role into that one tensor
+        self.expert_of: Dict[str, Tuple[str, int]] = {}
         order = ["rope_freqs.weight"] if self.rope_type == "llama3" else []
-        self.total_params = 0
+        self.total_params = self.expert_params = 0
+        seen: Dict[str, int] = {}
         for name, shape, _ in iter_hf_entries(self.dir_model):
             if name.endswith(SKIPPED_HF_TENSORS):
                 continue
-            self.total_params += int(np.prod(shape)) if len(shape) else 1
+            numel = int(np.prod(shape)) if len(shape) else 1
+            self.total_params += numel
+            if ".block_sparse_moe.experts." in name:  # (the converter's own rule and name arithmetic)
+                parts = name.split(".")
+                bid, xid, wid = int(parts[2]), int(parts[5]), parts[6]
+                unit = map_tensor_name(f"layers.{bid}.feed_forward.experts.{wid}.weight")
+                if len(shape) != 2 or shape[0] % 64:
+                    raise NotImplementedError(f"level_db: {name} has shape {tuple(shape)}; an expert matrix whose rows are no "
+                                              f"multiple of 64 cannot be packed into a slot of {unit}")
+                self.expert_params += numel
+                self.expert_of[name.removesuffix(".weight")] = (unit, xid)
+                seen[unit] = seen.get(unit, 0) + 1
+                if seen[unit] == self.n_experts:  # the converter adds the merged tensor with its last expert
+                    order.append(unit)
+                continue
             self.tensor_of[name.removesuffix(".weight")] = map_tensor_name(name)
             order.append(map_tensor_name(name))
+        short = sorted(u for u, n in seen.items() if n != self.n_experts)
+        if short:
+            raise ValueError(f"level_db: {short[0]} has {seen[short[0]]} expert matrices in the checkpoint, config.json says "
+                             f"{self.n_experts}")
+        # (unit tensor, ggml type) -> [buffer [E, R, C / 256 * type_size], slots filled, path]; allocated on the first slice
+        self.units: Dict[Tuple[str, int], list] = {}
         self.writer = level_db.LevelDbWriter(db)
         self.writer.set_order(order)
         self.packed = set()   # HF module names whose levels are in the database
@@ -671,6 +697,9 @@ class _LevelDbSink:
         dev, C = q.device, q.shape[1]
         self.device = dev  # (finish() encodes the Q8_0 level where the walks ran)
         tensors = [None if mem is None else self.tensor_of.get(mem[0]) for mem in members]
+        slots = [None if mem is None else self._slot_of(mem[0]) for mem in members]
+        if any(sl is not None for sl in slots):
+            return self._pack_expert_walk(stacked, bands, members, tensors, slots)
         if all(t is None for t in tensors):
             return []
         r0, srcs = 0, []
@@ -691,10 +720,104 @@ class _LevelDbSink:
             r0 = r1
         return outs
 
+    # ---- stacked expert units ----
+    def _slot_of(self, name: str) -> Optional[Tuple[str, int]]:
+        """(unit tensor, slot) of a synthesized expert Linear `...mlp.experts.<e>.w1|w3|w2` (or its checkpoint name)."""
+        return self.expert_of.get(moe_calibration.checkpoint_name(name))
+
+    def _unit_slice(self, unit: str, e: int, t: int, R: int, C: int, device) -> torch.Tensor:
+        """Slot e of the unit's level of type t as a flat byte view: the device buffer [E, R, C / block * type_size] is
+        allocated, and the level registered with its 3-D shape, when the first slice is asked for."""
+        from .gguf_writer import GGML_QUANT_SIZES
+        bs, ts = GGML_QUANT_SIZES[int(t)]
+        rec = self.units.get((unit, int(t)))
+        cuda = torch.device(device).type == "cuda"
+        if rec is None:
+            buf = torch.empty((self.n_experts, R, C // bs * ts), dtype=torch.uint8, device=device)
+            born = None
+            if cuda:  # where, and after what, the buffer came to be: see the rule below
+                born = (torch.cuda.current_stream(device), torch.cuda.Event())
+                born[1].record(born[0])
+            rec = self.units[(unit, int(t))] = [buf, set(), self.writer.register(unit, (self.n_experts, R, C), int(t)), born]
+        buf, filled, _, born = rec
+        # THE RULE for a buffer shared by the lanes of a block.  It is allocated under whichever lane asks first, and the
+        # caching allocator may hand that lane a block whose earlier tenant (a working copy, a workspace of an earlier walk)
+        # is still in use by kernels queued on that SAME stream -- safe there, in stream order, and nowhere else.  So a lane
+        # on another stream waits for the event recorded on the allocating stream at allocation before its first write, and
+        # the buffer is marked as used on that lane's stream so that it is not reused under it once it is dropped.
+        if born is not None:
+            here = torch.cuda.current_stream(device)
+            if here != born[0]:
+                here.wait_event(born[1])
+                buf.record_stream(here)
+        if tuple(buf.shape[1:]) != (R, C // bs * ts) or e in filled or not 0 <= e < self.n_experts:
+            raise RuntimeError(f"level_db: slot {e} of {unit} (type {int(t)}) is out of range, filled twice or of another shape "
+                               f"than {tuple(buf.shape)}")
+        filled.add(e)
+        return buf[e].view(-1)
+
+    def _pack_expert_walk(self, stacked, bands, members, tensors, slots):
+        """pack_walk for a walk with expert bands: band k goes straight into slot e of its unit's buffer (caller-owned outs
+        of ONE gq_pack_bands launch; with rows a multiple of 64 every slice is 16-byte aligned).  No rotary row gather, no
+        per-expert temporary.  A stale band, and a band of a plain Linear in the same walk, get a buffer of their own."""
+        from .gguf_writer import GGML_QUANT_SIZES
+        q = stacked[0]
+        dev, C = q.device, q.shape[1]
+        outs, srcs, r0 = [], [], 0
+        for (r1, t), mem, tensor, slot in zip(bands, members, tensors, slots):
+            if (r1 - r0) % 64:
+                raise NotImplementedError(f"level_db: a band of {r1 - r0} rows next to an expert band (multiples of 64 only)")
+            if slot is not None:
+                outs.append(self._unit_slice(slot[0], slot[1], int(t), r1 - r0, C, dev))
+                srcs.append(None)
+            else:
+                outs.append(torch.empty((r1 - r0) * (C // 256) * GGML_QUANT_SIZES[int(t)][1], dtype=torch.uint8, device=dev))
+                srcs.append(self._row_src(tensor, r1 - r0, dev) if tensor is not None else None)
+            r0 = r1
+        outs = _ops.pack_bands(stacked, bands, outs, srcs)
+        r0 = 0
+        for (r1, t), mem, tensor, slot, out in zip(bands, members, tensors, slots, outs):
+            if slot is None and tensor is not None:
+                path = self.writer.register(tensor, (r1 - r0, C), int(t))
+                self.items.append((path, RAW_BYTES, (out.view(-1),)))
+                self.packed.add(mem[0])
+            r0 = r1
+        return outs
+
+    def _encode_iq4_expert(self, slot, weight: torch.Tensor, importance: Optional[torch.Tensor]) -> List[torch.Tensor]:
+        """encode_iq4 for one expert matrix: each type's bytes go into slot e of the unit's buffer."""
+        from .gguf_writer import GGML_QUANT_SIZES
+        w = weight.detach()
+        if w.dim() != 2 or w.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise NotImplementedError(f"level_db_iq4: {slot[0]} has a {w.dtype} expert weight of shape {tuple(w.shape)}")
+        w = w.contiguous()
+        outs = []
+        for t in self.iq4:
+            if w.shape[1] % GGML_QUANT_SIZES[t][0]:
+                continue
+            out = self._unit_slice(slot[0], slot[1], t, w.shape[0], w.shape[1], w.device)
+            outs.append(_ops.quantize_iq4(w, t, importance, None, out=out))
+        return outs
+
+    def end_group(self) -> None:
+        """The block's _quant_group is over: every started (unit, level) must hold all E slices -- a hole raises -- and its
+        bytes are queued for the saver."""
+        for (unit, t), (buf, filled, path, _) in self.units.items():
+            if len(filled) != self.n_experts:
+                missing = sorted(set(range(self.n_experts)) - filled)
+                raise RuntimeError(f"level_db: {unit} (type {t}) was started but slots {missing} of {self.n_experts} were never "
+                                   f"filled: a unit is written whole or not at all")
+            self.items.append((path, RAW_BYTES, (buf.view(-1),)))
+            self.packed.add(unit)
+        self.units = {}
+
     def encode_iq4(self, name: str, weight: torch.Tensor, importance: Optional[torch.Tensor]) -> List[torch.Tensor]:
         """The IQ4 levels of HF module `name` from its unmodified `weight` [R, C] on the current stream: one gq_quantize_iq4
         launch per type, the bytes booked and queued like a walk's.  Nothing for a module the database does not hold."""
         from .gguf_writer import GGML_QUANT_SIZES
+        slot = self._slot_of(name)
+        if slot is not None and self.iq4:
+            return self._encode_iq4_expert(slot, weight, importance)
         tensor = self.tensor_of.get(name)
         if tensor is None or not self.iq4:
             return []
@@ -729,10 +852,10 @@ class _LevelDbSink:
         factorisation and column flags, handle.layer.weight still the block's unmodified weight.  Per type a fresh working
         copy with the dead columns of the first one (as GPTQ.compute_levels makes its later levels'), one walk, one pack."""
         imp = self._iq4_imp.pop(name, None)
-        tensor = self.tensor_of.get(name)
-        if tensor is None or not self.iq4:
+        tensor, slot = self.tensor_of.get(name), self._slot_of(name)
+        if (tensor is None and slot is None) or not self.iq4:
             return []
-        rows = self._row_src(tensor, handle.d_row, handle.W_device)
+        rows = self._row_src(tensor, handle.d_row, handle.W_device) if slot is None else None
         outs = []
         for t in self.iq4:
             if handle.d_col % 256:
@@ -740,9 +863,13 @@ class _LevelDbSink:
             handle.make_working_copy()
             _ops.w_prepare(handle._last_cf, handle.W)
             q, d, ls, _ = _ops.gptq_quantize_iq4(handle.W, handle._last_U, t, handle.block_size, imp)
-            blocks = _ops.pack_iq4(t, q, d, ls, rows)
-            path = self.writer.register(tensor, (handle.d_row, handle.d_col), t)
-            self.items.append((path, RAW_BYTES, (blocks.view(-1),)))
+            if slot is not None:  # packed straight into slot e of the unit's buffer
+                blocks = _ops.pack_iq4(t, q, d, ls, None,
+                                       out=self._unit_slice(slot[0], slot[1], t, handle.d_row, handle.d_col, q.device))
+            else:
+                blocks = _ops.pack_iq4(t, q, d, ls, rows)
+                path = self.writer.register(tensor, (handle.d_row, handle.d_col), t)
+                self.items.append((path, RAW_BYTES, (blocks.view(-1),)))
             outs += [blocks, handle.W]
         return outs
 
@@ -757,7 +884,7 @@ class _LevelDbSink:
                                           rope_freqs_llama3)
         w = self.writer
         kv = GGUFWriter(None, "llama")  # collects the key/value data; never written
-        add_model_metadata(kv, self.hp, self.dir_model, FTYPE["f16"][0], self.total_params, 0, self.vocab)
+        add_model_metadata(kv, self.hp, self.dir_model, FTYPE["f16"][0], self.total_params, self.expert_params, self.vocab)
         w.set_metadata(kv_records(kv.kv))
 
         def plain(tensor, data):
@@ -767,9 +894,29 @@ class _LevelDbSink:
 
         if self.rope_type == "llama3":
             plain("rope_freqs.weight", rope_freqs_llama3(self.hp))
+        pending: Dict[str, dict] = {}  # unit tensor -> {slot: the checkpoint's expert matrix}, until all E are read
         for name, _, get in iter_hf_entries(self.dir_model):
             base = name.removesuffix(".weight")
             if name.endswith(SKIPPED_HF_TENSORS):
+                continue
+            if base in self.expert_of:
+                unit, e = self.expert_of[base]
+                if unit in self.packed and not self.q8_0:
+                    continue
+                got = pending.setdefault(unit, {})
+                got[e] = get()
+                if len(got) < self.n_experts:
+                    continue
+                x = torch.stack([got[i] for i in range(self.n_experts)], dim=0)  # [E, R, C], as the converter stacks them
+                del pending[unit]
+                if unit in self.packed:  # the 8.5-bit level of a packed unit: [E R, C] through ONE gq_quantize_q8_0
+                    x = x.to(self.device)
+                    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+                        x = x.float()
+                    blocks = _ops.quantize_q8_0(x.view(-1, x.shape[-1]).contiguous(), None)
+                    w.add_level(unit, tuple(x.shape), GGMLType.Q8_0, blocks.view(x.shape[0], x.shape[1], -1).cpu().numpy())
+                else:
+                    plain(unit, x)
                 continue
             if base in self.packed:
                 if self.q8_0:  # the 8.5-bit level: RTN of the checkpoint's own weights, registered after the K-quant levels
@@ -829,7 +976,8 @@ class Quantizer:
     @torch.no_grad()
     def quantize_levels(self, levels, propagate, level_db: Optional[str] = None, trees: bool = True,
                         level_db_model: Optional[str] = None, level_db_vocab: bool = True, level_db_q8_0: bool = False,
-                        level_db_iq4=(), level_db_iq4_importance: str = "hessian", level_db_iq4_method: str = "rtn") -> None:
+                        level_db_iq4=(), level_db_iq4_importance: str = "hessian", level_db_iq4_method: str = "rtn",
+                        fused_experts: bool = False) -> None:
         """The level database in one pass: every quantizable module at every level of `levels`, one ordinary tree per level
         under <save_dir>/<LEVEL>/ (level_tree_name; same schema, same writer as quantize()).  The calibration forwards, the
         Hessians, the factorisations and the column walk are those of ONE run (BlockSchedule.quantize_levels).
@@ -849,6 +997,12 @@ class Quantizer:
         the importance of a column (`level_db_iq4_importance` "hessian"; "none": unweighted) -- _LevelDbSink.
         `level_db_iq4_method` "rtn" (default): round-to-nearest; "gptq": the IQ4 levels of every Linear come out of GPTQ's
         column walk on the IQ4 grid with the same importance (gq_gptq_quantize_iq4; embed / lm_head stay round-to-nearest).
+        `fused_experts=True`: fused experts (transformers 5.x MixtralExperts) that quantizable_modules names are walked as in
+        quantize() -- moe_calibration.CalibExperts per block, hooks on the synthesized experts.<e>.w1 / w3 / w2 Linears, the
+        propagated level written back through the views; every tree goes under the checkpoint's name
+        (<save_dir>/<LEVEL>/model.layers.N.block_sparse_moe.experts.<e>.w{1,2,3}), an expert no calibration token reaches has
+        H = I (its K-quant levels are round-to-nearest), and the database holds the stacked units.  Without it such a model
+        is refused, by name.
         Everything is refused before any work; a failed run leaves no database."""
         levels, propagate = check_levels(levels, propagate)
         if dist_utils.get_world_size() > 1:
@@ -863,9 +1017,14 @@ class Quantizer:
             raise ValueError("quantize_levels: level_db_iq4 needs level_db (the IQ4 levels are levels of the database)")
         check_iq4_levels(level_db_iq4, level_db_iq4_importance, level_db_iq4_method)
         fused = moe_calibration.named_fused_experts(self.model, self.block_modules + ".", self.quantizable_modules)
-        if fused:
+        if fused and not fused_experts:
             raise NotImplementedError(f"quantize_levels: {fused[0][0]} ({type(fused[0][1]).__name__}) keeps fused experts that "
-                                      "quantizable_modules names; the level build for MoE is not built (quantize() takes them)")
+                                      "quantizable_modules names; their level build is opt-in: pass fused_experts=True "
+                                      "(quant.py --level_fused_experts)")
+        for name, layer in fused:  # refused before any work, as install() would per block
+            why = moe_calibration.why_not_adaptable(layer)
+            if why:
+                raise NotImplementedError(f"{name} ({type(layer).__name__}): --quantizable_modules names its experts, but {why}")
         sink = None
         if level_db is not None:
             if os.environ.get("GQ_SAVE_SKIP") == "1":
@@ -1108,9 +1267,11 @@ class Quantizer:
             for n, per_level in sched.quantize_levels(levels, propagate, extra=after, pack=sink.pack_walk if sink else None,
                                                       before=before).items():
                 for t in levels if getattr(self, "_level_trees", True) else ():
-                    item = self._save(level_tree_name(t, n), t, *per_level[t], defer=True)
+                    item = self._save(level_tree_name(t, self._tree_names.get(n, n)), t, *per_level[t], defer=True)
                     if item is not None:
                         batch.append(item)
+            if sink is not None:
+                sink.end_group()  # (a unit with a hole raises here)
             if sink is not None and os.environ.get("GQ_SAVE_SKIP") != "1":
                 batch.extend(sink.take())
             self._saver.put_many(batch)
