@@ -65,6 +65,9 @@ SWITCH_EXPERTS_MAX_JOBS = 71  # GQ_SWITCH_EXPERTS_MAX_JOBS: jobs of one launch (
 # include/gptq_gguf_moe_errest.h: gq_quad_form for the E experts of a stacked tensor, each with its own Hessian (additive in the same way)
 EXPORTS_MOE_ERREST = ("gq_quad_form_experts_workspace_bytes", "gq_quad_form_experts")
 QUAD_EXPERTS_MAX = 256  # GQ_QUAD_EXPERTS_MAX: experts of one gq_quad_form_experts call
+# include/gptq_gguf_qknorm.h: Qwen3's per-head q / k RMSNorm and the rotary embedding of the calibration forward, one launch (additive in the same way)
+EXPORTS_QKNORM = ("gq_fwd_qk_norm_rope",)
+QK_NORM_HEAD_DIMS = (64, 128, 256)  # the head sizes gq_fwd_qk_norm_rope takes
 
 
 class GQError(RuntimeError):
@@ -193,6 +196,7 @@ def lib():
     L.gq_moe_route.argtypes = [vp, i64, i64, vp, vp, vp]
     L.gq_linear_packed_experts.argtypes = [ci, vp, i64, i64, i64, vp, i64, i64, vp, vp, i64, ci, vp, vp]
     L.gq_fwd_moe_combine.argtypes = [vp, vp, vp, vp, vp, ci, i64, i64, i64, i64, ci, vp, vp]
+    L.gq_fwd_qk_norm_rope.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, cf, ci, vp, vp]
     L.gq_level_switch_experts.argtypes = [ctypes.POINTER(SwitchExpertsJob), ci, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
@@ -202,7 +206,7 @@ def lib():
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_IQ4_GPTQ + EXPORTS_QGEMM +
-                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH + EXPORTS_MOE_ERREST):
+                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH + EXPORTS_MOE_ERREST + EXPORTS_QKNORM):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

@@ -8,6 +8,9 @@ those three with one gfx950 kernel each (csrc/gq_forward.hip) for the duration o
     LlamaRMSNorm.forward       -> ops.fwd_rmsnorm   (fp32 statistics, rounded to the dtype where the module rounds)
     apply_rotary_pos_emb       -> ops.fwd_rope      (per-op rounding of the eager expression)
     LlamaMLP.forward           -> down_proj(ops.fwd_silu_mul(gate_proj(x), up_proj(x)))
+    Qwen3Attention.forward     -> q_norm, k_norm and the rotary embedding of both through ONE ops.fwd_qk_norm_rope
+                                  (csrc/forward/gq_qk_norm_rope.hip; the per-head norms are 64 .. 256 wide, which the
+                                  RMSNorm kernels above do not take, so without it they are HF eager code)
 
 The Linear modules are still called through `nn.Module.__call__`, so the Hessian hooks see the same inputs.  Two guards
 (ADVICE r03): (1) the kernels were written for ONE definition of each function -- `_PINNED` holds the hashes of the
@@ -68,11 +71,17 @@ def _sha(fn) -> str:
 #   apply_rotary_pos_emb:  (q * cos) + (rotate_half(q) * sin), same for k, cos / sin unsqueezed at unsqueeze_dim
 #   rotate_half:           cat((-x[..., D/2:], x[..., :D/2]), -1)
 #   LlamaMLP.forward:      down_proj(act_fn(gate_proj(x)) * up_proj(x))
-_PINNED = {"norm": "3480f6ca9ea40b53", "rope": "d2c323856b661430", "rotate_half": "e011a50957282b58", "mlp": "1923407024d5de0b"}
+#   Qwen3Attention.forward (transformers' Qwen3, 5.x): q_norm(q_proj(x).view(B, L, -1, D)).transpose(1, 2), the same for
+#                          k with k_norm, v without a norm; apply_rotary_pos_emb(q, k, cos, sin); the cache update; the
+#                          attention interface; o_proj -- Qwen3RMSNorm.forward being LlamaRMSNorm.forward's text
+_PINNED = {"norm": "3480f6ca9ea40b53", "rope": "d2c323856b661430", "rotate_half": "e011a50957282b58", "mlp": "1923407024d5de0b",
+           "qwen3_attn": "d7e568784937795f"}
+QK_NORM_HEAD_DIMS = (64, 128, 256)  # include/gptq_gguf_qknorm.h
 
 _norm_verdict = {}  # (C, dtype, rows) -> True: the ordered kernel reproduced the eager module bit for bit on first use
 _rope_verdict = {}  # (L, heads q, heads k, D, dtype, batch) -> True: fwd_rope == the eager expression on first use
 _mlp_verdict = {}   # (intermediate size, dtype, rows) -> True: fwd_silu_mul == act_fn(g) * u on first use
+_qkn_verdict = {}   # _qkn_key(...) -> True: fwd_qk_norm_rope == q_norm / k_norm / apply_rotary_pos_emb (outputs and statistics)
 
 
 def reset_verdicts():
@@ -80,6 +89,7 @@ def reset_verdicts():
     _norm_verdict.clear()
     _rope_verdict.clear()
     _mlp_verdict.clear()
+    _qkn_verdict.clear()
 
 
 def _rmsnorm_forward(orig, allow_free_order: bool):
@@ -173,7 +183,71 @@ def _mlp_forward(orig):
     return forward
 
 
-def _targets(free_order_norm: bool = True) -> List[Tuple[object, str, object]]:
+def _qkn_key(B, L, Hq, Hk, D, dtype):
+    """The class of inputs one verdict of the fused q / k norm + rotary kernel covers.  ATen's summation order at these row
+    lengths was measured NOT to depend on the number of rows (profiles/qk_norm_order_probe.py), unlike at
+    the wide rows of _rmsnorm_forward; the sizes stay in the key all the same -- they are what the eager rotary expression
+    and the kernel's lane arithmetic see, and a re-check per shape costs one forward's worth of eager code."""
+    return (B, L, Hq, Hk, D, dtype)
+
+
+def _qwen3_attention_forward(orig, mod):
+    """Qwen3Attention.forward with q_norm, k_norm and apply_rotary_pos_emb through ops.fwd_qk_norm_rope.  `mod` is the
+    modelling module: its apply_rotary_pos_emb, attention registry and eager attention are looked up at call time, as the
+    original's globals are.  Everything but the three replaced calls is the original's text."""
+    def forward(self, hidden_states, position_embeddings, attention_mask, past_key_values=None, **kwargs):
+        x = hidden_states
+        D = getattr(self, "head_dim", None)
+        qn, kn = getattr(self, "q_norm", None), getattr(self, "k_norm", None)
+        ok = (past_key_values is None and torch.is_tensor(x) and x.is_cuda and x.dtype in _16BIT and x.dim() == 3
+              and x.numel() > 0 and not torch.is_grad_enabled() and D in QK_NORM_HEAD_DIMS
+              and isinstance(position_embeddings, (tuple, list)) and len(position_embeddings) == 2
+              and type(qn) is mod.Qwen3RMSNorm and type(kn) is mod.Qwen3RMSNorm
+              and qn.variance_epsilon == kn.variance_epsilon and qn.weight.dtype == kn.weight.dtype == x.dtype
+              and qn.weight.shape == kn.weight.shape == (D,))
+        if ok:
+            cos, sin = position_embeddings
+            B, L = x.shape[:2]
+            ok = (torch.is_tensor(cos) and torch.is_tensor(sin) and cos.dim() == 3 and cos.shape == sin.shape
+                  and cos.dtype == sin.dtype == x.dtype and cos.shape[1] == L and cos.shape[2] == D and cos.shape[0] in (1, B))
+        if not ok:
+            return orig(self, hidden_states, position_embeddings, attention_mask, past_key_values, **kwargs)
+        input_shape = x.shape[:-1]
+        hidden_shape = (*input_shape, -1, D)
+        # the four Linears are entered exactly once each, through nn.Module.__call__, in the original's order: the Hessian
+        # hooks see every input once whether or not the kernel is trusted
+        q4, k4 = self.q_proj(x).view(hidden_shape), self.k_proj(x).view(hidden_shape)
+        value_states = self.v_proj(x).view(hidden_shape).transpose(1, 2)
+        key = _qkn_key(B, L, q4.shape[2], k4.shape[2], D, x.dtype)
+        verdict = _qkn_verdict.get(key) if q4.is_contiguous() and k4.is_contiguous() else False
+        got = None
+        if verdict is not False:
+            c, s_ = cos, sin
+            if c.shape[0] != B:
+                c, s_ = c.expand(B, L, D), s_.expand(B, L, D)
+            got = ops.fwd_qk_norm_rope(q4, k4, qn.weight.contiguous(), kn.weight.contiguous(), c.contiguous(), s_.contiguous(),
+                                       qn.variance_epsilon, want_stats=verdict is None)
+        if verdict:
+            query_states, key_states = got[0].transpose(1, 2), got[1].transpose(1, 2)
+        else:  # the eager expressions: what is returned until the kernel has reproduced them on this class, and if it has not
+            query_states, key_states = mod.apply_rotary_pos_emb(qn(q4).transpose(1, 2), kn(k4).transpose(1, 2), cos, sin)
+            if verdict is None:
+                # 16-bit outputs hide most differences of the summation order: the fp32 statistics must agree row by row too
+                var = torch.cat([q4.to(torch.float32).pow(2).mean(-1).reshape(-1), k4.to(torch.float32).pow(2).mean(-1).reshape(-1)])
+                r = torch.rsqrt(var + qn.variance_epsilon)
+                _qkn_verdict[key] = bool(torch.equal(query_states, got[0].transpose(1, 2)) and torch.equal(key_states, got[1].transpose(1, 2))
+                                         and torch.equal(got[2][:, 0], var) and torch.equal(got[2][:, 1], r))
+        attention_interface = mod.ALL_ATTENTION_FUNCTIONS.get_interface(self.config._attn_implementation, mod.eager_attention_forward)
+        attn_output, attn_weights = attention_interface(
+            self, query_states, key_states, value_states, attention_mask,
+            dropout=0.0 if not self.training else self.attention_dropout, scaling=self.scaling,
+            sliding_window=self.sliding_window, **kwargs)
+        attn_output = attn_output.reshape(*input_shape, -1).contiguous()
+        return self.o_proj(attn_output), attn_weights
+    return forward
+
+
+def _targets(free_order_norm: bool = True, qk_norm_rope: bool = True) -> List[Tuple[object, str, object]]:
     """(owner, attribute, replacement) for every installed family whose module text equals Llama's.  free_order_norm:
     RMSNorm may fall back to the free-order kernel where the ordered one is not verified (level "all")."""
     from transformers.models.llama import modeling_llama as ref
@@ -219,7 +293,28 @@ def _targets(free_order_norm: bool = True) -> List[Tuple[object, str, object]]:
                 out.append((mod, "apply_rotary_pos_emb", _rope(fn)))
         except (OSError, TypeError):
             pass
+        attn = vars(mod).get("Qwen3Attention") if fam == "qwen3" else None
+        if qk_norm_rope and attn is not None:
+            # the fused kernel is ONE definition of the norm, the rotary embedding and the attention forward around them:
+            # all three texts of this module must be the pinned ones
+            try:
+                same = (_sha(attn.forward) == _PINNED["qwen3_attn"] and want_norm is not None and want_rope is not None
+                        and _body(mod.Qwen3RMSNorm.forward) == want_norm and _body(mod.apply_rotary_pos_emb) == want_rope
+                        and _sha(mod.rotate_half) == _PINNED["rotate_half"])
+            except (OSError, TypeError, AttributeError):
+                same = False
+            if same:
+                out.append((attn, "forward", _qwen3_attention_forward(attn.forward, mod)))
+            else:
+                warnings.warn("forward_fused: transformers' Qwen3 ['attention'] differ from the definitions the HIP kernels "
+                              "implement; these stay on HF eager code", RuntimeWarning)
     return out
+
+
+# Level "exact" installs the fused q / k norm + rotary kernel: it is bit-identical or not used, and it was measured not to be
+# slower than the two eager Qwen3RMSNorm + two fwd_rope launches it replaces at any of the three points of
+# profiles/qk_norm_rope_rate.txt (0.26 - 0.34 of their time).  False keeps it behind "all" only.
+QK_NORM_ROPE_IN_EXACT = True
 
 
 def level_of(flag) -> str:
@@ -251,7 +346,7 @@ def fused_forward(enabled=True):
     ops.lib()  # fail loudly here, not in the middle of a forward
     saved = []
     try:
-        for owner, attr, new in _targets(free_order_norm=(level == "all")):
+        for owner, attr, new in _targets(free_order_norm=(level == "all"), qk_norm_rope=(level == "all" or QK_NORM_ROPE_IN_EXACT)):
             saved.append((owner, attr, vars(owner)[attr] if attr in vars(owner) else getattr(owner, attr)))
             setattr(owner, attr, new)
         yield [f"{getattr(o, '__name__', o)}.{a}" for o, a, _ in saved]

@@ -785,6 +785,27 @@ def fwd_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Ten
     return out
 
 
+def fwd_qk_norm_rope(q: torch.Tensor, k: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                     eps: float, want_stats: bool = False, out=None):
+    """Qwen3's q_norm / k_norm (RMSNorm over head_dim) and apply_rotary_pos_emb on both projections in one launch
+    (gq_fwd_qk_norm_rope, include/gptq_gguf_qknorm.h): q [B, L, Hq, D], k [B, L, Hk, D] contiguous, wq / wk [D],
+    cos / sin [B, L, D] contiguous, one 16-bit dtype, D in 64 / 128 / 256.  Returns (q', k') in the layouts of q and k --
+    written into `out` = (q_out, k_out) if given --, and with want_stats also fp32 [B L (Hq + Hk), 2] = (mean(x^2),
+    rsqrt(mean + eps)) per row as the kernel computed them, the q rows first."""
+    _need_cuda(q, k, wq, wk, cos, sin)
+    B, L, Hq, D = q.shape
+    Hk = k.shape[2]
+    assert k.shape == (B, L, Hk, D) and cos.shape == (B, L, D) and sin.shape == (B, L, D) and wq.shape == (D,) and wk.shape == (D,)
+    assert all(t.is_contiguous() and t.dtype == q.dtype for t in (q, k, wq, wk, cos, sin))
+    q_out, k_out = out if out is not None else (torch.empty_like(q), torch.empty_like(k))
+    assert q_out.shape == q.shape and k_out.shape == k.shape and q_out.is_contiguous() and k_out.is_contiguous()
+    assert q_out.dtype == q.dtype == k_out.dtype
+    stats = torch.empty(B * L * (Hq + Hk), 2, dtype=torch.float32, device=q.device) if want_stats else None
+    check(lib().gq_fwd_qk_norm_rope(_ptr(q), _ptr(k), _ptr(wq), _ptr(wk), _ptr(cos), _ptr(sin), _ptr(q_out), _ptr(k_out), B * L,
+                                    Hq, Hk, D, float(eps), _DT[q.dtype], _ptr(stats), _stream(q)), "gq_fwd_qk_norm_rope")
+    return (q_out, k_out, stats) if want_stats else (q_out, k_out)
+
+
 def fwd_silu_mul(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     """silu(gate) * up (gq_fwd_silu_mul), fp16 / bf16 contiguous tensors of one shape."""
     _need_cuda(gate, up)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""pack_gptq_into_gguf.py -- HF Llama directory + quantized directory -> .gguf
+"""pack_gptq_into_gguf.py -- HF Llama / Mixtral / dense Qwen3 directory + quantized directory -> .gguf
 
 Keeps the reference CLI (`model --dir_model_quant --outfile --outtype`,
 quant/gptq/pack_gptq_into_gguf.py:8792-8884) and reproduces the part of that 9 kLoC llama.cpp
@@ -13,7 +13,9 @@ converter fork that touches the hot path:
   * `LlamaModel.set_vocab` (:2126-2139): the SentencePiece vocabulary (`tokenizer.model` -> tokenizer model "llama",
     scores, token types, byte fallback; :1018-1118 -- TinyLlama, Llama-2, Mistral, Mixtral) and the byte-level BPE one
     (Llama-3), both closed by gguf.SpecialVocab's keys (special token ids, add_bos/eos flags, chat template).
-Everything else of the fork (110 other architectures, Mistral-format / tekken vocabularies, split files, remote
+  * Qwen3 (`Qwen3ForCausalLM`, architecture "qwen3"): TextModel's + Qwen2Model's parameters (:594-638, :3008-3015), no q / k
+    row permute, the q_norm / k_norm tensors, pre-tokenizer "qwen2".
+Everything else of the fork (109 other architectures, Mistral-format / tekken vocabularies, split files, remote
 models) is out of scope and REFUSED loudly rather than mis-written.  The container is written by gguf_writer.py
 (spec-level; whole-file byte identity with gguf-py 0.17.1 is UNPINNED: that package cannot be installed here and no
 reference-produced file exists to compare with), the tensor payloads by the GPU bit-packers.
@@ -55,6 +57,8 @@ _BLOCK_TABLE = {"input_layernorm.weight": "attn_norm.weight", "post_attention_la
                 "self_attn.v_proj.weight": "attn_v.weight", "self_attn.o_proj.weight": "attn_output.weight",
                 "mlp.gate_proj.weight": "ffn_gate.weight", "mlp.up_proj.weight": "ffn_up.weight",
                 "mlp.down_proj.weight": "ffn_down.weight",
+                # Qwen3: the per-head RMSNorm weights over head_dim (gguf-py tensor_mapping ATTN_Q_NORM / ATTN_K_NORM)
+                "self_attn.q_norm.weight": "attn_q_norm.weight", "self_attn.k_norm.weight": "attn_k_norm.weight",
                 # Mixtral (registered under LlamaModel, reference :2120-2124): router + the merged expert tensors
                 "block_sparse_moe.gate.weight": "ffn_gate_inp.weight",
                 "feed_forward.experts.w1.weight": "ffn_gate_exps.weight",
@@ -62,8 +66,23 @@ _BLOCK_TABLE = {"input_layernorm.weight": "attn_norm.weight", "post_attention_la
                 "feed_forward.experts.w3.weight": "ffn_up_exps.weight"}
 
 
+# HF model class -> the GGUF architecture string (the reference's ModelBase.register / model_arch: LlamaModel :2120-2124,
+# Qwen3Model :3692-3694).  "llama" alone stores q / k rows permuted (LlamaModel.modify_tensors); Qwen2Model's does not.
+GGUF_ARCH = {"LlamaForCausalLM": "llama", "LLaMAForCausalLM": "llama", "MistralForCausalLM": "llama",
+             "MixtralForCausalLM": "llama", "Qwen3ForCausalLM": "qwen3"}
+
+
+def gguf_arch(hp: dict) -> str:
+    """The GGUF architecture string of a config.json; NotImplementedError for a model class this packer does not write."""
+    arch = hp.get("architectures", ["LlamaForCausalLM"])[0]
+    if arch not in GGUF_ARCH:
+        raise NotImplementedError(f"Model {arch} is not supported by this packer (Llama family, Mixtral and dense Qwen3 only; "
+                                  "Qwen3MoeForCausalLM's fused experts and Qwen2ForCausalLM's q / k / v biases are out of scope)")
+    return GGUF_ARCH[arch]
+
+
 def map_tensor_name(name: str) -> str:
-    """HF Llama / Mixtral -> GGUF tensor names (gguf-py tensor_mapping, llama arch)."""
+    """HF Llama / Mixtral / Qwen3 -> GGUF tensor names (gguf-py tensor_mapping; the block names are shared by the archs)."""
     if name == "model.embed_tokens.weight":
         return "token_embd.weight"
     if name == "model.norm.weight":
@@ -223,8 +242,10 @@ def create_vocab_sentencepiece(dir_model: Path, vocab_size: Optional[int]):
 GGUF_PY_FIM_COMPAT = False
 
 
-def add_tokenizer(w: GGUFWriter, dir_model: Path, vocab_size: int):
-    """LlamaModel.set_vocab (reference :2126-2139): the SentencePiece vocabulary when the checkpoint has a
+def add_tokenizer(w: GGUFWriter, dir_model: Path, vocab_size: int, arch: str = "llama"):
+    """Architecture "qwen3": Qwen2Model.set_vocab (reference :3002-3006) -- the same two paths without LlamaModel's tail
+    (no add_space_prefix key), and the byte-level BPE path names the pre-tokenizer "qwen2", the id the reference's hash
+    table gives every Qwen tokenizer (:776-778, :818-820).  Architecture "llama": LlamaModel.set_vocab (reference :2126-2139): the SentencePiece vocabulary when the checkpoint has a
     tokenizer.model (Llama-2, TinyLlama, Mistral, Mixtral: tokenizer model "llama", pre-tokenizer "default", scores,
     byte fallback; :1018-1028), else the byte-level BPE path (`gpt2`, Llama-3; :2137).  The middle fallback
     (`_set_vocab_llama_hf`: a tokenizer.json of a SentencePiece-derived vocabulary without tokenizer.model) is not
@@ -237,7 +258,8 @@ def add_tokenizer(w: GGUFWriter, dir_model: Path, vocab_size: int):
         w.add_array("tokenizer.ggml.scores", scores, GGUFValueType.FLOAT32)
         w.add_array("tokenizer.ggml.token_type", types, GGUFValueType.INT32)
         add_special_vocab(w, dir_model, len(tokens))
-        _add_space_prefix(w, dir_model, vocab_size)
+        if arch == "llama":
+            _add_space_prefix(w, dir_model, vocab_size)
         return
     tj = dir_model / "tokenizer.json"
     if not tj.exists():
@@ -265,15 +287,16 @@ def add_tokenizer(w: GGUFWriter, dir_model: Path, vocab_size: int):
     # spaces INSIDE a part as chr(ord(' ') + 256), the byte-level alphabet's letter for 0x20
     merges = [m if isinstance(m, str) else " ".join("".join(chr(ord(c) + 256) if c == " " else c for c in part) for part in m)
               for m in tok["model"].get("merges", [])]
-    if vocab_size != 128256:
+    if arch == "llama" and vocab_size != 128256:
         print("warning: tokenizer.ggml.pre is written as 'llama-bpe' (the Llama-3 pre-tokenizer); the reference "
               "identifies the pre-tokenizer by a hash of a probe string, which is not reproduced", file=sys.stderr)
     w.add_string("tokenizer.ggml.model", "gpt2")
-    w.add_string("tokenizer.ggml.pre", "llama-bpe")
+    w.add_string("tokenizer.ggml.pre", "qwen2" if arch == "qwen3" else "llama-bpe")
     w.add_array("tokenizer.ggml.tokens", tokens, GGUFValueType.STRING)
     w.add_array("tokenizer.ggml.token_type", types, GGUFValueType.INT32)
     add_special_vocab(w, dir_model, len(tokens), merges=merges)
-    _add_space_prefix(w, dir_model, vocab_size)
+    if arch == "llama":
+        _add_space_prefix(w, dir_model, vocab_size)
 
 
 def _add_space_prefix(w: GGUFWriter, dir_model: Path, vocab_size: Optional[int] = None) -> None:
@@ -373,9 +396,12 @@ def plain_tensor(new_name: str, data: torch.Tensor, outtype: str):
 
 
 def rope_setup(hp: dict):
-    """-> (rope_scaling dict, rope type in lower case); NotImplementedError for what the reference's LlamaModel does not write."""
+    """-> (rope_scaling dict, rope type in lower case); NotImplementedError for what the reference's LlamaModel does not write.
+    Qwen3 (Qwen2Model.set_gguf_parameters, :3008-3015) writes yarn's three keys and nothing for any other type."""
     rope_scaling = hp.get("rope_scaling") or {}
     rope_type = str(rope_scaling.get("rope_type", rope_scaling.get("type", ""))).lower()
+    if gguf_arch(hp) == "qwen3":
+        return rope_scaling, rope_type
     if rope_type not in ("", "default", "linear", "llama3"):
         raise NotImplementedError(f"rope_scaling type {rope_type!r}: the reference's LlamaModel writes linear scaling "
                                   "keys and llama3 rope_freqs only (:2172-2175, :2259-2287); nothing else is reproduced")
@@ -390,30 +416,40 @@ def add_model_metadata(w, hp: dict, dir_model: Path, file_type: int, total_param
     n_head = hp["num_attention_heads"]
     n_experts = hp.get("num_local_experts")
     rope_scaling, rope_type = rope_setup(hp)
+    arch = gguf_arch(hp)
     w.add_string("general.type", "model")
     w.add_string("general.name", hp.get("_name_or_path") or dir_model.name)
     if total_params > 0:
         w.add_string("general.size_label", size_label(total_params, expert_params, n_experts or 0))
-    w.add_uint32("llama.block_count", hp["num_hidden_layers"])
-    for key, gg, kind in (("max_position_embeddings", "llama.context_length", "u"), ("hidden_size", "llama.embedding_length", "u"),
-                          ("intermediate_size", "llama.feed_forward_length", "u"), ("num_attention_heads", "llama.attention.head_count", "u"),
-                          ("num_key_value_heads", "llama.attention.head_count_kv", "u"), ("rope_theta", "llama.rope.freq_base", "f"),
-                          ("rms_norm_eps", "llama.attention.layer_norm_rms_epsilon", "f"),
-                          ("num_local_experts", "llama.expert_count", "u"), ("num_experts_per_tok", "llama.expert_used_count", "u")):
+    w.add_uint32(f"{arch}.block_count", hp["num_hidden_layers"])
+    for key, gg, kind in (("max_position_embeddings", f"{arch}.context_length", "u"), ("hidden_size", f"{arch}.embedding_length", "u"),
+                          ("intermediate_size", f"{arch}.feed_forward_length", "u"), ("num_attention_heads", f"{arch}.attention.head_count", "u"),
+                          ("num_key_value_heads", f"{arch}.attention.head_count_kv", "u"), ("rope_theta", f"{arch}.rope.freq_base", "f"),
+                          ("rms_norm_eps", f"{arch}.attention.layer_norm_rms_epsilon", "f"),
+                          ("num_local_experts", f"{arch}.expert_count", "u"), ("num_experts_per_tok", f"{arch}.expert_used_count", "u")):
         if hp.get(key) is not None:
             (w.add_uint32 if kind == "u" else w.add_float32)(gg, hp[key])
     if hp.get("head_dim") is not None:
-        w.add_uint32("llama.attention.key_length", hp["head_dim"])
-        w.add_uint32("llama.attention.value_length", hp["head_dim"])
+        w.add_uint32(f"{arch}.attention.key_length", hp["head_dim"])
+        w.add_uint32(f"{arch}.attention.value_length", hp["head_dim"])
     w.add_uint32("general.file_type", file_type)
-    w.add_uint32("llama.vocab_size", hp["vocab_size"])
-    w.add_uint32("llama.rope.dimension_count", hp.get("head_dim") or hp["hidden_size"] // n_head)
-    if rope_type == "linear" and "factor" in rope_scaling:
-        w.add_string("llama.rope.scaling.type", "linear")
-        w.add_float32("llama.rope.scaling.factor", rope_scaling["factor"])
+    if arch == "llama":  # LlamaModel.set_gguf_parameters (:2160-2175)
+        w.add_uint32("llama.vocab_size", hp["vocab_size"])
+        w.add_uint32("llama.rope.dimension_count", hp.get("head_dim") or hp["hidden_size"] // n_head)
+        if rope_type == "linear" and "factor" in rope_scaling:
+            w.add_string("llama.rope.scaling.type", "linear")
+            w.add_float32("llama.rope.scaling.factor", rope_scaling["factor"])
+    else:  # Qwen2Model.set_gguf_parameters (:3008-3015), which Qwen3Model (:3692-3707) inherits unchanged
+        if (dir_model / "modules.json").is_file():
+            raise NotImplementedError("modules.json next to the checkpoint (a sentence-transformers embedding model): the "
+                                      "reference's pooling-type key (:1232-1260) is not reproduced")
+        if rope_type == "yarn" and "factor" in rope_scaling:
+            w.add_string(f"{arch}.rope.scaling.type", "yarn")
+            w.add_float32(f"{arch}.rope.scaling.factor", rope_scaling["factor"])
+            w.add_uint32(f"{arch}.rope.scaling.original_context_length", rope_scaling["original_max_position_embeddings"])
     w.add_uint32("general.quantization_version", 2)
     if vocab:
-        add_tokenizer(w, dir_model, hp["vocab_size"])
+        add_tokenizer(w, dir_model, hp["vocab_size"], arch)
 
 
 SKIPPED_HF_TENSORS = (".attention.masked_bias", ".attention.bias", ".rotary_emb.inv_freq")  # never written (reference :296-298)
@@ -439,9 +475,8 @@ def convert(dir_model: Path, dir_model_quant: Path, outfile: Path, outtype: str 
             tm[key] = tm.get(key, 0.0) + dt
 
     hp = json.load(open(dir_model / "config.json"))
-    arch = hp.get("architectures", ["LlamaForCausalLM"])[0]
-    if arch not in ("LlamaForCausalLM", "LLaMAForCausalLM", "MistralForCausalLM", "MixtralForCausalLM"):
-        raise NotImplementedError(f"Model {arch} is not supported by this packer (Llama family / Mixtral only)")
+    arch = gguf_arch(hp)
+    rotary_rows = arch == "llama"  # LlamaModel.modify_tensors permutes q / k rows; Qwen2Model's (Qwen3) leaves them in place
     n_head = hp["num_attention_heads"]
     n_kv = hp.get("num_key_value_heads", n_head)
     n_experts = hp.get("num_local_experts")
@@ -458,7 +493,7 @@ def convert(dir_model: Path, dir_model_quant: Path, outfile: Path, outtype: str 
     _, rope_type = rope_setup(hp)
 
     # ---- tensors first (the reference prepares them before the metadata: write() :444-447), extra tensors lead
-    w = GGUFWriter(str(outfile), "llama")
+    w = GGUFWriter(str(outfile), arch)
     index_map = {p.name: p for p in dir_model_quant.iterdir() if p.is_dir()} if dir_model_quant else {}  # :285-289
     tied = hp.get("tie_word_embeddings", False)
     names_seen = set()
@@ -487,7 +522,7 @@ def convert(dir_model: Path, dir_model_quant: Path, outfile: Path, outtype: str 
         numel = int(np.prod(shape)) if len(shape) else 1
         total_params += numel
         base = name.removesuffix(".weight")  # :305-306
-        is_q, is_k = name.endswith("q_proj.weight"), name.endswith("k_proj.weight")
+        is_q, is_k = rotary_rows and name.endswith("q_proj.weight"), rotary_rows and name.endswith("k_proj.weight")
         is_expert = ".block_sparse_moe.experts." in name
         payload = q_type = data = None
         if base in index_map and pipelined and not is_expert:
@@ -532,7 +567,7 @@ def convert(dir_model: Path, dir_model_quant: Path, outfile: Path, outtype: str 
                 x = x.contiguous().cuda()
                 clock("h2d", t0)
                 t0 = time.perf_counter()
-                out = ops.quantize_q8_0(x, rotary_row_dst(new_name, x.shape[0], n_head, n_kv, x.device))  # the q / k permute
+                out = ops.quantize_q8_0(x, rotary_row_dst(new_name, x.shape[0], n_head, n_kv, x.device) if rotary_rows else None)  # the q / k permute
                 torch.cuda.synchronize()
                 clock("q8_0", t0)
                 t0 = time.perf_counter()

@@ -607,7 +607,8 @@ class _LevelDbSink:
     files with level_db.LevelDbWriter; the bytes travel through the _Saver like a tree's tensors (RAW_BYTES items).  The
     key/value data and the tensors GPTQ does not quantize come from the model directory, by the converter's own rules
     (pack_gptq_into_gguf.add_model_metadata / plain_tensor with --outtype f16): the database is what converting every
-    level's tree and splitting the files with --exact leaves.  Dense Llama family only; the HF side is not written.
+    level's tree and splitting the files with --exact leaves.  Dense Llama family, dense Qwen3 (no q / k row gather) and Mixtral;
+    the HF side is not written.
     `q8_0`: every tensor whose K-quant levels were packed also gets the 8.5-bit level 8.5-Q8_0.pth -- round-to-nearest of
     the checkpoint's unmodified weights (gq_quantize_q8_0, q / k rows gathered on the way), what `llama-quantize Q8_0` and
     the splitter would leave; GPTQ has no part in it.
@@ -629,7 +630,7 @@ class _LevelDbSink:
         import json
         from pathlib import Path
         from . import level_db
-        from .pack_gptq_into_gguf import SKIPPED_HF_TENSORS, iter_hf_entries, map_tensor_name, rope_setup
+        from .pack_gptq_into_gguf import SKIPPED_HF_TENSORS, gguf_arch, iter_hf_entries, map_tensor_name, rope_setup
         if not dir_model or not os.path.isdir(dir_model) or not os.path.isfile(os.path.join(dir_model, "config.json")):
             raise ValueError(f"level_db needs the model as a local directory with config.json and *.safetensors (got "
                              f"{dir_model!r}): the key/value data and the plain tensors are read from it")
@@ -640,9 +641,11 @@ class _LevelDbSink:
         self.hp = json.load(open(self.dir_model / "config.json"))
         arch = self.hp.get("architectures", ["LlamaForCausalLM"])[0]
         self.n_experts = int(self.hp.get("num_local_experts") or 0)
-        dense = ("LlamaForCausalLM", "LLaMAForCausalLM", "MistralForCausalLM")
+        dense = ("LlamaForCausalLM", "LLaMAForCausalLM", "MistralForCausalLM", "Qwen3ForCausalLM")
         if not ((arch in dense and not self.n_experts) or (arch == "MixtralForCausalLM" and self.n_experts)):
-            raise NotImplementedError(f"level_db: {arch} (the dense Llama family, and MixtralForCausalLM with num_local_experts)")
+            raise NotImplementedError(f"level_db: {arch} (the dense Llama family, dense Qwen3, and MixtralForCausalLM with "
+                                      "num_local_experts; Qwen3MoeForCausalLM and Qwen2ForCausalLM's biases are out of scope)")
+        self.gguf_arch = gguf_arch(self.hp)  # "llama": q / k rows are stored in GGUF's rotary order; "qwen3": in place
         self.n_head = self.hp["num_attention_heads"]
         self.n_kv = self.hp.get("num_key_value_heads", self.n_head)
         _, self.rope_type = rope_setup(self.hp)
@@ -686,6 +689,8 @@ class _LevelDbSink:
 
     def _row_src(self, tensor: str, rows: int, device):
         from .gguf_loader import rotary_row_dst
+        if self.gguf_arch != "llama":
+            return None
         return rotary_row_dst(tensor, rows, self.n_head, self.n_kv, device)
 
     def pack_walk(self, stacked, bands, members):
@@ -883,7 +888,7 @@ class _LevelDbSink:
         from .pack_gptq_into_gguf import (FTYPE, SKIPPED_HF_TENSORS, add_model_metadata, iter_hf_entries, permute, plain_tensor,
                                           rope_freqs_llama3)
         w = self.writer
-        kv = GGUFWriter(None, "llama")  # collects the key/value data; never written
+        kv = GGUFWriter(None, self.gguf_arch)  # collects the key/value data; never written
         add_model_metadata(kv, self.hp, self.dir_model, FTYPE["f16"][0], self.total_params, self.expert_params, self.vocab)
         w.set_metadata(kv_records(kv.kv))
 
@@ -928,9 +933,9 @@ class _LevelDbSink:
                     w.add_level(tensor, tuple(x.shape), GGMLType.Q8_0, blocks.cpu().numpy())
                 continue
             data = get()
-            if name.endswith("q_proj.weight"):
+            if self.gguf_arch == "llama" and name.endswith("q_proj.weight"):
                 data = permute(data, self.n_head, self.n_head)
-            elif name.endswith("k_proj.weight"):
+            elif self.gguf_arch == "llama" and name.endswith("k_proj.weight"):
                 data = permute(data, self.n_head, self.n_kv)
             plain(self.tensor_of[base], data)
         return w.close()

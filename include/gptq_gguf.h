@@ -374,6 +374,9 @@ int gq_stage_to_host(void* host_dst, const void* src, int64_t nbytes, void* stre
      gq_fwd_rope      apply_rotary_pos_emb on one of q / k:  out = dtype(x cos) + dtype(rotate_half(x) sin);
                       x, out [tokens, heads, head_dim] (the projection's own layout), cos / sin [tokens, head_dim], head_dim % 16 == 0
      gq_fwd_silu_mul  LlamaMLP.forward's act_fn(gate) * up over n elements, n % 8 == 0
+   The families whose module text equals Llama's take them: "llama", "mistral", "qwen2", "qwen3", "mixtral".  "qwen3" also
+   replaces Qwen3Attention.forward's q_norm / k_norm / apply_rotary_pos_emb with ONE launch, gq_fwd_qk_norm_rope of the
+   additive extension gptq_gguf_qknorm.h.
    All pointers 16-byte aligned, tensors contiguous, out does not overlap an input. */
 int gq_fwd_rmsnorm(const void* x, const void* weight, void* out, int64_t tokens, int64_t C, float eps, int dtype, void* stream);
 /* gq_fwd_rmsnorm with mean(x^2) summed in the order of ATen's reduce kernel on a 64-wide wavefront (C % 512 == 0): bit-identical
