@@ -739,6 +739,17 @@ def chol_gemm(Cm: torch.Tensor, A: torch.Tensor, B: torch.Tensor, trans_b: bool,
     return Cm
 
 
+def pin_host(t: torch.Tensor) -> bool:
+    """hipHostRegister t's (host) memory; undone by cudaHostUnregister(t.data_ptr()).  False where the runtime refuses (a
+    virtual machine without the facility answers `invalid value`): the failed call leaves the calling thread's sticky "last
+    error" set, which the next launch check of that thread would report for an unrelated kernel -- it is consumed here, in the
+    runtime the library is bound to (dlsym on the library's handle searches its dependencies: torch's libamdhip64)."""
+    if int(torch.cuda.cudart().cudaHostRegister(t.data_ptr(), t.numel() * t.element_size(), 0)) == 0:
+        return True
+    lib().hipGetLastError()
+    return False
+
+
 def stage_to_host(dst: torch.Tensor, src: torch.Tensor, stream: "torch.cuda.Stream") -> None:
     """src (device, contiguous) -> dst (pinned host memory, same byte size) by a copy kernel on `stream`
     (gq_stage_to_host: no hipMemcpy, no copy-engine lock shared with the launching thread)."""

@@ -231,17 +231,23 @@ class _Saver:
         self.proc = ctx.Process(target=_writer_process, args=(self.save_dir, self.slots, self.inbox, self.freeq, self.outbox),
                                 daemon=True)
         self.proc.start()  # the child imports torch while the slots are pinned here
+        unpinned = None
         for sid, t in enumerate(self.slots):  # pin the shared pages: the copy kernels write through their device mapping
             try:
-                if int(torch.cuda.cudart().cudaHostRegister(t.data_ptr(), t.numel(), 0)) == 0:
+                if _ops.pin_host(t):
                     self._registered.append(t)
                     self._pinned_ids.add(sid)
                 else:
-                    self._kernel_copy = False  # an unpinned slot has no device mapping: hipMemcpyAsync stages it
-            except Exception:
-                self._kernel_copy = False
+                    unpinned = "the runtime refuses hipHostRegister"
+            except Exception as e:
+                unpinned = repr(e)
+            if unpinned is not None:
+                self._kernel_copy = False  # an unpinned slot has no device mapping: hipMemcpyAsync stages it
             self.freeq.put(sid)
             self._ready.set()  # the first slot is enough to start with (embed_tokens); the others follow
+        if unpinned is not None:  # said once per saver: the run is correct, and in the slow mode described at put_many
+            dist_utils.print_on_main(f"[gq] data.pth staging slots are not pinned ({unpinned}): staged with hipMemcpyAsync "
+                                     f"by the copier thread instead of gq_stage_to_host copy kernels", file=sys.stderr)
 
     def _loop(self):
         stream = None
