@@ -68,6 +68,10 @@ QUAD_EXPERTS_MAX = 256  # GQ_QUAD_EXPERTS_MAX: experts of one gq_quad_form_exper
 # include/gptq_gguf_qknorm.h: Qwen3's per-head q / k RMSNorm and the rotary embedding of the calibration forward, one launch (additive in the same way)
 EXPORTS_QKNORM = ("gq_fwd_qk_norm_rope",)
 QK_NORM_HEAD_DIMS = (64, 128, 256)  # the head sizes gq_fwd_qk_norm_rope takes
+# include/gptq_gguf_kvcache.h: a KV cache of Q8_0 blocks -- the append and the split-KV decode attention (additive in the same way)
+EXPORTS_KVCACHE = ("gq_kv_append_q8_0", "gq_attn_decode_q8_0", "gq_attn_decode_q8_0_workspace_bytes", "gq_attn_decode_q8_0_plan")
+ATTN_DECODE_MAX_COLS = 64  # GQ_ATTN_DECODE_MAX_COLS: (query head of a group, token) pairs G * T of one gq_attn_decode_q8_0 call
+KV_HEAD_DIMS = (64, 128)  # the head sizes of the Q8_0 cache
 
 
 class GQError(RuntimeError):
@@ -198,6 +202,11 @@ def lib():
     L.gq_fwd_moe_combine.argtypes = [vp, vp, vp, vp, vp, ci, i64, i64, i64, i64, ci, vp, vp]
     L.gq_fwd_qk_norm_rope.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, cf, ci, vp, vp]
     L.gq_level_switch_experts.argtypes = [ctypes.POINTER(SwitchExpertsJob), ci, vp]
+    L.gq_kv_append_q8_0.argtypes = [vp, vp, ci, i64, i64, i64, i64, i64, i64, i64, vp, vp, i64, i64, vp]
+    L.gq_attn_decode_q8_0.argtypes = [vp, ci, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, i64, i64, vp, cf, vp, vp, sz, vp]
+    L.gq_attn_decode_q8_0_workspace_bytes.argtypes = [i64, i64, i64, i64, i64]
+    L.gq_attn_decode_q8_0_workspace_bytes.restype = sz
+    L.gq_attn_decode_q8_0_plan.argtypes = [i64, i64, i64, i64] + [ctypes.POINTER(i64)] * 4
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -206,7 +215,8 @@ def lib():
     L.gq_prof_collect2.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_IQ4_GPTQ + EXPORTS_QGEMM +
-                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH + EXPORTS_MOE_ERREST + EXPORTS_QKNORM):
+                 EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH + EXPORTS_MOE_ERREST + EXPORTS_QKNORM +
+                 EXPORTS_KVCACHE):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

@@ -7,7 +7,7 @@ launch on the last row of logits (temperature, top-k, top-p, the draw) and a row
 
     python -m gptq_gguf_toolkit_amd.generate --model_name_or_path HF_DIR --prompt_ids ids.pt --max_new_tokens N \
         --output_file out.json [--gguf FILE [--packed [--moe_prefill grouped]] | --quant_weights_path DB --quant_config_path CFG] \
-        [--dtype float16] [--attn_implementation eager] [--tokenizer_name NAME]
+        [--dtype float16] [--attn_implementation eager] [--tokenizer_name NAME] [--kv_cache q8_0]
 
 Prompts are the `.pt` list of [1, L] id tensors that ppleval reads (no tokenizer is needed; with --tokenizer_name the new
 ids are also decoded to text).  The model is built by ppleval.load_hf_model / apply_weights.  Not here: an unbounded nucleus
@@ -27,20 +27,50 @@ if __package__ in (None, ""):  # run as a script: make the package importable un
 
 from . import ops, ppleval  # noqa: E402
 
+KV_CACHES = ("hf", "q8_0")
+
+
+class _kv_cache:
+    """kv_cache="hf": the forward makes its own DynamicCache (past_key_values=None).  "q8_0": a packed_kv_cache.Q8KVCache for
+    the prompt and the new tokens, installed on the model for the duration of the `with` block."""
+
+    def __init__(self, model, input_ids, max_new_tokens, kv_cache):
+        if kv_cache not in KV_CACHES:
+            raise ValueError(f"kv_cache={kv_cache!r} (one of {KV_CACHES})")
+        self.model, self.cache = model, None
+        if kv_cache == "q8_0":
+            from . import packed_kv_cache
+            self.mod = packed_kv_cache
+            self.cache = packed_kv_cache.Q8KVCache(model.config, input_ids.shape[0], input_ids.shape[1] + max_new_tokens,
+                                                   device=input_ids.device)
+
+    def __enter__(self):
+        return self.mod.install(self.model, self.cache) if self.cache is not None else None
+
+    def __exit__(self, *exc):
+        if self.cache is not None:
+            self.mod.restore(self.model)
+
 
 @torch.no_grad()
-def greedy(model, input_ids, max_new_tokens, return_logits=False, timings=None):
+def greedy(model, input_ids, max_new_tokens, return_logits=False, timings=None, kv_cache="hf"):
     """input_ids [B, L] -> ids [B, L + N], N = max_new_tokens >= 1: the argmax continuation.  One forward over the prompt,
     then N - 1 forwards of one token each with the cache the previous forward returned.  With return_logits also the
     [B, N, V] logits each new token was the argmax of.  `timings`, a dict, receives prefill_s and decode_s (wall time up to a
-    device synchronise after the prefill and after the last step)."""
+    device synchronise after the prefill and after the last step).  kv_cache="q8_0": the cache is kept as Q8_0 blocks and the
+    decode steps' attention is gq_attn_decode_q8_0 (packed_kv_cache.py)."""
     if input_ids.dim() != 2 or input_ids.shape[1] < 1 or max_new_tokens < 1:
         raise ValueError(f"greedy: input_ids must be [B, L >= 1] and max_new_tokens >= 1; got {tuple(input_ids.shape)}, "
                          f"{max_new_tokens}")
+    with _kv_cache(model, input_ids, max_new_tokens, kv_cache) as past:
+        return _greedy(model, input_ids, max_new_tokens, return_logits, timings, past)
+
+
+def _greedy(model, input_ids, max_new_tokens, return_logits, timings, past):
     sync = torch.cuda.synchronize if input_ids.is_cuda else (lambda: None)
     sync()
     t0 = time.perf_counter()
-    out = model(input_ids=input_ids, use_cache=True)
+    out = model(input_ids=input_ids, past_key_values=past, use_cache=True)
     rows = [out.logits[:, -1]]
     new = [rows[-1].argmax(-1)]
     sync()
@@ -59,7 +89,7 @@ def greedy(model, input_ids, max_new_tokens, return_logits=False, timings=None):
 
 @torch.no_grad()
 def sample(model, input_ids, max_new_tokens, temperature=1.0, top_k=40, top_p=1.0, generator=None, eos_token_id=None,
-           pad_token_id=None, eos_poll=8, return_logits=False, timings=None):
+           pad_token_id=None, eos_poll=8, return_logits=False, timings=None, kv_cache="hf"):
     """input_ids [B, L] -> ids [B, L + M], 1 <= M <= max_new_tokens: a sampled continuation.  One forward over the prompt that
     keeps the last position's logits only (logits_to_keep=1: a packed lm_head never produces [L, V]), then one-token forwards
     on the cache.  Every new token is ops.sample_logits of the last row -- temperature, then top_k, then top_p, then the
@@ -69,7 +99,8 @@ def sample(model, input_ids, max_new_tokens, temperature=1.0, top_k=40, top_p=1.
     pad_token_id (default: the first eos id) and its draws are ignored.  The finished mask lives on the device; the host asks
     `finished.all()` once every eos_poll steps and makes no other synchronise per step; the result is cut after the last step
     in which any row was unfinished, so M does not depend on eos_poll.  With return_logits also the [B, M, V] logits the
-    tokens were drawn from.  `timings` receives prefill_s, decode_s (as greedy) and stopped_at_eos (every row finished)."""
+    tokens were drawn from.  `timings` receives prefill_s, decode_s (as greedy) and stopped_at_eos (every row finished).
+    kv_cache as greedy's."""
     if input_ids.dim() != 2 or input_ids.shape[1] < 1 or max_new_tokens < 1:
         raise ValueError(f"sample: input_ids must be [B, L >= 1] and max_new_tokens >= 1; got {tuple(input_ids.shape)}, "
                          f"{max_new_tokens}")
@@ -79,6 +110,13 @@ def sample(model, input_ids, max_new_tokens, temperature=1.0, top_k=40, top_p=1.
         raise ValueError(f"sample: top_p={top_p} must be in (0, 1], temperature={temperature} >= 0, eos_poll={eos_poll} >= 1")
     eos = [] if eos_token_id is None else [int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple))
                                                             else [eos_token_id])]
+    with _kv_cache(model, input_ids, max_new_tokens, kv_cache) as past:
+        return _sample(model, input_ids, max_new_tokens, temperature, top_k, top_p, generator, eos, pad_token_id, eos_poll,
+                       return_logits, timings, past)
+
+
+def _sample(model, input_ids, max_new_tokens, temperature, top_k, top_p, generator, eos, pad_token_id, eos_poll, return_logits,
+            timings, past):
     B, dev = input_ids.shape[0], input_ids.device
     sync = torch.cuda.synchronize if input_ids.is_cuda else (lambda: None)
     if eos:
@@ -101,7 +139,7 @@ def sample(model, input_ids, max_new_tokens, temperature=1.0, top_k=40, top_p=1.
 
     sync()
     t0 = time.perf_counter()
-    out = model(input_ids=input_ids, use_cache=True, logits_to_keep=1)
+    out = model(input_ids=input_ids, past_key_values=past, use_cache=True, logits_to_keep=1)
     draw(out.logits)
     sync()
     t1 = time.perf_counter()
@@ -153,6 +191,9 @@ def parse_args(argv=None):
     p.add_argument("--attn_implementation", type=str, default=None, choices=["eager", "sdpa", "flash_attention_2"],
                    help="Attention implementation: eager, sdpa, or flash_attention_2")
     p.add_argument("--tokenizer_name", type=str, default=None, help="also decode the new ids to text with this tokenizer")
+    p.add_argument("--kv_cache", type=str, default="hf", choices=list(KV_CACHES),
+                   help="hf: the 16-bit DynamicCache and --attn_implementation; q8_0: K and V as Q8_0 blocks (8.5 bits per value) "
+                        "and the decode attention on them (gq_attn_decode_q8_0)")
     args = p.parse_args(argv)
     if args.packed and not args.gguf:
         p.error("--packed needs --gguf")
@@ -194,9 +235,9 @@ def main(argv=None):
         tm = {}
         if args.do_sample:
             out = sample(model, ids.to(device), args.max_new_tokens, args.temperature, args.top_k, args.top_p, generator,
-                         args.eos_token_id, timings=tm)
+                         args.eos_token_id, timings=tm, kv_cache=args.kv_cache)
         else:
-            out = greedy(model, ids.to(device), args.max_new_tokens, timings=tm)
+            out = greedy(model, ids.to(device), args.max_new_tokens, timings=tm, kv_cache=args.kv_cache)
         new = out[0, ids.shape[1]:].tolist()
         steps = len(new) - 1  # the first new token comes from the prefill
         rec = {"prompt_tokens": int(ids.shape[1]), "new_ids": new, "prefill_s": tm["prefill_s"], "decode_s": tm["decode_s"],

@@ -1402,3 +1402,102 @@ def sample_logits(logits: torch.Tensor, u: Optional[torch.Tensor], top_k: int, t
     check(lib().gq_sample_logits(_ptr(logits), _DT[logits.dtype], B, V, ld, int(top_k), float(top_p), float(temperature),
                                  _ptr(u), _ptr(ids), _stream(logits)), "gq_sample_logits")
     return ids
+
+
+ATTN_DECODE_MAX_COLS = _cabi.ATTN_DECODE_MAX_COLS
+KV_HEAD_DIMS = _cabi.KV_HEAD_DIMS
+
+
+def kv_row_bytes(D: int) -> int:
+    """Bytes of one row of the Q8_0 KV cache: D / 32 blocks of 34 bytes (include/gptq_gguf_kvcache.h)."""
+    if int(D) not in KV_HEAD_DIMS:
+        raise _cabi.GQError(f"Q8_0 KV cache: head_dim D={int(D)} (64 or 128)")
+    return int(D) // 32 * 34
+
+
+def _kv_operand(who: str, name: str, x: torch.Tensor):
+    """a [B, H, T, D] fp16 / bf16 operand read through its strides: unit stride over D, the others multiples of 8"""
+    if x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16):
+        raise _cabi.GQError(f"{who}: {name} must be a fp16 / bf16 [B, H, T, D] tensor; got {x.dtype} {tuple(x.shape)}")
+    kv_row_bytes(x.shape[3])
+    if x.stride(3) != 1 or any(x.shape[i] > 1 and x.stride(i) % 8 for i in range(3)):
+        raise _cabi.GQError(f"{who}: {name} needs a unit stride over D and strides of b, h, t that are multiples of 8 elements; "
+                            f"got strides {tuple(x.stride())}")
+    return [x.stride(i) if x.shape[i] > 1 else 0 for i in range(3)]
+
+
+def _kv_caches(who: str, k_cache: torch.Tensor, v_cache: torch.Tensor, B: int, D: int, pos0: int, T: int):
+    rb = kv_row_bytes(D)
+    for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if c.dtype != torch.uint8 or c.dim() != 4 or c.shape[0] != B or c.shape[3] != rb or c.shape[2] % 4 or not c.is_contiguous():
+            raise _cabi.GQError(f"{who}: {name} must be a contiguous uint8 [B={B}, Hkv, S_cap, {rb}] tensor with S_cap % 4 == 0; "
+                                f"got {c.dtype} {tuple(c.shape)}")
+    if k_cache.shape != v_cache.shape:
+        raise _cabi.GQError(f"{who}: k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} differ")
+    if pos0 < 0 or pos0 + T > k_cache.shape[2]:
+        raise _cabi.GQError(f"{who}: pos0={pos0} + T={T} > S_cap={k_cache.shape[2]}")
+
+
+def kv_append_q8_0(k_cache: torch.Tensor, v_cache: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, pos0: int) -> None:
+    """Encode the T new rows k_new / v_new [B, Hkv, T, D] (fp16 / bf16; any strides of b, h, t that are multiples of 8, the
+    same for both -- the transposed view of an attention layer is taken as it is) into positions pos0 .. pos0 + T - 1 of the
+    uint8 [B, Hkv, S_cap, D / 32 * 34] caches, one launch (gq_kv_append_q8_0): bit for bit quantize_q8_0 of each row."""
+    who = "kv_append_q8_0"
+    sk, sv = _kv_operand(who, "k_new", k_new), _kv_operand(who, "v_new", v_new)
+    if k_new.shape != v_new.shape or k_new.dtype != v_new.dtype or sk != sv:
+        raise _cabi.GQError(f"{who}: k_new and v_new must agree in shape, dtype and strides; got {tuple(k_new.shape)} "
+                            f"{tuple(k_new.stride())} and {tuple(v_new.shape)} {tuple(v_new.stride())}")
+    B, Hkv, T, D = k_new.shape
+    _kv_caches(who, k_cache, v_cache, B, D, int(pos0), T)
+    if k_cache.shape[1] != Hkv or min(B, Hkv, T) < 1:
+        raise _cabi.GQError(f"{who}: {tuple(k_new.shape)} rows for caches {tuple(k_cache.shape)}")
+    _need_cuda(k_cache, v_cache, k_new, v_new)
+    check(lib().gq_kv_append_q8_0(_ptr(k_new), _ptr(v_new), _DT[k_new.dtype], *sk, B, Hkv, T, D, _ptr(k_cache), _ptr(v_cache),
+                                  k_cache.shape[2], int(pos0), _stream(k_cache)), "gq_kv_append_q8_0")
+
+
+def attn_decode_workspace_bytes(S: int, B: int, Hkv: int, cols: int, D: int) -> int:
+    """Workspace of attn_decode_q8_0 over a cache of S = pos0 + T positions with cols = G * T columns (no GPU needed)."""
+    n = int(lib().gq_attn_decode_q8_0_workspace_bytes(int(S), int(B), int(Hkv), int(cols), int(D)))
+    if n == 0:
+        raise _cabi.GQError(f"attn_decode_workspace_bytes: S={S} B={B} Hkv={Hkv} G*T={cols} D={D} is not a shape of attn_decode_q8_0")
+    return n
+
+
+def attn_decode_plan(S: int, B: int, Hkv: int, cols: int) -> dict:
+    """The split of attn_decode_q8_0 (csrc/attn/gq_attn_plan.hpp): splits chunks of `chunk` positions; min_chunk, the longest
+    cache that is never split; turn, the positions a workgroup takes per turn of its loop (no GPU needed)."""
+    v = [ctypes.c_int64() for _ in range(4)]
+    check(lib().gq_attn_decode_q8_0_plan(int(S), int(B), int(Hkv), int(cols), *[ctypes.byref(x) for x in v]), "gq_attn_decode_q8_0_plan")
+    return dict(zip(("splits", "chunk", "min_chunk", "turn"), (int(x.value) for x in v)))
+
+
+def attn_decode_q8_0(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos0: int, scale: float,
+                     kv_start: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                     ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention of the T query tokens q [B, Hq, T, D] (fp16 / bf16, strides as kv_append_q8_0's) at positions pos0 .. pos0 +
+    T - 1 over the first pos0 + T rows of the Q8_0 caches, causal, with positions below kv_start[b] (int32 [B] on the device)
+    masked: gq_attn_decode_q8_0, include/gptq_gguf_kvcache.h.  G * T <= ATTN_DECODE_MAX_COLS.  Returns contiguous
+    [B, T, Hq, D].  The caller keeps kv_start[b] <= pos0."""
+    who = "attn_decode_q8_0"
+    sq = _kv_operand(who, "q", q)
+    B, Hq, T, D = q.shape
+    _kv_caches(who, k_cache, v_cache, B, D, int(pos0), T)
+    Hkv = k_cache.shape[1]
+    if min(B, Hq, T) < 1 or Hq % Hkv:
+        raise _cabi.GQError(f"{who}: q {tuple(q.shape)} for caches {tuple(k_cache.shape)} (Hq must be a multiple of Hkv)")
+    if Hq // Hkv * T > ATTN_DECODE_MAX_COLS:
+        raise _cabi.GQError(f"{who}: G*T={Hq // Hkv}*{T} (more than {ATTN_DECODE_MAX_COLS} columns; the prefill is not this kernel's)")
+    if kv_start is not None and (kv_start.dtype != torch.int32 or kv_start.shape != (B,) or kv_start.device != q.device):
+        raise _cabi.GQError(f"{who}: kv_start must be int32 [{B}] on {q.device}; got {kv_start.dtype} {tuple(kv_start.shape)}")
+    _need_cuda(q, k_cache, v_cache, kv_start, out, ws)
+    need = attn_decode_workspace_bytes(pos0 + T, B, Hkv, Hq // Hkv * T, D)
+    if ws is None:
+        ws = _ws(need, q.device)
+    if out is None:
+        out = torch.empty(B, T, Hq, D, dtype=q.dtype, device=q.device)
+    assert out.shape == (B, T, Hq, D) and out.dtype == q.dtype and out.is_contiguous() and ws.dtype == torch.uint8
+    check(lib().gq_attn_decode_q8_0(_ptr(q), _DT[q.dtype], *sq, B, Hq, Hkv, T, D, _ptr(k_cache), _ptr(v_cache), k_cache.shape[2],
+                                    int(pos0), _ptr(kv_start.contiguous() if kv_start is not None else None), float(scale), _ptr(out),
+                                    _ptr(ws), ws.numel(), _stream(q)), "gq_attn_decode_q8_0")
+    return out
