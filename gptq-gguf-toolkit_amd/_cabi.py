@@ -72,6 +72,8 @@ QK_NORM_HEAD_DIMS = (64, 128, 256)  # the head sizes gq_fwd_qk_norm_rope takes
 EXPORTS_KVCACHE = ("gq_kv_append_q8_0", "gq_attn_decode_q8_0", "gq_attn_decode_q8_0_workspace_bytes", "gq_attn_decode_q8_0_plan")
 ATTN_DECODE_MAX_COLS = 64  # GQ_ATTN_DECODE_MAX_COLS: (query head of a group, token) pairs G * T of one gq_attn_decode_q8_0 call
 KV_HEAD_DIMS = (64, 128)  # the head sizes of the Q8_0 cache
+# include/gptq_gguf_kvprefill.h: the attention of many query tokens over that cache, one tiled launch (additive in the same way)
+EXPORTS_KVPREFILL = ("gq_attn_prefill_q8_0", "gq_attn_prefill_q8_0_plan")
 
 
 class GQError(RuntimeError):
@@ -207,6 +209,8 @@ def lib():
     L.gq_attn_decode_q8_0_workspace_bytes.argtypes = [i64, i64, i64, i64, i64]
     L.gq_attn_decode_q8_0_workspace_bytes.restype = sz
     L.gq_attn_decode_q8_0_plan.argtypes = [i64, i64, i64, i64] + [ctypes.POINTER(i64)] * 4
+    L.gq_attn_prefill_q8_0.argtypes = [vp, ci, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, i64, i64, vp, cf, vp, vp]
+    L.gq_attn_prefill_q8_0_plan.argtypes = [i64, i64] + [ctypes.POINTER(i64)] * 3
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -216,7 +220,7 @@ def lib():
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_IQ4_GPTQ + EXPORTS_QGEMM +
                  EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH + EXPORTS_MOE_ERREST + EXPORTS_QKNORM +
-                 EXPORTS_KVCACHE):
+                 EXPORTS_KVCACHE + EXPORTS_KVPREFILL):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Let a model continue a prompt, greedily or by sampling: one prefill forward, then one-token forwards on the HF KV cache.
+"""Let a model continue a prompt, greedily or by sampling: one prefill forward (or, with `--prefill_chunk N`, one forward per
+piece of N prompt tokens through the same cache), then one-token forwards on the HF KV cache.
 With `--gguf FILE --packed` the Linears of the blocks stay GGUF block bytes on the device and every decode step reads them
 through gq_gemv_packed (PackedLinear routes inputs of a few tokens there), the prefill through gq_linear_packed; with
 `--packed_vocab` token_embd and output stay packed as well.  With `--do_sample` every new token is one gq_sample_logits
@@ -7,7 +8,7 @@ launch on the last row of logits (temperature, top-k, top-p, the draw) and a row
 
     python -m gptq_gguf_toolkit_amd.generate --model_name_or_path HF_DIR --prompt_ids ids.pt --max_new_tokens N \
         --output_file out.json [--gguf FILE [--packed [--moe_prefill grouped]] | --quant_weights_path DB --quant_config_path CFG] \
-        [--dtype float16] [--attn_implementation eager] [--tokenizer_name NAME] [--kv_cache q8_0]
+        [--dtype float16] [--attn_implementation eager] [--tokenizer_name NAME] [--kv_cache q8_0 [--kv_prefill q8_0]] [--prefill_chunk N]
 
 Prompts are the `.pt` list of [1, L] id tensors that ppleval reads (no tokenizer is needed; with --tokenizer_name the new
 ids are also decoded to text).  The model is built by ppleval.load_hf_model / apply_weights.  Not here: an unbounded nucleus
@@ -28,21 +29,25 @@ if __package__ in (None, ""):  # run as a script: make the package importable un
 from . import ops, ppleval  # noqa: E402
 
 KV_CACHES = ("hf", "q8_0")
+KV_PREFILLS = ("sdpa", "q8_0")
 
 
 class _kv_cache:
     """kv_cache="hf": the forward makes its own DynamicCache (past_key_values=None).  "q8_0": a packed_kv_cache.Q8KVCache for
-    the prompt and the new tokens, installed on the model for the duration of the `with` block."""
+    the prompt and the new tokens, installed on the model for the duration of the `with` block; kv_prefill="q8_0" lets the
+    later pieces of a chunked prompt attend on the packed cache (gq_attn_prefill_q8_0)."""
 
-    def __init__(self, model, input_ids, max_new_tokens, kv_cache):
+    def __init__(self, model, input_ids, max_new_tokens, kv_cache, kv_prefill="sdpa"):
         if kv_cache not in KV_CACHES:
             raise ValueError(f"kv_cache={kv_cache!r} (one of {KV_CACHES})")
+        if kv_prefill not in KV_PREFILLS or (kv_prefill != "sdpa" and kv_cache != "q8_0"):
+            raise ValueError(f"kv_prefill={kv_prefill!r} (one of {KV_PREFILLS}; q8_0 needs kv_cache='q8_0')")
         self.model, self.cache = model, None
         if kv_cache == "q8_0":
             from . import packed_kv_cache
             self.mod = packed_kv_cache
             self.cache = packed_kv_cache.Q8KVCache(model.config, input_ids.shape[0], input_ids.shape[1] + max_new_tokens,
-                                                   device=input_ids.device)
+                                                   device=input_ids.device, prefill=kv_prefill)
 
     def __enter__(self):
         return self.mod.install(self.model, self.cache) if self.cache is not None else None
@@ -52,25 +57,39 @@ class _kv_cache:
             self.mod.restore(self.model)
 
 
+def _prefill(model, input_ids, past, prefill_chunk, **kw):
+    """The forward over the prompt: one call, or with prefill_chunk = N > 0 one call per piece of N tokens through the same
+    cache, so that no activation is larger than a piece.  Returns the last call's output."""
+    if prefill_chunk < 0:
+        raise ValueError(f"prefill_chunk={prefill_chunk} (0: one forward; N > 0: pieces of N tokens)")
+    step = prefill_chunk or input_ids.shape[1]
+    for i in range(0, input_ids.shape[1], step):
+        out = model(input_ids=input_ids[:, i:i + step], past_key_values=past, use_cache=True, **kw)
+        past = out.past_key_values
+    return out
+
+
 @torch.no_grad()
-def greedy(model, input_ids, max_new_tokens, return_logits=False, timings=None, kv_cache="hf"):
+def greedy(model, input_ids, max_new_tokens, return_logits=False, timings=None, kv_cache="hf", prefill_chunk=0, kv_prefill="sdpa"):
     """input_ids [B, L] -> ids [B, L + N], N = max_new_tokens >= 1: the argmax continuation.  One forward over the prompt,
     then N - 1 forwards of one token each with the cache the previous forward returned.  With return_logits also the
     [B, N, V] logits each new token was the argmax of.  `timings`, a dict, receives prefill_s and decode_s (wall time up to a
     device synchronise after the prefill and after the last step).  kv_cache="q8_0": the cache is kept as Q8_0 blocks and the
-    decode steps' attention is gq_attn_decode_q8_0 (packed_kv_cache.py)."""
+    decode steps' attention is gq_attn_decode_q8_0 (packed_kv_cache.py).  prefill_chunk=N > 0 feeds the prompt in pieces of N
+    tokens through the same cache (prefill_s covers all pieces); kv_prefill="q8_0" (with kv_cache="q8_0") lets the later pieces
+    attend on the packed cache with gq_attn_prefill_q8_0."""
     if input_ids.dim() != 2 or input_ids.shape[1] < 1 or max_new_tokens < 1:
         raise ValueError(f"greedy: input_ids must be [B, L >= 1] and max_new_tokens >= 1; got {tuple(input_ids.shape)}, "
                          f"{max_new_tokens}")
-    with _kv_cache(model, input_ids, max_new_tokens, kv_cache) as past:
-        return _greedy(model, input_ids, max_new_tokens, return_logits, timings, past)
+    with _kv_cache(model, input_ids, max_new_tokens, kv_cache, kv_prefill) as past:
+        return _greedy(model, input_ids, max_new_tokens, return_logits, timings, past, prefill_chunk)
 
 
-def _greedy(model, input_ids, max_new_tokens, return_logits, timings, past):
+def _greedy(model, input_ids, max_new_tokens, return_logits, timings, past, prefill_chunk=0):
     sync = torch.cuda.synchronize if input_ids.is_cuda else (lambda: None)
     sync()
     t0 = time.perf_counter()
-    out = model(input_ids=input_ids, past_key_values=past, use_cache=True)
+    out = _prefill(model, input_ids, past, prefill_chunk)
     rows = [out.logits[:, -1]]
     new = [rows[-1].argmax(-1)]
     sync()
@@ -89,7 +108,7 @@ def _greedy(model, input_ids, max_new_tokens, return_logits, timings, past):
 
 @torch.no_grad()
 def sample(model, input_ids, max_new_tokens, temperature=1.0, top_k=40, top_p=1.0, generator=None, eos_token_id=None,
-           pad_token_id=None, eos_poll=8, return_logits=False, timings=None, kv_cache="hf"):
+           pad_token_id=None, eos_poll=8, return_logits=False, timings=None, kv_cache="hf", prefill_chunk=0, kv_prefill="sdpa"):
     """input_ids [B, L] -> ids [B, L + M], 1 <= M <= max_new_tokens: a sampled continuation.  One forward over the prompt that
     keeps the last position's logits only (logits_to_keep=1: a packed lm_head never produces [L, V]), then one-token forwards
     on the cache.  Every new token is ops.sample_logits of the last row -- temperature, then top_k, then top_p, then the
@@ -100,7 +119,7 @@ def sample(model, input_ids, max_new_tokens, temperature=1.0, top_k=40, top_p=1.
     `finished.all()` once every eos_poll steps and makes no other synchronise per step; the result is cut after the last step
     in which any row was unfinished, so M does not depend on eos_poll.  With return_logits also the [B, M, V] logits the
     tokens were drawn from.  `timings` receives prefill_s, decode_s (as greedy) and stopped_at_eos (every row finished).
-    kv_cache as greedy's."""
+    kv_cache, prefill_chunk and kv_prefill as greedy's (every piece keeps its last row of logits only)."""
     if input_ids.dim() != 2 or input_ids.shape[1] < 1 or max_new_tokens < 1:
         raise ValueError(f"sample: input_ids must be [B, L >= 1] and max_new_tokens >= 1; got {tuple(input_ids.shape)}, "
                          f"{max_new_tokens}")
@@ -110,13 +129,13 @@ def sample(model, input_ids, max_new_tokens, temperature=1.0, top_k=40, top_p=1.
         raise ValueError(f"sample: top_p={top_p} must be in (0, 1], temperature={temperature} >= 0, eos_poll={eos_poll} >= 1")
     eos = [] if eos_token_id is None else [int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple))
                                                             else [eos_token_id])]
-    with _kv_cache(model, input_ids, max_new_tokens, kv_cache) as past:
+    with _kv_cache(model, input_ids, max_new_tokens, kv_cache, kv_prefill) as past:
         return _sample(model, input_ids, max_new_tokens, temperature, top_k, top_p, generator, eos, pad_token_id, eos_poll,
-                       return_logits, timings, past)
+                       return_logits, timings, past, prefill_chunk)
 
 
 def _sample(model, input_ids, max_new_tokens, temperature, top_k, top_p, generator, eos, pad_token_id, eos_poll, return_logits,
-            timings, past):
+            timings, past, prefill_chunk=0):
     B, dev = input_ids.shape[0], input_ids.device
     sync = torch.cuda.synchronize if input_ids.is_cuda else (lambda: None)
     if eos:
@@ -139,7 +158,7 @@ def _sample(model, input_ids, max_new_tokens, temperature, top_k, top_p, generat
 
     sync()
     t0 = time.perf_counter()
-    out = model(input_ids=input_ids, past_key_values=past, use_cache=True, logits_to_keep=1)
+    out = _prefill(model, input_ids, past, prefill_chunk, logits_to_keep=1)
     draw(out.logits)
     sync()
     t1 = time.perf_counter()
@@ -194,7 +213,16 @@ def parse_args(argv=None):
     p.add_argument("--kv_cache", type=str, default="hf", choices=list(KV_CACHES),
                    help="hf: the 16-bit DynamicCache and --attn_implementation; q8_0: K and V as Q8_0 blocks (8.5 bits per value) "
                         "and the decode attention on them (gq_attn_decode_q8_0)")
+    p.add_argument("--prefill_chunk", type=int, default=0,
+                   help="0: one forward over the prompt; N > 0: feed the prompt in pieces of N tokens through the same cache")
+    p.add_argument("--kv_prefill", type=str, default="sdpa", choices=list(KV_PREFILLS),
+                   help="with --kv_cache q8_0: the attention of a later piece of the prompt over the filled cache -- sdpa: decode "
+                        "the cache to 16 bits and call torch SDPA; q8_0: read it packed (gq_attn_prefill_q8_0)")
     args = p.parse_args(argv)
+    if args.kv_prefill != "sdpa" and args.kv_cache != "q8_0":
+        p.error("--kv_prefill q8_0 needs --kv_cache q8_0")
+    if args.prefill_chunk < 0:
+        p.error("--prefill_chunk must be at least 0")
     if args.packed and not args.gguf:
         p.error("--packed needs --gguf")
     if args.packed_vocab and not args.packed:
@@ -235,9 +263,11 @@ def main(argv=None):
         tm = {}
         if args.do_sample:
             out = sample(model, ids.to(device), args.max_new_tokens, args.temperature, args.top_k, args.top_p, generator,
-                         args.eos_token_id, timings=tm, kv_cache=args.kv_cache)
+                         args.eos_token_id, timings=tm, kv_cache=args.kv_cache, prefill_chunk=args.prefill_chunk,
+                         kv_prefill=args.kv_prefill)
         else:
-            out = greedy(model, ids.to(device), args.max_new_tokens, timings=tm, kv_cache=args.kv_cache)
+            out = greedy(model, ids.to(device), args.max_new_tokens, timings=tm, kv_cache=args.kv_cache,
+                         prefill_chunk=args.prefill_chunk, kv_prefill=args.kv_prefill)
         new = out[0, ids.shape[1]:].tolist()
         steps = len(new) - 1  # the first new token comes from the prefill
         rec = {"prompt_tokens": int(ids.shape[1]), "new_ids": new, "prefill_s": tm["prefill_s"], "decode_s": tm["decode_s"],

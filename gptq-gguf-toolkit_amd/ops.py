@@ -1501,3 +1501,36 @@ def attn_decode_q8_0(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
                                     int(pos0), _ptr(kv_start.contiguous() if kv_start is not None else None), float(scale), _ptr(out),
                                     _ptr(ws), ws.numel(), _stream(q)), "gq_attn_decode_q8_0")
     return out
+
+
+def attn_prefill_plan(T: int, G: int) -> dict:
+    """The plan of attn_prefill_q8_0 (csrc/attn/gq_attn_prefill_plan.hpp): the G * T columns of a KV head in `blocks` blocks of
+    `block_cols`, one workgroup each, which walks the positions in turns of `turn` (no GPU needed)."""
+    v = [ctypes.c_int64() for _ in range(3)]
+    check(lib().gq_attn_prefill_q8_0_plan(int(T), int(G), *[ctypes.byref(x) for x in v]), "gq_attn_prefill_q8_0_plan")
+    return dict(zip(("block_cols", "turn", "blocks"), (int(x.value) for x in v)))
+
+
+def attn_prefill_q8_0(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos0: int, scale: float,
+                      kv_start: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention of any number of query tokens q [B, Hq, T, D] (fp16 / bf16, strides as kv_append_q8_0's) at positions pos0 ..
+    pos0 + T - 1 over the first pos0 + T rows of the Q8_0 caches, causal, with positions below kv_start[b] (int32 [B] on the
+    device) masked: gq_attn_prefill_q8_0, include/gptq_gguf_kvprefill.h -- one launch, no workspace.  kv_start[b] may exceed
+    pos0 (a left-padded first chunk): a token below it gets a row of exact zeros.  Returns contiguous [B, T, Hq, D]."""
+    who = "attn_prefill_q8_0"
+    sq = _kv_operand(who, "q", q)
+    B, Hq, T, D = q.shape
+    _kv_caches(who, k_cache, v_cache, B, D, int(pos0), T)
+    Hkv = k_cache.shape[1]
+    if min(B, Hq, T) < 1 or Hq % Hkv:
+        raise _cabi.GQError(f"{who}: q {tuple(q.shape)} for caches {tuple(k_cache.shape)} (Hq must be a multiple of Hkv)")
+    if kv_start is not None and (kv_start.dtype != torch.int32 or kv_start.shape != (B,) or kv_start.device != q.device):
+        raise _cabi.GQError(f"{who}: kv_start must be int32 [{B}] on {q.device}; got {kv_start.dtype} {tuple(kv_start.shape)}")
+    _need_cuda(q, k_cache, v_cache, kv_start, out)
+    if out is None:
+        out = torch.empty(B, T, Hq, D, dtype=q.dtype, device=q.device)
+    assert out.shape == (B, T, Hq, D) and out.dtype == q.dtype and out.is_contiguous()
+    check(lib().gq_attn_prefill_q8_0(_ptr(q), _DT[q.dtype], *sq, B, Hq, Hkv, T, D, _ptr(k_cache), _ptr(v_cache), k_cache.shape[2],
+                                     int(pos0), _ptr(kv_start.contiguous() if kv_start is not None else None), float(scale), _ptr(out),
+                                     _stream(q)), "gq_attn_prefill_q8_0")
+    return out

@@ -16,7 +16,11 @@ of any other form, more tokens.  The fallback decodes the slabs it needs with op
 the caller's mask; on an empty cache the prefill attends over the fresh 16-bit K / V, as llama.cpp does.  Left padding is
 declared by the caller (`cache.set_left_padding(attention_mask)`): a 4-D mask is not searched for its form on the device, so an
 undeclared mask is a general one.  Architectures: those whose attention is LlamaAttention's forward (Llama, Mixtral, Qwen3);
-a model with sliding-window layers is refused by name."""
+a model with sliding-window layers is refused by name.
+
+`Q8KVCache(..., prefill="q8_0")` sends the calls of MORE than ops.ATTN_DECODE_MAX_COLS columns on a non-empty cache -- a later
+chunk of a prompt fed in pieces, a later turn of a conversation -- to ops.attn_prefill_q8_0, which reads the cache at its stored
+size, under the same condition on the mask; the default prefill="sdpa" keeps the fallback for them."""
 import torch
 from transformers import AttentionInterface, AttentionMaskInterface
 from transformers.cache_utils import Cache, CacheLayerMixin
@@ -26,6 +30,7 @@ from . import ops
 
 ATTN_NAME = "gq_q8_kv"
 MODEL_TYPES = ("llama", "mixtral", "qwen3")
+PREFILLS = ("sdpa", "q8_0")  # many query columns over a non-empty cache: the 16-bit fallback, or gq_attn_prefill_q8_0
 
 
 class Q8Layer(CacheLayerMixin):
@@ -82,9 +87,12 @@ class Q8Layer(CacheLayerMixin):
 
 
 class Q8KVCache(Cache):
-    def __init__(self, config, batch, capacity, dtype=None, device=None):
+    def __init__(self, config, batch, capacity, dtype=None, device=None, prefill="sdpa"):
         cfg = config.get_text_config()
         refuse_unsupported(cfg)
+        if prefill not in PREFILLS:
+            raise ValueError(f"Q8KVCache: prefill={prefill!r} (one of {PREFILLS})")
+        self.prefill = prefill
         head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         super().__init__(layers=[Q8Layer(batch, cfg.num_key_value_heads, head_dim, capacity, device)
                                  for _ in range(cfg.num_hidden_layers)])
@@ -126,6 +134,8 @@ def q8_kv_attention(module, query, key, value, attention_mask, dropout=0.0, scal
         if cache.kv_start is not None and cache._max_start > pos0:
             raise ValueError(f"Q8KVCache: left padding of {cache._max_start} positions exceeds the cache's {pos0}")
         return ops.attn_decode_q8_0(query, layer.keys, layer.values, pos0, scale, cache.kv_start), None
+    if pos0 > 0 and cache.prefill == "q8_0" and (attention_mask is None or cache.kv_start is not None):
+        return ops.attn_prefill_q8_0(query, layer.keys, layer.values, pos0, scale, cache.kv_start), None
     if pos0 > 0:
         key, value = layer.decoded(query.dtype)
     if attention_mask is None and T > 1:
@@ -136,13 +146,22 @@ def q8_kv_attention(module, query, key, value, attention_mask, dropout=0.0, scal
     return out.transpose(1, 2).contiguous(), None
 
 
+def _mask_none_when_causal(*args, attention_mask=None, allow_is_causal_skip=True, **kwargs):
+    """The mask function of a cache with prefill="q8_0": sdpa_mask, but None for EVERY plain causal call without a padding
+    mask -- sdpa_mask builds a 4-D mask for a chunk of tokens on a non-empty cache, and a 4-D mask is a general one here.  The
+    kernels apply the causal mask themselves, and the fallback builds its own when it is given none."""
+    if attention_mask is None and allow_is_causal_skip:
+        return None
+    return sdpa_mask(*args, attention_mask=attention_mask, allow_is_causal_skip=allow_is_causal_skip, **kwargs)
+
+
 def install(model, cache):
     """Point the model at the Q8_0 attention for the time `cache` is in use; restore(model) undoes it."""
     if hasattr(model, "_gq_q8_prev_attn"):
         raise RuntimeError("Q8KVCache: install() on a model that has a cache installed; restore(model) first")
     refuse_unsupported(model.config.get_text_config())
     AttentionInterface.register(ATTN_NAME, q8_kv_attention)
-    AttentionMaskInterface.register(ATTN_NAME, sdpa_mask)
+    AttentionMaskInterface.register(ATTN_NAME, _mask_none_when_causal if cache.prefill == "q8_0" else sdpa_mask)
     model._gq_q8_prev_attn = model.config._attn_implementation
     model.config._attn_implementation = ATTN_NAME
     for m in model.modules():
