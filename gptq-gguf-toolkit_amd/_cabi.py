@@ -74,6 +74,9 @@ ATTN_DECODE_MAX_COLS = 64  # GQ_ATTN_DECODE_MAX_COLS: (query head of a group, to
 KV_HEAD_DIMS = (64, 128)  # the head sizes of the Q8_0 cache
 # include/gptq_gguf_kvprefill.h: the attention of many query tokens over that cache, one tiled launch (additive in the same way)
 EXPORTS_KVPREFILL = ("gq_attn_prefill_q8_0", "gq_attn_prefill_q8_0_plan")
+# include/gptq_gguf_qgemm_a8.h: the packed forward on int8 activations -- the activation quantizer and the integer GEMM (additive in the same way)
+EXPORTS_QGEMM_A8 = ("gq_quantize_act_q8", "gq_linear_packed_a8")
+A8_TYPES = (10, 11, 12, 13, 14, 8)  # the q_types gq_linear_packed_a8 serves: the K-quants and Q8_0
 
 
 class GQError(RuntimeError):
@@ -211,6 +214,8 @@ def lib():
     L.gq_attn_decode_q8_0_plan.argtypes = [i64, i64, i64, i64] + [ctypes.POINTER(i64)] * 4
     L.gq_attn_prefill_q8_0.argtypes = [vp, ci, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, i64, i64, vp, cf, vp, vp]
     L.gq_attn_prefill_q8_0_plan.argtypes = [i64, i64] + [ctypes.POINTER(i64)] * 3
+    L.gq_quantize_act_q8.argtypes = [vp, i64, i64, ci, vp, vp, vp, vp]
+    L.gq_linear_packed_a8.argtypes = [ci, vp, vp, i64, i64, vp, vp, vp, i64, vp, ci, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -220,7 +225,7 @@ def lib():
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_IQ4_GPTQ + EXPORTS_QGEMM +
                  EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH + EXPORTS_MOE_ERREST + EXPORTS_QKNORM +
-                 EXPORTS_KVCACHE + EXPORTS_KVPREFILL):
+                 EXPORTS_KVCACHE + EXPORTS_KVPREFILL + EXPORTS_QGEMM_A8):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

@@ -292,7 +292,7 @@ def packed_expert_tensors(model: torch.nn.Module, path: str) -> Dict[str, dict]:
 
 
 def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bool = False,
-                 moe_prefill: str = "loop") -> Dict[str, torch.Tensor]:
+                 moe_prefill: str = "loop", act: str = "fp") -> Dict[str, torch.Tensor]:
     """The packed half of load_into_model: the Linears of packed_linear_tensors become PackedLinear holding the file's
     block bytes (with the rotary row gather of attn_q / attn_k as row_src); the modules of packed_expert_tensors become
     PackedExperts (or, per expert, PackedLinear on a slice view) on ONE device copy of each merged tensor; with `vocab` also
@@ -322,7 +322,7 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
             key = (name.rsplit(".", 2)[-2], shape[0])
             if key not in rows:
                 rows[key] = rotary_row_src(name, shape[0], arch, n_head, n_kv, ref.device)
-            packed = replace_linear(model, by_gguf[name])
+            packed = replace_linear(model, by_gguf[name], act)
             packed.set_level(_host(buf, off, nbytes).to(ref.device), int(gt), rows[key])
         elif name in users:
             held[name] = dev = _host(buf, off, nbytes).to(ref.device)  # the merged tensor's bytes: uploaded once
@@ -345,7 +345,8 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
                                                expert_layout=expert_layout_of(model)) if k not in skip}
 
 
-def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill: str = "loop") -> torch.nn.Module:
+def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill: str = "loop",
+                    packed_act: str = "fp") -> torch.nn.Module:
     """Load the file's weights into `model` (parameters on a GPU), strict on names and shapes.  A tied lm_head (no
     `output.weight` in the file) follows token_embd.
     packed=True: the K-quant, Q8_0, IQ4_NL and IQ4_XS tensors of the blocks' nn.Linear modules stay packed on the device -- each such Linear
@@ -357,14 +358,19 @@ def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill
     packed="all": that, and the vocabulary ends of packed_vocab_tensors: model.embed_tokens becomes a
     packed_embedding.PackedEmbedding and lm_head a PackedLinear on the file's block bytes (a file without output.weight gives
     both the same tensor: one device copy); an end stored as F16 / F32 loads dense as without it.
-    moe_prefill (with packed): "loop" or "grouped", the prefill path of the PackedExperts modules (PackedExperts.prefill)."""
+    moe_prefill (with packed): "loop" or "grouped", the prefill path of the PackedExperts modules (PackedExperts.prefill).
+    packed_act (with packed): "fp" or "q8", PackedLinear's `act` for the blocks' Linears -- "q8" sends their prefill through
+    the int8-activation GEMM (ops.linear_packed_q8); experts and the vocabulary ends keep the 16-bit route."""
     if packed not in (False, True, "all"):
         raise ValueError(f"load_into_model: packed must be False, True or 'all', got {packed!r}")
     if moe_prefill not in ("loop", "grouped") or (moe_prefill != "loop" and not packed):
         raise ValueError(f"load_into_model: moe_prefill must be 'loop' or 'grouped' (with packed), got {moe_prefill!r} with "
                          f"packed={packed!r}")
+    if packed_act not in ("fp", "q8") or (packed_act != "fp" and not packed):
+        raise ValueError(f"load_into_model: packed_act must be 'fp' or 'q8' (with packed), got {packed_act!r} with "
+                         f"packed={packed!r}")
     ref = next(model.parameters())
-    sd = (_load_packed(model, path, ref, vocab=packed == "all", moe_prefill=moe_prefill) if packed
+    sd = (_load_packed(model, path, ref, vocab=packed == "all", moe_prefill=moe_prefill, act=packed_act) if packed
           else load_state_dict(path, ref.device, ref.dtype, expert_layout_of(model)))
     want = model.state_dict()
     if "lm_head.weight" in want and "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:

@@ -69,13 +69,18 @@ def packed_fits(level_bytes: Sequence[int], dense_bytes: Sequence[int], capacity
 class LevelStore:
 
     def __init__(self, model: nn.Module, db: str, device, layer_names: Optional[Sequence[str]] = None,
-                 capacity_bytes: Optional[int] = None, resident: str = "dense", moe_prefill: str = "loop"):
+                 capacity_bytes: Optional[int] = None, resident: str = "dense", moe_prefill: str = "loop",
+                 packed_act: str = "fp"):
         """layer_names: the Linears and expert units to hold (default: every nn.Linear of the model that has a directory in
         `db`, and the units `<module>.{gate,up,down}_proj` of every experts-shaped module that have one).
         capacity_bytes: the device memory the levels may take (default: what torch reports free on `device`).
         resident: "dense" -- the model keeps its nn.Linear weights and a switch decodes into them; "packed" -- the Linears
         become PackedLinear, their dense weights are freed (credited in the capacity check) and a switch swaps references.
-        moe_prefill: packed residency's PackedExperts.prefill ("loop" or "grouped")."""
+        moe_prefill: packed residency's PackedExperts.prefill ("loop" or "grouped").
+        packed_act: packed residency's PackedLinear.act ("fp", or "q8": prefill on int8 activations, ops.linear_packed_q8)."""
+        if packed_act not in ("fp", "q8") or (packed_act != "fp" and resident != "packed"):
+            raise ValueError(f"packed_act must be 'fp' or 'q8' (with resident='packed'), got {packed_act!r} with resident={resident!r}")
+        self.packed_act = packed_act
         if resident not in ("dense", "packed"):
             raise ValueError(f"resident must be 'dense' or 'packed', got {resident!r}")
         if moe_prefill not in ("loop", "grouped"):
@@ -149,7 +154,7 @@ class LevelStore:
                             self.layers[other] = packed
             elif resident == "packed":  # the dense weight goes first, so that the peak is packed_peak_bytes'
                 self.freed_bytes += packed_linear.dense_bytes(self.layers[name])
-                self.layers[name] = packed_linear.replace_linear(model, name)
+                self.layers[name] = packed_linear.replace_linear(model, name, packed_act)
             for lv in lvs:
                 self._upload(name, lv)
         self.state: Dict[str, Optional[float]] = {name: None for name in self.layers}

@@ -1181,6 +1181,72 @@ def gemv_packed(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src: Opt
     return y
 
 
+# ---- the packed forward on int8 activations (gq_quantize_act_q8, gq_linear_packed_a8) ----
+A8_TYPES = _cabi.A8_TYPES
+
+
+def quantize_act_q8(x: torch.Tensor):
+    """x [..., C] fp16 / bf16, contiguous, C % 256 == 0 -> (xq int8 [..., C], xd fp32 [..., C / 256], xbsum int16 [..., C / 16]):
+    per 256 consecutive values of a token, q = rint(x * (127 / amax)) and d = amax / 127 in fp32, xbsum the exact sums of 16
+    codes (include/gptq_gguf_qgemm_a8.h states every operation).  One launch on the current stream of x's device."""
+    _need_cuda(x)
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise _cabi.GQError(f"quantize_act_q8: x must be fp16 or bf16 (there is no fp32 path); got {x.dtype}")
+    if x.dim() < 1 or not x.is_contiguous() or x.numel() == 0 or x.shape[-1] % 256:
+        raise _cabi.GQError(f"quantize_act_q8: x must be a non-empty contiguous [..., C] tensor with C % 256 == 0; got "
+                            f"{tuple(x.shape)} strides {tuple(x.stride())}")
+    C, lead = x.shape[-1], x.shape[:-1]
+    xq = torch.empty(*lead, C, dtype=torch.int8, device=x.device)
+    xd = torch.empty(*lead, C // 256, dtype=torch.float32, device=x.device)
+    xbsum = torch.empty(*lead, C // 16, dtype=torch.int16, device=x.device)
+    check(lib().gq_quantize_act_q8(_ptr(x), x.numel() // C, C, _DT[x.dtype], _ptr(xq), _ptr(xd), _ptr(xbsum), _stream(x)),
+          "gq_quantize_act_q8")
+    return xq, xd, xbsum
+
+
+def linear_packed_a8(q_type: int, blocks: torch.Tensor, xq: torch.Tensor, xd: torch.Tensor, xbsum: torch.Tensor,
+                     row_src: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """The activations of quantize_act_q8 times the packed weight [R, C] of linear_packed (same `blocks` and `row_src` rules;
+    q_type a K-quant 10..14 or Q8_0 8 -- IQ4_NL / IQ4_XS are refused) -> y [..., R] in out_dtype (fp16 or bf16).  Integer
+    products on the matrix pipe, the scales applied to int32 sums, fp32 accumulation over the superblocks, one rounding;
+    the weight is never rounded to 16 bits (include/gptq_gguf_qgemm_a8.h).  No dense weight, no workspace, no host read."""
+    _need_cuda(blocks, xq, xd, xbsum, row_src)
+    k = int(q_type)
+    if k not in A8_TYPES:
+        raise _cabi.GQError(f"linear_packed_a8: q_type {k} is not served on int8 activations (a K-quant 10..14 or Q8_0 8)")
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise _cabi.GQError(f"linear_packed_a8: out_dtype must be fp16 or bf16 (there is no fp32 path); got {out_dtype}")
+    C, lead = xq.shape[-1] if xq.dim() else 0, tuple(xq.shape[:-1])
+    if (xq.dtype != torch.int8 or xd.dtype != torch.float32 or xbsum.dtype != torch.int16 or xq.numel() == 0 or C % 256
+            or tuple(xd.shape) != lead + (C // 256,) or tuple(xbsum.shape) != lead + (C // 16,)
+            or not (xq.is_contiguous() and xd.is_contiguous() and xbsum.is_contiguous())):
+        raise _cabi.GQError(f"linear_packed_a8: (xq, xd, xbsum) must be quantize_act_q8's contiguous int8 [..., C], fp32 "
+                            f"[..., C / 256], int16 [..., C / 16] with C % 256 == 0; got {xq.dtype} {tuple(xq.shape)}, "
+                            f"{xd.dtype} {tuple(xd.shape)}, {xbsum.dtype} {tuple(xbsum.shape)}")
+    for t in (blocks, xd, xbsum, row_src):
+        if t is not None and t.device != xq.device:
+            raise _cabi.GQError(f"linear_packed_a8: every tensor must be on one device ({xq.device}); got one on {t.device}")
+    bs, ts = block_geometry(k)
+    row_bytes = C // bs * ts
+    if (blocks.dtype != torch.uint8 or blocks.dim() not in (1, 2) or not blocks.is_contiguous() or blocks.numel() == 0
+            or blocks.numel() % row_bytes or (blocks.dim() == 2 and blocks.shape[1] != row_bytes)):
+        raise _cabi.GQError(f"linear_packed_a8: packed blocks of q_type {k} for C={C} must be contiguous uint8, R rows of "
+                            f"{row_bytes} bytes; got {blocks.dtype} {tuple(blocks.shape)}")
+    R, T = blocks.numel() // row_bytes, xq.numel() // C
+    if row_src is not None and (row_src.dtype != torch.int32 or row_src.numel() != R or not row_src.is_contiguous()):
+        raise _cabi.GQError(f"linear_packed_a8: row_src must be a contiguous int32 [{R}] tensor")
+    y = torch.empty(*lead, R, dtype=out_dtype, device=xq.device)
+    check(lib().gq_linear_packed_a8(k, _ptr(blocks), _ptr(row_src), R, C, _ptr(xq), _ptr(xd), _ptr(xbsum), T, _ptr(y),
+                                    _DT[out_dtype], _stream(xq)), "gq_linear_packed_a8")
+    return y
+
+
+def linear_packed_q8(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_packed's arguments through the integer path: quantize_act_q8(x), then linear_packed_a8 into x's dtype.  The
+    result differs from linear_packed's by the 8-bit quantization of x (at most half a step d per element)."""
+    return linear_packed_a8(q_type, blocks, *quantize_act_q8(x), row_src=row_src, out_dtype=x.dtype)
+
+
 # ---- the grouped expert GEMV of a packed MoE layer's decode step (gq_gemv_packed_experts) ----
 MOE_MAX_PAIRS = _cabi.MOE_MAX_PAIRS
 

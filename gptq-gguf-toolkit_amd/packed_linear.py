@@ -8,6 +8,10 @@
 The weight operand of that GEMM is, bit for bit, what a dense level switch (ops.level_switch) writes for the same level, so
 a packed-resident model differs from a dense-resident one only by the fp32 summation order of its Linears.  A level that
 is a dense tensor of the model's dtype (the database's plain F16 / BF16 levels) goes through F.linear on the stored tensor.
+With act="q8" (opt-in; the default is "fp") a packed level of a type that ops.linear_packed_a8 serves (K-quants, Q8_0) and an
+input of more than gemv_max_t tokens go through ops.linear_packed_q8: the activations are quantized to int8 blocks of 256 and
+multiplied with the weight's integer codes -- the kind of arithmetic a runtime that loads the .gguf uses, and other numerics
+than the dense model's.  Decode steps stay on ops.gemv_packed; dense levels and IQ4_NL / IQ4_XS keep their route.
 There is no fallback: a PackedLinear without a level, or with an input of another dtype, raises."""
 from typing import Dict, Iterable, Optional
 
@@ -26,8 +30,11 @@ class PackedLinear(nn.Module):
     gemv_max_t = ops.GEMV_MAX_T
 
     def __init__(self, in_features: int, out_features: int, bias: Optional[nn.Parameter] = None,
-                 dtype: torch.dtype = torch.float16):
+                 dtype: torch.dtype = torch.float16, act: str = "fp"):
         super().__init__()
+        if act not in ("fp", "q8"):
+            raise ValueError(f'PackedLinear: act must be "fp" or "q8", not {act!r}')
+        self.act = act
         if dtype not in (torch.float16, torch.bfloat16):
             raise TypeError(f"PackedLinear computes in fp16 or bf16 (there is no fp32 path), not {dtype}")
         self.in_features, self.out_features = int(in_features), int(out_features)
@@ -66,7 +73,9 @@ class PackedLinear(nn.Module):
         if self.q_type is None:
             return F.linear(x, self.blocks, self.bias)
         few = 1 <= x.numel() // self.in_features <= min(self.gemv_max_t, ops.GEMV_MAX_T)
-        y = (ops.gemv_packed if few else ops.linear_packed)(self.q_type, self.blocks, x.contiguous(), self.row_src)
+        int8 = self.act == "q8" and not few and self.q_type in ops.A8_TYPES
+        fn = ops.gemv_packed if few else ops.linear_packed_q8 if int8 else ops.linear_packed
+        y = fn(self.q_type, self.blocks, x.contiguous(), self.row_src)
         return y if self.bias is None else y + self.bias
 
     @torch.no_grad()
@@ -80,25 +89,26 @@ class PackedLinear(nn.Module):
 
     def extra_repr(self) -> str:
         return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, "
-                f"q_type={self.q_type}")
+                f"q_type={self.q_type}, act={self.act}")
 
 
-def replace_linear(model: nn.Module, name: str) -> PackedLinear:
-    """Swap the nn.Linear `name` for a PackedLinear of its shape, dtype and bias; its dense weight is dropped."""
+def replace_linear(model: nn.Module, name: str, act: str = "fp") -> PackedLinear:
+    """Swap the nn.Linear `name` for a PackedLinear of its shape, dtype and bias (and activation route `act`); its dense weight
+    is dropped."""
     layer = model.get_submodule(name)
     if not isinstance(layer, nn.Linear):
         raise TypeError(f"PackedLinear replaces nn.Linear only, {name} is a {type(layer).__name__}")
-    packed = PackedLinear(layer.in_features, layer.out_features, layer.bias, layer.weight.dtype)
+    packed = PackedLinear(layer.in_features, layer.out_features, layer.bias, layer.weight.dtype, act)
     packed.train(layer.training)
     parent, _, leaf = name.rpartition(".")
     setattr(model.get_submodule(parent) if parent else model, leaf, packed)
     return packed
 
 
-def install(model: nn.Module, names: Iterable[str]) -> Dict[str, PackedLinear]:
+def install(model: nn.Module, names: Iterable[str], act: str = "fp") -> Dict[str, PackedLinear]:
     """{name: PackedLinear}: every named nn.Linear of `model` replaced; nothing holds their dense [R, C] storage afterwards
     (unless the caller does)."""
-    return {name: replace_linear(model, name) for name in names}
+    return {name: replace_linear(model, name, act) for name in names}
 
 
 def dense_bytes(layer: nn.Linear) -> int:
