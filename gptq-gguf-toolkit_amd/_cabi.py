@@ -77,6 +77,8 @@ EXPORTS_KVPREFILL = ("gq_attn_prefill_q8_0", "gq_attn_prefill_q8_0_plan")
 # include/gptq_gguf_qgemm_a8.h: the packed forward on int8 activations -- the activation quantizer and the integer GEMM (additive in the same way)
 EXPORTS_QGEMM_A8 = ("gq_quantize_act_q8", "gq_linear_packed_a8")
 A8_TYPES = (10, 11, 12, 13, 14, 8)  # the q_types gq_linear_packed_a8 serves: the K-quants and Q8_0
+# include/gptq_gguf_moe_gemm_a8.h: the packed MoE prefill on int8 activations -- the grouped integer GEMM and SwiGLU fused into the quantizer (additive in the same way)
+EXPORTS_MOE_GEMM_A8 = ("gq_linear_packed_experts_a8", "gq_silu_mul_quantize_act_q8")
 
 
 class GQError(RuntimeError):
@@ -216,6 +218,8 @@ def lib():
     L.gq_attn_prefill_q8_0_plan.argtypes = [i64, i64] + [ctypes.POINTER(i64)] * 3
     L.gq_quantize_act_q8.argtypes = [vp, i64, i64, ci, vp, vp, vp, vp]
     L.gq_linear_packed_a8.argtypes = [ci, vp, vp, i64, i64, vp, vp, vp, i64, vp, ci, vp]
+    L.gq_linear_packed_experts_a8.argtypes = [ci, vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, vp, i64, vp, ci, vp]
+    L.gq_silu_mul_quantize_act_q8.argtypes = [vp, vp, i64, i64, ci, vp, vp, vp, vp]
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -225,7 +229,7 @@ def lib():
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_IQ4_GPTQ + EXPORTS_QGEMM +
                  EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH + EXPORTS_MOE_ERREST + EXPORTS_QKNORM +
-                 EXPORTS_KVCACHE + EXPORTS_KVPREFILL + EXPORTS_QGEMM_A8):
+                 EXPORTS_KVCACHE + EXPORTS_KVPREFILL + EXPORTS_QGEMM_A8 + EXPORTS_MOE_GEMM_A8):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

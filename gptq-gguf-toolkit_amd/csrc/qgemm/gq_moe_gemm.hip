@@ -22,26 +22,17 @@
 #include "../../../include/gptq_gguf_moe_gemm.h"
 
 #include "../search/gq_block_host.hpp"
+#include "gq_moe_lookup.hpp"
 #include "gq_qgemm_core.hpp"
 
 namespace gq {
 namespace {
 
 using namespace gemmcore;
+using namespace moelookup;  // MAXE, PER, wave_scan and the (expert, tile) lookup (shared with gq_moe_gemm_a8.hip)
 
-constexpr int MAXE = GQ_MOE_ROUTE_MAX_EXPERTS, PER = MAXE / 64;  // experts per lane of a wave-wide scan
-constexpr int RT = 1024, RW = RT / 64;                           // threads and waves of the route workgroup
-static_assert(MAXE % 64 == 0 && MAXE <= RT, "four experts per lane; one thread per expert");
-
-// inclusive prefix sum of v over the 64 lanes
-__device__ __forceinline__ int wave_scan(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
+constexpr int RT = 1024, RW = RT / 64;  // threads and waves of the route workgroup
+static_assert(MAXE <= RT, "one thread per expert");
 
 __global__ __launch_bounds__(RT) void moe_route_kernel(const int32_t* __restrict__ pair_expert, int P, int E,
                                                        int32_t* __restrict__ expert_start, int32_t* __restrict__ order) {
@@ -113,33 +104,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __shared__ int64_t sbase[TR];
     const int tid = threadIdx.x, lane = tid & 63;
     const int b = blockIdx.x / n_rt;  // row tiles fastest: they share x and the expert
-    // this workgroup's (expert, tile): lane l holds the starts of experts 4 l .. 4 l + 3 and the end of the last
-    int st[PER + 1], nt[PER], s = 0;
-#pragma unroll
-    for (int k = 0; k <= PER; ++k) {
-        const int e = PER * lane + k;
-        st[k] = expert_start[e < E ? e : E];
-    }
-#pragma unroll
-    for (int k = 0; k < PER; ++k) s += nt[k] = (st[k + 1] - st[k] + TT - 1) / TT;  // (0 from E on: equal starts)
-    const int inc = wave_scan(s, lane);
-    const uint64_t hit = __ballot(b >= inc - s && b < inc);
-    if (hit == 0) return;  // uniform over the workgroup: every wave read the same starts
-    int e = 0, pos0 = 0, cnt = 0;
-    {
-        int bb = b - (inc - s);
-        bool found = false;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            if (!found && bb < nt[k]) {
-                found = true, e = PER * lane + k, pos0 = st[k] + bb * TT;
-                cnt = st[k + 1] - pos0 < TT ? st[k + 1] - pos0 : TT;
-            }
-            bb -= nt[k];
-        }
-        const int src = __builtin_ctzll(hit);
-        e = __shfl(e, src), pos0 = __shfl(pos0, src), cnt = __shfl(cnt, src);
-    }
+    int e, pos0, cnt;  // this workgroup's (expert, tile)
+    if (!expert_tile<TT>(expert_start, E, b, lane, e, pos0, cnt)) return;  // uniform over the workgroup: every wave read the same starts
     const int64_t r0 = (int64_t)(blockIdx.x % n_rt) * TR;
     const int nr = (int)((R - r0) < TR ? (R - r0) : TR), ntt = (cnt + 15) >> 4;
     const int64_t nsb = C / 256;

@@ -4,7 +4,7 @@
     python -m gptq_gguf_toolkit_amd.evo_quant_search --model_name_or_path HF_DIR --quant_weights_path DB \
         --calibration_data ids.pt --eval_datasets eval.pt --generations G --offspring N --target_bitwidth B \
         --survivors_per_selection 4 1 --tokens_per_selection 2048 16384 [--group_rule size|name|none] \
-        [--fitness_fn kl|ppl|sparse_kl] [--targets_on device|cpu] [--resident dense|packed [--packed_act q8]]
+        [--fitness_fn kl|ppl|sparse_kl] [--targets_on device|cpu] [--resident dense|packed [--packed_act q8] [--moe_prefill grouped [--moe_act q8]]]
 
 The loop of the reference's main() (:401-779) is restated as functions of their arguments -- scan_available_bitwidths (level_db's),
 calculate_total_bits, get_next_bitwidth, initial_parent / initial_candidates, mutate, make_offspring, minibatch, selection,
@@ -431,6 +431,9 @@ def parse_args(argv=None):
     p.add_argument("--moe_prefill", type=str, default="loop", choices=["loop", "grouped"],
                    help="with --resident packed: how the packed experts of a MoE model take more than a decode step's tokens "
                         "(PackedExperts.prefill)")
+    p.add_argument("--moe_act", type=str, default="fp", choices=["fp", "q8"],
+                   help="with --resident packed --moe_prefill grouped: fp (default), or q8: the experts' grouped prefill multiplies int8 activations "
+                        "with the blocks' integer codes (PackedExperts.act; K-quants and Q8_0)")
     p.add_argument("--packed_act", type=str, default="fp", choices=["fp", "q8"],
                    help="with --resident packed: fp (default), or q8: the Linears' prefill multiplies int8 activations with the "
                         "blocks' integer codes (PackedLinear.act; K-quants and Q8_0)")
@@ -450,6 +453,8 @@ def parse_args(argv=None):
     # every refusal BEFORE any work
     if args.packed_act != "fp" and args.resident != "packed":
         p.error("--packed_act needs --resident packed")
+    if args.moe_act != "fp" and (args.resident != "packed" or args.moe_prefill != "grouped"):
+        p.error("--moe_act needs --resident packed --moe_prefill grouped")
     for what, names in (("calibration_data", [args.calibration_data]), ("eval_datasets", args.eval_datasets)):
         for name in names:
             if not os.path.isfile(name):
@@ -605,7 +610,7 @@ def _run(args, ranks, device):
         target_logits, where = collect_targets(model, calibration_data, args.fitness_fn, args.kl_topk, args.targets_on)
     # refuses what does not fit before uploading
     store = LevelStore(model, args.quant_weights_path, device, layer_names, resident=args.resident,
-                       moe_prefill=args.moe_prefill, packed_act=args.packed_act)
+                       moe_prefill=args.moe_prefill, packed_act=args.packed_act, moe_act=args.moe_act)
     store.grouped_layer_names = grouped
     say(f"level store: {store.bytes()} bytes on {device}" +
           (f", {store.freed_bytes} bytes of dense weights freed" if args.resident == "packed" else ""))

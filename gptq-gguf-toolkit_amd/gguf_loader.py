@@ -292,7 +292,7 @@ def packed_expert_tensors(model: torch.nn.Module, path: str) -> Dict[str, dict]:
 
 
 def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bool = False,
-                 moe_prefill: str = "loop", act: str = "fp") -> Dict[str, torch.Tensor]:
+                 moe_prefill: str = "loop", act: str = "fp", moe_act: str = "fp") -> Dict[str, torch.Tensor]:
     """The packed half of load_into_model: the Linears of packed_linear_tensors become PackedLinear holding the file's
     block bytes (with the rotary row gather of attn_q / attn_k as row_src); the modules of packed_expert_tensors become
     PackedExperts (or, per expert, PackedLinear on a slice view) on ONE device copy of each merged tensor; with `vocab` also
@@ -329,7 +329,7 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
             for mod, role, e in users[name]:
                 if e is None:
                     m = model.get_submodule(mod)
-                    (m if hasattr(m, "set_level") else replace_experts(model, mod, moe_prefill)).set_level(role, dev, int(gt))
+                    (m if hasattr(m, "set_level") else replace_experts(model, mod, moe_prefill, moe_act)).set_level(role, dev, int(gt))
                 else:
                     replace_linear(model, mod).set_level(dev.view(shape[0], -1)[e], int(gt))
         elif any(g == name for g, _ in ends.values()):
@@ -346,7 +346,7 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
 
 
 def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill: str = "loop",
-                    packed_act: str = "fp") -> torch.nn.Module:
+                    packed_act: str = "fp", moe_act: str = "fp") -> torch.nn.Module:
     """Load the file's weights into `model` (parameters on a GPU), strict on names and shapes.  A tied lm_head (no
     `output.weight` in the file) follows token_embd.
     packed=True: the K-quant, Q8_0, IQ4_NL and IQ4_XS tensors of the blocks' nn.Linear modules stay packed on the device -- each such Linear
@@ -360,7 +360,9 @@ def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill
     both the same tensor: one device copy); an end stored as F16 / F32 loads dense as without it.
     moe_prefill (with packed): "loop" or "grouped", the prefill path of the PackedExperts modules (PackedExperts.prefill).
     packed_act (with packed): "fp" or "q8", PackedLinear's `act` for the blocks' Linears -- "q8" sends their prefill through
-    the int8-activation GEMM (ops.linear_packed_q8); experts and the vocabulary ends keep the 16-bit route."""
+    the int8-activation GEMM (ops.linear_packed_q8); experts and the vocabulary ends keep the 16-bit route.
+    moe_act (with moe_prefill="grouped"): "fp" or "q8", PackedExperts' `act` -- "q8" sends the grouped prefill of the experts
+    through the int8-activation grouped GEMM (ops.linear_packed_experts_a8)."""
     if packed not in (False, True, "all"):
         raise ValueError(f"load_into_model: packed must be False, True or 'all', got {packed!r}")
     if moe_prefill not in ("loop", "grouped") or (moe_prefill != "loop" and not packed):
@@ -369,8 +371,11 @@ def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill
     if packed_act not in ("fp", "q8") or (packed_act != "fp" and not packed):
         raise ValueError(f"load_into_model: packed_act must be 'fp' or 'q8' (with packed), got {packed_act!r} with "
                          f"packed={packed!r}")
+    if moe_act not in ("fp", "q8") or (moe_act != "fp" and moe_prefill != "grouped"):
+        raise ValueError(f"load_into_model: moe_act must be 'fp' or 'q8' (with moe_prefill='grouped'), got {moe_act!r} with "
+                         f"moe_prefill={moe_prefill!r}")
     ref = next(model.parameters())
-    sd = (_load_packed(model, path, ref, vocab=packed == "all", moe_prefill=moe_prefill, act=packed_act) if packed
+    sd = (_load_packed(model, path, ref, vocab=packed == "all", moe_prefill=moe_prefill, act=packed_act, moe_act=moe_act) if packed
           else load_state_dict(path, ref.device, ref.dtype, expert_layout_of(model)))
     want = model.state_dict()
     if "lm_head.weight" in want and "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:

@@ -70,14 +70,15 @@ class LevelStore:
 
     def __init__(self, model: nn.Module, db: str, device, layer_names: Optional[Sequence[str]] = None,
                  capacity_bytes: Optional[int] = None, resident: str = "dense", moe_prefill: str = "loop",
-                 packed_act: str = "fp"):
+                 packed_act: str = "fp", moe_act: str = "fp"):
         """layer_names: the Linears and expert units to hold (default: every nn.Linear of the model that has a directory in
         `db`, and the units `<module>.{gate,up,down}_proj` of every experts-shaped module that have one).
         capacity_bytes: the device memory the levels may take (default: what torch reports free on `device`).
         resident: "dense" -- the model keeps its nn.Linear weights and a switch decodes into them; "packed" -- the Linears
         become PackedLinear, their dense weights are freed (credited in the capacity check) and a switch swaps references.
         moe_prefill: packed residency's PackedExperts.prefill ("loop" or "grouped").
-        packed_act: packed residency's PackedLinear.act ("fp", or "q8": prefill on int8 activations, ops.linear_packed_q8)."""
+        packed_act: packed residency's PackedLinear.act ("fp", or "q8": prefill on int8 activations, ops.linear_packed_q8).
+        moe_act: PackedExperts.act of moe_prefill="grouped" ("fp", or "q8": ops.linear_packed_experts_a8)."""
         if packed_act not in ("fp", "q8") or (packed_act != "fp" and resident != "packed"):
             raise ValueError(f"packed_act must be 'fp' or 'q8' (with resident='packed'), got {packed_act!r} with resident={resident!r}")
         self.packed_act = packed_act
@@ -85,7 +86,9 @@ class LevelStore:
             raise ValueError(f"resident must be 'dense' or 'packed', got {resident!r}")
         if moe_prefill not in ("loop", "grouped"):
             raise ValueError(f"moe_prefill must be 'loop' or 'grouped', got {moe_prefill!r}")
-        self.resident, self.freed_bytes, self.moe_prefill = resident, 0, moe_prefill
+        if moe_act not in ("fp", "q8") or (moe_act != "fp" and moe_prefill != "grouped"):
+            raise ValueError(f"moe_act must be 'fp' or 'q8' (with moe_prefill='grouped'), got {moe_act!r} with moe_prefill={moe_prefill!r}")
+        self.resident, self.freed_bytes, self.moe_prefill, self.moe_act = resident, 0, moe_prefill, moe_act
         self.model, self.db, self.device = model, db, torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:  # "cuda" -> the current device, as tensors report it
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -148,7 +151,7 @@ class LevelStore:
                 mod = self.units[name][0]
                 if not isinstance(self.layers[name], packed_experts.PackedExperts):
                     self.freed_bytes += _experts_dense_bytes(self.layers[name])
-                    packed = packed_experts.replace_experts(model, mod, moe_prefill)
+                    packed = packed_experts.replace_experts(model, mod, moe_prefill, moe_act)
                     for other, (m, _) in self.units.items():
                         if m == mod:
                             self.layers[other] = packed

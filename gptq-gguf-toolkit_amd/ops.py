@@ -1252,14 +1252,16 @@ MOE_MAX_PAIRS = _cabi.MOE_MAX_PAIRS
 
 
 def _packed_experts_args(who: str, q_type, blocks, E, R, x, idx, idx_check, pairs_per_row, max_E, max_E_name, max_P, max_P_name,
-                         E_first: bool):
-    """The argument checks the two grouped expert ops share -> (k, E, R, C, x_rows, P, ppr).  idx: the op's index tensors;
+                         E_first: bool, codes: bool = False):
+    """The argument checks the grouped expert ops share -> (k, E, R, C, x_rows, P, ppr).  idx: the op's index tensors;
     idx_check() refuses them in the op's own words and returns P.  E_first: the op names a bad E / R before its index tensors
-    (linear_packed_experts), else after the pairs (gemv_packed_experts).  _need_cuda comes last: the refusals before it name
-    their value for tensors on any device."""
+    (linear_packed_experts), else after the pairs (gemv_packed_experts).  codes: x is quantize_act_q8's int8 codes
+    (linear_packed_experts_a8).  _need_cuda comes last: the refusals before it name their value for tensors on any device."""
     k, E, R, ppr = int(q_type), int(E), int(R), int(pairs_per_row)
     bs, ts = block_geometry(k)
-    if x.dtype not in (torch.float16, torch.bfloat16):
+    if codes and x.dtype != torch.int8:
+        raise _cabi.GQError(f"{who}: xq must be quantize_act_q8's int8 codes; got {x.dtype}")
+    if not codes and x.dtype not in (torch.float16, torch.bfloat16):
         raise _cabi.GQError(f"{who}: x must be fp16 or bf16 (there is no fp32 path); got {x.dtype}")
     if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
         raise _cabi.GQError(f"{who}: x must be a non-empty contiguous [x_rows, C] tensor; got {tuple(x.shape)} strides "
@@ -1367,6 +1369,70 @@ def linear_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: 
     check(lib().gq_linear_packed_experts(k, _ptr(blocks), E, R, C, _ptr(x), x_rows, ppr, _ptr(expert_start), _ptr(order), P,
                                          _DT[x.dtype], _ptr(y), _stream(x)), "gq_linear_packed_experts")
     return y
+
+
+# ---- the packed MoE prefill on int8 activations (gq_linear_packed_experts_a8, gq_silu_mul_quantize_act_q8) ----
+def linear_packed_experts_a8(q_type: int, blocks: torch.Tensor, E: int, R: int, xq: torch.Tensor, xd: torch.Tensor,
+                             xbsum: torch.Tensor, route, pairs_per_row: int, out_dtype: torch.dtype) -> torch.Tensor:
+    """linear_packed_experts on the activations of quantize_act_q8 (or silu_mul_quantize_act_q8): y [P, R] in out_dtype (fp16
+    or bf16) with y[p] = W[expert of pair p] (xq, xd, xbsum)[p // pairs_per_row] for every pair of `route` =
+    moe_route(pair_expert, E), in ONE launch on the int8 matrix pipe.  q_type is one of A8_TYPES (IQ4_NL / IQ4_XS are
+    refused); xq int8 [x_rows, C], xd fp32 [x_rows, C / 256], xbsum int16 [x_rows, C / 16] contiguous, x_rows * pairs_per_row =
+    P = route[1].numel().  Row p is bit for bit linear_packed_a8(q_type, that expert's slice, row p // pairs_per_row of the
+    three).  A pair in no run of the route is skipped and its row of y stays as torch.empty left it.  Nothing is read by the
+    host: no synchronisation (include/gptq_gguf_moe_gemm_a8.h)."""
+    who = "linear_packed_experts_a8"
+    expert_start, order = route
+    if int(q_type) not in A8_TYPES:
+        raise _cabi.GQError(f"{who}: q_type {int(q_type)} is not served on int8 activations (a K-quant 10..14 or Q8_0 8)")
+    if out_dtype not in (torch.float16, torch.bfloat16):
+        raise _cabi.GQError(f"{who}: out_dtype must be fp16 or bf16 (there is no fp32 path); got {out_dtype}")
+
+    if xq.dim() == 2:  # (any other xq is refused below, with the checks shared with the fp op)
+        n, C = xq.shape
+        if (xd.dtype != torch.float32 or xbsum.dtype != torch.int16 or tuple(xd.shape) != (n, C // 256)
+                or tuple(xbsum.shape) != (n, C // 16) or not (xd.is_contiguous() and xbsum.is_contiguous())):
+            raise _cabi.GQError(f"{who}: (xd, xbsum) must be quantize_act_q8's contiguous fp32 [{n}, {C // 256}] and int16 "
+                                f"[{n}, {C // 16}]; got {xd.dtype} {tuple(xd.shape)}, {xbsum.dtype} {tuple(xbsum.shape)}")
+
+    def pairs():
+        for name, t, n in (("expert_start", expert_start, int(E) + 1), ("order", order, order.numel())):
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != n:
+                raise _cabi.GQError(f"{who}: route: {name} must be a contiguous int32 [{n}] tensor (moe_route's output for "
+                                    f"E={int(E)}); got {t.dtype} {tuple(t.shape)}")
+        return order.numel()
+
+    k, E, R, C, x_rows, P, ppr = _packed_experts_args(
+        who, q_type, blocks, E, R, xq, (xd, xbsum, *route), pairs, pairs_per_row, MOE_ROUTE_MAX_EXPERTS,
+        f"MOE_ROUTE_MAX_EXPERTS={MOE_ROUTE_MAX_EXPERTS}", MOE_ROUTE_MAX_PAIRS, "MOE_ROUTE_MAX_PAIRS", E_first=True, codes=True)
+    y = torch.empty(P, R, dtype=out_dtype, device=xq.device)
+    check(lib().gq_linear_packed_experts_a8(k, _ptr(blocks), E, R, C, _ptr(xq), _ptr(xd), _ptr(xbsum), x_rows, ppr,
+                                            _ptr(expert_start), _ptr(order), P, _ptr(y), _DT[out_dtype], _stream(xq)),
+          "gq_linear_packed_experts_a8")
+    return y
+
+
+def silu_mul_quantize_act_q8(gate: torch.Tensor, up: torch.Tensor):
+    """quantize_act_q8(fwd_silu_mul(gate, up)), byte for byte, in ONE launch and without the 16-bit product being written:
+    gate, up contiguous fp16 / bf16 [..., I] of one shape and dtype, I % 256 == 0 -> (xq int8 [..., I], xd fp32 [..., I / 256],
+    xbsum int16 [..., I / 16]) (include/gptq_gguf_moe_gemm_a8.h)."""
+    who = "silu_mul_quantize_act_q8"
+    if gate.dtype not in (torch.float16, torch.bfloat16) or up.dtype != gate.dtype:
+        raise _cabi.GQError(f"{who}: gate and up must both be fp16 or both bf16 (there is no fp32 path); got {gate.dtype}, {up.dtype}")
+    if (gate.dim() < 1 or gate.shape != up.shape or not (gate.is_contiguous() and up.is_contiguous()) or gate.numel() == 0
+            or gate.shape[-1] % 256):
+        raise _cabi.GQError(f"{who}: gate and up must be non-empty contiguous [..., I] tensors of one shape with I % 256 == 0; "
+                            f"got {tuple(gate.shape)}, {tuple(up.shape)}")
+    if up.device != gate.device:
+        raise _cabi.GQError(f"{who}: every tensor must be on one device ({gate.device}); got one on {up.device}")
+    _need_cuda(gate, up)
+    I, lead = gate.shape[-1], gate.shape[:-1]
+    xq = torch.empty(*lead, I, dtype=torch.int8, device=gate.device)
+    xd = torch.empty(*lead, I // 256, dtype=torch.float32, device=gate.device)
+    xbsum = torch.empty(*lead, I // 16, dtype=torch.int16, device=gate.device)
+    check(lib().gq_silu_mul_quantize_act_q8(_ptr(gate), _ptr(up), gate.numel() // I, I, _DT[gate.dtype], _ptr(xq), _ptr(xd),
+                                            _ptr(xbsum), _stream(gate)), "gq_silu_mul_quantize_act_q8")
+    return xq, xd, xbsum
 
 
 # ---- the calibration forward of fused (dense) experts: the combine with transformers' roundings (gq_fwd_moe_combine) ----

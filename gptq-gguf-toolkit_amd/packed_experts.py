@@ -20,6 +20,11 @@ top_k_weights [T, K]).  Three paths:
     kernel) with ops.fwd_silu_mul in between, and the decode path's combine.  Nothing on this path reads a result back
     either: no unique, no nonzero, no where-without-other, no .item().  The chunks bound the three [P, I] temporaries
     (about 0.7 GB at Mixtral's I = 14336 and the default 8192 pairs).
+    With act = "q8" (opt-in; the default is "fp") and all three roles of a type in ops.A8_TYPES (K-quants, Q8_0) the chunk runs
+    on int8 activations instead: ONE ops.quantize_act_q8 of the hidden states shared by the gate and the up launch of
+    ops.linear_packed_experts_a8, ops.silu_mul_quantize_act_q8 (SwiGLU written as codes, 1 + 1/8 + 1/64 bytes per value
+    instead of the 16-bit activation), the down launch, the same combine.  A role of another type (IQ4_NL, IQ4_XS) keeps the
+    module on the fp launches.  The decode path and the loop path do not look at act.
   * the loop path, otherwise (prefill = "loop" is the default): per hit expert its tokens are gathered and multiplied with the expert's slice of the stacked
     tensor (a view) by ops.gemv_packed (1 .. gemv_max_t tokens) or ops.linear_packed, and added with index_add_, as
     transformers does.  Finding the hit experts and their tokens synchronises with the host.
@@ -50,6 +55,10 @@ class PackedExperts(nn.Module):
     # has the measurement).  An instance may override either.
     prefill = "loop"
     prefill_max_pairs = 8192
+    # What the grouped prefill multiplies with: "fp" (the 16-bit activations, ops.linear_packed_experts) or "q8" (int8
+    # activations on the integer matrix pipe, ops.linear_packed_experts_a8; DESIGN K36 has the measurement).  The numerics of
+    # "q8" are not the dense model's (an activation is at most half a step of its superblock off), so the default stays "fp".
+    act = "fp"
 
     def __init__(self, num_experts: int, hidden_dim: int, intermediate_dim: int, dtype: torch.dtype = torch.float16):
         super().__init__()
@@ -114,6 +123,10 @@ class PackedExperts(nn.Module):
                 and self.num_experts <= ops.MOE_ROUTE_MAX_EXPERTS and not self.takes_decode_path(T, K)
                 and all(self.levels[r] is not None and self.levels[r][1] is not None for r in ROLES))
 
+    def takes_q8_path(self, T: int, K: int) -> bool:
+        """Whether forward sends T tokens with K experts each through the grouped prefill on int8 activations."""
+        return (self.act == "q8" and self.takes_prefill_path(T, K) and all(self.levels[r][1] in ops.A8_TYPES for r in ROLES))
+
     def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
         for r in ROLES:
             self._level(r)
@@ -126,6 +139,8 @@ class PackedExperts(nn.Module):
                           f"{tuple(top_k_weights.shape)} must both be [T={hidden_states.shape[0]}, K]")
         if self.prefill not in ("loop", "grouped"):
             raise GQError(f"PackedExperts.prefill must be 'loop' or 'grouped', got {self.prefill!r}")
+        if self.act not in ("fp", "q8"):
+            raise GQError(f"PackedExperts.act must be 'fp' or 'q8', got {self.act!r}")
         if self.takes_decode_path(T, K):
             return self._forward_grouped(hidden_states.contiguous(), top_k_index, top_k_weights)
         if self.takes_prefill_path(T, K):
@@ -159,14 +174,23 @@ class PackedExperts(nn.Module):
         T, K = top_k_index.shape
         (gb, gq), (ub, uq), (db, dq) = (self.levels[r] for r in ROLES)
         step = max(1, min(self.prefill_max_pairs, ops.MOE_ROUTE_MAX_PAIRS) // K)  # tokens of a chunk
+        q8 = self.takes_q8_path(T, K)
         outs = []
         for t0 in range(0, T, step):
             xs, ws = x[t0:t0 + step], top_k_weights[t0:t0 + step]
             pairs = top_k_index[t0:t0 + step].reshape(-1).to(torch.int32)  # stays on the device
             route = ops.moe_route(pairs, E)
-            gate = ops.linear_packed_experts(gq, gb, E, I, xs, route, K)
-            up = ops.linear_packed_experts(uq, ub, E, I, xs, route, K)
-            down = ops.linear_packed_experts(dq, db, E, H, ops.fwd_silu_mul(gate, up), route, 1)  # [pairs, H]
+            if q8:
+                xa = ops.quantize_act_q8(xs)  # one quantized input for gate and up
+                gate = ops.linear_packed_experts_a8(gq, gb, E, I, *xa, route, K, self.dtype)
+                up = ops.linear_packed_experts_a8(uq, ub, E, I, *xa, route, K, self.dtype)
+                act = ops.silu_mul_quantize_act_q8(gate, up)
+                del gate, up  # the codes replace them: the down launch's output may take their memory
+                down = ops.linear_packed_experts_a8(dq, db, E, H, *act, route, 1, self.dtype)
+            else:
+                gate = ops.linear_packed_experts(gq, gb, E, I, xs, route, K)
+                up = ops.linear_packed_experts(uq, ub, E, I, xs, route, K)
+                down = ops.linear_packed_experts(dq, db, E, H, ops.fwd_silu_mul(gate, up), route, 1)  # [pairs, H]
             outs.append(self._combine(down, pairs, ws))
         return outs[0] if len(outs) == 1 else torch.cat(outs)
 
@@ -213,12 +237,15 @@ def experts_shaped(layer: nn.Module) -> bool:
             and gu.shape[0] == dn.shape[0] and gu.shape[1] == 2 * dn.shape[2] and gu.shape[2] == dn.shape[1])
 
 
-def replace_experts(model: nn.Module, name: str, prefill: str = "loop") -> PackedExperts:
+def replace_experts(model: nn.Module, name: str, prefill: str = "loop", act: str = "fp") -> PackedExperts:
     """Swap the MixtralExperts-shaped module `name` for a PackedExperts of its shape and dtype; its dense parameters are
     dropped.  The activation must be SiLU (ops.fwd_silu_mul is the only fused activation).  prefill: "loop" (the class
-    default) or "grouped", the path of inputs beyond the decode step."""
+    default) or "grouped", the path of inputs beyond the decode step; act: "fp" (the class default) or "q8", what the grouped
+    prefill multiplies with."""
     if prefill not in ("loop", "grouped"):
         raise ValueError(f"PackedExperts: prefill must be 'loop' or 'grouped', got {prefill!r}")
+    if act not in ("fp", "q8"):
+        raise ValueError(f"PackedExperts: act must be 'fp' or 'q8', got {act!r}")
     layer = model.get_submodule(name)
     if isinstance(layer, PackedExperts) or not experts_shaped(layer):
         raise TypeError(f"PackedExperts replaces a module with gate_up_proj [E, 2I, H] and down_proj [E, H, I] only, {name} is "
@@ -231,13 +258,15 @@ def replace_experts(model: nn.Module, name: str, prefill: str = "loop") -> Packe
     packed.train(layer.training)
     if prefill != PackedExperts.prefill:
         packed.prefill = prefill
+    if act != PackedExperts.act:
+        packed.act = act
     parent, _, leaf = name.rpartition(".")
     setattr(model.get_submodule(parent) if parent else model, leaf, packed)
     return packed
 
 
-def install_experts(model: nn.Module, names: Iterable[str], prefill: str = "loop") -> Dict[str, PackedExperts]:
+def install_experts(model: nn.Module, names: Iterable[str], prefill: str = "loop", act: str = "fp") -> Dict[str, PackedExperts]:
     """{name: PackedExperts}: every named expert module of `model` replaced; nothing holds their dense storage afterwards
     (unless the caller does).  prefill="grouped": their inputs beyond the decode step take the device-side routing and the
-    grouped GEMMs instead of the per-expert loop."""
-    return {name: replace_experts(model, name, prefill) for name in names}
+    grouped GEMMs instead of the per-expert loop; act="q8": those GEMMs run on int8 activations."""
+    return {name: replace_experts(model, name, prefill, act) for name in names}

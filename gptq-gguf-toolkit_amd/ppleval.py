@@ -3,7 +3,7 @@
 eval/ppleval.py (:25-120 flags, :124-152 load_compressed_weights, :207-229 the result JSON) on the gq_eval_* kernels.
 
     python -m gptq_gguf_toolkit_amd.ppleval --model_name_or_path HF_DIR --eval_datasets ids.pt --output_file out.json \
-        [--quant_weights_path DB [--quant_config_path FILE] [--quant_default_level N] | --gguf FILE [--packed [--packed_vocab] [--moe_prefill grouped] [--packed_act q8]]] \
+        [--quant_weights_path DB [--quant_config_path FILE] [--quant_default_level N] | --gguf FILE [--packed [--packed_vocab] [--moe_prefill grouped [--moe_act q8]] [--packed_act q8]]] \
         [--kl_against none|model|gguf:FILE]
 
 Evaluation data are `.pt` files of [1, L] id tensors (no tokenizer, no download).  Left out: --memory_efficient, wandb,
@@ -61,6 +61,9 @@ def parse_args(argv=None):
     p.add_argument("--moe_prefill", type=str, default="loop", choices=["loop", "grouped"],
                    help="with --packed: how the packed experts of a MoE model take more than a decode step's tokens -- the "
                         "per-expert loop, or device-side routing and one grouped GEMM per projection")
+    p.add_argument("--moe_act", type=str, default="fp", choices=["fp", "q8"],
+                   help="with --moe_prefill grouped: fp (default), or q8: the experts' grouped prefill multiplies int8 activations "
+                        "with the blocks' integer codes (PackedExperts.act; K-quants and Q8_0)")
     p.add_argument("--packed_act", type=str, default="fp", choices=["fp", "q8"],
                    help="with --packed: fp (default) multiplies 16-bit activations with the decoded blocks; q8 quantizes the "
                         "activations to int8 blocks of 256 and multiplies integers (K-quants and Q8_0; prefill only), the kind "
@@ -74,6 +77,8 @@ def parse_args(argv=None):
         p.error("--packed_vocab needs --packed")
     if args.moe_prefill != "loop" and not args.packed:
         p.error("--moe_prefill needs --packed")
+    if args.moe_act != "fp" and args.moe_prefill != "grouped":
+        p.error("--moe_act needs --moe_prefill grouped")
     if args.gguf and args.quant_weights_path:
         p.error("--gguf and --quant_weights_path are mutually exclusive")
     if args.kl_against not in ("none", "model") and not (args.kl_against.startswith("gguf:") and args.kl_against[5:]):
@@ -136,6 +141,7 @@ def apply_weights(model, args):
         prefill = getattr(args, "moe_prefill", "loop")  # (named only where it is not the loader's default)
         gguf_loader.load_into_model(model, args.gguf, packed="all" if packed and getattr(args, "packed_vocab", False) else packed,
                                     **({"moe_prefill": prefill} if prefill != "loop" else {}),
+                                    **({"moe_act": "q8"} if getattr(args, "moe_act", "fp") == "q8" else {}),
                                     **({"packed_act": "q8"} if getattr(args, "packed_act", "fp") == "q8" else {}))
     elif args.quant_weights_path:
         load_compressed_weights(model, args.quant_weights_path, args.quant_config_path, args.quant_default_level)
