@@ -292,7 +292,7 @@ def packed_expert_tensors(model: torch.nn.Module, path: str) -> Dict[str, dict]:
 
 
 def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bool = False,
-                 moe_prefill: str = "loop", act: str = "fp", moe_act: str = "fp") -> Dict[str, torch.Tensor]:
+                 moe_prefill: str = "loop", act: str = "fp", moe_act: str = "fp", decode_act: str = "fp") -> Dict[str, torch.Tensor]:
     """The packed half of load_into_model: the Linears of packed_linear_tensors become PackedLinear holding the file's
     block bytes (with the rotary row gather of attn_q / attn_k as row_src); the modules of packed_expert_tensors become
     PackedExperts (or, per expert, PackedLinear on a slice view) on ONE device copy of each merged tensor; with `vocab` also
@@ -322,7 +322,7 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
             key = (name.rsplit(".", 2)[-2], shape[0])
             if key not in rows:
                 rows[key] = rotary_row_src(name, shape[0], arch, n_head, n_kv, ref.device)
-            packed = replace_linear(model, by_gguf[name], act)
+            packed = replace_linear(model, by_gguf[name], act, decode_act)
             packed.set_level(_host(buf, off, nbytes).to(ref.device), int(gt), rows[key])
         elif name in users:
             held[name] = dev = _host(buf, off, nbytes).to(ref.device)  # the merged tensor's bytes: uploaded once
@@ -336,7 +336,7 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
             held[name] = _host(buf, off, nbytes).to(ref.device)
     for mod, (g, gt) in ends.items():
         if mod == "lm_head":
-            replace_linear(model, mod).set_level(held[g], int(gt))
+            replace_linear(model, mod, decode_act=decode_act).set_level(held[g], int(gt))
         else:
             replace_embedding(model, mod).set_level(held[g], int(gt))
     skip = {m + ".weight" for m in list(keep) + list(ends) + [m for m, r in experts.items() if "weight" in r]}
@@ -346,7 +346,7 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
 
 
 def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill: str = "loop",
-                    packed_act: str = "fp", moe_act: str = "fp") -> torch.nn.Module:
+                    packed_act: str = "fp", moe_act: str = "fp", packed_decode_act: str = "fp") -> torch.nn.Module:
     """Load the file's weights into `model` (parameters on a GPU), strict on names and shapes.  A tied lm_head (no
     `output.weight` in the file) follows token_embd.
     packed=True: the K-quant, Q8_0, IQ4_NL and IQ4_XS tensors of the blocks' nn.Linear modules stay packed on the device -- each such Linear
@@ -362,7 +362,10 @@ def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill
     packed_act (with packed): "fp" or "q8", PackedLinear's `act` for the blocks' Linears -- "q8" sends their prefill through
     the int8-activation GEMM (ops.linear_packed_q8); experts and the vocabulary ends keep the 16-bit route.
     moe_act (with moe_prefill="grouped"): "fp" or "q8", PackedExperts' `act` -- "q8" sends the grouped prefill of the experts
-    through the int8-activation grouped GEMM (ops.linear_packed_experts_a8)."""
+    through the int8-activation grouped GEMM (ops.linear_packed_experts_a8).
+    packed_decode_act (with packed): "fp" or "q8", PackedLinear's `decode_act` for the blocks' Linears and a packed lm_head --
+    "q8" sends their decode steps of 1 .. ops.GEMV_A8_MAX_T tokens through the int8-activation GEMV (ops.gemv_packed_q8);
+    experts keep the 16-bit route."""
     if packed not in (False, True, "all"):
         raise ValueError(f"load_into_model: packed must be False, True or 'all', got {packed!r}")
     if moe_prefill not in ("loop", "grouped") or (moe_prefill != "loop" and not packed):
@@ -371,11 +374,15 @@ def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill
     if packed_act not in ("fp", "q8") or (packed_act != "fp" and not packed):
         raise ValueError(f"load_into_model: packed_act must be 'fp' or 'q8' (with packed), got {packed_act!r} with "
                          f"packed={packed!r}")
+    if packed_decode_act not in ("fp", "q8") or (packed_decode_act != "fp" and not packed):
+        raise ValueError(f"load_into_model: packed_decode_act must be 'fp' or 'q8' (with packed), got {packed_decode_act!r} with "
+                         f"packed={packed!r}")
     if moe_act not in ("fp", "q8") or (moe_act != "fp" and moe_prefill != "grouped"):
         raise ValueError(f"load_into_model: moe_act must be 'fp' or 'q8' (with moe_prefill='grouped'), got {moe_act!r} with "
                          f"moe_prefill={moe_prefill!r}")
     ref = next(model.parameters())
-    sd = (_load_packed(model, path, ref, vocab=packed == "all", moe_prefill=moe_prefill, act=packed_act, moe_act=moe_act) if packed
+    sd = (_load_packed(model, path, ref, vocab=packed == "all", moe_prefill=moe_prefill, act=packed_act, moe_act=moe_act,
+                       decode_act=packed_decode_act) if packed
           else load_state_dict(path, ref.device, ref.dtype, expert_layout_of(model)))
     want = model.state_dict()
     if "lm_head.weight" in want and "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:

@@ -1247,6 +1247,39 @@ def linear_packed_q8(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src
     return linear_packed_a8(q_type, blocks, *quantize_act_q8(x), row_src=row_src, out_dtype=x.dtype)
 
 
+# ---- the decode step on int8 activations (gq_gemv_packed_a8, gq_gemv_a8_plan) ----
+GEMV_A8_MAX_T = _cabi.GEMV_A8_MAX_T
+
+
+def gemv_a8_plan(T: int, R: int, C: int) -> dict:
+    """How gemv_packed_q8 runs T tokens against a packed [R, C] weight (gq_gemv_a8_plan, no device needed): lds_bytes of the
+    quantized image of x, rows_per_turn of a workgroup's grid-stride loop, grid_cap, grid, and fits (the image is within the
+    LDS budget; a call that does not fit is refused)."""
+    v = [ctypes.c_int64() for _ in range(5)]
+    check(lib().gq_gemv_a8_plan(int(T), int(R), int(C), *[ctypes.byref(x) for x in v]), "gq_gemv_a8_plan")
+    d = dict(zip(("lds_bytes", "rows_per_turn", "grid_cap", "grid", "fits"), (int(x.value) for x in v)))
+    d["fits"] = bool(d["fits"])
+    return d
+
+
+def gemv_packed_q8(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemv_packed's arguments on int8 activations (gq_gemv_packed_a8), for 1 <= T = x.numel() // C <= GEMV_A8_MAX_T tokens and
+    a q_type of A8_TYPES (IQ4_NL / IQ4_XS are refused): ONE launch quantizes x as quantize_act_q8 does (into LDS) and multiplies
+    the weight's integer codes with it -- linear_packed_q8's terms in another fp32 summation order, one rounding
+    (include/gptq_gguf_qgemv_a8.h).  A (T, C) whose image does not fit LDS (gemv_a8_plan) is refused.  No workspace, no host
+    read."""
+    k, R, C, T = _packed_args("gemv_packed_q8", q_type, blocks, x, row_src)
+    if k not in A8_TYPES:
+        raise _cabi.GQError(f"gemv_packed_q8: q_type {k} is not served on int8 activations (a K-quant 10..14 or Q8_0 8)")
+    if T > GEMV_A8_MAX_T:
+        raise _cabi.GQError(f"gemv_packed_q8: T={T} tokens, at most GEMV_A8_MAX_T={GEMV_A8_MAX_T} (gemv_packed takes up to "
+                            f"{GEMV_MAX_T})")
+    y = torch.empty(*x.shape[:-1], R, dtype=x.dtype, device=x.device)
+    check(lib().gq_gemv_packed_a8(k, _ptr(blocks), _ptr(row_src), R, C, _ptr(x), T, _DT[x.dtype], _ptr(y), _stream(x)),
+          "gq_gemv_packed_a8")
+    return y
+
+
 # ---- the grouped expert GEMV of a packed MoE layer's decode step (gq_gemv_packed_experts) ----
 MOE_MAX_PAIRS = _cabi.MOE_MAX_PAIRS
 

@@ -12,6 +12,9 @@ With act="q8" (opt-in; the default is "fp") a packed level of a type that ops.li
 input of more than gemv_max_t tokens go through ops.linear_packed_q8: the activations are quantized to int8 blocks of 256 and
 multiplied with the weight's integer codes -- the kind of arithmetic a runtime that loads the .gguf uses, and other numerics
 than the dense model's.  Decode steps stay on ops.gemv_packed; dense levels and IQ4_NL / IQ4_XS keep their route.
+With decode_act="q8" (opt-in as well, independent of act) an input of 1 .. ops.GEMV_A8_MAX_T tokens, for such a level and a
+(T, C) whose quantized image fits LDS (ops.gemv_a8_plan), goes through ops.gemv_packed_q8: the same integer arithmetic in one
+launch, quantizer included.  More tokens, IQ4 and dense levels keep the routes above.
 There is no fallback: a PackedLinear without a level, or with an input of another dtype, raises."""
 from typing import Dict, Iterable, Optional
 
@@ -30,11 +33,13 @@ class PackedLinear(nn.Module):
     gemv_max_t = ops.GEMV_MAX_T
 
     def __init__(self, in_features: int, out_features: int, bias: Optional[nn.Parameter] = None,
-                 dtype: torch.dtype = torch.float16, act: str = "fp"):
+                 dtype: torch.dtype = torch.float16, act: str = "fp", decode_act: str = "fp"):
         super().__init__()
         if act not in ("fp", "q8"):
             raise ValueError(f'PackedLinear: act must be "fp" or "q8", not {act!r}')
-        self.act = act
+        if decode_act not in ("fp", "q8"):
+            raise ValueError(f'PackedLinear: decode_act must be "fp" or "q8", not {decode_act!r}')
+        self.act, self.decode_act = act, decode_act
         if dtype not in (torch.float16, torch.bfloat16):
             raise TypeError(f"PackedLinear computes in fp16 or bf16 (there is no fp32 path), not {dtype}")
         self.in_features, self.out_features = int(in_features), int(out_features)
@@ -72,9 +77,13 @@ class PackedLinear(nn.Module):
         self._need_level()
         if self.q_type is None:
             return F.linear(x, self.blocks, self.bias)
-        few = 1 <= x.numel() // self.in_features <= min(self.gemv_max_t, ops.GEMV_MAX_T)
+        T = x.numel() // self.in_features
+        few = 1 <= T <= min(self.gemv_max_t, ops.GEMV_MAX_T)
         int8 = self.act == "q8" and not few and self.q_type in ops.A8_TYPES
         fn = ops.gemv_packed if few else ops.linear_packed_q8 if int8 else ops.linear_packed
+        if (self.decode_act == "q8" and 1 <= T <= ops.GEMV_A8_MAX_T and self.q_type in ops.A8_TYPES
+                and ops.gemv_a8_plan(T, self.out_features, self.in_features)["fits"]):
+            fn = ops.gemv_packed_q8
         y = fn(self.q_type, self.blocks, x.contiguous(), self.row_src)
         return y if self.bias is None else y + self.bias
 
@@ -89,26 +98,26 @@ class PackedLinear(nn.Module):
 
     def extra_repr(self) -> str:
         return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, "
-                f"q_type={self.q_type}, act={self.act}")
+                f"q_type={self.q_type}, act={self.act}, decode_act={self.decode_act}")
 
 
-def replace_linear(model: nn.Module, name: str, act: str = "fp") -> PackedLinear:
-    """Swap the nn.Linear `name` for a PackedLinear of its shape, dtype and bias (and activation route `act`); its dense weight
-    is dropped."""
+def replace_linear(model: nn.Module, name: str, act: str = "fp", decode_act: str = "fp") -> PackedLinear:
+    """Swap the nn.Linear `name` for a PackedLinear of its shape, dtype and bias (and activation routes `act`, `decode_act`); its
+    dense weight is dropped."""
     layer = model.get_submodule(name)
     if not isinstance(layer, nn.Linear):
         raise TypeError(f"PackedLinear replaces nn.Linear only, {name} is a {type(layer).__name__}")
-    packed = PackedLinear(layer.in_features, layer.out_features, layer.bias, layer.weight.dtype, act)
+    packed = PackedLinear(layer.in_features, layer.out_features, layer.bias, layer.weight.dtype, act, decode_act)
     packed.train(layer.training)
     parent, _, leaf = name.rpartition(".")
     setattr(model.get_submodule(parent) if parent else model, leaf, packed)
     return packed
 
 
-def install(model: nn.Module, names: Iterable[str], act: str = "fp") -> Dict[str, PackedLinear]:
+def install(model: nn.Module, names: Iterable[str], act: str = "fp", decode_act: str = "fp") -> Dict[str, PackedLinear]:
     """{name: PackedLinear}: every named nn.Linear of `model` replaced; nothing holds their dense [R, C] storage afterwards
     (unless the caller does)."""
-    return {name: replace_linear(model, name, act) for name in names}
+    return {name: replace_linear(model, name, act, decode_act) for name in names}
 
 
 def dense_bytes(layer: nn.Linear) -> int:
