@@ -82,6 +82,8 @@ EXPORTS_MOE_GEMM_A8 = ("gq_linear_packed_experts_a8", "gq_silu_mul_quantize_act_
 # include/gptq_gguf_qgemv_a8.h: the decode step on int8 activations -- the quantizer fused into a dot4 GEMV, and its plan (additive in the same way)
 EXPORTS_QGEMV_A8 = ("gq_gemv_packed_a8", "gq_gemv_a8_plan")
 GEMV_A8_MAX_T = 4  # GQ_GEMV_A8_MAX_T: tokens of one gq_gemv_packed_a8 call
+# include/gptq_gguf_moe_gemv_a8.h: the MoE decode step on int8 activations -- the grouped expert dot4 GEMV, and its plan (additive in the same way)
+EXPORTS_MOE_GEMV_A8 = ("gq_gemv_packed_experts_a8", "gq_gemv_experts_a8_plan")
 
 
 class GQError(RuntimeError):
@@ -225,6 +227,8 @@ def lib():
     L.gq_silu_mul_quantize_act_q8.argtypes = [vp, vp, i64, i64, ci, vp, vp, vp, vp]
     L.gq_gemv_packed_a8.argtypes = [ci, vp, vp, i64, i64, vp, i64, ci, vp, vp]
     L.gq_gemv_a8_plan.argtypes = [i64, i64, i64] + [ctypes.POINTER(i64)] * 5
+    L.gq_gemv_packed_experts_a8.argtypes = [ci, vp, i64, i64, i64, vp, vp, i64, vp, i64, i64, ci, vp, vp]
+    L.gq_gemv_experts_a8_plan.argtypes = [i64, i64, i64] + [ctypes.POINTER(i64)] * 5
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -234,7 +238,7 @@ def lib():
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_IQ4_GPTQ + EXPORTS_QGEMM +
                  EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH + EXPORTS_MOE_ERREST + EXPORTS_QKNORM +
-                 EXPORTS_KVCACHE + EXPORTS_KVPREFILL + EXPORTS_QGEMM_A8 + EXPORTS_MOE_GEMM_A8 + EXPORTS_QGEMV_A8):
+                 EXPORTS_KVCACHE + EXPORTS_KVPREFILL + EXPORTS_QGEMM_A8 + EXPORTS_MOE_GEMM_A8 + EXPORTS_QGEMV_A8 + EXPORTS_MOE_GEMV_A8):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

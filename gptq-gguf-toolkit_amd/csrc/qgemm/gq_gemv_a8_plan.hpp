@@ -1,6 +1,7 @@
 // gq_gemv_a8_plan.hpp -- the pure plan of one gq_gemv_packed_a8 call (K37, qgemm/gq_gemv_a8.hip): the LDS image of the
 // quantized activations and whether it fits, the rows a workgroup takes per turn of its grid-stride loop, the cap of the
-// grid and the grid.  Plain arithmetic, no HIP header: the launcher and gq_gemv_a8_plan read this one text.
+// grid and the grid; and the same for one gq_gemv_packed_experts_a8 call (K38, qgemm/gq_moe_gemv_a8.hip).  Plain arithmetic,
+// no HIP header: the launchers, gq_gemv_a8_plan and gq_gemv_experts_a8_plan read this one text.
 #pragma once
 
 #include <cstdint>
@@ -44,6 +45,44 @@ inline GemvA8Plan make_gemv_a8_plan(int64_t T, int64_t R, int64_t C) {
     p.turns = (R + GEMV_A8_ROWS - 1) / GEMV_A8_ROWS;
     p.grid_cap = GEMV_A8_GRID_CAP;
     p.grid = p.turns < p.grid_cap ? p.turns : p.grid_cap;
+    p.fits = p.lds_bytes <= GEMV_A8_LDS_BUDGET;
+    return p;
+}
+
+// ---- gq_gemv_packed_experts_a8 (K38, qgemm/gq_moe_gemv_a8.hip): the grid is (grid_x, E) and only the workgroups of a hit
+// expert work.  The host cannot know how many experts a step hits, so the cap is per expert: with two hit experts (Mixtral
+// at T = 1) 128 is one workgroup per CU.  Measured against 64 and 256 in profiles/moe_gemv_a8_rate.txt (DESIGN K38).
+#ifndef GQ_GEMV_EXPERTS_A8_GRID_X_CAP  // (the profile's A/B builds the library with another value)
+#define GQ_GEMV_EXPERTS_A8_GRID_X_CAP 128
+#endif
+constexpr int64_t GEMV_EXPERTS_A8_GRID_X_CAP = GQ_GEMV_EXPERTS_A8_GRID_X_CAP;
+constexpr int GEMV_EXPERTS_A8_PASS = 4;  // matching pairs of a pass: the tokens of one image
+// The kernel switches per workgroup between the 1 .. 4-token instances of the row walk.  Defined (A/B builds only): one
+// 4-token instance with idle columns instead, whose image always has 4 rows.
+#ifdef GQ_GEMV_EXPERTS_A8_IDLE_COLUMNS
+constexpr bool GEMV_EXPERTS_A8_IDLE_COLUMNS = true;
+#else
+constexpr bool GEMV_EXPERTS_A8_IDLE_COLUMNS = false;
+#endif
+
+struct GemvExpertsA8Plan {
+    int64_t image_rows;     // min(P, GEMV_EXPERTS_A8_PASS): the most rows of x a pass quantizes
+    int64_t lds_bytes;      // the image of image_rows rows (make_gemv_a8_plan's layout)
+    int64_t rows_per_turn;  // GEMV_A8_ROWS
+    int64_t grid_x_cap;     // GEMV_EXPERTS_A8_GRID_X_CAP
+    int64_t grid_x;         // min(ceil(R / rows_per_turn), grid_x_cap): workgroup (b, e) takes row groups b, b + grid_x, ... of expert e
+    bool fits;              // lds_bytes <= GEMV_A8_LDS_BUDGET
+};
+
+// P >= 1, R >= 1, C % 256 == 0 (the caller has checked)
+inline GemvExpertsA8Plan make_gemv_experts_a8_plan(int64_t P, int64_t R, int64_t C) {
+    GemvExpertsA8Plan p{};
+    p.image_rows = P < GEMV_EXPERTS_A8_PASS && !GEMV_EXPERTS_A8_IDLE_COLUMNS ? P : GEMV_EXPERTS_A8_PASS;
+    p.lds_bytes = gemv_a8_off_d(p.image_rows, C) + p.image_rows * C / 64;
+    p.rows_per_turn = GEMV_A8_ROWS;
+    p.grid_x_cap = GEMV_EXPERTS_A8_GRID_X_CAP;
+    const int64_t turns = (R + GEMV_A8_ROWS - 1) / GEMV_A8_ROWS;
+    p.grid_x = turns < p.grid_x_cap ? turns : p.grid_x_cap;
     p.fits = p.lds_bytes <= GEMV_A8_LDS_BUDGET;
     return p;
 }

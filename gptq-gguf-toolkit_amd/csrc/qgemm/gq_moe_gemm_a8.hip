@@ -86,13 +86,9 @@ __global__ __launch_bounds__(256) void silu_mul_quantize_act_q8_kernel(const uin
     const uint32_t G[4] = {g4.x, g4.y, g4.z, g4.w}, U[4] = {u4.x, u4.y, u4.z, u4.w};
     float v[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {  // fwd_silu_mul_kernel's operations: ATen silu x / (1 + exp(-x)) in fp32, rounded, times up, rounded
+    for (int k = 0; k < 8; ++k) {
         const uint16_t gb = (uint16_t)(G[k >> 1] >> (16 * (k & 1))), ub = (uint16_t)(U[k >> 1] >> (16 * (k & 1)));
-        const float g = BF16 ? bf2f(gb) : h2f(gb), u = BF16 ? bf2f(ub) : h2f(ub);
-        const float sf = g / (1.0f + expf(-g));
-        const float s = BF16 ? bf2f(f2bf(sf)) : h2f(f2h(sf));
-        const float hf = s * u;
-        v[k] = BF16 ? bf2f(f2bf(hf)) : h2f(f2h(hf));
+        v[k] = silu_mul_rounded<BF16>(BF16 ? bf2f(gb) : h2f(gb), BF16 ? bf2f(ub) : h2f(ub));
     }
     quantize_superblock(v, on, sbi, piece, xq, xd, xbsum);
 }

@@ -17,22 +17,13 @@
 
 #include "../search/gq_block_host.hpp"
 #include "gq_gemv_core.hpp"
+#include "gq_moe_lookup.hpp"
 
 namespace gq {
 namespace {
 
 using namespace gemvcore;
-
-// the position of the n-th (from 0) set bit of m, n < popcount(m): six halvings, no cross-lane traffic
-__device__ __forceinline__ int nth_set_bit(uint64_t m, int n) {
-    int pos = 0;
-#pragma unroll
-    for (int w = 32; w; w >>= 1) {
-        const int c = __builtin_popcountll((m >> pos) & ((1ull << w) - 1));
-        if (n >= c) n -= c, pos += w;
-    }
-    return pos;
-}
+using moelookup::nth_set_bit;
 
 template <int QT, bool BF16>
 __global__ __launch_bounds__(64 * MAX_NW) void gemv_packed_experts_kernel(const uint8_t* __restrict__ blocks, int64_t R, int64_t C,

@@ -1,7 +1,8 @@
 // gq_moe_lookup.hpp -- how a workgroup of a grouped expert GEMM finds its (expert, token tile) from gq_moe_route's
 // expert_start: E + 1 <= 257 values, five per lane, the number of token tiles of a lane's four experts, one prefix sum over the
 // wave and a ballot.  Every wave of the workgroup computes the same answer, so no LDS and no barrier is spent on it.
-// gq_moe_gemm.hip (K25) and gq_moe_gemm_a8.hip (K36) include it.  Device code only.
+// gq_moe_gemm.hip (K25) and gq_moe_gemm_a8.hip (K36) include it; the grouped expert GEMVs (K24, K38) take nth_set_bit from
+// here.  Device code only.
 #pragma once
 #include "../../../include/gptq_gguf_moe_gemm.h"
 #include "../gq_common.hpp"
@@ -11,6 +12,18 @@ namespace moelookup {
 
 constexpr int MAXE = GQ_MOE_ROUTE_MAX_EXPERTS, PER = MAXE / 64;  // experts per lane of a wave-wide scan
 static_assert(MAXE % 64 == 0, "four experts per lane");
+
+// the position of the n-th (from 0) set bit of m, n < popcount(m): six halvings, no cross-lane traffic.  The grouped expert
+// GEMVs (gq_moe_gemv.hip, K24; gq_moe_gemv_a8.hip, K38) find the pairs of their expert's ballot mask with it.
+__device__ __forceinline__ int nth_set_bit(uint64_t m, int n) {
+    int pos = 0;
+#pragma unroll
+    for (int w = 32; w; w >>= 1) {
+        const int c = __builtin_popcountll((m >> pos) & ((1ull << w) - 1));
+        if (n >= c) n -= c, pos += w;
+    }
+    return pos;
+}
 
 // inclusive prefix sum of v over the 64 lanes
 __device__ __forceinline__ int wave_scan(int v, int lane) {

@@ -1,6 +1,7 @@
 // gq_qgemm_a8_core.hpp -- the one text of the packed tile GEMM on int8 activations and of the activation quantizer's rule.
 //   tile_pass_a8        staging, K loop and epilogue of a workgroup of 4 waves that owns [TT = 128 tokens, TR = 128 rows]
 //   quantize_superblock 8 values of a lane -> codes, group sums and the step of the superblock its 32 lanes own
+//   silu_mul_rounded    SwiGLU's two roundings in front of that rule, for the quantizers that fuse it
 // gq_qgemm_a8.hip (K35: tile token i = token t0 + i of the activations and of y) and gq_moe_gemm_a8.hip (K36: tile token i =
 // the i-th pair of an expert's run, its activation row gathered and its y row scattered through a list in LDS) include it, so
 // for one weight row and one quantized input row the two GEMMs run the same instructions in the same order: per superblock an
@@ -10,6 +11,7 @@
 // Device code only: the entry points' type dispatch and operand checks are search/gq_block_host.hpp's.
 #pragma once
 #include <float.h>
+#include <math.h>
 
 #include "gq_qgemm_core.hpp"
 
@@ -79,6 +81,17 @@ __device__ __forceinline__ void quantize_superblock(const float v[8], bool on, i
         if (!(piece & 1)) xbsum[sbi * 16 + (piece >> 1)] = (int16_t)s;
         if (piece == 0) xd[sbi] = d;
     }
+}
+
+// gq_fwd_silu_mul's operations on one element (fwd_silu_mul_kernel's): ATen's silu g / (1 + exp(-g)) in fp32, rounded to the
+// 16-bit type, times up, rounded again -> the value the quantizer sees.  gq_silu_mul_quantize_act_q8 (K36) and the prologue of
+// gq_gemv_packed_experts_a8 (K38) run this text.
+template <bool BF16>
+__device__ __forceinline__ float silu_mul_rounded(float g, float u) {
+    const float sf = g / (1.0f + expf(-g));
+    const float s = BF16 ? bf2f(f2bf(sf)) : h2f(f2h(sf));
+    const float hf = s * u;
+    return BF16 ? bf2f(f2bf(hf)) : h2f(f2h(hf));
 }
 
 // ------------------------------------------------------------------------------------------------ the GEMM

@@ -292,7 +292,8 @@ def packed_expert_tensors(model: torch.nn.Module, path: str) -> Dict[str, dict]:
 
 
 def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bool = False,
-                 moe_prefill: str = "loop", act: str = "fp", moe_act: str = "fp", decode_act: str = "fp") -> Dict[str, torch.Tensor]:
+                 moe_prefill: str = "loop", act: str = "fp", moe_act: str = "fp", decode_act: str = "fp",
+                 *, moe_decode_act: str = "fp") -> Dict[str, torch.Tensor]:
     """The packed half of load_into_model: the Linears of packed_linear_tensors become PackedLinear holding the file's
     block bytes (with the rotary row gather of attn_q / attn_k as row_src); the modules of packed_expert_tensors become
     PackedExperts (or, per expert, PackedLinear on a slice view) on ONE device copy of each merged tensor; with `vocab` also
@@ -329,7 +330,7 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
             for mod, role, e in users[name]:
                 if e is None:
                     m = model.get_submodule(mod)
-                    (m if hasattr(m, "set_level") else replace_experts(model, mod, moe_prefill, moe_act)).set_level(role, dev, int(gt))
+                    (m if hasattr(m, "set_level") else replace_experts(model, mod, moe_prefill, moe_act, decode_act=moe_decode_act)).set_level(role, dev, int(gt))
                 else:
                     replace_linear(model, mod).set_level(dev.view(shape[0], -1)[e], int(gt))
         elif any(g == name for g, _ in ends.values()):
@@ -346,7 +347,8 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
 
 
 def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill: str = "loop",
-                    packed_act: str = "fp", moe_act: str = "fp", packed_decode_act: str = "fp") -> torch.nn.Module:
+                    packed_act: str = "fp", moe_act: str = "fp", packed_decode_act: str = "fp", *,
+                    moe_decode_act: str = "fp") -> torch.nn.Module:
     """Load the file's weights into `model` (parameters on a GPU), strict on names and shapes.  A tied lm_head (no
     `output.weight` in the file) follows token_embd.
     packed=True: the K-quant, Q8_0, IQ4_NL and IQ4_XS tensors of the blocks' nn.Linear modules stay packed on the device -- each such Linear
@@ -365,7 +367,9 @@ def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill
     through the int8-activation grouped GEMM (ops.linear_packed_experts_a8).
     packed_decode_act (with packed): "fp" or "q8", PackedLinear's `decode_act` for the blocks' Linears and a packed lm_head --
     "q8" sends their decode steps of 1 .. ops.GEMV_A8_MAX_T tokens through the int8-activation GEMV (ops.gemv_packed_q8);
-    experts keep the 16-bit route."""
+    experts keep the 16-bit route unless moe_decode_act says otherwise.
+    moe_decode_act (with packed): "fp" or "q8", PackedExperts' `decode_act` -- "q8" sends the experts' decode steps of
+    1 .. ops.GEMV_A8_MAX_T tokens through the int8-activation grouped GEMV (ops.gemv_packed_experts_q8)."""
     if packed not in (False, True, "all"):
         raise ValueError(f"load_into_model: packed must be False, True or 'all', got {packed!r}")
     if moe_prefill not in ("loop", "grouped") or (moe_prefill != "loop" and not packed):
@@ -377,12 +381,15 @@ def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill
     if packed_decode_act not in ("fp", "q8") or (packed_decode_act != "fp" and not packed):
         raise ValueError(f"load_into_model: packed_decode_act must be 'fp' or 'q8' (with packed), got {packed_decode_act!r} with "
                          f"packed={packed!r}")
+    if moe_decode_act not in ("fp", "q8") or (moe_decode_act != "fp" and not packed):
+        raise ValueError(f"load_into_model: moe_decode_act must be 'fp' or 'q8' (with packed), got {moe_decode_act!r} with "
+                         f"packed={packed!r}")
     if moe_act not in ("fp", "q8") or (moe_act != "fp" and moe_prefill != "grouped"):
         raise ValueError(f"load_into_model: moe_act must be 'fp' or 'q8' (with moe_prefill='grouped'), got {moe_act!r} with "
                          f"moe_prefill={moe_prefill!r}")
     ref = next(model.parameters())
     sd = (_load_packed(model, path, ref, vocab=packed == "all", moe_prefill=moe_prefill, act=packed_act, moe_act=moe_act,
-                       decode_act=packed_decode_act) if packed
+                       decode_act=packed_decode_act, moe_decode_act=moe_decode_act) if packed
           else load_state_dict(path, ref.device, ref.dtype, expert_layout_of(model)))
     want = model.state_dict()
     if "lm_head.weight" in want and "lm_head.weight" not in sd and "model.embed_tokens.weight" in sd:

@@ -70,7 +70,7 @@ class LevelStore:
 
     def __init__(self, model: nn.Module, db: str, device, layer_names: Optional[Sequence[str]] = None,
                  capacity_bytes: Optional[int] = None, resident: str = "dense", moe_prefill: str = "loop",
-                 packed_act: str = "fp", moe_act: str = "fp"):
+                 packed_act: str = "fp", moe_act: str = "fp", *, moe_decode_act: str = "fp"):
         """layer_names: the Linears and expert units to hold (default: every nn.Linear of the model that has a directory in
         `db`, and the units `<module>.{gate,up,down}_proj` of every experts-shaped module that have one).
         capacity_bytes: the device memory the levels may take (default: what torch reports free on `device`).
@@ -78,7 +78,12 @@ class LevelStore:
         become PackedLinear, their dense weights are freed (credited in the capacity check) and a switch swaps references.
         moe_prefill: packed residency's PackedExperts.prefill ("loop" or "grouped").
         packed_act: packed residency's PackedLinear.act ("fp", or "q8": prefill on int8 activations, ops.linear_packed_q8).
-        moe_act: PackedExperts.act of moe_prefill="grouped" ("fp", or "q8": ops.linear_packed_experts_a8)."""
+        moe_act: PackedExperts.act of moe_prefill="grouped" ("fp", or "q8": ops.linear_packed_experts_a8).
+        moe_decode_act: packed residency's PackedExperts.decode_act ("fp", or "q8": ops.gemv_packed_experts_q8)."""
+        if moe_decode_act not in ("fp", "q8") or (moe_decode_act != "fp" and resident != "packed"):
+            raise ValueError(f"moe_decode_act must be 'fp' or 'q8' (with resident='packed'), got {moe_decode_act!r} with "
+                             f"resident={resident!r}")
+        self.moe_decode_act = moe_decode_act
         if packed_act not in ("fp", "q8") or (packed_act != "fp" and resident != "packed"):
             raise ValueError(f"packed_act must be 'fp' or 'q8' (with resident='packed'), got {packed_act!r} with resident={resident!r}")
         self.packed_act = packed_act
@@ -151,7 +156,7 @@ class LevelStore:
                 mod = self.units[name][0]
                 if not isinstance(self.layers[name], packed_experts.PackedExperts):
                     self.freed_bytes += _experts_dense_bytes(self.layers[name])
-                    packed = packed_experts.replace_experts(model, mod, moe_prefill, moe_act)
+                    packed = packed_experts.replace_experts(model, mod, moe_prefill, moe_act, decode_act=moe_decode_act)
                     for other, (m, _) in self.units.items():
                         if m == mod:
                             self.layers[other] = packed

@@ -1350,6 +1350,53 @@ def gemv_packed_experts(q_type: int, blocks: torch.Tensor, E: int, R: int, x: to
     return y
 
 
+# ---- the MoE decode step on int8 activations (gq_gemv_packed_experts_a8, gq_gemv_experts_a8_plan) ----
+def gemv_experts_a8_plan(P: int, R: int, C: int) -> dict:
+    """How gemv_packed_experts_q8 runs P pairs against a stacked [E, R, C] weight (gq_gemv_experts_a8_plan, no device needed):
+    lds_bytes of the quantized image of min(P, 4) rows, rows_per_turn of a workgroup's grid-stride loop over an expert's rows,
+    grid_x_cap, grid_x (the launch's grid is (grid_x, E)) and fits (the image is within the LDS budget; a call that does not
+    fit is refused)."""
+    v = [ctypes.c_int64() for _ in range(5)]
+    check(lib().gq_gemv_experts_a8_plan(int(P), int(R), int(C), *[ctypes.byref(x) for x in v]), "gq_gemv_experts_a8_plan")
+    d = dict(zip(("lds_bytes", "rows_per_turn", "grid_x_cap", "grid_x", "fits"), (int(x.value) for x in v)))
+    d["fits"] = bool(d["fits"])
+    return d
+
+
+def gemv_packed_experts_q8(q_type: int, blocks: torch.Tensor, E: int, R: int, x: torch.Tensor, pair_expert: torch.Tensor,
+                           pairs_per_row: int, x_up: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemv_packed_experts' arguments on int8 activations (gq_gemv_packed_experts_a8), for a q_type of A8_TYPES (IQ4_NL / IQ4_XS
+    are refused): ONE launch quantizes the input row of every pair as quantize_act_q8 does (into LDS) and multiplies its
+    expert's integer codes with it.  Row p is bit for bit gemv_packed_q8(q_type, expert pair_expert[p]'s slice,
+    x[p // pairs_per_row]).  x_up: None, or a tensor of x's shape and dtype -- the input is then fwd_silu_mul(x, x_up), computed
+    inside the kernel and never written (the down launch: x the gate and x_up the up result, pairs_per_row = 1).  A (P, C) whose
+    image does not fit LDS (gemv_experts_a8_plan) is refused.  An id outside [0, E) is not checked: that pair is skipped and its
+    row of y stays as torch.empty left it.  No workspace, no host read."""
+    who = "gemv_packed_experts_q8"
+
+    def pairs():
+        if pair_expert.dtype != torch.int32 or pair_expert.dim() != 1 or not pair_expert.is_contiguous():
+            raise _cabi.GQError(f"{who}: pair_expert must be a contiguous int32 [P] tensor; got {pair_expert.dtype} "
+                                f"{tuple(pair_expert.shape)}")
+        return pair_expert.numel()
+
+    if int(q_type) not in A8_TYPES:
+        raise _cabi.GQError(f"{who}: q_type {int(q_type)} is not served on int8 activations (a K-quant 10..14 or Q8_0 8)")
+    idx = (pair_expert,) if x_up is None else (pair_expert, x_up)
+    if x_up is not None and (x_up.dtype != x.dtype or x_up.shape != x.shape or not x_up.is_contiguous()):
+        raise _cabi.GQError(f"{who}: x_up must be a contiguous {x.dtype} {tuple(x.shape)} tensor like x; got {x_up.dtype} "
+                            f"{tuple(x_up.shape)}")
+    k, E, R, C, x_rows, P, ppr = _packed_experts_args(who, q_type, blocks, E, R, x, idx, pairs, pairs_per_row, 65535, "65535",
+                                                      MOE_MAX_PAIRS, "MOE_MAX_PAIRS", E_first=False)
+    plan = gemv_experts_a8_plan(P, R, C)  # before any allocation
+    if not plan["fits"]:
+        raise _cabi.GQError(f"{who}: P={P} C={C}: the quantized image of x, {plan['lds_bytes']} bytes, does not fit LDS")
+    y = torch.empty(P, R, dtype=x.dtype, device=x.device)
+    check(lib().gq_gemv_packed_experts_a8(k, _ptr(blocks), E, R, C, _ptr(x), _ptr(x_up), x_rows, _ptr(pair_expert), P, ppr,
+                                          _DT[x.dtype], _ptr(y), _stream(x)), "gq_gemv_packed_experts_a8")
+    return y
+
+
 # ---- the packed MoE prefill: device-side routing (gq_moe_route) and the grouped expert GEMM (gq_linear_packed_experts) ----
 MOE_ROUTE_MAX_EXPERTS = _cabi.MOE_ROUTE_MAX_EXPERTS
 MOE_ROUTE_MAX_PAIRS = _cabi.MOE_ROUTE_MAX_PAIRS

@@ -13,6 +13,11 @@ top_k_weights [T, K]).  Three paths:
     ops.gemv_packed_experts launches (gate, up, down: one launch each over every (token, expert) pair, the expert ids read
     on the device), ops.fwd_silu_mul in between, then the sum over k in fp32, k ascending, and one rounding to the model's
     dtype.  Nothing on this path reads a result back: no nonzero, no where-without-other, no .item().
+    With decode_act = "q8" (opt-in; the default is "fp"), T <= ops.GEMV_A8_MAX_T tokens, all three roles of a type in
+    ops.A8_TYPES and inputs whose quantized image fits LDS (ops.gemv_experts_a8_plan) the step runs on int8 activations
+    instead: three ops.gemv_packed_experts_q8 launches and no fwd_silu_mul launch -- gate and up quantize the hidden states
+    inside the kernel, the down launch takes (gate, up) and computes SwiGLU in its prologue, so the [P, I] activation is
+    never written.  Steps of more tokens and a role of another type (IQ4_NL, IQ4_XS) keep the 16-bit launches.
   * the prefill path, for any other input of a module with prefill = "grouped", all three levels packed and at most
     ops.MOE_ROUTE_MAX_EXPERTS experts: per chunk of at most prefill_max_pairs // K tokens one ops.moe_route launch (the
     pairs sorted by expert on the device), three ops.linear_packed_experts launches (gate and up with the hidden states,
@@ -24,7 +29,8 @@ top_k_weights [T, K]).  Three paths:
     on int8 activations instead: ONE ops.quantize_act_q8 of the hidden states shared by the gate and the up launch of
     ops.linear_packed_experts_a8, ops.silu_mul_quantize_act_q8 (SwiGLU written as codes, 1 + 1/8 + 1/64 bytes per value
     instead of the 16-bit activation), the down launch, the same combine.  A role of another type (IQ4_NL, IQ4_XS) keeps the
-    module on the fp launches.  The decode path and the loop path do not look at act.
+    module on the fp launches.  The decode path looks at decode_act only, the prefill path at act only (the two are
+    independent); the loop path looks at neither.
   * the loop path, otherwise (prefill = "loop" is the default): per hit expert its tokens are gathered and multiplied with the expert's slice of the stacked
     tensor (a view) by ops.gemv_packed (1 .. gemv_max_t tokens) or ops.linear_packed, and added with index_add_, as
     transformers does.  Finding the hit experts and their tokens synchronises with the host.
@@ -59,6 +65,10 @@ class PackedExperts(nn.Module):
     # activations on the integer matrix pipe, ops.linear_packed_experts_a8; DESIGN K36 has the measurement).  The numerics of
     # "q8" are not the dense model's (an activation is at most half a step of its superblock off), so the default stays "fp".
     act = "fp"
+    # What the decode path multiplies with: "fp" (ops.gemv_packed_experts) or "q8" (int8 activations quantized inside the
+    # kernel, ops.gemv_packed_experts_q8, for steps of at most ops.GEMV_A8_MAX_T tokens; DESIGN K38 has the measurement).
+    # Independent of act, and opt-in for the same reason.
+    decode_act = "fp"
 
     def __init__(self, num_experts: int, hidden_dim: int, intermediate_dim: int, dtype: torch.dtype = torch.float16):
         super().__init__()
@@ -127,6 +137,12 @@ class PackedExperts(nn.Module):
         """Whether forward sends T tokens with K experts each through the grouped prefill on int8 activations."""
         return (self.act == "q8" and self.takes_prefill_path(T, K) and all(self.levels[r][1] in ops.A8_TYPES for r in ROLES))
 
+    def takes_q8_decode_path(self, T: int, K: int) -> bool:
+        """Whether forward sends T tokens with K experts each through the three grouped launches on int8 activations."""
+        return (self.decode_act == "q8" and self.takes_decode_path(T, K) and T <= ops.GEMV_A8_MAX_T
+                and all(self.levels[r][1] in ops.A8_TYPES for r in ROLES)
+                and all(ops.gemv_experts_a8_plan(T * K, *self.role_shape(r))["fits"] for r in ("gate", "down")))
+
     def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
         for r in ROLES:
             self._level(r)
@@ -141,6 +157,8 @@ class PackedExperts(nn.Module):
             raise GQError(f"PackedExperts.prefill must be 'loop' or 'grouped', got {self.prefill!r}")
         if self.act not in ("fp", "q8"):
             raise GQError(f"PackedExperts.act must be 'fp' or 'q8', got {self.act!r}")
+        if self.decode_act not in ("fp", "q8"):
+            raise GQError(f"PackedExperts.decode_act must be 'fp' or 'q8', got {self.decode_act!r}")
         if self.takes_decode_path(T, K):
             return self._forward_grouped(hidden_states.contiguous(), top_k_index, top_k_weights)
         if self.takes_prefill_path(T, K):
@@ -164,6 +182,11 @@ class PackedExperts(nn.Module):
         T, K = top_k_index.shape
         pairs = top_k_index.reshape(-1).to(torch.int32)  # pair p = (token p // K, choice p % K); stays on the device
         (gb, gq), (ub, uq), (db, dq) = (self.levels[r] for r in ROLES)
+        if self.takes_q8_decode_path(T, K):
+            gate = ops.gemv_packed_experts_q8(gq, gb, E, I, x, pairs, K)
+            up = ops.gemv_packed_experts_q8(uq, ub, E, I, x, pairs, K)
+            down = ops.gemv_packed_experts_q8(dq, db, E, H, gate, pairs, 1, x_up=up)  # SwiGLU in the prologue: [T * K, H]
+            return self._combine(down, pairs, top_k_weights)
         gate = ops.gemv_packed_experts(gq, gb, E, I, x, pairs, K)
         up = ops.gemv_packed_experts(uq, ub, E, I, x, pairs, K)
         down = ops.gemv_packed_experts(dq, db, E, H, ops.fwd_silu_mul(gate, up), pairs, 1)  # [T * K, H]
@@ -237,22 +260,24 @@ def experts_shaped(layer: nn.Module) -> bool:
             and gu.shape[0] == dn.shape[0] and gu.shape[1] == 2 * dn.shape[2] and gu.shape[2] == dn.shape[1])
 
 
-def replace_experts(model: nn.Module, name: str, prefill: str = "loop", act: str = "fp") -> PackedExperts:
+def replace_experts(model: nn.Module, name: str, prefill: str = "loop", act: str = "fp", *, decode_act: str = "fp") -> PackedExperts:
     """Swap the MixtralExperts-shaped module `name` for a PackedExperts of its shape and dtype; its dense parameters are
     dropped.  The activation must be SiLU (ops.fwd_silu_mul is the only fused activation).  prefill: "loop" (the class
     default) or "grouped", the path of inputs beyond the decode step; act: "fp" (the class default) or "q8", what the grouped
-    prefill multiplies with."""
+    prefill multiplies with; decode_act: "fp" (the class default) or "q8", what the decode path multiplies with."""
     if prefill not in ("loop", "grouped"):
         raise ValueError(f"PackedExperts: prefill must be 'loop' or 'grouped', got {prefill!r}")
     if act not in ("fp", "q8"):
         raise ValueError(f"PackedExperts: act must be 'fp' or 'q8', got {act!r}")
+    if decode_act not in ("fp", "q8"):
+        raise ValueError(f"PackedExperts: decode_act must be 'fp' or 'q8', got {decode_act!r}")
     layer = model.get_submodule(name)
     if isinstance(layer, PackedExperts) or not experts_shaped(layer):
         raise TypeError(f"PackedExperts replaces a module with gate_up_proj [E, 2I, H] and down_proj [E, H, I] only, {name} is "
                         f"a {type(layer).__name__}")
-    act = getattr(layer, "act_fn", None)
-    if act is not None and not isinstance(act, nn.SiLU) and "silu" not in type(act).__name__.lower():
-        raise TypeError(f"PackedExperts computes silu(gate) * up only, {name} has the activation {type(act).__name__}")
+    fn = getattr(layer, "act_fn", None)  # (not `act`: that is the argument)
+    if fn is not None and not isinstance(fn, nn.SiLU) and "silu" not in type(fn).__name__.lower():
+        raise TypeError(f"PackedExperts computes silu(gate) * up only, {name} has the activation {type(fn).__name__}")
     E, H, I = layer.down_proj.shape
     packed = PackedExperts(E, H, I, layer.down_proj.dtype)
     packed.train(layer.training)
@@ -260,13 +285,17 @@ def replace_experts(model: nn.Module, name: str, prefill: str = "loop", act: str
         packed.prefill = prefill
     if act != PackedExperts.act:
         packed.act = act
+    if decode_act != PackedExperts.decode_act:
+        packed.decode_act = decode_act
     parent, _, leaf = name.rpartition(".")
     setattr(model.get_submodule(parent) if parent else model, leaf, packed)
     return packed
 
 
-def install_experts(model: nn.Module, names: Iterable[str], prefill: str = "loop", act: str = "fp") -> Dict[str, PackedExperts]:
+def install_experts(model: nn.Module, names: Iterable[str], prefill: str = "loop", act: str = "fp", *,
+                    decode_act: str = "fp") -> Dict[str, PackedExperts]:
     """{name: PackedExperts}: every named expert module of `model` replaced; nothing holds their dense storage afterwards
     (unless the caller does).  prefill="grouped": their inputs beyond the decode step take the device-side routing and the
-    grouped GEMMs instead of the per-expert loop; act="q8": those GEMMs run on int8 activations."""
-    return {name: replace_experts(model, name, prefill, act) for name in names}
+    grouped GEMMs instead of the per-expert loop; act="q8": those GEMMs run on int8 activations; decode_act="q8": decode steps of at most
+    ops.GEMV_A8_MAX_T tokens run on int8 activations."""
+    return {name: replace_experts(model, name, prefill, act, decode_act=decode_act) for name in names}
