@@ -84,6 +84,10 @@ EXPORTS_QGEMV_A8 = ("gq_gemv_packed_a8", "gq_gemv_a8_plan")
 GEMV_A8_MAX_T = 4  # GQ_GEMV_A8_MAX_T: tokens of one gq_gemv_packed_a8 call
 # include/gptq_gguf_moe_gemv_a8.h: the MoE decode step on int8 activations -- the grouped expert dot4 GEMV, and its plan (additive in the same way)
 EXPORTS_MOE_GEMV_A8 = ("gq_gemv_packed_experts_a8", "gq_gemv_experts_a8_plan")
+# include/gptq_gguf_qgemv_group_a8.h: the projections of one input (q / k / v; gate / up with SwiGLU) in one dot4 GEMV launch, and its plan (additive in the same way)
+EXPORTS_QGEMV_GROUP_A8 = ("gq_gemv_packed_group_a8", "gq_gemv_group_a8_plan")
+GEMV_GROUP_MAX = 4  # GQ_GEMV_GROUP_MAX: members of one gq_gemv_packed_group_a8 call
+GEMV_GROUP_SPLIT, GEMV_GROUP_SWIGLU = 0, 1  # GQ_GEMV_GROUP_SPLIT, GQ_GEMV_GROUP_SWIGLU
 
 
 class GQError(RuntimeError):
@@ -111,6 +115,12 @@ class SwitchExpertsJob(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("E", ctypes.c_int64), ("R", ctypes.c_int64),
                 ("C", ctypes.c_int64), ("dst_expert_stride", ctypes.c_int64), ("kind", ctypes.c_int32),
                 ("out_dtype", ctypes.c_int32)]
+
+
+class GemvMember(ctypes.Structure):
+    """gq_gemv_member_t"""
+    _fields_ = [("q_type", ctypes.c_int), ("blocks", ctypes.c_void_p), ("row_src", ctypes.c_void_p), ("R", ctypes.c_int64),
+                ("y", ctypes.c_void_p)]
 
 
 class Band(ctypes.Structure):
@@ -229,6 +239,8 @@ def lib():
     L.gq_gemv_a8_plan.argtypes = [i64, i64, i64] + [ctypes.POINTER(i64)] * 5
     L.gq_gemv_packed_experts_a8.argtypes = [ci, vp, i64, i64, i64, vp, vp, i64, vp, i64, i64, ci, vp, vp]
     L.gq_gemv_experts_a8_plan.argtypes = [i64, i64, i64] + [ctypes.POINTER(i64)] * 5
+    L.gq_gemv_packed_group_a8.argtypes = [ctypes.POINTER(GemvMember), ci, i64, vp, i64, ci, ci, vp]
+    L.gq_gemv_group_a8_plan.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(i64), ci, i64, i64, ci] + [ctypes.POINTER(i64)] * 4
     L.gq_prof_enable.argtypes = [ctypes.c_uint]
     L.gq_prof_enable.restype = None
     L.gq_prof_name.argtypes = [ci]
@@ -238,7 +250,7 @@ def lib():
                                    ctypes.POINTER(ctypes.c_double)]
     for name in (EXPORTS + EXPORTS_ERREST + EXPORTS_SEARCH + EXPORTS_LEVELS + EXPORTS_LEVELPACK + EXPORTS_Q8 + EXPORTS_IQ4_ENCODE + EXPORTS_IQ4_GPTQ + EXPORTS_QGEMM +
                  EXPORTS_QGEMV + EXPORTS_SAMPLE + EXPORTS_MOE + EXPORTS_MOE_GEMM + EXPORTS_MOE_CALIB + EXPORTS_MOE_SEARCH + EXPORTS_MOE_ERREST + EXPORTS_QKNORM +
-                 EXPORTS_KVCACHE + EXPORTS_KVPREFILL + EXPORTS_QGEMM_A8 + EXPORTS_MOE_GEMM_A8 + EXPORTS_QGEMV_A8 + EXPORTS_MOE_GEMV_A8):
+                 EXPORTS_KVCACHE + EXPORTS_KVPREFILL + EXPORTS_QGEMM_A8 + EXPORTS_MOE_GEMM_A8 + EXPORTS_QGEMV_A8 + EXPORTS_MOE_GEMV_A8 + EXPORTS_QGEMV_GROUP_A8):
         getattr(L, name)  # raises AttributeError if the .so lacks a declared symbol
     _lib = L
     return L

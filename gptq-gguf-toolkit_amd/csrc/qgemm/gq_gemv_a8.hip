@@ -52,17 +52,18 @@ __global__ __launch_bounds__(NT) void gemv_packed_a8_kernel(const uint8_t* __res
     extern __shared__ __attribute__((aligned(16))) uint8_t a8_img[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), p = lane & 3, g4 = lane >> 2;
     const int nsb = C / 256;
-    auto row_of = [=](int64_t r) { return row_src ? (int64_t)row_src[r] : r; };
+    auto row_at = rows_of<QT>(blocks, [=](int64_t r) { return row_src ? (int64_t)row_src[r] : r; }, nsb);
 
     const int64_t r = (int64_t)blockIdx.x * GEMV_A8_ROWS + wave;
     uint32_t cur[NRAW<QT>] = {};
-    if (r < R) load_item<QT>(blocks, row_of, nsb, g4, p, cur, r, 0);  // in flight during the prologue
+    if (r < R) load_item<QT>(row_at, nsb, g4, p, cur, r, 0);  // in flight during the prologue
 
     // ---- the prologue: x -> the image; the T rows of x are the image's superblocks in order
     quantize_image(TT, TT * nsb, C, [](int sbi) { return (int64_t)sbi * 256; }, x, nullptr, bf16, a8_img);
     __syncthreads();
 
-    row_walk<QT, TT>(blocks, row_of, R, C, r, cur, a8_img, bf16, y, [](int t) { return t; });
+    row_walk<QT, TT>(row_at, R, C, r, rows_apart((int64_t)gridDim.x * GEMV_A8_ROWS), cur, a8_img,
+                     store_rows(y, R, bf16, [](int t) { return t; }));
 }
 
 template <int QT, int TT>

@@ -1,8 +1,9 @@
 // gq_gemv_a8_core.hpp -- the one text of the dot4 GEMV on int8 activations: what a lane loads of a superblock (piece,
 // load_raw, load_item), the integer part of a lane against the quantized image in LDS (lane_dots) and the walk of a wave over
-// its rows (row_walk).  gq_gemv_a8.hip (K37: the rows of one weight, token t = row t of x and of y) and gq_moe_gemv_a8.hip
-// (K38: the rows of one expert's slice of a stacked tensor, token t = the t-th matching pair of a pass) include it, so for one
-// weight row and one quantized input row the two kernels run the same instructions in the same order: row p of K38's y is
+// its rows (row_walk).  gq_gemv_a8.hip (K37: the rows of one weight, token t = row t of x and of y), gq_moe_gemv_a8.hip
+// (K38: the rows of one expert's slice of a stacked tensor, token t = the t-th matching pair of a pass) and
+// gq_gemv_group_a8.hip (K39: the rows of up to four weights of one input on a partitioned grid) include it, so for one
+// weight row and one quantized input row the three kernels run the same instructions in the same order: row p of K38's y is
 // bit for bit K37's result at T = 1 on that slice and that input row.  A token's accumulator is touched by no other token, so
 // the number of tokens of an instance does not change a token's bits either.  The form is described at the head of
 // gq_gemv_a8.hip.  Device code only.
@@ -67,12 +68,16 @@ __device__ __forceinline__ void load_raw(const uint8_t* A, int p, uint32_t* w) {
 }
 
 // lane group g4's superblock of step `st` of row r (r < R) of a weight of nsb superblocks per row, if the row has one;
-// row_of(r): the packed row that holds row r
-template <int QT, class RowOf>
-__device__ __forceinline__ void load_item(const uint8_t* __restrict__ blocks, RowOf row_of, int nsb, int g4, int p, uint32_t* w,
-                                          int64_t r, int st) {
+// row_at(r): the first byte of the packed row that holds row r
+template <int QT, class RowAt>
+__device__ __forceinline__ void load_item(RowAt row_at, int nsb, int g4, int p, uint32_t* w, int64_t r, int st) {
     const int j = GEMV_A8_STEP * st + g4;
-    if (j < nsb) load_raw<QT>(blocks + ((int64_t)row_of(r) * nsb + j) * ROWB<QT>, p, w);
+    if (j < nsb) load_raw<QT>(row_at(r) + (int64_t)j * ROWB<QT>, p, w);
+}
+// row_at of a weight whose row r is packed row row_of(r) of `blocks`
+template <int QT, class RowOf>
+__device__ __forceinline__ auto rows_of(const uint8_t* __restrict__ blocks, RowOf row_of, int nsb) {
+    return [=](int64_t r) { return blocks + (int64_t)row_of(r) * nsb * ROWB<QT>; };
 }
 
 __device__ __forceinline__ u32x4 lds16(const int8_t* p) { return *reinterpret_cast<const u32x4*>(p); }
@@ -193,13 +198,13 @@ __device__ __forceinline__ void quantize_image(int T, int tot, int C, Src src, c
     }
 }
 
-// The walk of a wave over its rows r, r + gridDim.x * GEMV_A8_ROWS, .. (< R) against the image of TT tokens at a8_img, after
-// the barrier that follows the prologue.  cur: the wave's share of step 0 of row r, loaded before the prologue (load_item).
-// yrow(t): the row of y that token t is stored to, negative: an idle column, not stored; lane t stores token t, rounded once.
-template <int QT, int TT, class RowOf, class YRow>
-__device__ __forceinline__ void row_walk(const uint8_t* __restrict__ blocks, RowOf row_of, int64_t R, int C, int64_t r,
-                                         uint32_t (&cur)[NRAW<QT>], const uint8_t* a8_img, int bf16, uint16_t* __restrict__ y,
-                                         YRow yrow) {
+// The walk of a wave over its rows r, next(r), next(next(r)), .. (< R) against the image of TT tokens at a8_img, after the
+// barrier that follows the prologue.  row_at: load_item's.  cur: the wave's share of step 0 of row r, loaded before the
+// prologue (load_item).  done(t, r, v): called by every lane at the end of row r with token t's sum v, the same in all 64
+// lanes and not yet rounded; it rounds and stores (K37, K38: lane t, once, to y) or keeps (K39's gate rows).
+template <int QT, int TT, class RowAt, class Next, class Done>
+__device__ __forceinline__ void row_walk(RowAt row_at, int64_t R, int C, int64_t r, Next next, uint32_t (&cur)[NRAW<QT>],
+                                         const uint8_t* a8_img, Done done) {
     constexpr int NW = NRAW<QT>;
     const int lane = threadIdx.x & 63, p = lane & 3, g4 = lane >> 2;
     const int nsb = C / 256, nsteps = (nsb + GEMV_A8_STEP - 1) / GEMV_A8_STEP;
@@ -214,9 +219,9 @@ __device__ __forceinline__ void row_walk(const uint8_t* __restrict__ blocks, Row
     while (r < R) {
         int nstep = step + 1;
         int64_t nr = r;
-        if (nstep == nsteps) nstep = 0, nr = r + (int64_t)gridDim.x * GEMV_A8_ROWS;
+        if (nstep == nsteps) nstep = 0, nr = next(r);
         uint32_t nxt[NW] = {};
-        if (nr < R) load_item<QT>(blocks, row_of, nsb, g4, p, nxt, nr, nstep);
+        if (nr < R) load_item<QT>(row_at, nsb, g4, p, nxt, nr, nstep);
 
         const int j = GEMV_A8_STEP * step + g4;
         const bool active = j < nsb;
@@ -253,8 +258,7 @@ __device__ __forceinline__ void row_walk(const uint8_t* __restrict__ blocks, Row
                 float v = facc[t];
 #pragma unroll
                 for (int m = GEMV_A8_LANES; m < 64; m <<= 1) v += __shfl_xor(v, m);
-                const int64_t yr = yrow(t);
-                if (lane == t && yr >= 0) y[yr * R + r] = bf16 ? f2bf(v) : f2h(v);
+                done(t, r, v);
                 facc[t] = 0.f;
             }
         }
@@ -262,6 +266,21 @@ __device__ __forceinline__ void row_walk(const uint8_t* __restrict__ blocks, Row
         for (int i = 0; i < NW; ++i) cur[i] = nxt[i];
         r = nr, step = nstep;
     }
+}
+
+// done of a walk that stores: lane t writes token t of row r, rounded once, to row yrow(t) of y [., R] (negative: an idle
+// column, not stored)
+template <class YRow>
+__device__ __forceinline__ auto store_rows(uint16_t* __restrict__ y, int64_t R, int bf16, YRow yrow) {
+    const int lane = threadIdx.x & 63;
+    return [=](int t, int64_t r, float v) {
+        const int64_t yr = yrow(t);
+        if (lane == t && yr >= 0) y[yr * R + r] = bf16 ? f2bf(v) : f2h(v);
+    };
+}
+// next of a walk whose rows lie `stride` apart
+__device__ __forceinline__ auto rows_apart(int64_t stride) {
+    return [=](int64_t r) { return r + stride; };
 }
 
 }  // namespace gemva8

@@ -76,12 +76,13 @@ __global__ __launch_bounds__(NT) void gemv_packed_experts_a8_kernel(const uint8_
     const uint64_t m = __ballot(lane < P && pair_expert[lane] == e);
     if (m == 0) return;  // uniform over the workgroup: every wave read the same ids
     const int nm = __builtin_popcountll(m), nsb = C / 256;
-    auto row_of = [=](int64_t r) { return (int64_t)e * R + r; };  // expert e's slice of the stacked tensor
+    auto row_at = rows_of<QT>(blocks, [=](int64_t r) { return (int64_t)e * R + r; }, nsb);  // expert e's slice of the stacked tensor
+    auto next = rows_apart((int64_t)gridDim.x * GEMV_A8_ROWS);
     for (int first = 0;;) {
         const int n = nm - first < GEMV_EXPERTS_A8_PASS ? nm - first : GEMV_EXPERTS_A8_PASS;
         const int64_t r = (int64_t)blockIdx.x * GEMV_A8_ROWS + wave;
         uint32_t cur[NRAW<QT>] = {};
-        if (r < R) load_item<QT>(blocks, row_of, nsb, g4, p, cur, r, 0);  // in flight during the prologue
+        if (r < R) load_item<QT>(row_at, nsb, g4, p, cur, r, 0);  // in flight during the prologue
         uint32_t pk = 0, xk = 0;  // the pass's pairs and their rows of x, from the mask
         for (int i = 0; i < n; ++i) {
             const int q = nth_set_bit(m, first + i);
@@ -92,12 +93,12 @@ __global__ __launch_bounds__(NT) void gemv_packed_experts_a8_kernel(const uint8_
         gather_image(T, n, C, xk, x, x_up, bf16, a8_img);
         __syncthreads();
         // byte t of pk: the row of y of token t
-        auto yrow = [=](int t) { return t < n ? (int)((pk >> (8 * t)) & 0xffu) : -1; };
+        auto done = store_rows(y, R, bf16, [=](int t) { return t < n ? (int)((pk >> (8 * t)) & 0xffu) : -1; });
         switch (T) {
-        case 1: row_walk<QT, 1>(blocks, row_of, R, C, r, cur, a8_img, bf16, y, yrow); break;
-        case 2: row_walk<QT, 2>(blocks, row_of, R, C, r, cur, a8_img, bf16, y, yrow); break;
-        case 3: row_walk<QT, 3>(blocks, row_of, R, C, r, cur, a8_img, bf16, y, yrow); break;
-        default: row_walk<QT, 4>(blocks, row_of, R, C, r, cur, a8_img, bf16, y, yrow); break;
+        case 1: row_walk<QT, 1>(row_at, R, C, r, next, cur, a8_img, done); break;
+        case 2: row_walk<QT, 2>(row_at, R, C, r, next, cur, a8_img, done); break;
+        case 3: row_walk<QT, 3>(row_at, R, C, r, next, cur, a8_img, done); break;
+        default: row_walk<QT, 4>(row_at, R, C, r, next, cur, a8_img, done); break;
         }
         if ((first += GEMV_EXPERTS_A8_PASS) >= nm) return;
         __syncthreads();  // every wave has finished reading the image: the next pass may write it

@@ -7,7 +7,7 @@ through gq_gemv_packed (PackedLinear routes inputs of a few tokens there), the p
 launch on the last row of logits (temperature, top-k, top-p, the draw) and a row stops at `--eos_token_id`.
 
     python -m gptq_gguf_toolkit_amd.generate --model_name_or_path HF_DIR --prompt_ids ids.pt --max_new_tokens N \
-        --output_file out.json [--gguf FILE [--packed [--decode_act q8] [--moe_decode_act q8] [--moe_prefill grouped [--moe_act q8]]] | --quant_weights_path DB --quant_config_path CFG] \
+        --output_file out.json [--gguf FILE [--packed [--decode_act q8 [--decode_group on]] [--moe_decode_act q8] [--moe_prefill grouped [--moe_act q8]]] | --quant_weights_path DB --quant_config_path CFG] \
         [--dtype float16] [--attn_implementation eager] [--tokenizer_name NAME] [--kv_cache q8_0 [--kv_prefill q8_0]] [--prefill_chunk N]
 
 Prompts are the `.pt` list of [1, L] id tensors that ppleval reads (no tokenizer is needed; with --tokenizer_name the new
@@ -202,6 +202,9 @@ def parse_args(argv=None):
     p.add_argument("--decode_act", type=str, default="fp", choices=["fp", "q8"],
                    help="with --packed: fp (default), or q8: decode steps of the blocks' Linears (and a packed lm_head) multiply int8 "
                         "activations with the blocks' integer codes (PackedLinear.decode_act, gq_gemv_packed_a8; K-quants and Q8_0)")
+    p.add_argument("--decode_group", type=str, default="off", choices=["off", "on"],
+                   help="with --packed --decode_act q8: off (default), or on: q / k / v, and gate / up with SwiGLU, of a decode step run "
+                        "in one launch each (packed_group.install_groups, gq_gemv_packed_group_a8): the same bits, half the launches")
     p.add_argument("--moe_decode_act", type=str, default="fp", choices=["fp", "q8"],
                    help="with --packed: fp (default), or q8: decode steps of a MoE model's experts multiply int8 activations with "
                         "the blocks' integer codes (PackedExperts.decode_act, gq_gemv_packed_experts_a8; K-quants and Q8_0)")
@@ -240,6 +243,8 @@ def parse_args(argv=None):
         p.error("--moe_prefill needs --packed")
     if args.decode_act != "fp" and not args.packed:
         p.error("--decode_act needs --packed")
+    if args.decode_group != "off" and not (args.packed and args.decode_act == "q8"):
+        p.error("--decode_group needs --packed --decode_act q8")
     if args.moe_decode_act != "fp" and not args.packed:
         p.error("--moe_decode_act needs --packed")
     if args.moe_act != "fp" and args.moe_prefill != "grouped":

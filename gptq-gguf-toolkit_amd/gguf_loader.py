@@ -348,7 +348,7 @@ def _load_packed(model: torch.nn.Module, path: str, ref: torch.Tensor, vocab: bo
 
 def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill: str = "loop",
                     packed_act: str = "fp", moe_act: str = "fp", packed_decode_act: str = "fp", *,
-                    moe_decode_act: str = "fp") -> torch.nn.Module:
+                    moe_decode_act: str = "fp", packed_decode_group: bool = False) -> torch.nn.Module:
     """Load the file's weights into `model` (parameters on a GPU), strict on names and shapes.  A tied lm_head (no
     `output.weight` in the file) follows token_embd.
     packed=True: the K-quant, Q8_0, IQ4_NL and IQ4_XS tensors of the blocks' nn.Linear modules stay packed on the device -- each such Linear
@@ -369,7 +369,10 @@ def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill
     "q8" sends their decode steps of 1 .. ops.GEMV_A8_MAX_T tokens through the int8-activation GEMV (ops.gemv_packed_q8);
     experts keep the 16-bit route unless moe_decode_act says otherwise.
     moe_decode_act (with packed): "fp" or "q8", PackedExperts' `decode_act` -- "q8" sends the experts' decode steps of
-    1 .. ops.GEMV_A8_MAX_T tokens through the int8-activation grouped GEMV (ops.gemv_packed_experts_q8)."""
+    1 .. ops.GEMV_A8_MAX_T tokens through the int8-activation grouped GEMV (ops.gemv_packed_experts_q8).
+    packed_decode_group (with packed_decode_act="q8"): True runs the q / k / v of an attention block, and the gate / up of a
+    dense MLP with SwiGLU, of such a decode step in one launch each (packed_group.install_groups, ops.gemv_packed_group_q8,
+    ops.gemv_swiglu_packed_q8): the same bits in four Linear launches per layer instead of eight."""
     if packed not in (False, True, "all"):
         raise ValueError(f"load_into_model: packed must be False, True or 'all', got {packed!r}")
     if moe_prefill not in ("loop", "grouped") or (moe_prefill != "loop" and not packed):
@@ -384,6 +387,9 @@ def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill
     if moe_decode_act not in ("fp", "q8") or (moe_decode_act != "fp" and not packed):
         raise ValueError(f"load_into_model: moe_decode_act must be 'fp' or 'q8' (with packed), got {moe_decode_act!r} with "
                          f"packed={packed!r}")
+    if packed_decode_group not in (False, True) or (packed_decode_group and packed_decode_act != "q8"):
+        raise ValueError(f"load_into_model: packed_decode_group must be False or True (with packed_decode_act='q8'), got "
+                         f"{packed_decode_group!r} with packed_decode_act={packed_decode_act!r}")
     if moe_act not in ("fp", "q8") or (moe_act != "fp" and moe_prefill != "grouped"):
         raise ValueError(f"load_into_model: moe_act must be 'fp' or 'q8' (with moe_prefill='grouped'), got {moe_act!r} with "
                          f"moe_prefill={moe_prefill!r}")
@@ -401,4 +407,7 @@ def load_into_model(model: torch.nn.Module, path: str, packed=False, moe_prefill
         if tuple(t.shape) != tuple(want[k].shape):
             raise ValueError(f"{path}: {k} has shape {tuple(t.shape)}, the model expects {tuple(want[k].shape)}")
     model.load_state_dict(sd, strict=True)
+    if packed_decode_group:
+        from .packed_group import install_groups
+        install_groups(model)
     return model

@@ -1280,6 +1280,68 @@ def gemv_packed_q8(q_type: int, blocks: torch.Tensor, x: torch.Tensor, row_src: 
     return y
 
 
+# ---- the projections of one input in one launch (gq_gemv_packed_group_a8, gq_gemv_group_a8_plan) ----
+GEMV_GROUP_MAX = _cabi.GEMV_GROUP_MAX
+
+
+def gemv_group_a8_plan(q_types, R, C: int, T: int, swiglu: bool = False) -> dict:
+    """How gemv_packed_group_q8 (swiglu: gemv_swiglu_packed_q8) runs T tokens against the members' packed [R_m, C] weights
+    (gq_gemv_group_a8_plan, no device needed): lds_bytes of the quantized image of x, grid, first_wg (n + 1 entries: member m
+    owns workgroups first_wg[m] .. first_wg[m + 1] - 1, shared by largest remainder on the weight bytes; swiglu: [0, 0, grid],
+    the pair shares every workgroup) and fits (the image is within the LDS budget; a call that does not fit is refused)."""
+    q_types, R = [int(q) for q in q_types], [int(r) for r in R]
+    n = len(q_types)
+    if len(R) != n:
+        raise _cabi.GQError(f"gemv_group_a8_plan: {n} q_types and {len(R)} row counts")
+    lds, grid, fits = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    first = (ctypes.c_int64 * (n + 1))()
+    check(lib().gq_gemv_group_a8_plan((ctypes.c_int * max(n, 1))(*q_types), (ctypes.c_int64 * max(n, 1))(*R), n, int(C), int(T),
+                                      _cabi.GEMV_GROUP_SWIGLU if swiglu else _cabi.GEMV_GROUP_SPLIT, ctypes.byref(lds),
+                                      ctypes.byref(grid), first, ctypes.byref(fits)), "gq_gemv_group_a8_plan")
+    return dict(lds_bytes=int(lds.value), grid=int(grid.value), first_wg=[int(v) for v in first], fits=bool(fits.value))
+
+
+def _gemv_group(who: str, members, x: torch.Tensor, mode: int):
+    """The checks and the call of the two group ops -> [y_m] (SWIGLU: [act])."""
+    members = list(members)
+    if not 1 <= len(members) <= GEMV_GROUP_MAX:
+        raise _cabi.GQError(f"{who}: {len(members)} members (not in [1, GEMV_GROUP_MAX={GEMV_GROUP_MAX}])")
+    table, ys, C, T = (_cabi.GemvMember * len(members))(), [], None, None
+    for i, (q_type, blocks, row_src) in enumerate(members):
+        k, R, C, T = _packed_args(f"{who}: member {i}", q_type, blocks, x, row_src)
+        if k not in A8_TYPES:
+            raise _cabi.GQError(f"{who}: member {i}: q_type {k} is not served on int8 activations (a K-quant 10..14 or Q8_0 8)")
+        y = None
+        if mode == _cabi.GEMV_GROUP_SPLIT or i == 0:
+            y = torch.empty(*x.shape[:-1], R, dtype=x.dtype, device=x.device)
+            ys.append(y)
+        table[i] = _cabi.GemvMember(k, blocks.data_ptr(), row_src.data_ptr() if row_src is not None else None, R,
+                                    y.data_ptr() if y is not None else None)
+    if T > GEMV_A8_MAX_T:
+        raise _cabi.GQError(f"{who}: T={T} tokens, at most GEMV_A8_MAX_T={GEMV_A8_MAX_T}")
+    check(lib().gq_gemv_packed_group_a8(table, len(members), C, _ptr(x), T, _DT[x.dtype], mode, _stream(x)), "gq_gemv_packed_group_a8")
+    return ys
+
+
+def gemv_packed_group_q8(members, x: torch.Tensor):
+    """[gemv_packed_q8(q_type, blocks, x, row_src) for (q_type, blocks, row_src) in members], bit for bit, in ONE launch
+    (gq_gemv_packed_group_a8, GQ_GEMV_GROUP_SPLIT): 1 .. GEMV_GROUP_MAX packed weights of the same C, of any mixture of the
+    A8_TYPES, share x [..., C] (1 .. GEMV_A8_MAX_T tokens), which every workgroup quantizes once; the grid is shared among the
+    members by their weight bytes (gemv_group_a8_plan).  The q / k / v of an attention block.  No workspace, no host read."""
+    return _gemv_group("gemv_packed_group_q8", members, x, _cabi.GEMV_GROUP_SPLIT)
+
+
+def gemv_swiglu_packed_q8(q_type: int, gate_blocks: torch.Tensor, up_blocks: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """fwd_silu_mul(gemv_packed_q8(q_type, gate_blocks, x), gemv_packed_q8(q_type, up_blocks, x)), bit for bit, in ONE launch
+    (gq_gemv_packed_group_a8, GQ_GEMV_GROUP_SWIGLU): a wave walks gate row r and up row r back to back and stores only the
+    activation [..., R]; the gate and up results are never written.  Both weights are [R, C] of one q_type of A8_TYPES."""
+    who = "gemv_swiglu_packed_q8"
+    if gate_blocks.numel() != up_blocks.numel():
+        raise _cabi.GQError(f"{who}: gate and up must be packed weights of one shape and type; got {gate_blocks.numel()} and "
+                            f"{up_blocks.numel()} bytes")
+    return _gemv_group(who, [(q_type, gate_blocks, None), (q_type, up_blocks, None)], x, _cabi.GEMV_GROUP_SWIGLU)[0]
+
+
 # ---- the grouped expert GEMV of a packed MoE layer's decode step (gq_gemv_packed_experts) ----
 MOE_MAX_PAIRS = _cabi.MOE_MAX_PAIRS
 

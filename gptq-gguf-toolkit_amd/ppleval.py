@@ -144,7 +144,8 @@ def apply_weights(model, args):
                                     **({"moe_act": "q8"} if getattr(args, "moe_act", "fp") == "q8" else {}),
                                     **({"packed_act": "q8"} if getattr(args, "packed_act", "fp") == "q8" else {}),
                                     **({"packed_decode_act": "q8"} if getattr(args, "decode_act", "fp") == "q8" else {}),
-                                    **({"moe_decode_act": "q8"} if getattr(args, "moe_decode_act", "fp") == "q8" else {}))
+                                    **({"moe_decode_act": "q8"} if getattr(args, "moe_decode_act", "fp") == "q8" else {}),
+                                    **({"packed_decode_group": True} if getattr(args, "decode_group", "off") == "on" else {}))
     elif args.quant_weights_path:
         load_compressed_weights(model, args.quant_weights_path, args.quant_config_path, args.quant_default_level)
     return model
